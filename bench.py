@@ -11,6 +11,12 @@ Workload at N=1: BASELINE.json configs[1] -- NeuralCX MLP, synthetic 2048-d feat
 batch 512, H=256, L=1, dropout 0.25, Adam lr 1e-4.  --scaling weak (default): each rank keeps batch 512
 (global batch 512 N); --scaling strong: the GLOBAL batch stays 512 (SURVEY 8e's partition: 512 / N triplets per
 rank, the optimisation problem of options/cx/*.yaml).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up (preheat + W steps), times the K steps and prints the line (metric, value, unit, dtype,
+ms_per_step, ...).  --full adds everything else the line used to carry, each from runs of its own: the no-preheat window
+(ms_per_step_no_preheat), the per-kernel roofline with the held shader clock, the held-out Recall@1/@5 and the CPU
+baseline.  --dump-outputs DIR writes the tensors the last timed step returned (scores, loss, per-row loss, ranks, hits)
+and the updated parameters of rank 0 as DIR/<name>.npy; the inputs are seeded, so two builds compare output for output.
 """
 import argparse
 import json
@@ -153,6 +159,26 @@ def cpu_baseline(dev, feats, steps=50, warmup=10, one_thread_steps=12, heldout=1
                             train_steps=n_train, heldout_triplets=heldout))
 
 
+def dump_outputs(out_dir, arrays, budget=64 << 20, seed=0):
+    """Write every tensor of `arrays` as <out_dir>/<name>.npy, floating point as float32, integers as float64.  When they
+    exceed `budget` bytes in all, each tensor of more than 1 Mi elements is replaced by a fixed, seeded sample of its
+    flattened elements (sorted indices from numpy's default_rng(seed + its position)), sized to fit the budget."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: (v.detach().float() if v.is_floating_point() else v.detach().double()) for k, v in arrays.items()}
+    nbytes = lambda v: v.numel() * v.element_size()
+    big = [k for k, v in arrays.items() if v.numel() > (1 << 20)]
+    small = sum(nbytes(v) for k, v in arrays.items() if k not in big)
+    total = small + sum(nbytes(arrays[k]) for k in big)
+    for i, (k, v) in enumerate(arrays.items()):
+        if total > budget and k in big:
+            n = int(v.numel() * (budget - small) / (total - small) * 0.99)
+            idx = np.unique(np.random.default_rng(seed + i).integers(0, v.numel(), size=n))
+            v = v.reshape(-1).index_select(0, torch.from_numpy(idx).to(v.device))
+        np.save(os.path.join(out_dir, k + ".npy"), v.cpu().numpy())
+
+
 def workload_label(args, c):
     """Which BASELINE.json config the flags select (the default flags are configs[1], the headline)."""
     if args.c3:
@@ -189,6 +215,11 @@ def main():
                          "to reach its operating point (measured: the first of 20 timed steps after 5 warm-up steps runs 8 %% slower than the "
                          "25th); 0 = none.  Reported in the JSON line")
     ap.add_argument("--heldout", type=int, default=1024, help="held-out planted triplets for Recall@1/@5 (after the timed steps; and of the CPU/HIP same-training comparison)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the no-preheat window, the per-kernel roofline and held clock, "
+                         "the held-out Recall@1/@5 and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (and the updated parameters) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -263,9 +294,11 @@ def main():
     fence()                                         # (builds the RCCL communicator before any step)
     # What the conditioning buys, on the same line: a short timed window from the cold state -- W warm-up steps, then
     # min(K, 10) timed steps, fenced like the headline window -- BEFORE the preheat.  Reported as `ms_per_step_no_preheat`
-    # (never `value`); these steps train the same weights on the same batches, they are not part of the K timed steps.
+    # (never `value`); these steps train the same weights on the same batches, they are not part of the K timed steps, and
+    # the weights and optimizer state they leave are put back, so that the timed steps compute what a plain run computes.
     ms_cold = None
-    if args.preheat_ms > 0 and args.steps > 0:
+    if args.full and args.preheat_ms > 0 and args.steps > 0:
+        state0, opt0 = eng.state_dict(), eng.optimizer_state()
         nc = min(args.steps, 10)
         for i in range(args.warmup):
             step(i)
@@ -281,10 +314,14 @@ def main():
         ms_cold = dict(ms_per_step=round(float(tcold.item()) / nc * 1e3, 4), steps=nc, warmup=args.warmup,
                        note="the same fenced measurement from the cold state, taken before the preheat and before the headline window")
         eng.comm_events = []
+        eng.load_state(state0)
+        eng.load_optimizer_state(opt0)
+        del state0, opt0
+        fence()
     # The HIP events of the per-kernel timing are created BEFORE the warm-up (creating 2 x (4 K + 8) events takes the host
     # long enough for an idle chip to drop its clocks between warm-up and the timed region); the warm-up launches are
     # recorded too and dropped below.
-    if rank == 0:
+    if args.full and rank == 0:
         _lib.profile_begin(["MAIN", "DW1C"], max_launches=4 * (args.steps + args.warmup) + 8)
     if args.preheat_ms > 0:             # device conditioning, not workload steps: reported as `preheat_ms`
         xa = torch.randn(4096, 4096, device=dev); xb = torch.randn(4096, 4096, device=dev)
@@ -318,15 +355,19 @@ def main():
         loss = float(lt.item())
     # HIP events of the timed launches are read BEFORE anything else launches the same kernels (round 2's line summed the
     # MAIN launches of the 4 evaluation batches below into the timed steps' total: 0.344 ms reported for a 0.30 ms kernel)
-    prof = _lib.profile_end() if rank == 0 else None
+    prof = _lib.profile_end() if args.full and rank == 0 else None
     if prof:                                        # drop the warm-up steps' launches (MAIN: 1 per step, DW1C: 1 or 2 per step)
         for k, v in prof.items():
             per_step = len(v) // (args.steps + args.warmup) if (args.steps + args.warmup) else 0
             prof[k] = v[per_step * args.warmup:]
+    if args.dump_outputs and rank == 0:             # what the last timed step handed its caller, before anything else runs
+        outs = {k: v for k, v in r.items() if torch.is_tensor(v)}
+        outs.update({"param." + n: v for n, v in eng.params.views.items()})
+        dump_outputs(args.dump_outputs, outs)
     # Recall@1/@5 (the other half of BASELINE.json's metric) of the weights after warmup + steps, on held-out triplets of the
     # same planted synthetic distribution (rank 0's replica; replicas are identical)
     rec = None
-    if rank == 0 and args.heldout > 0 and mutan is None:
+    if args.full and rank == 0 and args.heldout > 0 and mutan is None:
         hd = SyntheticCX(n_triplets=args.heldout, K=args.K, n_img=args.n_img, seed=4321, device=dev, feats=data.feats)
         hits = torch.zeros(2, dtype=torch.int64, device=dev)
         hb = 256
@@ -343,7 +384,7 @@ def main():
         # back to back, from in-kernel stamps of MAIN (ncx_profile_stamps: s_memtime / s_memrealtime at entry and exit of
         # every workgroup of the last of `nd` further steps).  Ranks > 0 of a multi-GPU run idle at the final barrier.
         clock = None
-        if not args.bf16 and world == 1:
+        if args.full and not args.bf16 and world == 1:
             nd = 12
             st = torch.zeros(16 * 8192, dtype=torch.int64, device=dev)
             _lib.profile_stamps(st)
@@ -363,99 +404,99 @@ def main():
                              kernel_span_us=round(float(w[:, 15].max() - w[:, 14].min()) / 100.0, 1),
                              how="in-kernel stamps of the last of %d back-to-back diagnostic steps after the timed region: "
                                  "d(s_memtime) / d(s_memrealtime) x 100 MHz per workgroup, median" % nd)
-        # Algorithmic flops per launch (SURVEY 8d conventions: one-hot rank columns = 0 flops; the a_emb_other
-        # segment is consumed in its re-associated form softmax(a) . (E . W^T): A columns instead of da).
-        p_cols = 2 * c["dv"] + 1 + c["dz"] + c["A"]                     # candidate segments
-        s_cols = c["dv"] + c["dq"] + c["dz"] + c["da"]                  # per-triplet shared segments
-        flops = {"MAIN": 2.0 * M * c["H"] * p_cols,                     # h1 = candidates . W1 slices
-                 "DW1C": 2.0 * M * c["H"] * p_cols + 2.0 * args.batch * c["H"] * s_cols}   # all dW1 columns + dGt
-        d0 = eng._dims(pool[0][0], True, 1.0 / gb)
-        plans = {k: _lib.plan_query(d0, k) for k in ("MAIN", "DW1C")}
-        names = {"MAIN": "k_main_fwd (csrc/ncx_main.h): linear_1 forward, the candidate segments chained into one fp32-MFMA accumulator "
-                         "(v_other and v_orig*v_other as one per-triplet fold where the plan says so), Sh / ReLU / Dropout epilogue; tile: %s"
-                         % plans["MAIN"]["tile"],
-                 "DW1C": "linear_1 weight gradient (all columns + dGt): k_dw_km8 (v_other + v_mult columns in one MFMA pass, per-triplet "
-                         "fold, 8 k-chunks, one 8-wave workgroup per CU on 256 x 64 tile pairs; other shapes: k_dw_km) + k_dw_tn8 (dGt and every other column block: one balanced launch of 8-wave workgroups on 256 x 64 "
-                         "tiles; shapes it does not cover: seg_gemm TN %s grouped) + their merged fixed-order reduction"
-                         % plans["DW1C"]["tile"]}
-        peak = PEAK_F32_MFMA_TFLOPS
-        if args.x6:
-            x6note = (" [--x6 (NOT the headline): %s -- three bf16 planes per fp32 operand, six v_mfma_f32_16x16x32_bf16 per 16x16x32 block, fp32 accumulate; "
-                      "achieved / frac stay fp32-EQUIVALENT flops against the fp32-MFMA peak (the kernels are bound by LDS + load-return traffic, not by the matrix cores: DESIGN 5d)]")
-            names["MAIN"] += x6note % "k_main_fwd<..., X6>"
-            names["DW1C"] += x6note % "k_dw_km_x6 + k_dw_tn8_x6 instead of k_dw_km + k_dw_tn8"
-        if args.bf16:
-            peak = PEAK_BF16_MFMA_TFLOPS
-            names = {"MAIN": "gemm_bf16_nt (packed candidate rows . packed weights^T, fwd; 64x64 or 128x128 tiles by workgroup count; weight pack excluded)",
-                     "DW1C": "gemm_bf16_tn 128x128, 8 k-chunks (one per XCD) + dpre cast + reduce/scatter (all candidate weight-grad columns + dGt)"}
-            for k in plans:
-                plans[k] = dict(plans[k], tile="bf16", ksplit=1 if k == "MAIN" else 8)
-        # per STEP: the weight gradient of linear_1 is two launches under one id (fused v_other / v_mult kernel + grouped rest)
-        per = {k: sum(v) / args.steps for k, v in prof.items() if v}
-        # the dominant KERNEL is the one with the longest single launch (DW1C is two launches per step: the per-step sum of a
-        # pair must not outrank the one launch that is longer than either of them)
-        per_launch = {k: sum(v) / len(v) for k, v in prof.items() if v}
-        dom = max(per_launch, key=per_launch.get) if per_launch else None
-        # flops the matrix cores EXECUTE for `flops` (padding of reduction extents to 32; the per-triplet folds run 32
-        # (K = 24) or 64 (K = 48) row blocks per triplet for the two 2048-deep segments at once: 4 MFMA row blocks instead of 2 x 3)
-        pad32 = lambda n: (n + 31) // 32 * 32
-        rest_cols = pad32(c["K"] + 1) + pad32(c["dz"]) + pad32(c["A"])
-        fold_fwd = plans["MAIN"]["tile"].startswith(("48x64", "96x64", "192x64"))
-        blk = 32 if c["K"] == 24 else 64
-        executed = {"MAIN": 2.0 * c["H"] * ((args.batch * blk if fold_fwd else 2 * M) * c["dv"] + M * rest_cols),
-                    "DW1C": (2.0 * c["H"] * M * (c["dv"] + c["K"] + 1 + c["dz"] + c["A"]) + 2.0 * args.batch * c["H"] * s_cols) if c["K"] % 24 == 0 and args.batch >= 256
-                            else flops["DW1C"]}
         roof = None
-        if dom:
-            ach = flops[dom] / (per[dom] * 1e-3) / 1e12
-            # HBM bytes per launch of that kernel from the committed PMC passes (collected offline as the guide
-            # prescribes: separate --pmc runs, FETCH_SIZE x2 on gfx950), per workload
-            traffic, traffic_source = None, None
-            wl = "c5" if (args.bf16 and (args.batch, c["K"]) == (1024, 48)) else "c3" if args.c3 else \
-                 ("x6" if args.x6 else "c2") if (args.batch, c["K"], c["H"], c["L"], args.bf16) == (512, 24, 256, 1, False) else None
-            for tname in ("r4_traffic.json", "r3_traffic.json", "r2_traffic.json"):
-                tpath = os.path.join(ROOT, "profiles", tname)
-                if wl and os.path.exists(tpath):
-                    tj = json.load(open(tpath))
-                    tj = tj.get(wl, tj if wl == "c2" else {})
-                    if tj.get(dom, {}).get("bytes_per_launch"):
-                        traffic = tj[dom]["bytes_per_launch"]
-                        traffic_source = "profiles/%s: %s" % (tname, tj.get("_source", "rocprofv3 --pmc passes of this workload"))
-                        break
-            # spread over the timed launches (per step: DW1C sums its two launches)
-            nl = max(1, len(prof[dom]) // args.steps)
-            series = [sum(prof[dom][i * nl:(i + 1) * nl]) for i in range(args.steps)]
-            srt = sorted(series)
-            k5 = min(5, len(series))
-            roof = dict(bound="mfma", kernel=names[dom], achieved=round(ach, 2), peak=peak,
-                        unit="TFLOP/s", frac=round(ach / peak, 4),
-                        frac_basis="ALGORITHMIC flops (SURVEY 8d numerator) / launch time / peak; `frac_executed` beside it counts only the flops the matrix cores execute",
-                        traffic=traffic, traffic_source=traffic_source,
-                        launch_ms=round(per[dom], 4), launch_ms_min=round(srt[0], 4), launch_ms_median=round(srt[len(srt) // 2], 4),
-                        launch_ms_max=round(srt[-1], 4), launch_ms_first5=round(sum(series[:k5]) / k5, 4),
-                        launch_ms_last5=round(sum(series[-k5:]) / k5, 4), launch_ms_head=[round(x, 4) for x in series[:12]],
-                        algorithmic_gflop_per_launch=round(flops[dom] / 1e9, 3),
-                        other={k: dict(launch_ms=round(v, 4), launches_per_step=len(prof[k]) // args.steps, tflops=round(flops[k] / (v * 1e-3) / 1e12, 2),
-                                       mfma_executed_gflop=round(executed[k] / 1e9, 3), plan=plans[k]) for k, v in per.items()})
+        if args.full:
+            # Algorithmic flops per launch (SURVEY 8d conventions: one-hot rank columns = 0 flops; the a_emb_other
+            # segment is consumed in its re-associated form softmax(a) . (E . W^T): A columns instead of da).
+            p_cols = 2 * c["dv"] + 1 + c["dz"] + c["A"]                     # candidate segments
+            s_cols = c["dv"] + c["dq"] + c["dz"] + c["da"]                  # per-triplet shared segments
+            flops = {"MAIN": 2.0 * M * c["H"] * p_cols,                     # h1 = candidates . W1 slices
+                     "DW1C": 2.0 * M * c["H"] * p_cols + 2.0 * args.batch * c["H"] * s_cols}   # all dW1 columns + dGt
+            d0 = eng._dims(pool[0][0], True, 1.0 / gb)
+            plans = {k: _lib.plan_query(d0, k) for k in ("MAIN", "DW1C")}
+            names = {"MAIN": "k_main_fwd (csrc/ncx_main.h): linear_1 forward, the candidate segments chained into one fp32-MFMA accumulator "
+                             "(v_other and v_orig*v_other as one per-triplet fold where the plan says so), Sh / ReLU / Dropout epilogue; tile: %s"
+                             % plans["MAIN"]["tile"],
+                     "DW1C": "linear_1 weight gradient (all columns + dGt): k_dw_km8 (v_other + v_mult columns in one MFMA pass, per-triplet "
+                             "fold, 8 k-chunks, one 8-wave workgroup per CU on 256 x 64 tile pairs; other shapes: k_dw_km) + k_dw_tn8 (dGt and every other column block: one balanced launch of 8-wave workgroups on 256 x 64 "
+                             "tiles; shapes it does not cover: seg_gemm TN %s grouped) + their merged fixed-order reduction"
+                             % plans["DW1C"]["tile"]}
+            peak = PEAK_F32_MFMA_TFLOPS
             if args.x6:
-                # the matrix cores execute SIX bf16 products per fp32-equivalent one: price the line against the dense bf16 peak by executed bf16 flops
-                ex6 = 6.0 * executed[dom] / (per[dom] * 1e-3) / 1e12
-                roof.update(achieved=round(ex6, 2), peak=PEAK_BF16_MFMA_TFLOPS, frac=round(ex6 / PEAK_BF16_MFMA_TFLOPS, 4),
-                            frac_basis="EXECUTED bf16 MFMA flops (6 plane products per fp32-equivalent product, reduction extents padded to 32) / launch time / dense bf16 peak; "
-                                       "the kernel is bound by LDS + load-return traffic, not by the matrix cores (DESIGN 5d)",
-                            fp32_equivalent_algorithmic_tflops=round(ach, 2), bf16_mfma_executed_gflop=round(6.0 * executed[dom] / 1e9, 3))
-            elif not args.bf16:
-                ex = executed[dom] / (per[dom] * 1e-3) / 1e12
-                roof.update(mfma_executed_gflop=round(executed[dom] / 1e9, 3), executed_tflops=round(ex, 2), frac_executed=round(ex / peak, 4),
-                            peak_assumes_mhz=2400)
-                if clock:
-                    held = peak * clock["sclk_mhz"] / 2400.0
-                    roof.update(clock, peak_at_held_clock=round(held, 1), frac_of_peak_at_held_clock=round(ach / held, 4),
-                                frac_executed_at_held_clock=round(ex / held, 4))
+                x6note = (" [--x6 (NOT the headline): %s -- three bf16 planes per fp32 operand, six v_mfma_f32_16x16x32_bf16 per 16x16x32 block, fp32 accumulate; "
+                          "achieved / frac stay fp32-EQUIVALENT flops against the fp32-MFMA peak (the kernels are bound by LDS + load-return traffic, not by the matrix cores: DESIGN 5d)]")
+                names["MAIN"] += x6note % "k_main_fwd<..., X6>"
+                names["DW1C"] += x6note % "k_dw_km_x6 + k_dw_tn8_x6 instead of k_dw_km + k_dw_tn8"
+            if args.bf16:
+                peak = PEAK_BF16_MFMA_TFLOPS
+                names = {"MAIN": "gemm_bf16_nt (packed candidate rows . packed weights^T, fwd; 64x64 or 128x128 tiles by workgroup count; weight pack excluded)",
+                         "DW1C": "gemm_bf16_tn 128x128, 8 k-chunks (one per XCD) + dpre cast + reduce/scatter (all candidate weight-grad columns + dGt)"}
+                for k in plans:
+                    plans[k] = dict(plans[k], tile="bf16", ksplit=1 if k == "MAIN" else 8)
+            # per STEP: the weight gradient of linear_1 is two launches under one id (fused v_other / v_mult kernel + grouped rest)
+            per = {k: sum(v) / args.steps for k, v in prof.items() if v}
+            # the dominant KERNEL is the one with the longest single launch (DW1C is two launches per step: the per-step sum of a
+            # pair must not outrank the one launch that is longer than either of them)
+            per_launch = {k: sum(v) / len(v) for k, v in prof.items() if v}
+            dom = max(per_launch, key=per_launch.get) if per_launch else None
+            # flops the matrix cores EXECUTE for `flops` (padding of reduction extents to 32; the per-triplet folds run 32
+            # (K = 24) or 64 (K = 48) row blocks per triplet for the two 2048-deep segments at once: 4 MFMA row blocks instead of 2 x 3)
+            pad32 = lambda n: (n + 31) // 32 * 32
+            rest_cols = pad32(c["K"] + 1) + pad32(c["dz"]) + pad32(c["A"])
+            fold_fwd = plans["MAIN"]["tile"].startswith(("48x64", "96x64", "192x64"))
+            blk = 32 if c["K"] == 24 else 64
+            executed = {"MAIN": 2.0 * c["H"] * ((args.batch * blk if fold_fwd else 2 * M) * c["dv"] + M * rest_cols),
+                        "DW1C": (2.0 * c["H"] * M * (c["dv"] + c["K"] + 1 + c["dz"] + c["A"]) + 2.0 * args.batch * c["H"] * s_cols) if c["K"] % 24 == 0 and args.batch >= 256
+                                else flops["DW1C"]}
+            if dom:
+                ach = flops[dom] / (per[dom] * 1e-3) / 1e12
+                # HBM bytes per launch of that kernel from the committed PMC passes (collected offline as the guide
+                # prescribes: separate --pmc runs, FETCH_SIZE x2 on gfx950), per workload
+                traffic, traffic_source = None, None
+                wl = "c5" if (args.bf16 and (args.batch, c["K"]) == (1024, 48)) else "c3" if args.c3 else \
+                     ("x6" if args.x6 else "c2") if (args.batch, c["K"], c["H"], c["L"], args.bf16) == (512, 24, 256, 1, False) else None
+                for tname in ("r4_traffic.json", "r3_traffic.json", "r2_traffic.json"):
+                    tpath = os.path.join(ROOT, "profiles", tname)
+                    if wl and os.path.exists(tpath):
+                        tj = json.load(open(tpath))
+                        tj = tj.get(wl, tj if wl == "c2" else {})
+                        if tj.get(dom, {}).get("bytes_per_launch"):
+                            traffic = tj[dom]["bytes_per_launch"]
+                            traffic_source = "profiles/%s: %s" % (tname, tj.get("_source", "rocprofv3 --pmc passes of this workload"))
+                            break
+                # spread over the timed launches (per step: DW1C sums its two launches)
+                nl = max(1, len(prof[dom]) // args.steps)
+                series = [sum(prof[dom][i * nl:(i + 1) * nl]) for i in range(args.steps)]
+                srt = sorted(series)
+                k5 = min(5, len(series))
+                roof = dict(bound="mfma", kernel=names[dom], achieved=round(ach, 2), peak=peak,
+                            unit="TFLOP/s", frac=round(ach / peak, 4),
+                            frac_basis="ALGORITHMIC flops (SURVEY 8d numerator) / launch time / peak; `frac_executed` beside it counts only the flops the matrix cores execute",
+                            traffic=traffic, traffic_source=traffic_source,
+                            launch_ms=round(per[dom], 4), launch_ms_min=round(srt[0], 4), launch_ms_median=round(srt[len(srt) // 2], 4),
+                            launch_ms_max=round(srt[-1], 4), launch_ms_first5=round(sum(series[:k5]) / k5, 4),
+                            launch_ms_last5=round(sum(series[-k5:]) / k5, 4), launch_ms_head=[round(x, 4) for x in series[:12]],
+                            algorithmic_gflop_per_launch=round(flops[dom] / 1e9, 3),
+                            other={k: dict(launch_ms=round(v, 4), launches_per_step=len(prof[k]) // args.steps, tflops=round(flops[k] / (v * 1e-3) / 1e12, 2),
+                                           mfma_executed_gflop=round(executed[k] / 1e9, 3), plan=plans[k]) for k, v in per.items()})
+                if args.x6:
+                    # the matrix cores execute SIX bf16 products per fp32-equivalent one: price the line against the dense bf16 peak by executed bf16 flops
+                    ex6 = 6.0 * executed[dom] / (per[dom] * 1e-3) / 1e12
+                    roof.update(achieved=round(ex6, 2), peak=PEAK_BF16_MFMA_TFLOPS, frac=round(ex6 / PEAK_BF16_MFMA_TFLOPS, 4),
+                                frac_basis="EXECUTED bf16 MFMA flops (6 plane products per fp32-equivalent product, reduction extents padded to 32) / launch time / dense bf16 peak; "
+                                           "the kernel is bound by LDS + load-return traffic, not by the matrix cores (DESIGN 5d)",
+                                fp32_equivalent_algorithmic_tflops=round(ach, 2), bf16_mfma_executed_gflop=round(6.0 * executed[dom] / 1e9, 3))
+                elif not args.bf16:
+                    ex = executed[dom] / (per[dom] * 1e-3) / 1e12
+                    roof.update(mfma_executed_gflop=round(executed[dom] / 1e9, 3), executed_tflops=round(ex, 2), frac_executed=round(ex / peak, 4),
+                                peak_assumes_mhz=2400)
+                    if clock:
+                        held = peak * clock["sclk_mhz"] / 2400.0
+                        roof.update(clock, peak_at_held_clock=round(held, 1), frac_of_peak_at_held_clock=round(ach / held, 4),
+                                    frac_executed_at_held_clock=round(ex / held, 4))
         out = dict(metric="VQA-CX triplets/sec (24 candidates each), NeuralCX training step",
                    value=round(gb * args.steps / dt, 1), unit="triplets/s", n_gpus=world, steps=args.steps,
-                   warmup=args.warmup, preheat_ms=args.preheat_ms, ms_per_step=round(dt / args.steps * 1e3, 4),
-                   ms_per_step_no_preheat=ms_cold, higher_is_better=True,
+                   warmup=args.warmup, preheat_ms=args.preheat_ms, ms_per_step=round(dt / args.steps * 1e3, 4), higher_is_better=True,
                    scaling=args.scaling, vs_baseline=None, dtype="bf16 operands / f32 accumulate (first-layer GEMMs), f32 elsewhere" if args.bf16 else
                          "f32 via bf16x6 in the three big kernels (linear_1 forward, its weight gradient: three bf16 planes per fp32 operand, six plane products, f32 accumulate; error vs fp64 = the fp32-MFMA kernels'), f32 elsewhere -- NOT the headline" if args.x6 else "f32",
                    data="synthetic",
@@ -465,8 +506,9 @@ def main():
                                         % (c["K"], args.batch, args.scaling, gb, c["H"], c["L"],
                                            "bf16 operands / fp32 accumulate for the linear_1 and answer-embedding products, fp32 elsewhere" if args.bf16 else "fp32"),
                                global_batch=gb, per_rank_batch=args.batch, candidates=c["K"], dim_h=c["H"], n_layers=c["L"],
-                               parallelism="dp%d" % world, feature_table_rows=args.n_img, final_loss=round(loss, 5)),
-                   roofline=roof)
+                               parallelism="dp%d" % world, feature_table_rows=args.n_img, final_loss=round(loss, 5)))
+        if args.full:
+            out.update(ms_per_step_no_preheat=ms_cold, roofline=roof)
         if rec is not None:
             out["recall_at_1"], out["recall_at_5"] = round(rec[0], 4), round(rec[1], 4)
             out["recall_note"] = ("HIP path, %d held-out planted synthetic triplets, after %d training steps (chance: 0.0417 / 0.2083)"
@@ -486,7 +528,7 @@ def main():
                 out["rccl"] = dict(nranks=world, version=None, note="NCX_DIST_BACKEND=%s rehearsal: NOT RCCL" % backend)
             if stall:
                 out["rccl"]["exposed_wait"] = stall
-        if not args.no_cpu_baseline and world == 1 and (c["dv"], c["K"]) == (2048, 24):
+        if args.full and not args.no_cpu_baseline and world == 1 and (c["dv"], c["K"]) == (2048, 24):
             out["cpu_baseline"] = cpu_baseline(dev, data.feats, steps=args.cpu_steps, heldout=args.heldout)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -63,3 +63,37 @@ def test_bench_n1_needs_no_launcher(monkeypatch):
     except SystemExit as e:
         assert "needs an MI355X" in str(e)
     assert not called
+
+
+def test_dump_outputs_dtypes_budget_and_fixed_sample(tmp_path):
+    """--dump-outputs' writer: floating point as float32, integers as float64; above the budget every large array becomes a
+    fixed, seeded sample of its elements, so two runs of the same build write the same files."""
+    import numpy as np
+    import torch
+    import bench
+    arrays = {"loss": torch.tensor(2.5, dtype=torch.float64), "hits": torch.tensor([3, 4], dtype=torch.int32),
+              "big": torch.arange(3 << 20, dtype=torch.float32), "big2": torch.ones(2 << 20)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    a = {f[:-4]: np.load(str(tmp_path / "all" / f)) for f in os.listdir(str(tmp_path / "all"))}
+    assert a["loss"].dtype == np.float32 and a["hits"].dtype == np.float64 and a["hits"].tolist() == [3, 4]
+    assert np.array_equal(a["big"], np.arange(3 << 20, dtype=np.float32))           # within the budget: everything, whole
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), arrays, budget=8 << 20)
+        assert sum(os.path.getsize(str(tmp_path / run / f)) for f in os.listdir(str(tmp_path / run))) <= 8 << 20
+    s1, s2 = np.load(str(tmp_path / "s1" / "big.npy")), np.load(str(tmp_path / "s2" / "big.npy"))
+    assert np.array_equal(s1, s2) and 0 < s1.size < 3 << 20 and (np.diff(s1) > 0).all()   # sorted distinct elements
+    assert np.load(str(tmp_path / "s1" / "hits.npy")).tolist() == [3, 4]                 # small arrays stay whole
+
+
+def test_bench_full_and_dump_outputs_are_options(monkeypatch, tmp_path):
+    """--full and --dump-outputs parse (without a GPU the run then stops where every run does)."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "1", "--full", "--dump-outputs", str(tmp_path)])
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    import torch
+    if torch.cuda.is_available():
+        return
+    try:
+        bench.main()
+    except SystemExit as e:
+        assert "needs an MI355X" in str(e)

@@ -83,10 +83,10 @@ def test_cli_options_and_shipped_yaml_schema():
             assert k in o["cx_model"]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/options/cx"), reason="reference checkout only exists in the build container")
 def test_reference_yaml_files_load_unchanged():
+    """The 19 option files of the reference's options/cx/, stored verbatim under tests/golden/g9_reference_options_cx/."""
     import counterexamples as cli
-    d = "/root/reference/options/cx"
+    d = os.path.join(ROOT, "tests", "golden", "g9_reference_options_cx")
     n = 0
     for f in sorted(os.listdir(d)):
         a = cli.build_parser().parse_args(["--synthetic", "--path_opt", os.path.join(d, f)])

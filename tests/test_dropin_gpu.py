@@ -842,3 +842,33 @@ def test_bench_two_ranks_on_one_card_gloo_rehearsal():
     assert d["rccl"]["exposed_wait"]["bucket1_ms"] >= 0 and d["rccl"]["exposed_wait"]["bucket2_ms"] >= 0      # (stall of the compute stream per bucket)
     assert d["value"] > 0 and abs(d["value"] - 128 / (d["ms_per_step"] * 1e-3)) <= 0.01 * d["value"]
     assert np.isfinite(d["config"]["final_loss"]) and 2.0 < d["config"]["final_loss"] < 4.0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run prints the headline fields only (the roofline, the no-preheat window, Recall and the CPU
+    baseline are --full's), times exactly --steps steps, and --dump-outputs writes what the last timed step returned plus
+    the updated parameters: float32 / float64 arrays, 64 MB at most, the same bits from two runs with the same arguments."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for i in range(2):
+        out = str(tmp_path / ("d%d" % i))
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "64",
+                            "--n_img", "4096", "--preheat-ms", "0", "--dump-outputs", out], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "triplets/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["value"] > 0 and abs(d["value"] - 64 / (d["ms_per_step"] * 1e-3)) <= 0.01 * d["value"]
+        assert not {"roofline", "ms_per_step_no_preheat", "recall_at_5", "cpu_baseline"} & set(d)
+        files = sorted(os.listdir(out))
+        assert {"scores.npy", "loss.npy", "hits.npy", "param.linear_1.weight.npy"} <= set(files), files
+        assert sum(os.path.getsize(os.path.join(out, f)) for f in files) <= 64 << 20
+        arrs = {f: np.load(os.path.join(out, f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert arrs["scores.npy"].shape == (64, 24) and np.isfinite(arrs["scores.npy"]).all()
+        assert abs(float(arrs["loss.npy"].reshape(-1)[0]) - d["config"]["final_loss"]) <= 1e-4
+        dumps.append(arrs)
+    for f, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][f]), f

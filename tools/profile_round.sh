@@ -10,9 +10,9 @@ TAG=${1:-r4}; KEY=${2:-c2}
 if [ $# -ge 2 ]; then shift 2; else shift $#; fi
 RND=${TAG%%[!a-z0-9]*}; RND=${RND:0:2}              # round prefix of the tag (r4_01 -> r4): the traffic file is per round
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
-OUT=$ROOT/gpurun_out
+OUT=$(realpath -m "${NCX_OUT:-$ROOT/out}")          # output folder (NCX_OUT, relative to the directory this is started from)
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --heldout 0 $*"
+B="python3 $ROOT/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --heldout 0 $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace -- $B > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/${TAG}_trace.err
 S="python3 $ROOT/bench.py --steps 4 --warmup 2 --preheat-ms 0 --no-cpu-baseline --heldout 0 $*"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/${TAG}_pmc_fetch -- $S > /dev/null 2> $OUT/${TAG}_pmc_fetch.err
