@@ -279,6 +279,23 @@ int ncx_knn(const float* table, int32_t n, const float* queries, int32_t nq, int
             int32_t norms_ready, void* workspace, size_t workspace_bytes, int64_t* out_idx, float* out_dist,
             void* stream);
 
+/* ---- the semantic baseline scorer (reference vqa/models/cx.py:159-210, SemanticBaseline) ---------------------------
+ * ncx_cosine_gram replaces cx.py:174-175 (emb_pairs = sklearn cosine_similarity(emb)): gram [A, A] = E^ . E^^T with
+ * E^ = emb [A, da] row-normalised in fp64 (a zero row stays zero: its similarities are all 0, the diagonal included), the
+ * product on the library's fp32 MFMA engine in column chunks whose partial products are summed in fp64.
+ * Workspace: ncx_cosine_gram_workspace_bytes (256-byte aligned; E^ plus an fp64 [A, A] accumulator).
+ * 1 <= A <= 8192, 1 <= da, A x pad4(da) <= 2^28. */
+size_t ncx_cosine_gram_workspace_bytes(int32_t A, int32_t da);
+int ncx_cosine_gram(const float* emb, int32_t A, int32_t da, void* ws, size_t ws_bytes, float* gram, void* stream);
+/* ncx_semantic_scores replaces the scorer's double loop (cx.py:182-209) for a batch, in one launch:
+ *   p = softmax(a_knns[b, k, :]);  s = lam (gram[aid_b, :] . p - p[aid_b]) - (1 - lam) log(p[aid_b] + 1e-8)
+ *   scores [B, K] = softmax over k of s (probabilities, as the reference returns);  raw [B, K] = s (nullable).
+ * a_knns [B, K, A] logits; aid [B] int32.  An aid outside [0, A) is never read at: that question's row is NaN and
+ * *bad_id_flag is set to 1 (never cleared here; the caller zeroes it).  Both softmaxes subtract the max (the reference's
+ * do not: NaN there for a logit above ~88.7).  1 <= K <= 64, 1 <= A <= 4096, B >= 1.  Bit-identical from run to run. */
+int ncx_semantic_scores(const float* a_knns, const int32_t* aid, int32_t B, int32_t K, int32_t A, const float* gram,
+                        float lam, float* scores, float* raw, int32_t* bad_id_flag, void* stream);
+
 /* ---- diagnostics (bench.py / tests only; the only process-global state, off by default) --------------
  * GEMM ids: 0 Gt = W1[:,a_other].E^T, 1 Sh (shared segments), 2 MAIN (candidate segments, the dominant
  * forward kernel), 3 hidden layer l>=2 forward, 4 dW1 candidate columns (+dGt; the dominant backward

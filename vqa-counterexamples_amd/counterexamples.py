@@ -49,9 +49,9 @@ def build_parser():
     p.add_argument("--path_opt", default=os.path.join(HERE, "options", "cx", "neuralcx_256_1_all.yaml"), type=str)
     p.add_argument("--vqa_model", default="mutan_noatt_train", type=str)
     # (the reference makes -cx required, counterexamples.py:44; here NeuralModel is the default and the flag spellings are kept)
-    p.add_argument("-cx", "--cx_model", default="NeuralModel", type=str, help="NeuralModel | RandomBaseline | DistanceBaseline | BlackBox")
-    p.add_argument("-lb", "--sb_lambda", type=float, help="semantic baseline lambda (counterexamples.py:49; no NeuralModel code path "
-                                                          "reads it, in the reference either: accepted and ignored with a warning)")
+    p.add_argument("-cx", "--cx_model", default="NeuralModel", type=str, help="NeuralModel | RandomBaseline | DistanceBaseline | BlackBox | SemanticBaseline")
+    p.add_argument("-lb", "--sb_lambda", type=float, help="semantic baseline lambda (counterexamples.py:49): required by -cx SemanticBaseline; "
+                                                          "the other models ignore it (with a warning)")
     p.add_argument("--pairwise", action="store_true")
     p.add_argument("-dev", "--dev_mode", action="store_true", help="small train/val subsets")
     p.add_argument("--pretrained_vqa", dest="pretrained_vqa", action="store_true")
@@ -118,6 +118,7 @@ class Runner:
         self.gb = options["optim"]["batch_size"]
         self.baseline = None if args.cx_model == "NeuralModel" else args.cx_model
         self.runs_dir = None
+        self.sem_gram = self.sem_flag = None
 
     def log(self, *a):
         if self.rank == 0:
@@ -133,6 +134,8 @@ class Runner:
         self.val = SyntheticCX(n_triplets=a.syn_val, n_img=a.syn_images, seed=4321, feats=self.train.feats, **kw)
         self.test = self.val
         self.vqa = None
+        if self.baseline == "SemanticBaseline":
+            self.set_semantic_embedding(synthetic_answer_embedding(self.opt["vqa"]["nans"]))
 
     def load_real(self):
         """counterexamples.py:181-262: pickles, feature tables, VQA model (+ checkpoint), answer embedding -- loaded once
@@ -172,6 +175,12 @@ class Runner:
             else:
                 self.log("Warning: no answer embedding at '{}' (random initialisation)".format(pe))
         self.engine.init_parameters(seed=42, emb=emb)
+        if self.baseline == "SemanticBaseline":
+            # counterexamples.py:244-246: read from the trainset directory whatever pretrained_emb says
+            pe = os.path.join(vqa_dir, "answer_embedding.pickle")
+            if not os.path.isfile(pe):
+                raise SystemExit("-cx SemanticBaseline needs the answer embedding: {} is missing".format(pe))
+            self.set_semantic_embedding(formats.load_answer_embedding(pe, n_answers=len(trainset["vocab_answers"])))
         if not a.no_vqa_cache:                      # frozen VQA model: its outputs are per-example constants
             seen = set()
             for name, ds in (("train", self.train), ("val", self.val), ("test", self.test)):
@@ -180,6 +189,11 @@ class Runner:
                 seen.add(id(ds))
                 nbytes = ds.cache_vqa_outputs(lambda img_idx, wids, ds=ds: self._vqa_outputs(ds, img_idx, wids))
                 self.log("=> cached VQA outputs of the {} split: {} examples, {:.2f} GB".format(name, ds.N, nbytes / 1e9))
+
+    def set_semantic_embedding(self, emb):
+        """SemanticBaseline.set_answer_embedding (cx.py:173-175): the cosine Gram, built once on the device."""
+        self.sem_gram = ops.cosine_gram(torch.from_numpy(np.ascontiguousarray(emb, dtype=np.float32)).to(self.dev))
+        self.sem_flag = torch.zeros(1, dtype=torch.int32, device=self.dev)
 
     def _vqa_outputs(self, data, img_idx, wids):
         """q_emb, z_orig, z_knns, a_knns of the frozen VQA model for a block of examples (vqa_forward, cx.py:64-104)."""
@@ -249,6 +263,10 @@ class Runner:
             scores = torch.rand(B, K, device=self.dev)
         elif self.baseline == "DistanceBaseline":
             scores = torch.arange(K - 1, -1, -1, dtype=torch.float32, device=self.dev).repeat(B, 1)
+        elif self.baseline == "SemanticBaseline":
+            # cx.py:182-209; its probabilities go to the loss / Recall kernel as the reference's eval_model feeds them to
+            # CrossEntropyLoss and recallAtK (:464-466).  A bad answer id is reported after the loop (main), not per batch.
+            scores = ops.semantic_scores(b.a_knns, b.answer_aids, self.sem_gram, self.args.sb_lambda, bad_flag=self.sem_flag)
         else:
             scores = blackbox_scores(b.a_knns, b.answer_aids).contiguous()
         r = ops.ranking_loss(scores, gt, want_grad=False)
@@ -305,13 +323,21 @@ class Runner:
         return info, len(info) + 1, last.get("recall_5", last.get("recall"))     # the reference KeyErrors here (:580)
 
 
+def synthetic_answer_embedding(n_answers, dim_a=2400, seed=2400):
+    """--synthetic stand-in for answer_embedding.pickle: N(0, 1) rows [n_answers, dim_a], numpy default_rng(2400)."""
+    return np.random.default_rng(seed).standard_normal((n_answers, dim_a), dtype=np.float32)
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     options = load_options(args)
-    if args.cx_model not in ("NeuralModel", "RandomBaseline", "DistanceBaseline", "BlackBox"):
-        raise SystemExit("--cx_model {}: only NeuralModel and the RandomBaseline / DistanceBaseline / BlackBox scorers are "
-                         "provided (the reference's other models are outside the accelerated path)".format(args.cx_model))
-    if args.sb_lambda is not None:
+    if args.cx_model not in ("NeuralModel", "RandomBaseline", "DistanceBaseline", "BlackBox", "SemanticBaseline"):
+        raise SystemExit("--cx_model {}: only NeuralModel and the RandomBaseline / DistanceBaseline / BlackBox / SemanticBaseline "
+                         "scorers are provided (the reference's other models are outside the accelerated path)".format(args.cx_model))
+    if args.cx_model == "SemanticBaseline":
+        if args.sb_lambda is None:                                         # counterexamples.py:240-242
+            raise ValueError("If semantic baseline is selected then --sb_lambda must also be provided.")
+    elif args.sb_lambda is not None:
         print("warning: -lb/--sb_lambda {} is accepted for command-line compatibility and ignored (no {} code path reads it)".format(
             args.sb_lambda, args.cx_model), file=sys.stderr)
     if args.pairwise or args.viz:
@@ -331,6 +357,8 @@ def main(argv=None):
         t0 = time.time()
         res = r.evaluate(r.test if args.test else r.val)
         torch.cuda.synchronize()
+        if r.sem_flag is not None:
+            ops.check_semantic_ids(r.sem_flag)
         n = (r.test if args.test else r.val).N
         r.report("test" if args.test else "val", 1, res)
         r.log("{}: {} triplets in {:.2f} s ({:.0f} triplets/s)".format(r.baseline, n, time.time() - t0, n / (time.time() - t0)))

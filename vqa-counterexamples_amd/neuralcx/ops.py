@@ -6,6 +6,7 @@ hot path runs in libneuralcx_hip.so.  Reference surface these mirror:
   neuralcx_forward / NeuralCXFunction   vqa/models/cx.py:279-333 (NeuralModel.forward below vqa_forward)
   ranking_loss                           counterexamples.py:310,334 + recallAtK (counterexamples.py:501-506)
   adam_step                              torch.optim.Adam as used at counterexamples.py:275-276,339
+  cosine_gram / semantic_scores          SemanticBaseline.set_answer_embedding / forward (vqa/models/cx.py:174-175,182-209)
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -293,6 +294,75 @@ def vqa_forward(feats: torch.Tensor, img_idx: torch.Tensor, q_emb: torch.Tensor,
                                           C.c_void_p(z_k.data_ptr()), C.c_void_p(a_k.data_ptr()),
                                           C.c_void_p(a_o.data_ptr()) if a_o is not None else None, _stream()), "ncx_vqa_forward")
     return a_o, z_o, a_k, z_k
+
+
+def cosine_gram(emb: torch.Tensor) -> torch.Tensor:
+    """sklearn cosine_similarity(emb) on the device (ncx_cosine_gram; reference cx.py:174-175): [A, da] fp32 -> [A, A] fp32.
+    A zero row stays zero (its similarities are 0, the diagonal included), as sklearn's normalisation leaves it."""
+    if emb.dim() != 2:
+        raise ValueError("cosine_gram takes a 2-d [A, da] embedding, got %s" % (tuple(emb.shape),))
+    emb = emb.contiguous()
+    A, da = emb.shape
+    need = _lib.lib().ncx_cosine_gram_workspace_bytes(A, da)
+    if need == 0:
+        raise _lib.NcxError("ncx_cosine_gram_workspace_bytes: unsupported shape %s" % (tuple(emb.shape),))
+    ws = torch.empty(need + 256, dtype=torch.uint8, device=emb.device)
+    gram = torch.empty(A, A, dtype=torch.float32, device=emb.device)
+    p, n = _ws_ptr(ws)
+    _lib.check(_lib.lib().ncx_cosine_gram(_ptr(emb, torch.float32, "emb"), A, da, p, n, C.c_void_p(gram.data_ptr()), _stream()),
+               "ncx_cosine_gram")
+    return gram
+
+
+_SEM_FLAGS: Dict[torch.device, torch.Tensor] = {}
+
+
+def semantic_bad_flag(device) -> torch.Tensor:
+    """The per-device int32 flag ncx_semantic_scores sets on an answer id outside [0, A) (sticky until checked)."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    f = _SEM_FLAGS.get(device)
+    if f is None:
+        f = _SEM_FLAGS[device] = torch.zeros(1, dtype=torch.int32, device=device)
+    return f
+
+
+def semantic_scores(a_knns: torch.Tensor, aids: torch.Tensor, gram: torch.Tensor, lam: float, want_raw: bool = False,
+                    bad_flag: Optional[torch.Tensor] = None):
+    """The semantic baseline scorer (ncx_semantic_scores; reference cx.py:182-209) on the current stream, no host sync:
+    a_knns [B, K, A] logits, aids [B] answer ids, gram [A, A] (cosine_gram) -> scores [B, K] (softmax over k: probabilities,
+    as the reference returns), and with want_raw the pre-softmax s [B, K] as well: (scores, raw).
+    An id outside [0, A) leaves NaN in its row and sets `bad_flag` (default: semantic_bad_flag(device)); the IndexError is
+    raised by check_semantic_ids -- deferred, so that an evaluation loop pays one host sync at its end, not one per batch."""
+    if a_knns.dim() != 3:
+        raise ValueError("a_knns must be [B, K, A], got %s" % (tuple(a_knns.shape),))
+    B, K, A = a_knns.shape
+    if tuple(aids.shape) != (B,):
+        raise ValueError("aids must be [%d], got %s" % (B, tuple(aids.shape)))
+    if tuple(gram.shape) != (A, A):
+        raise ValueError("gram must be [%d, %d] (the logits' width), got %s" % (A, A, tuple(gram.shape)))
+    a_knns, gram = a_knns.float().contiguous(), gram.contiguous()
+    aids = aids.to(torch.int32).contiguous()
+    if bad_flag is None:
+        bad_flag = semantic_bad_flag(a_knns.device)
+    scores = torch.empty(B, K, dtype=torch.float32, device=a_knns.device)
+    raw = torch.empty(B, K, dtype=torch.float32, device=a_knns.device) if want_raw else None
+    _lib.check(_lib.lib().ncx_semantic_scores(_ptr(a_knns, torch.float32, "a_knns"), _ptr(aids, torch.int32, "aids"), B, K, A,
+                                              _ptr(gram, torch.float32, "gram"), float(lam), C.c_void_p(scores.data_ptr()),
+                                              _ptr(raw, torch.float32, "raw"), _ptr(bad_flag, torch.int32, "bad_flag"), _stream()),
+               "ncx_semantic_scores")
+    return (scores, raw) if want_raw else scores
+
+
+def check_semantic_ids(bad_flag: Optional[torch.Tensor] = None, device=None) -> None:
+    """Raises IndexError (what the reference's numpy indexing emb_pairs[aid, :] raises, cx.py:194) if a semantic_scores call
+    since the last check saw an answer id outside [0, A); clears the flag.  Synchronises with the flag's stream."""
+    if bad_flag is None:
+        bad_flag = semantic_bad_flag(device if device is not None else "cuda")
+    if int(bad_flag.item()):
+        bad_flag.zero_()
+        raise IndexError("answer_aids outside [0, A) in a semantic_scores call")
 
 
 class WorkspacePool:

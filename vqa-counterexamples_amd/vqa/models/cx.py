@@ -7,7 +7,8 @@ the state_dict keys (`answer_embedding.weight`, `linear_1.*`, `linear_2.*`, `lin
 code are interchangeable.  Everything below `vqa_forward` -- the answer-embedding products, the 24-way feature
 synthesis/concat, the Linear+ReLU+Dropout stack, `out`, and the whole backward -- runs in the HIP library
 (libneuralcx_hip.so) through `neuralcx.ops.NeuralCXFunction`.  There is no PyTorch fallback for that part:
-on a machine without the library or without a GPU `forward` raises.
+on a machine without the library or without a GPU `forward` raises.  `SemanticBaseline` (cx.py:159-210) keeps the
+reference's surface likewise; its cosine Gram and scorer run in the same library (see its docstring).
 
 Deliberate differences from the reference (all supersets):
   * knn_size may be 1..64 (the reference asserts == 24, cx.py:226); config 5 of BASELINE.json uses 48;
@@ -20,6 +21,7 @@ Deliberate differences from the reference (all supersets):
     `state_dict()` (every checkpoint save), or `check_answer_ids()`.  `strict_ids=True` (constructor keyword or attribute)
     restores the immediate raise at the price of one host sync per forward; on a CPU device the check is always immediate.
 """
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -78,13 +80,7 @@ class CXModelBase(nn.Module):
         vqa.eval()
         q_emb = vqa.seq2vec(question_wids)
         if self._hip_vqa_ok(image_features):
-            mw = self.__dict__.get("_mutan_weights")
-            if mw is None or mw.t["wv"].device != image_features.device:
-                mw = ops.MutanWeights(vqa)
-                self.__dict__["_mutan_weights"] = mw
-            feats = image_features.reshape(B * K1, -1).float().contiguous()
-            idx = torch.arange(B * K1, device=feats.device, dtype=torch.int32).view(B, K1)
-            a_o, z_o, a_k, z_k = ops.vqa_forward(feats, idx, q_emb.float().contiguous(), mw, want_a_orig=True)
+            a_o, z_o, a_k, z_k = self._hip_vqa_forward(image_features, q_emb, want_a_orig=True)
             return a_o, z_o, a_k, z_k, q_emb
         v = image_features.reshape(B * K1, -1)
         q_dup = q_emb.view(B, 1, -1).expand(B, K1, q_emb.size(-1)).reshape(B * K1, -1)
@@ -92,6 +88,17 @@ class CXModelBase(nn.Module):
         a = vqa._classif(z)
         a, z = a.view(B, K1, -1), z.view(B, K1, -1)
         return (a[:, 0].contiguous(), z[:, 0].contiguous(), a[:, 1:].contiguous(), z[:, 1:].contiguous(), q_emb)
+
+    def _hip_vqa_forward(self, image_features, q_emb, want_a_orig):
+        """ncx_vqa_forward on the MUTAN weights of this module (stacked once per device)."""
+        B, K1 = image_features.size(0), self.knn_size + 1
+        mw = self.__dict__.get("_mutan_weights")
+        if mw is None or mw.t["wv"].device != image_features.device:
+            mw = ops.MutanWeights(self.vqa_model)
+            self.__dict__["_mutan_weights"] = mw
+        feats = image_features.reshape(B * K1, -1).float().contiguous()
+        idx = torch.arange(B * K1, device=feats.device, dtype=torch.int32).view(B, K1)
+        return ops.vqa_forward(feats, idx, q_emb.float().contiguous(), mw, want_a_orig=want_a_orig)
 
     def refresh_vqa_weights(self):
         """Call after loading a VQA checkpoint: the stacked MUTAN weights of the HIP path are cached."""
@@ -118,6 +125,91 @@ class BlackBox(CXModelBase):
     def forward(self, image_features, question_wids, answer_aids):
         _, _, a_knns, _, _ = self.vqa_forward(image_features, question_wids)
         return blackbox_scores(a_knns, answer_aids)
+
+
+class SemanticBaseline(CXModelBase):
+    """Scores candidates by how far the VQA model's answer distribution moves away from the original answer, in an answer
+    embedding space (reference cx.py:159-210; README row 'Semantic Baseline'):
+        p = softmax(a_knns[b, k]);  s_k = lam (emb_pairs[aid] . p - p[aid]) - (1 - lam) log(p[aid] + 1e-8);  softmax_k(s)
+    with emb_pairs the cosine Gram of the answer embedding.  The Gram is built on the device (ops.cosine_gram, once per
+    embedding and device) and the scorer is one HIP launch per batch (ops.semantic_scores); a_knns come from the HIP MUTAN
+    path.  There is no CPU fallback: on a CPU device `forward` raises.
+
+    Kept from the reference: the constructor, `set_lambda`, `set_answer_embedding` (numpy array or tensor), `lam` (0.5 by
+    default), the mutable `knn_size`, a `softmax` helper, the readable `emb_pairs` ([2000, 2000] zeros before an embedding is
+    set), forward returning fp32 [B, K] probabilities with requires_grad=True (nothing trains), and state_dict keys
+    (`vqa_model.*` only).  Deliberate differences (supersets):
+      * both softmaxes subtract the max: equal wherever the reference is finite, finite for logits above ~88.7 (NaN there);
+      * before set_answer_embedding the Gram is zeros of the logits' width (the reference's is [2000, 2000] whatever A is);
+      * an answer id outside [0, A) raises IndexError (numpy wraps a negative one in the reference);
+      * `emb_pairs` is a host copy of the device Gram, computed on first access (the reference computes it eagerly) and
+        cached outside the module's state; the constructor does not print the VQA options.
+    """
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.dim_z = self.vqa_model.opt["fusion"]["dim_mm"]
+        self.emb = None
+        self.lam = 0.5                     # cx.py:171 (default)
+        self.__dict__["_grams"] = {}       # device -> device Gram of self.emb (not module state: checkpoints stay vqa_model.*)
+
+    def set_lambda(self, lam):
+        self.lam = lam
+
+    def set_answer_embedding(self, emb):
+        if isinstance(emb, torch.Tensor):
+            emb = emb.detach()
+        else:
+            emb = np.asarray(emb)
+        if emb.ndim != 2:
+            raise ValueError("answer embedding must be [A, da], got %s" % (tuple(emb.shape),))
+        self.emb = emb
+        self.__dict__["_grams"] = {}
+
+    @staticmethod
+    def softmax(w):
+        e = np.exp(np.asarray(w) - np.max(w))
+        return e / np.sum(e)
+
+    def _gram(self, device, A):
+        grams = self.__dict__["_grams"]
+        g = grams.get((device, A))
+        if g is None:
+            if self.emb is None:
+                g = torch.zeros(A, A, dtype=torch.float32, device=device)
+            else:
+                if self.emb.shape[0] != A:
+                    raise ValueError("answer embedding has %d rows, the VQA model scores %d answers" % (self.emb.shape[0], A))
+                g = ops.cosine_gram(torch.as_tensor(self.emb).to(device=device, dtype=torch.float32))
+            grams[(device, A)] = g
+        return g
+
+    @property
+    def emb_pairs(self):
+        if self.emb is None:
+            return np.zeros((2000, 2000), np.float32)             # cx.py:168
+        if not torch.cuda.is_available():
+            raise ops._lib.NcxError("SemanticBaseline.emb_pairs is computed on the GPU (no CPU fallback)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        return self._gram(dev, self.emb.shape[0]).cpu().numpy()
+
+    def forward(self, image_features, question_wids, answer_aids):
+        if not image_features.is_cuda:
+            raise ops._lib.NcxError("SemanticBaseline runs on the GPU: move the inputs and the model there (no CPU fallback)")
+        assert image_features.size(1) == self.knn_size + 1
+        if self._hip_vqa_ok(image_features):
+            with torch.no_grad():
+                self.vqa_model.eval()
+                q_emb = self.vqa_model.seq2vec(question_wids)
+                _, _, a_knns, _ = self._hip_vqa_forward(image_features, q_emb, want_a_orig=False)
+        else:
+            _, _, a_knns, _, _ = self.vqa_forward(image_features, question_wids)
+        a_knns = a_knns.float().contiguous()
+        flag = torch.zeros(1, dtype=torch.int32, device=a_knns.device)
+        scores = ops.semantic_scores(a_knns, answer_aids.to(a_knns.device), self._gram(a_knns.device, a_knns.size(2)),
+                                     float(self.lam), bad_flag=flag)
+        ops.check_semantic_ids(flag)            # (the reference reads its scores back to the host per batch as well)
+        return scores.requires_grad_(True)      # cx.py:209
 
 
 class NeuralModel(CXModelBase):
