@@ -314,6 +314,14 @@ int ncx_semantic_scores(const float* a_knns, const int32_t* aid, int32_t B, int3
 #define NCX_GEMM_DAGT 8
 #define NCX_GEMM_DWL 9
 #define NCX_GEMM_DXL 10
+/* Not a GEMM id: ncx_plan_query(d, NCX_QUERY_DW1_ROUTE, out6) reports the routes of linear_1's weight gradient for a whole backward.
+ * out6 = {v columns: 0 none (bf16 variant: in its bf16 candidate product), 1 k_dw_km8, 2 k_dw_km_x6, 3 k_dw_km (per-triplet fold
+ *         kernels), 4 the grouped generic GEMM;
+ *         dGt + every other column block (bf16 variant: its fp32 shared segments): 0 grouped generic GEMM, 1 k_dw_tn8, 2 k_dw_tn8_x6;
+ *         pieces per workgroup of that TN launch's plan and its grid (reported even when the route is rejected; 0 / 0 where the
+ *         kernel's shape rules exclude it); dW1[:, a_other] on the TN kernel (1) or the chain GEMM (0); the piece limit (out6[2] above
+ *         it: grouped)} */
+#define NCX_QUERY_DW1_ROUTE 32
 int ncx_profile_begin(uint32_t gemm_mask /* bit i = gemm id i */, int32_t max_launches);
 int ncx_profile_end(float* ms, int32_t* ids, int32_t cap);
 /* In-kernel clock diagnostics of the MAIN launch (the fused forward kernel of linear_1): while `stamps` is non-NULL

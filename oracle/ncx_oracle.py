@@ -131,7 +131,8 @@ def forward_faithful(params: Dict[str, torch.Tensor], d: Dims,
     supplied by the caller as ordinary inputs (``a_knns`` then holds the [B,K,da] noise block,
     ``a_emb_gt_override`` the [B,da] one, ``v_rank_override`` [B,K,K] the per-candidate rank
     noise); zero-lesions (v_mult, v_dist) are handled here.
-    ``taps`` (tests only): receives ``pre1`` [B,K,H], the pre-activations of linear_1, and ``dist`` [B,K].
+    ``taps`` (tests only): receives ``pre<l>`` [B,K,H], the pre-activations of hidden layer ``l`` (``pre1``: linear_1), and
+    ``dist`` [B,K].
     """
     spec = dict(DEFAULT_SPEC, **(spec or {}))
     B = image_features.shape[0]
@@ -169,16 +170,18 @@ def forward_faithful(params: Dict[str, torch.Tensor], d: Dims,
         h = x
         for l in range(1, d.L + 1):                                 # cx.py:322-326
             pre = F.linear(h, params[f"linear_{l}.weight"], params[f"linear_{l}.bias"])
-            if taps is not None and l == 1:
-                taps.setdefault("pre1", []).append(pre.detach())
-                taps.setdefault("dist", []).append(v_dist.detach()[:, 0])
+            if taps is not None:
+                taps.setdefault("pre%d" % l, []).append(pre.detach())
+                if l == 1:
+                    taps.setdefault("dist", []).append(v_dist.detach()[:, 0])
             h = F.relu(pre)
             if keep_masks is not None:
                 m = keep_masks[l - 1].view(B, d.K, d.H)[:, i]
                 h = h * m / (1.0 - drop_p)
         scores.append(F.linear(h, params["out.weight"], params["out.bias"]))   # cx.py:327
     if taps is not None:
-        taps["pre1"] = torch.stack(taps["pre1"], dim=1)
+        for l in range(1, d.L + 1):
+            taps["pre%d" % l] = torch.stack(taps["pre%d" % l], dim=1)
         taps["dist"] = torch.stack(taps["dist"], dim=1)
     return torch.cat(scores, dim=1)                                 # cx.py:331
 
@@ -270,7 +273,10 @@ def forward_bf16(params: Dict[str, torch.Tensor], d: Dims, image_features, q_emb
     if keep_masks is not None:
         h = h * keep_masks[0].view(B * K, d.H) / (1.0 - drop_p)
     for l in range(2, d.L + 1):
-        h = F.relu(F.linear(h, params[f"linear_{l}.weight"], params[f"linear_{l}.bias"]))
+        pre = F.linear(h, params[f"linear_{l}.weight"], params[f"linear_{l}.bias"])
+        if taps is not None:
+            taps["pre%d" % l] = pre.detach().view(B, K, d.H)
+        h = F.relu(pre)
         if keep_masks is not None:
             h = h * keep_masks[l - 1].view(B * K, d.H) / (1.0 - drop_p)
     return F.linear(h, params["out.weight"], params["out.bias"]).view(B, K)

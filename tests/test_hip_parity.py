@@ -8,48 +8,10 @@ import pytest
 import torch
 
 from oracle import ncx_oracle as orc
-from helpers import GOLDEN, check_grads_against_golden, grad_tol, golden_names, load_golden
+from helpers import (GOLDEN, FIELD, check_grads_against_golden, check_phased_backward_bit_identical, compare_with_oracle, dev,
+                     full_size_case, golden_names, grad_tol, load_golden, random_case, run_hip, to_dev_batch, to_dev_params)
 
 pytestmark = pytest.mark.gpu
-
-FIELD = {"answer_embedding.weight": "answer_embedding", "linear_1.weight": "w1", "linear_1.bias": "b1",
-         "linear_2.weight": "w2", "linear_2.bias": "b2", "linear_3.weight": "w3", "linear_3.bias": "b3",
-         "out.weight": "w_out", "out.bias": "b_out"}
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def to_dev_params(params):
-    return {FIELD[k]: v.to(dev()).contiguous() for k, v in params.items()}
-
-
-def to_dev_batch(batch, spec=None, keep_mask=None, extra=None):
-    from neuralcx.ops import Batch
-    extra = extra or {}
-    g = lambda k: batch[k].to(dev())
-    return Batch.from_dense(g("image_features"), g("q_emb"), g("z_orig"), g("z_knns"), g("a_knns"),
-                            g("answer_aids"), keep_mask=None if keep_mask is None else keep_mask.to(dev()),
-                            **{k: v.to(dev()) for k, v in extra.items()})
-
-
-def run_hip(d, spec, params, batch, training=False, drop_p=0.0, keep_mask=None, seed=0, extra=None):
-    from neuralcx import ops
-    b = to_dev_batch(batch, spec, keep_mask, extra)
-    p = to_dev_params(params)
-    dims = ops.make_dims(b, H=d.H, L=d.L, da=d.da, A=d.A, flags=ops.flags_from_spec(spec), training=training,
-                         drop_p=drop_p, seed=seed)
-    ws = ops.alloc_workspace(dims, dev())
-    scores = ops.forward(dims, b, p, ws)
-    gt = batch["gt"].to(dev()).to(torch.int32)
-    lr = ops.ranking_loss(scores, gt)
-    grads = {k: torch.full_like(v, float("nan")) for k, v in p.items()}
-    ops.backward(dims, b, p, ws, lr["dscores"], grads)
-    torch.cuda.synchronize()
-    inv = {v: k for k, v in FIELD.items()}
-    return (scores.cpu(), lr, {inv[k]: v.cpu().numpy() for k, v in grads.items()})
-
 
 @pytest.mark.parametrize("name", golden_names())
 def test_golden_forward_loss_recall_backward(name):
@@ -65,37 +27,6 @@ def test_golden_forward_loss_recall_backward(name):
     for n, v in grads.items():
         assert np.isfinite(v).all(), n
     check_grads_against_golden(g, grads, rel=1e-4)
-
-
-def random_case(seed, B, d, scale=0.45):
-    rng = np.random.default_rng(seed)
-    t = lambda a: torch.from_numpy(a.astype(np.float32))
-    batch = dict(image_features=t(np.abs(rng.standard_normal((B, d.K + 1, d.dv))) * scale),
-                 q_emb=t(rng.standard_normal((B, d.dq)) * 0.3), z_orig=t(rng.standard_normal((B, d.dz))),
-                 z_knns=t(rng.standard_normal((B, d.K, d.dz))), a_knns=t(rng.standard_normal((B, d.K, d.A)) * 2),
-                 answer_aids=torch.from_numpy(rng.integers(0, d.A, size=B)), gt=torch.from_numpy(rng.integers(0, d.K, size=B)))
-    return batch
-
-
-def compare_with_oracle(d, spec, params, batch, training=False, drop_p=0.0, masks=None, seed=0, extra=None, use_rng=False):
-    keep = None if masks is None or use_rng else torch.stack(masks)
-    scores, lr, grads = run_hip(d, spec, params, batch, training=training, drop_p=drop_p, keep_mask=keep, seed=seed, extra=extra)
-    ob = dict(batch)
-    if extra:
-        ob.update(extra)
-    s_ref, l_ref, g_ref = orc.loss_and_grads(params, d, ob, spec=spec, drop_p=drop_p, keep_masks=masks)
-    assert np.abs(scores.numpy() - s_ref.numpy()).max() <= 1e-4
-    assert abs(float(lr["loss"].cpu()) - float(l_ref)) <= 1e-5
-    sr, gtn = s_ref.numpy(), batch["gt"].numpy()
-    gap = np.abs(sr - sr[np.arange(len(gtn)), gtn][:, None]); gap[np.arange(len(gtn)), gtn] = np.inf
-    safe = gap.min(1) > 2e-4                                  # rows without a near-tie around the ground truth
-    assert (lr["rank"].cpu().numpy()[safe] == orc.rank_of_gt(sr, gtn)[safe]).all()
-    for k, ref in g_ref.items():
-        ref = ref.numpy()
-        tol = grad_tol(k, ref, 1e-4)
-        err = np.abs(grads[k].reshape(ref.shape) - ref).max()
-        assert err <= tol, (k, err, tol)
-    return scores, lr, grads
 
 
 @pytest.mark.parametrize("B,K,H,L", [(1, 24, 16, 1), (7, 24, 20, 2), (13, 24, 48, 3), (5, 48, 32, 1), (33, 24, 96, 2)])
@@ -325,16 +256,6 @@ def test_full_dims_property_checks():
     assert torch.equal(ops.forward(dims, b, p, ws), s1)
 
 
-def _full_size_case(d, B, seed, bf16=False):
-    from helpers import condition_away_from_kinks, random_case_f32
-    params = orc.init_params(d, seed=42)
-    batch = random_case_f32(seed, B, d)
-    batch["answer_aids"][1] = batch["answer_aids"][0]            # a duplicated answer id (owner-computes scatter)
-    redrawn = condition_away_from_kinks(params, d, batch, seed, bf16=bf16)
-    assert redrawn < 4 * B
-    return params, batch
-
-
 def test_configs1_full_size_every_logit_and_gradient_vs_oracle():
     """BASELINE configs[1] at its stated size (B = 512, K = 24, dv = 2048, H = 256, L = 1: the real launch plan with every
     tile shape, k-split and the fused v-column kernel): ALL 12 288 logits, the loss, the ranks and EVERY gradient element
@@ -342,7 +263,7 @@ def test_configs1_full_size_every_logit_and_gradient_vs_oracle():
     logits <= 1e-4, loss <= 1e-5, gradients <= 1e-4 of the tensor's max with no floor (out.bias excepted: zero in
     maths).  Inputs are conditioned away from the ReLU kinks (helpers.condition_away_from_kinks)."""
     d = orc.Dims()
-    params, batch = _full_size_case(d, 512, 2024)
+    params, batch = full_size_case(d, 512, 2024)
     compare_with_oracle(d, None, params, batch)
 
 
@@ -409,7 +330,7 @@ def test_ragged_full_width_batch_vs_oracle():
     forward fold's ragged last tile), an odd number of triplets for the weight-gradient chunks, a batch the wave-per-triplet tail
     kernels do not divide evenly.  Every logit and every gradient against the oracle, same bounds as the configs[1] test."""
     d = orc.Dims()
-    params, batch = _full_size_case(d, 389, 777)
+    params, batch = full_size_case(d, 389, 777)
     compare_with_oracle(d, None, params, batch)
 
 
@@ -420,7 +341,7 @@ def test_configs4_shape_fp32_and_bf16_vs_oracles():
     <= 1e-3 of the tensor's max, no floor)."""
     d = orc.Dims(K=48)
     B = 1024
-    params, batch = _full_size_case(d, B, 4048)
+    params, batch = full_size_case(d, B, 4048)
     compare_with_oracle(d, None, params, batch)
     # bf16 variant: its own conditioning (bf16 pre-activations / the distance column near a bf16 rounding boundary)
     from helpers import condition_away_from_kinks
@@ -541,51 +462,13 @@ def test_phased_forward_is_bit_identical(shape):
 
 def test_phased_backward_is_bit_identical():
     """ncx_backward_phase 1 then 2, and 3 then 4, == ncx_backward (what the data-parallel engine relies on)."""
-    from neuralcx import ops
     # (H = 64, B = 20: the generic engine's grouped launch; H = 256, B = 128 / 160: the balanced 8-wave TN launch, whose aligned dGt part and
     #  rest sequence are launched separately by phases 5 | 2 and together by phase 0 -- same chunking, same slab slots, same sums)
     for L, H, B in ((1, 64, 20), (2, 64, 20), (1, 256, 128), (2, 256, 160)):
         d = orc.Dims(dv=96, dq=64, dz=24, A=40, H=H, L=L)
         params = orc.init_params(d, seed=9, gain=3.0)
         batch = random_case(31, B, d)
-        b = to_dev_batch(batch)
-        p = to_dev_params(params)
-        dims = ops.make_dims(b, H=d.H, L=d.L, da=d.da, A=d.A)
-        ws = ops.alloc_workspace(dims, dev())
-        scores = ops.forward(dims, b, p, ws)
-        lr = ops.ranking_loss(scores, batch["gt"].to(dev()).to(torch.int32))
-        g0 = {k: torch.full_like(v, float("nan")) for k, v in p.items()}
-        ops.backward(dims, b, p, ws, lr["dscores"], g0)
-        g12 = {k: torch.full_like(v, float("nan")) for k, v in p.items()}
-        ops.backward(dims, b, p, ws, lr["dscores"], g12, phase=1)
-        assert torch.isfinite(g12["answer_embedding"]).all() and torch.equal(g12["answer_embedding"], g0["answer_embedding"])
-        ops.backward(dims, b, p, ws, lr["dscores"], g12, phase=2)
-        for k in g0:
-            assert torch.equal(g0[k], g12[k]), k
-        # the other cut (3 | 4): everything but the embedding gradient, then the embedding gradient from dGt | dGgt;
-        # scaling that workspace block by 2 in between doubles the embedding gradient exactly (linearity: what DP sums)
-        g34 = {k: torch.full_like(v, float("nan")) for k, v in p.items()}
-        ops.backward(dims, b, p, ws, lr["dscores"], g34, phase=3)
-        for k in g0:
-            if k != "answer_embedding":
-                assert torch.equal(g0[k], g34[k]), k
-        blk = ops.ws_dgt_view(dims, ws)
-        assert blk.numel() == 2 * d.H * d.A
-        ops.backward(dims, b, p, ws, lr["dscores"], g34, phase=4)
-        assert torch.equal(g0["answer_embedding"], g34["answer_embedding"])
-        blk.mul_(2.0)
-        ops.backward(dims, b, p, ws, lr["dscores"], g34, phase=4)
-        assert torch.equal(2.0 * g0["answer_embedding"], g34["answer_embedding"])
-        # the three-way cut the DP engine uses (5 | 2 | 4): the block first, then linear_1.weight, then the embedding gradient
-        g524 = {k: torch.full_like(v, float("nan")) for k, v in p.items()}
-        ops.backward(dims, b, p, ws, lr["dscores"], g524, phase=5)
-        assert torch.isnan(g524["answer_embedding"]).all() and torch.isnan(g524["w1"]).all()
-        blk5 = ops.ws_dgt_view(dims, ws).clone()
-        ops.backward(dims, b, p, ws, lr["dscores"], g524, phase=2)
-        assert torch.equal(blk5, ops.ws_dgt_view(dims, ws))          # phase 2 leaves the exchanged block alone
-        ops.backward(dims, b, p, ws, lr["dscores"], g524, phase=4)
-        for k in g0:
-            assert torch.equal(g0[k], g524[k]), k
+        check_phased_backward_bit_identical(d, params, batch)
 
 
 def test_c_abi_rccl_handle_allreduce_on_one_rank():
@@ -713,7 +596,7 @@ def test_x6_runs_and_agrees_with_the_fp32_kernels_to_rounding(monkeypatch):
     against the oracle is 1e-4 of the max)."""
     from neuralcx import _lib, ops
     d = orc.Dims()
-    params, batch = _full_size_case(d, 512, 77)
+    params, batch = full_size_case(d, 512, 77)
     monkeypatch.setattr(ops, "EXTRA_FLAGS", 0)                       # (the suite may itself be running under NCX_X6=1)
     _, _, g32 = run_hip(d, None, params, batch)
     monkeypatch.setattr(ops, "EXTRA_FLAGS", _lib.NCX_F_X6)

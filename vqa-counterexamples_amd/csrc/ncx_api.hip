@@ -877,7 +877,7 @@ static void list_uses(const ncx_dims& d, GemmUse* u) {
         const bool km = dw_km_supported(d) && !(d.flags & NCX_F_BF16);     // v_other / v_mult columns: ncx_dwkm.hip
         const bool tn8 = dw_tn8_supported(d);                               // every other column block + dGt: ncx_dwtn.hip
         const long long segs_c[5] = {km ? 0 : d.dv, (!km && (d.flags & NCX_F_V_MULT)) ? d.dv : 0, tn8 ? 0 : d.K + 1, tn8 ? 0 : d.dz, tn8 ? 0 : (aemb ? d.A : d.da)};
-        const bool tn8s = tn8 || dw_tn8_shapes_ok(d);                       // (the bf16 variant: its fp32 shared segments take the TN kernel too)
+        const bool tn8s = dw_tn8_shared_ok(d);                              // (the bf16 variant: its fp32 shared segments take the TN kernel too)
         const long long segs_s[5] = {tn8s ? 0 : d.dv, tn8s ? 0 : d.dq, tn8s ? 0 : d.dz, tn8s ? 0 : d.da, 0};
         const bool grouped = i == U_DW1C || i == U_DW1S;
         auto grouped_tiles = [&](int bm, int bn) {
@@ -934,7 +934,7 @@ static void list_uses(const ncx_dims& d, GemmUse* u) {
     u[U_DW1S].plan.cfg = u[U_DW1C].plan.cfg;
     {
         int bm, bn; cfg_tile(u[U_DW1C].plan.cfg, bm, bn);
-        const bool tn8 = dw_tn8_shapes_ok(d);
+        const bool tn8 = dw_tn8_shared_ok(d);
         const long long segs_s[4] = {tn8 ? 0 : d.dv, tn8 ? 0 : d.dq, tn8 ? 0 : d.dz, tn8 ? 0 : d.da};
         const int S = u[U_DW1S].plan.split > 1 ? u[U_DW1S].plan.split : 1;
         u[U_DW1S].tiles = 0; u[U_DW1S].wgs = 0;
@@ -1031,6 +1031,12 @@ static SideStream* side_stream() {
         else (void)hipGetLastError();
     }
     return t.state == 1 ? &t : nullptr;
+}
+
+// backward_impl's choices for a whole backward (phases 0 / 1 + 2): the per-triplet fold kernel waits for the side stream's chain
+// (opt-in: NCX_SIDE_STREAM)
+static bool km_defers_to_side_stream(const ncx_dims& d) {
+    return dw_km_supported(d) && !(d.flags & NCX_F_BF16) && (d.flags & NCX_F_A_EMB) && side_stream() != nullptr && side_stream()->mode != 2;
 }
 // fork: the side stream waits for everything enqueued on `main` so far
 static int side_fork(SideStream* ss, hipStream_t main) {
@@ -1411,6 +1417,8 @@ int ncx_loss_rank(const float* scores, const int32_t* gt, int32_t B, int32_t K, 
 static inline bool emb_nt_form(const ncx_dims& d) {
     return (d.flags & NCX_F_A_EMB) && !(d.flags & NCX_F_BF16) && !ncx::hook_env("NCX_NO_EMB_NT");
 }
+// dW1[:, a_other] = dGt . E on the balanced TN kernel (not with the side stream: the kernel's slab is the main stream's)
+static inline bool dw1ak_on_tn8(const ncx_dims& d, bool side) { return ncx::dw_tn8_supported(d) && emb_nt_form(d) && !side; }
 extern "C" {
 int ncx_train_tail(const ncx_dims* dp, const ncx_params* p, void* workspace, size_t workspace_bytes, const int32_t* gt,
                    float* scores, float* loss_rows, float* loss, float* dscores, int32_t* rank, int32_t* hits,
@@ -1606,7 +1614,7 @@ static int backward_impl(const ncx_dims* dp, const ncx_inputs* in, const ncx_par
         const bool tn8 = dw_tn8_supported(d);               // dGt + every column block that is not the per-triplet fold's: ONE balanced launch (ncx_dwtn.hip)
         // With the side stream the per-triplet fold kernel (a full round of long workgroups) is launched AFTER the grouped
         // launch, next to the answer-embedding chain (dW1ak, dE: short latency-bound workgroups) that waits for dGt.
-        km_deferred = want_rest && km && aemb && do1 && do2 && side_stream() != nullptr && side_stream()->mode != 2;
+        km_deferred = want_rest && do1 && do2 && km_defers_to_side_stream(d);
         // the sums over its k-chunk partials ride in one launch with the split fix-up of the grouped GEMM below
         const bool km_merge = want_rest && km && !km_deferred && !hook_env("NCX_NO_MERGE_FIX");
         if (want_rest && km && !km_deferred) {      // v_other and v_mult columns in one MFMA pass (per-triplet fold)
@@ -1657,7 +1665,7 @@ static int backward_impl(const ncx_dims* dp, const ncx_inputs* in, const ncx_par
             add_c(x_plain(in->z_knns, d.dz, M, d.dz), g->w1 + o.z_other, din);
             add_c(x_plain(misc, w.ldm, M, d.K + 1), g->w1 + o.v_dist, din);
         }
-        if (want_rest && bf16 && dw_tn8_shapes_ok(d)) {      // bf16 variant: the fp32 shared segments' weight gradient on the balanced TN kernel
+        if (want_rest && bf16 && dw_tn8_shared_ok(d)) {      // bf16 variant: the fp32 shared segments' weight gradient on the balanced TN kernel
             Tn8Prob tp[4]; int np = 0;
             auto prob = [&](const float* X, long long ldx, int gsel, int N, float* out) {
                 tp[np] = Tn8Prob{};
@@ -1698,7 +1706,7 @@ static int backward_impl(const ncx_dims* dp, const ncx_inputs* in, const ncx_par
         hipStream_t se = ss ? ss->s : s;
         FixupArgs fix_ak{};
         Tn8ReduceArgs red_ak{};
-        const bool tn8_ak = dw_tn8_supported(d) && emb_nt && !ss;
+        const bool tn8_ak = dw1ak_on_tn8(d, ss != nullptr);
         if (ss) { rc = side_fork(ss, s); if (rc) return rc; }
         const bool bf16e = d.flags & NCX_F_BF16;
         const Bf16Emb bm = bf16e ? bf16_emb_layout(d, ws + w.bf_emb) : Bf16Emb{};
@@ -2014,7 +2022,19 @@ int ncx_wgmap_check(int32_t tiles_m, int32_t tiles_n, int32_t S) {
 }
 
 int ncx_plan_query(const ncx_dims* d, int32_t gemm_id, int32_t* out6) {
-    if (check_dims(d) != NCX_OK || !out6 || gemm_id < 0 || gemm_id >= U_COUNT) return NCX_E_DIMS;
+    if (check_dims(d) != NCX_OK || !out6) return NCX_E_DIMS;
+    if (gemm_id == NCX_QUERY_DW1_ROUTE) {      // the routes of linear_1's weight gradient, from the predicates backward_impl launches by
+        const bool bf16 = d->flags & NCX_F_BF16;
+        out6[0] = bf16 ? KM_FORM_NONE : dw_km_supported(*d) ? dw_km_form(*d) : KM_FORM_GROUPED;
+        out6[1] = (bf16 ? dw_tn8_shared_ok(*d) : dw_tn8_supported(*d)) ? (dw_tn8_x6(*d) ? 2 : 1) : 0;
+        int grid = 0;
+        out6[2] = dw_tn8_pieces(*d, bf16 ? TN8_LIST_SHARED : TN8_LIST_MAIN, &grid);
+        out6[3] = grid;
+        out6[4] = dw1ak_on_tn8(*d, km_defers_to_side_stream(*d)) ? 1 : 0;
+        out6[5] = TN8_MAX_SEG;
+        return NCX_OK;
+    }
+    if (gemm_id < 0 || gemm_id >= U_COUNT) return NCX_E_DIMS;
     GemmUse u[U_COUNT];
     list_uses(*d, u);
     out6[0] = u[gemm_id].form; out6[1] = (int32_t)u[gemm_id].M; out6[2] = (int32_t)u[gemm_id].N;

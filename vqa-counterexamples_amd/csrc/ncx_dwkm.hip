@@ -698,23 +698,32 @@ int dw_km_finish(const ncx_dims& d, const float* slab, float* g_vother, float* g
     return NCX_OK;
 }
 
+// The kernel dw_km launches for a shape that dw_km_supported accepts: the 8-wave 256 x 64 form where the shape has whole tiles (configs[1]
+// on one box: DW1C 0.2962-0.2970 ms against 0.3048, step 0.8465-0.8478 ms against 0.8578), its three-plane copy under NCX_F_X6, else k_dw_km
+int dw_km_form(const ncx_dims& d) {
+    const bool x6 = (d.flags & NCX_F_X6) && !hook_env("NCX_NO_X6") && !hook_env("NCX_NO_KM_X6");
+    const bool fits32 = (long long)d.n_img * d.dv * 4 < (1ll << 32) - 65536 && (long long)d.B * d.K * d.H * 4 < (1ll << 32) - 65536;      // (k_dw_km8's buffer loads: 32-bit byte offsets)
+    if (d.H % 256 == 0 && d.dv % 64 == 0 && fits32 && !x6 && !hook_env("NCX_NO_KM8") && !hook_env("NCX_KM_BM") && !hook_env("NCX_KM_T") && !hook_env("NCX_KM_ABL"))
+        return KM_FORM_8;
+    if (x6 && d.H % 256 == 0 && d.dv % 64 == 0 && fits32) return KM_FORM_X6;      // (K % 24 == 0: dw_km_supported)
+    return KM_FORM_GENERIC;
+}
+
 // finish = false: the caller sums the partials later with dw_km_finish (merged with the grouped GEMM's fix-up)
 int dw_km(const ncx_dims& d, const float* dpre, const float* feats, const int* idx_k, const int* idx_o, float* slab,
           float* g_vother, float* g_vmult, long long din, hipStream_t s, bool finish) {
     int chunk;
     const int S = km_chunks(d, chunk);
     constexpr int R = 24;
-    // the 8-wave 256 x 64 form where the shape has whole tiles (configs[1] on one box: DW1C 0.2962-0.2970 ms against 0.3048, step 0.8465-0.8478 ms against 0.8578)
-    const bool x6 = (d.flags & NCX_F_X6) && !hook_env("NCX_NO_X6") && !hook_env("NCX_NO_KM_X6");
-    const bool fits32 = (long long)d.n_img * d.dv * 4 < (1ll << 32) - 65536 && (long long)d.B * d.K * d.H * 4 < (1ll << 32) - 65536;      // (k_dw_km8's buffer loads: 32-bit byte offsets)
-    if (d.H % 256 == 0 && d.dv % 64 == 0 && fits32 && !x6 && !hook_env("NCX_NO_KM8") && !hook_env("NCX_KM_BM") && !hook_env("NCX_KM_T") && !hook_env("NCX_KM_ABL")) {
+    const int form = dw_km_form(d);
+    if (form == KM_FORM_8) {
         static DevMask attr8{0};
         NCX_HIP_TRY(set_max_lds_once(attr8, (const void*)k_dw_km8, KM8_LDS));
         hipLaunchKernelGGL(k_dw_km8, dim3((d.H / 256) * (d.dv / 64) * S), dim3(512), KM8_LDS, s, dpre, d.H, feats, d.dv, idx_k, idx_o, d.B, d.K, chunk, d.H / 256, S, slab);
         NCX_HIP_TRY(hipGetLastError());
         return finish ? dw_km_finish(d, slab, g_vother, g_vmult, din, nullptr, 0, s) : NCX_OK;
     }
-    if (x6 && d.H % 256 == 0 && d.dv % 64 == 0 && fits32) {      // (K % 24 == 0: dw_km_supported)
+    if (form == KM_FORM_X6) {
         static DevMask attr6{0};
         NCX_HIP_TRY(set_max_lds_once(attr6, (const void*)k_dw_km_x6, KM6_LDS));
         hipLaunchKernelGGL(k_dw_km_x6, dim3((d.H / 256) * (d.dv / 64) * S), dim3(512), KM6_LDS, s, dpre, d.H, feats, d.dv, idx_k, idx_o, d.B, d.K, chunk, d.H / 256, S, slab);

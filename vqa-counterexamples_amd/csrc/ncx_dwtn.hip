@@ -32,7 +32,6 @@
 namespace ncx {
 
 constexpr int TN8_PA = 256, TN8_PB = 80;                       // LDS pitches (floats): ds_read_b128 / ds_read_b64 fragment reads without conflicts
-constexpr int TN8_MAX_SEG = 16;                                // pieces per workgroup (host-checked)
 constexpr int TN8_SEG_WORDS = 16;
 
 typedef const __attribute__((address_space(1))) float* tn_gfptr;
@@ -627,7 +626,6 @@ static inline int tn8_cdiv(long long a, long long b) { return (int)((a + b - 1) 
 // NCX_F_X6: the launch runs on the bf16 matrix path with three-plane operands (k_dw_tn8_x6); the row-gather tables share LDS with six planes
 constexpr int TN6_MAX_B = 2048;
 bool dw_tn8_x6(const ncx_dims& d) { return (d.flags & NCX_F_X6) && d.B <= TN6_MAX_B && !hook_env("NCX_NO_X6"); }
-bool dw_tn8_supported(const ncx_dims& d) { return !(d.flags & NCX_F_BF16) && dw_tn8_shapes_ok(d); }
 // the bf16 variant keeps the per-triplet shared segments of linear_1 in fp32: their weight gradient takes this kernel too (rest sequence only)
 bool dw_tn8_shapes_ok(const ncx_dims& d) {
     if (hook_env("NCX_NO_TN8")) return false;
@@ -669,10 +667,60 @@ static Tn8Plan tn8_plan(const ncx_dims& d, const Tn8Prob* p, int np, int n_al, i
     return pl;
 }
 
+// Pieces per workgroup: the aligned chunk + every tile boundary its rest range can cross (the LDS table holds TN8_MAX_SEG)
+static int tn8_piece_bound(const Tn8Plan& pl, const int* rest_steps, int np, int n_al) {
+    if (np <= n_al) return 1;
+    int min_steps = 1 << 30;
+    for (int i = n_al; i < np; ++i) min_steps = rest_steps[i] < min_steps ? rest_steps[i] : min_steps;
+    return 1 + pl.R / min_steps + 2;
+}
+
+// The shapes (rows, N) of the problem lists backward_impl hands to this kernel, in its order (tn8_plan reads nothing else)
+static int tn8_list(const ncx_dims& d, int list, Tn8Prob* p, int* n_al) {
+    const int M = d.B * d.K;
+    const bool aemb = d.flags & NCX_F_A_EMB;
+    int np = 0;
+    auto prob = [&](int rows, int N) { p[np] = Tn8Prob{}; p[np].rows = rows; p[np].N = N; ++np; };
+    *n_al = 0;
+    if (list == TN8_LIST_AK) { prob(pad_to(d.A, 32), d.da); return np; }
+    if (list == TN8_LIST_MAIN) {
+        if (aemb) { prob(M, d.A); *n_al = 1; }            // dGt (aligned)
+        else prob(M, d.da);                                 // dW1[:, a_other]
+        prob(M, d.dz);                                      // dW1[:, z_other]
+        prob(M, pad_to(d.K + 1, 4));                        // dW1[:, dist | rank]
+    }
+    prob(d.B, d.dv); prob(d.B, d.dq); prob(d.B, d.dz); prob(d.B, d.da);      // the shared segments: v_orig, q, z_orig, a_gt
+    return np;
+}
+
+int dw_tn8_pieces(const ncx_dims& d, int list, int* grid) {
+    if (grid) *grid = 0;
+    if (!dw_tn8_shapes_ok(d)) return 0;
+    Tn8Prob p[TN8_MAX_PROB]; int n_al;
+    const int np = tn8_list(d, list, p, &n_al);
+    int rt[TN8_MAX_PROB], rs[TN8_MAX_PROB], r0[TN8_MAX_PROB], rp[TN8_MAX_PROB + 1];
+    const Tn8Plan pl = tn8_plan(d, p, np, n_al, rt, rs, r0, rp);
+    if (grid) *grid = pl.grid;
+    return tn8_piece_bound(pl, rs, np, n_al);
+}
+
+// Where a plan would need more pieces than the LDS table holds (wide H: many row tiles; the a_emb lesion: the long a_other block in the rest
+// sequence; K = 48), the products stay on the generic engine's grouped launch.  list_uses, ws_layout, dw_tn8_slab_bytes and backward_impl
+// all decide from these two predicates.
+bool dw_tn8_supported(const ncx_dims& d) {
+    if ((d.flags & NCX_F_BF16) || !dw_tn8_shapes_ok(d)) return false;
+    if (dw_tn8_pieces(d, TN8_LIST_MAIN, nullptr) > TN8_MAX_SEG) return false;
+    return !(d.flags & NCX_F_A_EMB) || dw_tn8_pieces(d, TN8_LIST_AK, nullptr) <= TN8_MAX_SEG;
+}
+bool dw_tn8_shared_ok(const ncx_dims& d) {
+    if (!(d.flags & NCX_F_BF16)) return dw_tn8_supported(d);
+    return dw_tn8_shapes_ok(d) && dw_tn8_pieces(d, TN8_LIST_SHARED, nullptr) <= TN8_MAX_SEG;
+}
+
 // Slab bytes for the problems backward_impl hands to this kernel (worst case over the lesion flags: the a_other column block joins
 // the rest sequence when the answer-embedding segment is lesioned)
 size_t dw_tn8_slab_bytes(const ncx_dims& d) {
-    if (!dw_tn8_shapes_ok(d)) return 0;
+    if (!dw_tn8_shared_ok(d)) return 0;
     const int cus = num_cus(), tiles_m = d.H / TN8_BM;
     const bool aemb = d.flags & NCX_F_A_EMB, bf16 = d.flags & NCX_F_BF16;
     long long al_wgs = 0;
@@ -694,10 +742,8 @@ static int tn8_fill(const ncx_dims& d, const Tn8Prob* probs, int np, int n_al, b
     }
     pl = tn8_plan(d, probs, np, n_al, a.rest_tiles, a.rest_steps, a.rest_tile0, a.rest_pre);
     if ((size_t)pl.n_slots * TN8_BM * TN8_BN * 4 > slab_bytes) return NCX_E_WORKSPACE;
-    // pieces per workgroup: the aligned chunk + every tile boundary its rest range can cross
-    int min_steps = 1 << 30;
-    for (int i = n_al; i < np; ++i) min_steps = a.rest_steps[i] < min_steps ? a.rest_steps[i] : min_steps;
-    if (np > n_al && 1 + pl.R / min_steps + 2 > TN8_MAX_SEG) return NCX_E_DIMS;
+    // (a backstop: the callers ask dw_tn8_supported / dw_tn8_shared_ok, which plan the same lists)
+    if (tn8_piece_bound(pl, a.rest_steps, np, n_al) > TN8_MAX_SEG) return NCX_E_DIMS;
     a.np = np; a.n_al = n_al; a.H = d.H; a.tiles_m = d.H / TN8_BM; a.B = d.B;
     a.S = pl.S; a.al_wgs = pl.al_wgs; a.al_tiles_n = n_al ? tn8_cdiv(probs[0].N, TN8_BN) : 0; a.R = pl.R;
     a.do_al = do_al && n_al; a.do_rest = do_rest && np > n_al;

@@ -112,6 +112,9 @@ int main_fold_rows(long long M, long long N);      // tile rows of the per-tripl
 // ncx_dwkm.hip: d linear_1.weight[:, v_other] and [:, v_mult] in one MFMA pass with a per-triplet fold
 constexpr int DW_KM_SPLIT = 8;
 bool dw_km_supported(const ncx_dims& d);
+// which kernel dw_km launches for the shape (the codes of NCX_QUERY_DW1_ROUTE, include/neuralcx.h)
+enum DwKmForm : int { KM_FORM_NONE = 0, KM_FORM_8 = 1, KM_FORM_X6 = 2, KM_FORM_GENERIC = 3, KM_FORM_GROUPED = 4 };
+int dw_km_form(const ncx_dims& d);
 size_t dw_km_slab_bytes(const ncx_dims& d);
 int dw_km(const ncx_dims& d, const float* dpre, const float* feats, const int* idx_k, const int* idx_o, float* slab,
           float* g_vother, float* g_vmult, long long din, hipStream_t s, bool finish = true);
@@ -120,6 +123,7 @@ int dw_km_finish(const ncx_dims& d, const float* slab, float* g_vother, float* g
 // ncx_dwtn.hip: every other row-reduction product of linear_1's weight gradient (dGt, z_other, dist | rank, the per-triplet shared
 // segments) as one balanced launch of 8-wave workgroups on 256 x 64 tiles
 constexpr int TN8_MAX_PROB = 8;
+constexpr int TN8_MAX_SEG = 16;             // pieces per workgroup (the LDS table of k_dw_tn8 / k_dw_tn8_x6; host-checked)
 struct Tn8Prob {             // out[h][n] = sum_r A[r][h] * x(r, n)
     const float* A;          // [rows][H]: dpre (rows = B K) or dSh (rows = B)
     const float* X; long long ldx;   // operand rows, x(r, n) = X[row(r) * ldx + n]
@@ -130,8 +134,15 @@ struct Tn8Prob {             // out[h][n] = sum_r A[r][h] * x(r, n)
     int rows_valid;          // 0: = rows.  Else operand rows >= rows_valid do not exist (their index is clamped) and A's rows there are ZERO
     float* outT; float* outT2; long long ldT; int padT2;   // optional transposed copies out^T[n][h] (ld ldT); outT2 also gets padT2 zero rows after n_valid
 };
-bool dw_tn8_supported(const ncx_dims& d);
-bool dw_tn8_shapes_ok(const ncx_dims& d);          // ... ignoring the bf16 flag (the variant's fp32 shared segments)
+bool dw_tn8_supported(const ncx_dims& d);          // the fp32 launch (dGt + rest, then dW1[:, a_other]): shapes and plans fit
+bool dw_tn8_shapes_ok(const ncx_dims& d);          // ... the shape rules alone, ignoring the bf16 flag and the plans
+bool dw_tn8_shared_ok(const ncx_dims& d);          // the per-triplet shared segments take the kernel (bf16 variant: on their own launch)
+// The problem lists backward_impl hands to the kernel, shapes only (rows, N): TN8_LIST_MAIN the fp32 launch (dGt aligned + 6 rest problems,
+// or 7 rest problems under the a_emb lesion), TN8_LIST_SHARED the bf16 variant's 4 shared segments, TN8_LIST_AK dW1[:, a_other].
+enum Tn8List : int { TN8_LIST_MAIN = 0, TN8_LIST_SHARED = 1, TN8_LIST_AK = 2 };
+// pieces per workgroup of that list's plan (the kernel's LDS table holds TN8_MAX_SEG) and its grid; 0 when dw_tn8_shapes_ok fails
+int dw_tn8_pieces(const ncx_dims& d, int list, int* grid);
+bool dw_tn8_x6(const ncx_dims& d);
 size_t dw_tn8_slab_bytes(const ncx_dims& d);
 // problems [0, n_al) (n_al <= 1): tile-aligned row chunks, one per workgroup; [n_al, np): laid end to end and cut into equal ranges.
 // do_al / do_rest: which part this call launches (the chunking of each part does not depend on the other: phased backward)

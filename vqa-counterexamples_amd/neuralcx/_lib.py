@@ -182,8 +182,17 @@ def profile_stamps(buf=None):
         check(lib().ncx_profile_stamps(C.c_void_p(buf.data_ptr()), buf.numel()), "ncx_profile_stamps")
 
 
+NCX_QUERY_DW1_ROUTE = 32        # include/neuralcx.h
+DW1_FOLD_FORMS = ("none", "k_dw_km8", "k_dw_km_x6", "k_dw_km", "grouped")
+DW1_TN_FORMS = ("grouped", "k_dw_tn8", "k_dw_tn8_x6")
+
+
 def plan_query(d, name):
     out = (C.c_int32 * 6)()
+    if name == "DW1_ROUTE":
+        check(lib().ncx_plan_query(C.byref(d), NCX_QUERY_DW1_ROUTE, out), "ncx_plan_query")
+        return dict(fold=DW1_FOLD_FORMS[out[0]], tn=DW1_TN_FORMS[out[1]], tn_pieces=out[2], tn_grid=out[3],
+                    a_other_on_tn=bool(out[4]), tn_max_pieces=out[5])
     check(lib().ncx_plan_query(C.byref(d), GEMM_IDS[name], out), "ncx_plan_query")
     return dict(form=("NT", "TN", "NN")[out[0]], M=out[1], N=out[2], ksteps=out[3],
                 tile=("64x64", "128x128", "96x128", "96x64", "128x64", "48x128", "48x64 (per-triplet fold of the two v segments)",
