@@ -296,6 +296,49 @@ int ncx_cosine_gram(const float* emb, int32_t A, int32_t da, void* ws, size_t ws
 int ncx_semantic_scores(const float* a_knns, const int32_t* aid, int32_t B, int32_t K, int32_t A, const float* gram,
                         float lam, float* scores, float* raw, int32_t* bad_id_flag, void* stream);
 
+/* ---- the trainable scorers LinearContext and PairwiseLinearModel (reference vqa/models/cx.py:139-156, 379-425) ---------
+ * Both train with the library's loss (ncx_loss_rank) and optimiser (ncx_adam_step): forward -> scores, ncx_loss_rank ->
+ * dscores, backward -> gradients (the reference's loop, counterexamples.py:330-339).  Neither model has dropout.
+ * Dims: 1 <= K <= 64, B >= 1, K dz >= 4.  PairwiseLinearModel also needs dv, dq, dz >= 4, A >= 1 (answers), n_img >= 1 (rows of
+ * the feature table); its hidden width and answer-embedding width are the reference's fixed 300 (cx.py:391-392). */
+typedef struct ncx_scorer_dims {
+    int32_t B, K, dv, dq, dz, A, n_img;
+} ncx_scorer_dims;
+
+/* PairwiseLinearModel's trainable tensors, state_dict names of the reference (cx.py:394-400). */
+typedef struct ncx_pairlin_params {
+    const float* answer_embedding;       /* answer_embedding.weight [A, 300]                         */
+    const float* w;  const float* b;     /* linear.weight [300, Din], Din = 2 dv + dq + 2 dz + 300;  .bias [300]
+                                            columns in the reference's concat order (cx.py:416):
+                                            v_orig | v_other | q_emb | z_orig | z_other | a_emb      */
+    const float* w_out; const float* b_out;  /* out.weight [1, 300], out.bias [1]                    */
+} ncx_pairlin_params;
+typedef struct ncx_pairlin_grads {
+    float* answer_embedding; float* w; float* b; float* w_out; float* b_out;   /* shapes of ncx_pairlin_params; overwritten */
+} ncx_pairlin_grads;
+
+/* Workspace of ncx_pairlin_forward / _backward (256-byte aligned); 0 for unsupported dims.  The backward reads what the forward
+ * left there: call both with the same dims, inputs and workspace. */
+size_t ncx_pairlin_workspace_bytes(const ncx_scorer_dims* d);
+/* Replaces PairwiseLinearModel.forward below vqa_forward (cx.py:401-425): scores [B, K] = relu(out(relu(linear(x_k)))).
+ * Reads in->feats, img_idx, q_emb, z_orig, z_knns, answer_aids (the other fields are ignored).  A feature row or answer id out of
+ * range is clamped and sets *bad_id_flag to 1 (never cleared here; the reference raises IndexError there). */
+int ncx_pairlin_forward(const ncx_scorer_dims* d, const ncx_inputs* in, const ncx_pairlin_params* p, void* workspace,
+                        size_t workspace_bytes, float* scores, int32_t* bad_id_flag, void* stream);
+/* Replaces loss.backward() (counterexamples.py:338) for PairwiseLinearModel: every gradient of ncx_pairlin_grads from dscores
+ * [B, K].  d answer_embedding is dense: rows no answer id points at are 0, duplicated ids are summed in batch order.
+ * Reads in->feats, q_emb, z_orig, z_knns; the feature rows and answer ids are the clamped ones ncx_pairlin_forward left in the
+ * workspace (in->img_idx and in->answer_aids are not read), as are h, P and the scores. */
+int ncx_pairlin_backward(const ncx_scorer_dims* d, const ncx_inputs* in, const ncx_pairlin_params* p, void* workspace,
+                         size_t workspace_bytes, const float* dscores, const ncx_pairlin_grads* g, void* stream);
+/* LinearContext (cx.py:147-155): scores [B, K] = z_knns.view(B, K dz) . w^T + b, w = linear.weight [K, K dz], b = linear.bias [K]. */
+size_t ncx_linctx_workspace_bytes(const ncx_scorer_dims* d);
+int ncx_linctx_forward(const ncx_scorer_dims* d, const float* z_knns, const float* w, const float* b, void* workspace,
+                       size_t workspace_bytes, float* scores, void* stream);
+/* ... its loss.backward(): gw = dscores^T . z_flat [K, K dz], gb = sum over b of dscores [K] (overwritten). */
+int ncx_linctx_backward(const ncx_scorer_dims* d, const float* z_knns, const float* dscores, void* workspace,
+                        size_t workspace_bytes, float* gw, float* gb, void* stream);
+
 /* ---- diagnostics (bench.py / tests only; the only process-global state, off by default) --------------
  * GEMM ids: 0 Gt = W1[:,a_other].E^T, 1 Sh (shared segments), 2 MAIN (candidate segments, the dominant
  * forward kernel), 3 hidden layer l>=2 forward, 4 dW1 candidate columns (+dGt; the dominant backward

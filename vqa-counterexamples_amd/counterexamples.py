@@ -40,6 +40,7 @@ import vqa.models as models                       # noqa: E402
 from vqa.models.cx import CXModelBase, blackbox_scores        # noqa: E402
 from neuralcx import dp, ops                      # noqa: E402
 from neuralcx.engine import NeuralCXEngine        # noqa: E402
+from neuralcx.scorers import LinearContextEngine, PairwiseLinearEngine        # noqa: E402
 from neuralcx.synth import SyntheticCX            # noqa: E402
 from neuralcx import formats                      # noqa: E402
 
@@ -49,7 +50,7 @@ def build_parser():
     p.add_argument("--path_opt", default=os.path.join(HERE, "options", "cx", "neuralcx_256_1_all.yaml"), type=str)
     p.add_argument("--vqa_model", default="mutan_noatt_train", type=str)
     # (the reference makes -cx required, counterexamples.py:44; here NeuralModel is the default and the flag spellings are kept)
-    p.add_argument("-cx", "--cx_model", default="NeuralModel", type=str, help="NeuralModel | RandomBaseline | DistanceBaseline | BlackBox | SemanticBaseline")
+    p.add_argument("-cx", "--cx_model", default="NeuralModel", type=str, help="NeuralModel | LinearContext | PairwiseLinearModel | RandomBaseline | DistanceBaseline | BlackBox | SemanticBaseline")
     p.add_argument("-lb", "--sb_lambda", type=float, help="semantic baseline lambda (counterexamples.py:49): required by -cx SemanticBaseline; "
                                                           "the other models ignore it (with a warning)")
     p.add_argument("--pairwise", action="store_true")
@@ -108,15 +109,22 @@ class Runner:
         cx = options["cx_model"]
         fus = options["model"]["fusion"]
         self.K = 24
-        self.engine = NeuralCXEngine(K=self.K, dv=fus["dim_v"], dq=fus["dim_q"], dz=fus["dim_mm"], da=2400,
-                                     A=options["vqa"]["nans"], H=cx["dim_h"], L=cx["n_layers"], drop_p=cx["drop_p"],
-                                     lr=options["optim"]["lr"], device=self.dev,
-                                     spec={k: cx.get(k, True) for k in ("v_mult", "v_dist", "v_rank", "a_emb")},
-                                     world_size=self.world, bf16=args.bf16, x6=getattr(args, "x6", False))
+        if args.cx_model == "PairwiseLinearModel":          # counterexamples.py:268-270 (cx.py:379-425)
+            self.engine = PairwiseLinearEngine(K=self.K, dv=fus["dim_v"], dq=fus["dim_q"], dz=fus["dim_mm"], A=options["vqa"]["nans"],
+                                               lr=options["optim"]["lr"], device=self.dev, world_size=self.world)
+        elif args.cx_model == "LinearContext":              # counterexamples.py:233-235 (cx.py:139-156)
+            self.engine = LinearContextEngine(K=self.K, dz=fus["dim_mm"], lr=options["optim"]["lr"], device=self.dev,
+                                              world_size=self.world)
+        else:
+            self.engine = NeuralCXEngine(K=self.K, dv=fus["dim_v"], dq=fus["dim_q"], dz=fus["dim_mm"], da=2400,
+                                         A=options["vqa"]["nans"], H=cx["dim_h"], L=cx["n_layers"], drop_p=cx["drop_p"],
+                                         lr=options["optim"]["lr"], device=self.dev,
+                                         spec={k: cx.get(k, True) for k in ("v_mult", "v_dist", "v_rank", "a_emb")},
+                                         world_size=self.world, bf16=args.bf16, x6=getattr(args, "x6", False))
         self.engine.rank = self.rank
         self.engine.init_parameters(seed=42)
         self.gb = options["optim"]["batch_size"]
-        self.baseline = None if args.cx_model == "NeuralModel" else args.cx_model
+        self.baseline = None if args.cx_model in TRAINABLE else args.cx_model
         self.runs_dir = None
         self.sem_gram = self.sem_flag = None
 
@@ -174,7 +182,8 @@ class Runner:
                 emb = formats.load_answer_embedding(pe, n_answers=len(trainset["vocab_answers"]))
             else:
                 self.log("Warning: no answer embedding at '{}' (random initialisation)".format(pe))
-        self.engine.init_parameters(seed=42, emb=emb)
+        if isinstance(self.engine, NeuralCXEngine):      # (PairwiseLinearModel's 300-wide embedding is never pretrained, cx.py:394)
+            self.engine.init_parameters(seed=42, emb=emb)
         if self.baseline == "SemanticBaseline":
             # counterexamples.py:244-246: read from the trainset directory whatever pretrained_emb says
             pe = os.path.join(vqa_dir, "answer_embedding.pickle")
@@ -323,6 +332,10 @@ class Runner:
         return info, len(info) + 1, last.get("recall_5", last.get("recall"))     # the reference KeyErrors here (:580)
 
 
+TRAINABLE = ("NeuralModel", "LinearContext", "PairwiseLinearModel")
+SCORERS = TRAINABLE + ("RandomBaseline", "DistanceBaseline", "BlackBox", "SemanticBaseline")
+
+
 def synthetic_answer_embedding(n_answers, dim_a=2400, seed=2400):
     """--synthetic stand-in for answer_embedding.pickle: N(0, 1) rows [n_answers, dim_a], numpy default_rng(2400)."""
     return np.random.default_rng(seed).standard_normal((n_answers, dim_a), dtype=np.float32)
@@ -331,9 +344,11 @@ def synthetic_answer_embedding(n_answers, dim_a=2400, seed=2400):
 def main(argv=None):
     args = build_parser().parse_args(argv)
     options = load_options(args)
-    if args.cx_model not in ("NeuralModel", "RandomBaseline", "DistanceBaseline", "BlackBox", "SemanticBaseline"):
-        raise SystemExit("--cx_model {}: only NeuralModel and the RandomBaseline / DistanceBaseline / BlackBox / SemanticBaseline "
-                         "scorers are provided (the reference's other models are outside the accelerated path)".format(args.cx_model))
+    if args.cx_model not in SCORERS:
+        raise SystemExit("--cx_model {}: the accelerated path provides {} (PairwiseModel needs --pairwise, which is outside "
+                         "it)".format(args.cx_model, " / ".join(SCORERS)))
+    if args.cx_model in ("LinearContext", "PairwiseLinearModel") and (args.bf16 or getattr(args, "x6", False)):
+        raise SystemExit("--bf16 / --x6 are variants of NeuralModel's kernels; -cx {} runs in fp32 only".format(args.cx_model))
     if args.cx_model == "SemanticBaseline":
         if args.sb_lambda is None:                                         # counterexamples.py:240-242
             raise ValueError("If semantic baseline is selected then --sb_lambda must also be provided.")
@@ -341,7 +356,7 @@ def main(argv=None):
         print("warning: -lb/--sb_lambda {} is accepted for command-line compatibility and ignored (no {} code path reads it)".format(
             args.sb_lambda, args.cx_model), file=sys.stderr)
     if args.pairwise or args.viz:
-        raise SystemExit("--pairwise / --viz are outside the accelerated path (SURVEY 8: out of scope)")
+        raise SystemExit("--pairwise (PairwiseModel, knn_size = 2) / --viz are outside the accelerated path (SURVEY 8: out of scope)")
     r = Runner(args, options)
     run = args.resume or "{}_{}".format(options["cx_model"].get("name", "neuralcx"), time.strftime("%m%d_%H%M%S"))
     save_dir = os.path.join(args.project_dir, "logs", "cx", run)
@@ -374,6 +389,8 @@ def main(argv=None):
     for epoch in range(start_epoch, options["optim"]["epochs"] + 1):
         tps = r.run_epoch(epoch)
         res = r.evaluate(r.val)
+        if hasattr(r.engine, "check_ids"):
+            r.engine.check_ids()                      # (PairwiseLinearModel: a feature row or answer id out of range raises here)
         r.report("val", epoch, res)
         r.log("Epoch {} throughput: {:.0f} triplets/s".format(epoch, tps))
         info.append(res)

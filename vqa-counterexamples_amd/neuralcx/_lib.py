@@ -21,7 +21,9 @@ EXPORTS = ("ncx_input_size", "ncx_workspace_bytes", "ncx_forward", "ncx_forward_
            "ncx_adam_step", "ncx_version", "ncx_profile_begin", "ncx_profile_end", "ncx_plan_query",
            "ncx_vqa_workspace_bytes", "ncx_vqa_forward", "ncx_knn_workspace_bytes", "ncx_knn", "ncx_cosine_gram_workspace_bytes", "ncx_cosine_gram", "ncx_semantic_scores",
            "ncx_ws_region", "ncx_wgmap_check",
-           "ncx_comm_unique_id", "ncx_comm_create", "ncx_comm_destroy", "ncx_allreduce", "ncx_train_tail", "ncx_profile_stamps")
+           "ncx_comm_unique_id", "ncx_comm_create", "ncx_comm_destroy", "ncx_allreduce", "ncx_train_tail", "ncx_profile_stamps",
+           "ncx_pairlin_workspace_bytes", "ncx_pairlin_forward", "ncx_pairlin_backward",
+           "ncx_linctx_workspace_bytes", "ncx_linctx_forward", "ncx_linctx_backward")
 
 
 class NcxDims(C.Structure):
@@ -51,6 +53,21 @@ class NcxGrads(C.Structure):
 class NcxMutanParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("wv", "bv", "wq", "bq", "whv", "bhv", "whq", "bhq", "wc", "bc")] + \
                [(n, C.c_int32) for n in ("dhv", "dhq", "R", "act_v", "act_q")]
+
+
+class NcxScorerDims(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "K", "dv", "dq", "dz", "A", "n_img")]
+
+
+_PL_NAMES = ("answer_embedding", "w", "b", "w_out", "b_out")
+
+
+class NcxPairlinParams(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in _PL_NAMES]
+
+
+class NcxPairlinGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in _PL_NAMES]
 
 
 class NcxError(RuntimeError):
@@ -134,6 +151,21 @@ def lib():
     L.ncx_allreduce.restype = C.c_int; L.ncx_allreduce.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.ncx_plan_query.restype = C.c_int
     L.ncx_plan_query.argtypes = [C.POINTER(NcxDims), C.c_int32, C.POINTER(C.c_int32)]
+    P_SD = C.POINTER(NcxScorerDims)
+    L.ncx_pairlin_workspace_bytes.restype = C.c_size_t
+    L.ncx_pairlin_workspace_bytes.argtypes = [P_SD]
+    L.ncx_pairlin_forward.restype = C.c_int
+    L.ncx_pairlin_forward.argtypes = [P_SD, C.POINTER(NcxInputs), C.POINTER(NcxPairlinParams), C.c_void_p, C.c_size_t,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ncx_pairlin_backward.restype = C.c_int
+    L.ncx_pairlin_backward.argtypes = [P_SD, C.POINTER(NcxInputs), C.POINTER(NcxPairlinParams), C.c_void_p, C.c_size_t,
+                                       C.c_void_p, C.POINTER(NcxPairlinGrads), C.c_void_p]
+    L.ncx_linctx_workspace_bytes.restype = C.c_size_t
+    L.ncx_linctx_workspace_bytes.argtypes = [P_SD]
+    L.ncx_linctx_forward.restype = C.c_int
+    L.ncx_linctx_forward.argtypes = [P_SD, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.ncx_linctx_backward.restype = C.c_int
+    L.ncx_linctx_backward.argtypes = [P_SD, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

@@ -7,6 +7,7 @@ hot path runs in libneuralcx_hip.so.  Reference surface these mirror:
   ranking_loss                           counterexamples.py:310,334 + recallAtK (counterexamples.py:501-506)
   adam_step                              torch.optim.Adam as used at counterexamples.py:275-276,339
   cosine_gram / semantic_scores          SemanticBaseline.set_answer_embedding / forward (vqa/models/cx.py:174-175,182-209)
+  pairlin_* / linctx_*                   PairwiseLinearModel / LinearContext forward and loss.backward() (cx.py:139-156,379-425)
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -363,6 +364,104 @@ def check_semantic_ids(bad_flag: Optional[torch.Tensor] = None, device=None) -> 
     if int(bad_flag.item()):
         bad_flag.zero_()
         raise IndexError("answer_aids outside [0, A) in a semantic_scores call")
+
+
+# ---- the trainable scorers LinearContext and PairwiseLinearModel (include/neuralcx.h) -----------------------------------------
+PAIRLIN_H = 300                     # dim_h = dim_a = 300 in the reference (cx.py:391-392)
+PAIRLIN_FIELDS = ("answer_embedding", "w", "b", "w_out", "b_out")
+PAIRLIN_STATE_TO_FIELD = {"answer_embedding.weight": "answer_embedding", "linear.weight": "w", "linear.bias": "b",
+                          "out.weight": "w_out", "out.bias": "b_out"}
+LINCTX_STATE_TO_FIELD = {"linear.weight": "w", "linear.bias": "b"}
+
+
+def pairlin_shapes(K, dv, dq, dz, A):
+    din = 2 * dv + dq + 2 * dz + PAIRLIN_H                      # cx.py:397-398
+    return {"answer_embedding.weight": (A, PAIRLIN_H), "linear.weight": (PAIRLIN_H, din), "linear.bias": (PAIRLIN_H,),
+            "out.weight": (1, PAIRLIN_H), "out.bias": (1,)}
+
+
+def linctx_shapes(K, dz):
+    return {"linear.weight": (K, K * dz), "linear.bias": (K,)}        # cx.py:145
+
+
+def pairlin_dims(batch: Batch, A: int) -> _lib.NcxScorerDims:
+    B, K1 = batch.img_idx.shape
+    d = _lib.NcxScorerDims()
+    d.B, d.K, d.dz, d.A = B, K1 - 1, batch.z_orig.shape[1], A
+    d.dv, d.n_img, d.dq = batch.feats.shape[1], batch.feats.shape[0], batch.q_emb.shape[1]
+    assert batch.z_knns.shape == (B, d.K, d.dz), batch.z_knns.shape
+    assert batch.q_emb.shape[0] == B and batch.z_orig.shape == (B, d.dz)
+    assert batch.answer_aids is not None and batch.answer_aids.shape == (B,)
+    return d
+
+
+def linctx_dims(z_knns: torch.Tensor) -> _lib.NcxScorerDims:
+    assert z_knns.dim() == 3, z_knns.shape
+    d = _lib.NcxScorerDims()
+    d.B, d.K, d.dz = z_knns.shape
+    return d
+
+
+def _pl_struct(tensors: Dict[str, torch.Tensor], cls):
+    s = cls()
+    for f in PAIRLIN_FIELDS:
+        setattr(s, f, _ptr(tensors.get(f), torch.float32, f))
+    return s
+
+
+def pairlin_workspace(d, device) -> torch.Tensor:
+    n = _lib.lib().ncx_pairlin_workspace_bytes(C.byref(d))
+    if n == 0:
+        raise _lib.NcxError("ncx_pairlin_workspace_bytes: unsupported dims")
+    return torch.empty(n + 256, dtype=torch.uint8, device=device)
+
+
+def pairlin_forward(d, batch: Batch, params: Dict[str, torch.Tensor], ws: torch.Tensor, bad_flag: Optional[torch.Tensor] = None):
+    """PairwiseLinearModel scores [B, K] (ncx_pairlin_forward); leaves h / P / clamped ids in `ws` for pairlin_backward.
+    A feature row or answer id out of range sets `bad_flag` (default: semantic_bad_flag(device); check_semantic_ids raises)."""
+    dev = batch.z_knns.device
+    if bad_flag is None:
+        bad_flag = semantic_bad_flag(dev)
+    scores = torch.empty(d.B, d.K, dtype=torch.float32, device=dev)
+    p, n = _ws_ptr(ws)
+    _lib.check(_lib.lib().ncx_pairlin_forward(C.byref(d), C.byref(batch.c_struct()), C.byref(_pl_struct(params, _lib.NcxPairlinParams)),
+                                              p, n, C.c_void_p(scores.data_ptr()), _ptr(bad_flag, torch.int32, "bad_flag"), _stream()),
+               "ncx_pairlin_forward")
+    return scores
+
+
+def pairlin_backward(d, batch: Batch, params: Dict[str, torch.Tensor], ws: torch.Tensor, dscores: torch.Tensor,
+                     grads: Dict[str, torch.Tensor]) -> None:
+    """Every gradient of PairwiseLinearModel (ncx_pairlin_backward) into `grads` (field names), after pairlin_forward on `ws`."""
+    p, n = _ws_ptr(ws)
+    _lib.check(_lib.lib().ncx_pairlin_backward(C.byref(d), C.byref(batch.c_struct()), C.byref(_pl_struct(params, _lib.NcxPairlinParams)),
+                                               p, n, _ptr(dscores, torch.float32, "dscores"),
+                                               C.byref(_pl_struct(grads, _lib.NcxPairlinGrads)), _stream()),
+               "ncx_pairlin_backward")
+
+
+def linctx_workspace(d, device) -> torch.Tensor:
+    n = _lib.lib().ncx_linctx_workspace_bytes(C.byref(d))
+    if n == 0:
+        raise _lib.NcxError("ncx_linctx_workspace_bytes: unsupported dims")
+    return torch.empty(n + 256, dtype=torch.uint8, device=device)
+
+
+def linctx_forward(d, z_knns: torch.Tensor, w: torch.Tensor, b: torch.Tensor, ws: torch.Tensor) -> torch.Tensor:
+    """LinearContext scores [B, K] = z_knns.view(B, K dz) . w^T + b (ncx_linctx_forward)."""
+    scores = torch.empty(d.B, d.K, dtype=torch.float32, device=z_knns.device)
+    p, n = _ws_ptr(ws)
+    _lib.check(_lib.lib().ncx_linctx_forward(C.byref(d), _ptr(z_knns, torch.float32, "z_knns"), _ptr(w, torch.float32, "w"),
+                                             _ptr(b, torch.float32, "b"), p, n, C.c_void_p(scores.data_ptr()), _stream()),
+               "ncx_linctx_forward")
+    return scores
+
+
+def linctx_backward(d, z_knns: torch.Tensor, dscores: torch.Tensor, ws: torch.Tensor, gw: torch.Tensor, gb: torch.Tensor) -> None:
+    p, n = _ws_ptr(ws)
+    _lib.check(_lib.lib().ncx_linctx_backward(C.byref(d), _ptr(z_knns, torch.float32, "z_knns"), _ptr(dscores, torch.float32, "dscores"),
+                                              p, n, _ptr(gw, torch.float32, "gw"), _ptr(gb, torch.float32, "gb"), _stream()),
+               "ncx_linctx_backward")
 
 
 class WorkspacePool:

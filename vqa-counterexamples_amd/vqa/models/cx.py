@@ -8,7 +8,10 @@ code are interchangeable.  Everything below `vqa_forward` -- the answer-embeddin
 synthesis/concat, the Linear+ReLU+Dropout stack, `out`, and the whole backward -- runs in the HIP library
 (libneuralcx_hip.so) through `neuralcx.ops.NeuralCXFunction`.  There is no PyTorch fallback for that part:
 on a machine without the library or without a GPU `forward` raises.  `SemanticBaseline` (cx.py:159-210) keeps the
-reference's surface likewise; its cosine Gram and scorer run in the same library (see its docstring).
+reference's surface likewise; its cosine Gram and scorer run in the same library (see its docstring).  `LinearContext`
+(cx.py:139-156) and `PairwiseLinearModel` (cx.py:379-425) keep the reference's constructor, submodule names and state_dict
+keys; their forward and backward run in the library through an autograd.Function, so the reference's loop with
+torch.optim.Adam trains them.
 
 Deliberate differences from the reference (all supersets):
   * knn_size may be 1..64 (the reference asserts == 24, cx.py:226); config 5 of BASELINE.json uses 48;
@@ -351,3 +354,105 @@ class NeuralModel(CXModelBase):
         batch = ops.Batch.from_dense(image_features.float(), q_emb.float(), z_orig.float(), z_knns.float(),
                                      a_knns.float(), answer_aids, **extra)
         return self.score_batch(batch)
+
+
+class _ScorerFunction(torch.autograd.Function):
+    """scores = scorer(inputs; params) with the hand-written HIP backward (ncx_pairlin_backward / ncx_linctx_backward).
+    `call` = {kind, dims, batch, names}: backward reads the dims, inputs and workspace of ITS forward from ctx."""
+
+    @staticmethod
+    def forward(ctx, call, *param_tensors):
+        d, batch, names = call["dims"], call["batch"], call["names"]
+        params = dict(zip(names, param_tensors))
+        dev = batch.z_knns.device
+        if call["kind"] == "pairlin":
+            ws = ops.pairlin_workspace(d, dev)
+            flag = torch.zeros(1, dtype=torch.int32, device=dev)
+            scores = ops.pairlin_forward(d, batch, params, ws, bad_flag=flag)
+            ops.check_semantic_ids(flag)            # nn.Embedding / the feature indexing raise on a bad index (cx.py:408-414)
+        else:
+            ws = ops.linctx_workspace(d, dev)
+            scores = ops.linctx_forward(d, batch.z_knns, params["w"], params["b"], ws)
+        ctx.call, ctx.ws = call, ws
+        ctx.save_for_backward(*param_tensors)
+        return scores
+
+    @staticmethod
+    def backward(ctx, dscores):
+        if ctx.ws is None:
+            raise RuntimeError("backward ran twice on one forward (retain_graph is not supported)")
+        call = ctx.call
+        d, batch, names = call["dims"], call["batch"], call["names"]
+        params = dict(zip(names, ctx.saved_tensors))
+        grads = {n: torch.empty_like(t) for n, t in params.items()}
+        dscores = dscores.float().contiguous()
+        if call["kind"] == "pairlin":
+            ops.pairlin_backward(d, batch, params, ctx.ws, dscores, grads)
+        else:
+            ops.linctx_backward(d, batch.z_knns, dscores, ctx.ws, grads["w"], grads["b"])
+        ctx.ws = None
+        return (None,) + tuple(grads[n] for n in names)
+
+
+class _TrainableScorer(CXModelBase):
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        if self.trainable_vqa:
+            raise NotImplementedError("trainable_vqa=True is not supported by the HIP path (frozen VQA model only)")
+
+    def _score(self, call, fields):
+        names = tuple(fields)
+        for t in fields.values():
+            if not t.is_cuda:
+                raise ops._lib.NcxError("%s runs on the GPU: call .cuda() (no CPU fallback)" % type(self).__name__)
+        call["names"] = names
+        return _ScorerFunction.apply(call, *[fields[n] for n in names])
+
+
+class LinearContext(_TrainableScorer):
+    """cx.py:139-156: scores = linear(z_knns.view(B, K dz)), linear = nn.Linear(K dz, K).  Forward and backward run in the
+    HIP library (ncx_linctx_forward / _backward); state_dict keys linear.weight, linear.bias (+ vqa_model.*)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.dim_z = self.vqa_model.opt["fusion"]["dim_mm"]
+        self.linear = nn.Linear(self.knn_size * self.dim_z, self.knn_size)
+
+    def forward(self, image_features, question_wids, answer_aids):
+        if not image_features.is_cuda:
+            raise ops._lib.NcxError("LinearContext runs on the GPU: move the inputs and the model there (no CPU fallback)")
+        _, _, _, z_knns, _ = self.vqa_forward(image_features, question_wids)
+        z_knns = z_knns.float().contiguous()
+        batch = ops.Batch(None, None, None, None, z_knns, None)
+        return self._score(dict(kind="linctx", dims=ops.linctx_dims(z_knns), batch=batch),
+                           {"w": self.linear.weight, "b": self.linear.bias})
+
+
+class PairwiseLinearModel(_TrainableScorer):
+    """cx.py:379-425: per candidate, relu(out(relu(linear(cat(v_orig, v_other, q_emb, z_orig, z_other, a_emb))))).  The concat is
+    never built (ncx_pairlin_forward / _backward, csrc/ncx_scorers.hip); state_dict keys answer_embedding.weight, linear.*,
+    out.* (+ vqa_model.*).  An answer id outside [0, A) raises IndexError (one host sync per forward)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        assert self.knn_size == 24                              # cx.py:384
+        fus = self.vqa_model.opt["fusion"]
+        self.dim_v, self.dim_q, self.dim_z = fus["dim_v"], fus["dim_q"], fus["dim_mm"]
+        self.dim_h = ops.PAIRLIN_H
+        self.dim_a = ops.PAIRLIN_H
+        self.answer_embedding = nn.Embedding(len(self.vqa_model.vocab_answers), self.dim_a)
+        self.linear = nn.Linear((2 * self.dim_v) + self.dim_q + (2 * self.dim_z) + self.dim_a, self.dim_h)
+        self.out = nn.Linear(self.dim_h, 1)
+        self.relu = nn.ReLU()
+
+    def forward(self, image_features, question_wids, answer_aids):
+        if not image_features.is_cuda:
+            raise ops._lib.NcxError("PairwiseLinearModel runs on the GPU: move the inputs and the model there (no CPU fallback)")
+        assert image_features.size(1) - 1 == self.knn_size     # cx.py:403
+        _, z_orig, _, z_knns, q_emb = self.vqa_forward(image_features, question_wids)
+        batch = ops.Batch.from_dense(image_features.float(), q_emb.float(), z_orig.float(), z_knns.float(),
+                                     z_knns.float(), answer_aids)
+        fields = {"answer_embedding": self.answer_embedding.weight, "w": self.linear.weight, "b": self.linear.bias,
+                  "w_out": self.out.weight, "b_out": self.out.bias}
+        return self._score(dict(kind="pairlin", dims=ops.pairlin_dims(batch, self.answer_embedding.num_embeddings), batch=batch),
+                           fields)
