@@ -339,6 +339,44 @@ int ncx_linctx_forward(const ncx_scorer_dims* d, const float* z_knns, const floa
 int ncx_linctx_backward(const ncx_scorer_dims* d, const float* z_knns, const float* dscores, void* workspace,
                         size_t workspace_bytes, float* gw, float* gb, void* stream);
 
+/* ---- the contrastive training path (reference contrastive.py; ContrastiveModel, vqa/models/cx.py:428-487) --------------------
+ * A siamese embedding h = relu(linear(cat(v, z))) of the P = knn_size + 1 images of an example (slot 0 the original), hidden
+ * width 300 (cx.py:437), trained with a margin loss on distances.  linear.weight is [300, dv + dz], columns v | z (cx.py:445,
+ * 471).  The model's answer_embedding.weight (cx.py:440-441) is never read and never receives a gradient: it has no entry here.
+ * Dims: B >= 1, 1 <= P - 1 <= 64, dv >= 4, dz >= 4, n_img >= 1 (rows of the feature table). */
+typedef struct ncx_contrastive_dims {
+    int32_t B, P, dv, dz, n_img;
+} ncx_contrastive_dims;
+/* Workspace of the four entry points below (256-byte aligned); 0 for unsupported dims.  distances / loss / backward read what
+ * the forward left there: call them with the same dims and workspace. */
+size_t ncx_contrastive_workspace_bytes(const ncx_contrastive_dims* d);
+/* Replaces ContrastiveModel.forward below vqa_forward (cx.py:448-472): h [B, P, 300] (nullable: it always stays in the workspace).
+ * Reads in->feats, img_idx [B, P], z_orig [B, dz], z_knns [B, P - 1, dz]; w = linear.weight, b = linear.bias.  The feature rows are
+ * gathered by id, never copied out dense.  A row id out of range is clamped and sets *bad_id_flag to 1 (never cleared here; the
+ * reference's indexing raises there). */
+int ncx_contrastive_forward(const ncx_contrastive_dims* d, const ncx_inputs* in, const float* w, const float* b, void* workspace,
+                            size_t workspace_bytes, float* h, int32_t* bad_id_flag, void* stream);
+/* Replaces ContrastiveModel.get_scores (cx.py:478-487): dist [B, P - 1], dist[b, k] = || h[b, 0] - h[b, k + 1] + 1e-6 ||_2
+ * (F.pairwise_distance).  h [B, P, 300] (16-byte aligned), or NULL: the h the forward left in the workspace (with h given the
+ * workspace is not read and may be NULL).  The evaluation (contrastive.py:274-279) ranks the distances with ncx_loss_rank: the
+ * counterexample should be the farthest. */
+int ncx_contrastive_distances(const ncx_contrastive_dims* d, const float* h, void* workspace, size_t workspace_bytes, float* dist,
+                              void* stream);
+/* Replaces the two ContrastiveLoss calls and loss.backward() down to the pre-activation (contrastive.py:217-219, 300-309), P = 3
+ * (original, counterexample, one other neighbour):
+ *   losses4 = scale x {sum_b max(margin - d_b1, 0)^2, sum_b d_b2^2, sum_b d_b1, sum_b d_b2}: with scale = 1 / B the reference's
+ *   loss_comp, loss_other and the two mean distances it logs (contrastive.py:229-231); dist [B, 2] = the per-example distances
+ *   (nullable).  The gradient with respect to the pre-activation stays in the workspace for ncx_contrastive_backward.
+ * Sums over b run in a fixed order: bit-identical from run to run. */
+int ncx_contrastive_loss(const ncx_contrastive_dims* d, void* workspace, size_t workspace_bytes, float margin, float scale,
+                         float* losses4, float* dist, void* stream);
+/* The rest of loss.backward() (contrastive.py:223): gw = d linear.weight [300, dv + dz], gb = d linear.bias [300] (overwritten).
+ * dh == NULL: from the pre-activation gradient ncx_contrastive_loss left in the workspace.  dh [B, P, 300] (16-byte aligned): the
+ * gradient with respect to h from outside (autograd of a caller's own loss); the ReLU mask is applied here.  Reads in->feats; the
+ * row ids and z are the ones the forward left in the workspace. */
+int ncx_contrastive_backward(const ncx_contrastive_dims* d, const ncx_inputs* in, void* workspace, size_t workspace_bytes,
+                             const float* dh, float* gw, float* gb, void* stream);
+
 /* ---- diagnostics (bench.py / tests only; the only process-global state, off by default) --------------
  * GEMM ids: 0 Gt = W1[:,a_other].E^T, 1 Sh (shared segments), 2 MAIN (candidate segments, the dominant
  * forward kernel), 3 hidden layer l>=2 forward, 4 dW1 candidate columns (+dGt; the dominant backward

@@ -23,7 +23,9 @@ EXPORTS = ("ncx_input_size", "ncx_workspace_bytes", "ncx_forward", "ncx_forward_
            "ncx_ws_region", "ncx_wgmap_check",
            "ncx_comm_unique_id", "ncx_comm_create", "ncx_comm_destroy", "ncx_allreduce", "ncx_train_tail", "ncx_profile_stamps",
            "ncx_pairlin_workspace_bytes", "ncx_pairlin_forward", "ncx_pairlin_backward",
-           "ncx_linctx_workspace_bytes", "ncx_linctx_forward", "ncx_linctx_backward")
+           "ncx_linctx_workspace_bytes", "ncx_linctx_forward", "ncx_linctx_backward",
+           "ncx_contrastive_workspace_bytes", "ncx_contrastive_forward", "ncx_contrastive_distances", "ncx_contrastive_loss",
+           "ncx_contrastive_backward")
 
 
 class NcxDims(C.Structure):
@@ -57,6 +59,10 @@ class NcxMutanParams(C.Structure):
 
 class NcxScorerDims(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("B", "K", "dv", "dq", "dz", "A", "n_img")]
+
+
+class NcxContrastiveDims(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "P", "dv", "dz", "n_img")]
 
 
 _PL_NAMES = ("answer_embedding", "w", "b", "w_out", "b_out")
@@ -166,6 +172,19 @@ def lib():
     L.ncx_linctx_forward.argtypes = [P_SD, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     L.ncx_linctx_backward.restype = C.c_int
     L.ncx_linctx_backward.argtypes = [P_SD, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    P_CD = C.POINTER(NcxContrastiveDims)
+    L.ncx_contrastive_workspace_bytes.restype = C.c_size_t
+    L.ncx_contrastive_workspace_bytes.argtypes = [P_CD]
+    L.ncx_contrastive_forward.restype = C.c_int
+    L.ncx_contrastive_forward.argtypes = [P_CD, C.POINTER(NcxInputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
+    L.ncx_contrastive_distances.restype = C.c_int
+    L.ncx_contrastive_distances.argtypes = [P_CD, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.ncx_contrastive_loss.restype = C.c_int
+    L.ncx_contrastive_loss.argtypes = [P_CD, C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ncx_contrastive_backward.restype = C.c_int
+    L.ncx_contrastive_backward.argtypes = [P_CD, C.POINTER(NcxInputs), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]
     _lib = L
     return L
 

@@ -8,6 +8,8 @@ hot path runs in libneuralcx_hip.so.  Reference surface these mirror:
   adam_step                              torch.optim.Adam as used at counterexamples.py:275-276,339
   cosine_gram / semantic_scores          SemanticBaseline.set_answer_embedding / forward (vqa/models/cx.py:174-175,182-209)
   pairlin_* / linctx_*                   PairwiseLinearModel / LinearContext forward and loss.backward() (cx.py:139-156,379-425)
+  contrastive_*                          ContrastiveModel.forward / get_scores, ContrastiveLoss and loss.backward()
+                                         (cx.py:428-487, contrastive.py:217-223,293-309)
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -462,6 +464,91 @@ def linctx_backward(d, z_knns: torch.Tensor, dscores: torch.Tensor, ws: torch.Te
     _lib.check(_lib.lib().ncx_linctx_backward(C.byref(d), _ptr(z_knns, torch.float32, "z_knns"), _ptr(dscores, torch.float32, "dscores"),
                                               p, n, _ptr(gw, torch.float32, "gw"), _ptr(gb, torch.float32, "gb"), _stream()),
                "ncx_linctx_backward")
+
+# ---- the contrastive path: ContrastiveModel + ContrastiveLoss (include/neuralcx.h) ----------------------------------------------
+CONTRASTIVE_H = 300                 # dim_h = dim_a = 300 (cx.py:437-439)
+CONTRASTIVE_MARGIN = 2.0            # ContrastiveLoss(margin=2.0), contrastive.py:300
+# answer_embedding.weight is constructed and saved but never read (cx.py:440-441, 458): it has no C ABI field
+CONTRASTIVE_STATE_TO_FIELD = {"linear.weight": "w", "linear.bias": "b"}
+
+
+def contrastive_shapes(dv, dz, A):
+    """state_dict of ContrastiveModel, in the order Adam's span is cut: linear.* first (trained), the embedding last (never)."""
+    return {"linear.weight": (CONTRASTIVE_H, dv + dz), "linear.bias": (CONTRASTIVE_H,), "answer_embedding.weight": (A, CONTRASTIVE_H)}
+
+
+def contrastive_dims(batch: Batch) -> _lib.NcxContrastiveDims:
+    """batch.img_idx [B, P], z_orig [B, dz], z_knns [B, P - 1, dz]; q_emb / a_knns / answer_aids are not read."""
+    B, P = batch.img_idx.shape
+    d = _lib.NcxContrastiveDims()
+    d.B, d.P, d.dv, d.dz, d.n_img = B, P, batch.feats.shape[1], batch.z_orig.shape[1], batch.feats.shape[0]
+    assert batch.z_orig.shape == (B, d.dz) and batch.z_knns.shape == (B, P - 1, d.dz), (batch.z_orig.shape, batch.z_knns.shape)
+    return d
+
+
+def contrastive_workspace(d, device) -> torch.Tensor:
+    n = _lib.lib().ncx_contrastive_workspace_bytes(C.byref(d))
+    if n == 0:
+        raise _lib.NcxError("ncx_contrastive_workspace_bytes: unsupported dims (1 <= P - 1 <= 64, dv >= 4, dz >= 4)")
+    return torch.empty(n + 256, dtype=torch.uint8, device=device)
+
+
+def _contrastive_inputs(batch: Batch) -> NcxInputs:
+    s = NcxInputs()
+    s.feats = _ptr(batch.feats, torch.float32, "feats")
+    s.img_idx = _ptr(batch.img_idx, torch.int32, "img_idx")
+    s.z_orig = _ptr(batch.z_orig, torch.float32, "z_orig")
+    s.z_knns = _ptr(batch.z_knns, torch.float32, "z_knns")
+    return s
+
+
+def contrastive_forward(d, batch: Batch, w: torch.Tensor, b: torch.Tensor, ws: torch.Tensor, bad_flag: Optional[torch.Tensor] = None,
+                        want_h: bool = True) -> Optional[torch.Tensor]:
+    """h [B, P, 300] = relu(linear(cat(v, z))) (ncx_contrastive_forward); h, the clamped row ids and z stay in `ws` for
+    contrastive_distances / _loss / _backward.  want_h = False: nothing is copied out (the engine's steps read the workspace).
+    A feature row out of range sets `bad_flag` (default: semantic_bad_flag(device); check_semantic_ids raises)."""
+    dev = batch.z_knns.device
+    if bad_flag is None:
+        bad_flag = semantic_bad_flag(dev)
+    h = torch.empty(d.B, d.P, CONTRASTIVE_H, dtype=torch.float32, device=dev) if want_h else None
+    p, n = _ws_ptr(ws)
+    _lib.check(_lib.lib().ncx_contrastive_forward(C.byref(d), C.byref(_contrastive_inputs(batch)), _ptr(w, torch.float32, "w"),
+                                                  _ptr(b, torch.float32, "b"), p, n, _ptr(h, torch.float32, "h"),
+                                                  _ptr(bad_flag, torch.int32, "bad_flag"), _stream()), "ncx_contrastive_forward")
+    return h
+
+
+def contrastive_distances(d, ws: Optional[torch.Tensor] = None, h: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dist [B, P - 1] = ||h_0 - h_k + 1e-6|| (get_scores, cx.py:478-487) from the h contrastive_forward left in `ws`, or from a
+    given h [B, P, 300]."""
+    dev = h.device if h is not None else ws.device
+    dist = torch.empty(d.B, d.P - 1, dtype=torch.float32, device=dev)
+    p, n = _ws_ptr(ws) if ws is not None else (None, 0)
+    _lib.check(_lib.lib().ncx_contrastive_distances(C.byref(d), _ptr(h, torch.float32, "h"), p, n, C.c_void_p(dist.data_ptr()), _stream()),
+               "ncx_contrastive_distances")
+    return dist
+
+
+def contrastive_loss(d, ws: torch.Tensor, scale: Optional[float] = None, margin: float = CONTRASTIVE_MARGIN):
+    """The two ContrastiveLoss terms of a P = 3 batch (contrastive.py:217-219) and the gradient down to the pre-activation (left in
+    `ws`).  -> dict(loss_comp, loss_other, loss, dist_comp, dist_other: 0-d device tensors; dist [B, 2])."""
+    dev = ws.device
+    out = torch.empty(4, dtype=torch.float32, device=dev)
+    dist = torch.empty(d.B, 2, dtype=torch.float32, device=dev)
+    p, n = _ws_ptr(ws)
+    _lib.check(_lib.lib().ncx_contrastive_loss(C.byref(d), p, n, float(margin), float(1.0 / d.B if scale is None else scale),
+                                               C.c_void_p(out.data_ptr()), C.c_void_p(dist.data_ptr()), _stream()), "ncx_contrastive_loss")
+    return dict(loss_comp=out[0], loss_other=out[1], loss=out[0] + out[1], dist_comp=out[2], dist_other=out[3], dist=dist)
+
+
+def contrastive_backward(d, batch: Batch, ws: torch.Tensor, gw: torch.Tensor, gb: torch.Tensor, dh: Optional[torch.Tensor] = None) -> None:
+    """d linear.weight / d linear.bias (ncx_contrastive_backward) from the pre-activation gradient contrastive_loss left in `ws`, or
+    from an outside gradient dh [B, P, 300] with respect to h."""
+    p, n = _ws_ptr(ws)
+    s = NcxInputs()
+    s.feats = _ptr(batch.feats, torch.float32, "feats")
+    _lib.check(_lib.lib().ncx_contrastive_backward(C.byref(d), C.byref(s), p, n, _ptr(dh, torch.float32, "dh"), _ptr(gw, torch.float32, "gw"),
+                                                   _ptr(gb, torch.float32, "gb"), _stream()), "ncx_contrastive_backward")
 
 
 class WorkspacePool:

@@ -11,7 +11,7 @@ on a machine without the library or without a GPU `forward` raises.  `SemanticBa
 reference's surface likewise; its cosine Gram and scorer run in the same library (see its docstring).  `LinearContext`
 (cx.py:139-156) and `PairwiseLinearModel` (cx.py:379-425) keep the reference's constructor, submodule names and state_dict
 keys; their forward and backward run in the library through an autograd.Function, so the reference's loop with
-torch.optim.Adam trains them.
+torch.optim.Adam trains them.  `ContrastiveModel` (cx.py:428-487), the model of the reference's second script contrastive.py, likewise.
 
 Deliberate differences from the reference (all supersets):
   * knn_size may be 1..64 (the reference asserts == 24, cx.py:226); config 5 of BASELINE.json uses 48;
@@ -456,3 +456,80 @@ class PairwiseLinearModel(_TrainableScorer):
                   "w_out": self.out.weight, "b_out": self.out.bias}
         return self._score(dict(kind="pairlin", dims=ops.pairlin_dims(batch, self.answer_embedding.num_embeddings), batch=batch),
                            fields)
+
+
+class _ContrastiveFunction(torch.autograd.Function):
+    """h = relu(linear(cat(v, z))) for the P images of every example, with the hand-written HIP backward
+    (ncx_contrastive_forward / _backward).  `call` = {dims, batch}: backward reads the dims, inputs and workspace of ITS forward."""
+
+    @staticmethod
+    def forward(ctx, call, w, b):
+        d, batch = call["dims"], call["batch"]
+        dev = batch.z_knns.device
+        ws = ops.contrastive_workspace(d, dev)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        h = ops.contrastive_forward(d, batch, w, b, ws, bad_flag=flag)
+        ctx.call, ctx.ws = call, ws
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        if ctx.ws is None:
+            raise RuntimeError("backward ran twice on one forward (retain_graph is not supported)")
+        d, batch = ctx.call["dims"], ctx.call["batch"]
+        gw = torch.empty(ops.CONTRASTIVE_H, d.dv + d.dz, dtype=torch.float32, device=dh.device)
+        gb = torch.empty(ops.CONTRASTIVE_H, dtype=torch.float32, device=dh.device)
+        ops.contrastive_backward(d, batch, ctx.ws, gw, gb, dh=dh.float().contiguous())
+        ctx.ws = None
+        return None, gw, gb
+
+
+class ContrastiveModel(CXModelBase):
+    """cx.py:428-487: a siamese embedding of the knn_size + 1 images of an example, h = relu(linear(cat(v_i, z_i))) [B, P, 300],
+    trained by contrastive.py with ContrastiveLoss on distances.  Forward and backward run in the HIP library
+    (csrc/ncx_contrastive.hip) through an autograd.Function, so the reference's own loss and torch.optim.Adam train it unchanged.
+    State keys answer_embedding.weight (constructed, never used, never given a gradient: cx.py:440-441, 458), linear.weight
+    [300, dim_v + dim_mm] (columns v | z), linear.bias (+ vqa_model.*).  knn_size is mutable (the reference flips it 2 <-> 24
+    around evaluation, contrastive.py:270, 287); 1..64 here."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        if self.trainable_vqa:
+            raise NotImplementedError("trainable_vqa=True is not supported by the HIP path (frozen VQA model only)")
+        fus = self.vqa_model.opt["fusion"]
+        self.dim_v, self.dim_q, self.dim_z = fus["dim_v"], fus["dim_q"], fus["dim_mm"]
+        self.dim_h = ops.CONTRASTIVE_H
+        self.dim_a = ops.CONTRASTIVE_H
+        self.answer_embedding = nn.Embedding(len(self.vqa_model.vocab_answers), self.dim_a)
+        self.linear = nn.Linear(self.dim_v + self.dim_z, self.dim_h)
+        self.relu = nn.ReLU()
+
+    def _embed(self, feats, img_idx, z_orig, z_knns):
+        if not (feats.is_cuda and self.linear.weight.is_cuda):
+            raise ops._lib.NcxError("ContrastiveModel runs on the GPU: move the inputs and the model there (no CPU fallback)")
+        batch = ops.Batch(feats.float().contiguous(), img_idx, None, z_orig.float().contiguous(), z_knns.float().contiguous(), None)
+        d = ops.contrastive_dims(batch)
+        return _ContrastiveFunction.apply(dict(dims=d, batch=batch), self.linear.weight, self.linear.bias)
+
+    def forward(self, image_features, question_wids, answer_aids):
+        B, P = image_features.size(0), image_features.size(1)
+        assert P == self.knn_size + 1                              # cx.py:451
+        _, z_orig, _, z_knns, _ = self.vqa_forward(image_features, question_wids)
+        feats = image_features.reshape(B * P, -1)
+        idx = torch.arange(B * P, device=feats.device, dtype=torch.int32).view(B, P)
+        return self._embed(feats, idx, z_orig, z_knns)
+
+    def get_hidden(self, v, z):
+        """relu(linear(cat(v, z))) for one image per row (cx.py:470-472): the library embeds at least two images per example, so
+        every row is presented twice and slot 0 returned."""
+        B = v.size(0)
+        idx = torch.arange(B, device=v.device, dtype=torch.int32).view(B, 1).expand(B, 2).contiguous()
+        return self._embed(v, idx, z, z.reshape(B, 1, -1))[:, 0]
+
+    @torch.no_grad()
+    def get_scores(self, h_orig, h_knns):
+        """Distances [B, P - 1] of every neighbour's embedding to the original's (cx.py:478-487), a device tensor."""
+        h = torch.cat([h_orig.unsqueeze(1), h_knns], dim=1).float().contiguous()
+        d = ops._lib.NcxContrastiveDims()
+        d.B, d.P, d.dv, d.dz, d.n_img = h.size(0), h.size(1), self.dim_v, self.dim_z, 1
+        return ops.contrastive_distances(d, h=h)
