@@ -296,6 +296,26 @@ int ncx_cosine_gram(const float* emb, int32_t A, int32_t da, void* ws, size_t ws
 int ncx_semantic_scores(const float* a_knns, const int32_t* aid, int32_t B, int32_t K, int32_t A, const float* gram,
                         float lam, float* scores, float* raw, int32_t* bad_id_flag, void* stream);
 
+/* ---- the similarity scorer (reference vqa/models/cx.py:490-518, SimilarityModel; no parameters) --------------------------
+ * ncx_similarity_scores replaces the scorer's loop over the candidates (cx.py:511-516) for a batch, in one launch:
+ *   scores[b, k] = cos(v_orig[b], v_knn[b, k]) + cos(z_orig[b], z_knn[b, k]) + CE(a_knns[b, k, :], aid[b])     (higher = better)
+ *   cos(x, y) = x . y / (max(|x|, 1e-8) max(|y|, 1e-8))  -- each norm clamped on its own, as F.cosine_similarity of
+ *               torch >= 1.12 does (tests/golden/g13_similarity.npz pins it with a row of norm < 1e-8 against one of norm
+ *               100: the older rule max(|x| |y|, 1e-8) gives ten times the value); an all-zero row gives 0
+ *   CE(a, aid) = logsumexp(a) - a[aid], the max subtracted first
+ * feats [n_img, dv] is the resident feature table and img_idx [B, K + 1] its row ids (column 0 the original image, 1..K
+ * the candidates): rows are gathered by id inside the kernel.  z_orig [B, dz], z_knns [B, K, dz], a_knns [B, K, A] logits,
+ * aid [B].  scores [B, K]; parts [B, K, 3] = v_cos | z_cos | xent (nullable).  A row id outside [0, n_img) or an answer id
+ * outside [0, A) is never read at: that question's row (and its parts) is NaN and *bad_id_flag is set to 1 (never cleared
+ * here; the caller zeroes it).  16-byte loads where a base pointer is 16-byte aligned and the row length a multiple of 4,
+ * dword loads otherwise.  1 <= K <= 64, 1 <= A <= 4096, dv, dz, n_img, B >= 1.  No atomics: bit-identical from run to run. */
+int ncx_similarity_scores(const float* feats, const int32_t* img_idx, int32_t n_img, int32_t dv,
+                          const float* z_orig, const float* z_knns, int32_t dz,
+                          const float* a_knns, const int32_t* aid, int32_t A,
+                          int32_t B, int32_t K,
+                          float* scores /*[B,K]*/, float* parts /*[B,K,3] v_cos|z_cos|xent, nullable*/,
+                          int32_t* bad_id_flag, void* stream);
+
 /* ---- the trainable scorers LinearContext and PairwiseLinearModel (reference vqa/models/cx.py:139-156, 379-425) ---------
  * Both train with the library's loss (ncx_loss_rank) and optimiser (ncx_adam_step): forward -> scores, ncx_loss_rank ->
  * dscores, backward -> gradients (the reference's loop, counterexamples.py:330-339).  Neither model has dropout.

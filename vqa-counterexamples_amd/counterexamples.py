@@ -50,7 +50,7 @@ def build_parser():
     p.add_argument("--path_opt", default=os.path.join(HERE, "options", "cx", "neuralcx_256_1_all.yaml"), type=str)
     p.add_argument("--vqa_model", default="mutan_noatt_train", type=str)
     # (the reference makes -cx required, counterexamples.py:44; here NeuralModel is the default and the flag spellings are kept)
-    p.add_argument("-cx", "--cx_model", default="NeuralModel", type=str, help="NeuralModel | LinearContext | PairwiseLinearModel | RandomBaseline | DistanceBaseline | BlackBox | SemanticBaseline")
+    p.add_argument("-cx", "--cx_model", default="NeuralModel", type=str, help="NeuralModel | LinearContext | PairwiseLinearModel | RandomBaseline | DistanceBaseline | BlackBox | SemanticBaseline | SimilarityModel")
     p.add_argument("-lb", "--sb_lambda", type=float, help="semantic baseline lambda (counterexamples.py:49): required by -cx SemanticBaseline; "
                                                           "the other models ignore it (with a warning)")
     p.add_argument("--pairwise", action="store_true")
@@ -126,7 +126,8 @@ class Runner:
         self.gb = options["optim"]["batch_size"]
         self.baseline = None if args.cx_model in TRAINABLE else args.cx_model
         self.runs_dir = None
-        self.sem_gram = self.sem_flag = None
+        self.sem_gram = None
+        self.sem_flag = torch.zeros(1, dtype=torch.int32, device=self.dev) if self.baseline == "SimilarityModel" else None
 
     def log(self, *a):
         if self.rank == 0:
@@ -276,6 +277,10 @@ class Runner:
             # cx.py:182-209; its probabilities go to the loss / Recall kernel as the reference's eval_model feeds them to
             # CrossEntropyLoss and recallAtK (:464-466).  A bad answer id is reported after the loop (main), not per batch.
             scores = ops.semantic_scores(b.a_knns, b.answer_aids, self.sem_gram, self.args.sb_lambda, bad_flag=self.sem_flag)
+        elif self.baseline == "SimilarityModel":
+            # cx.py:496-518 on the resident batch: the rows are gathered from the table inside the kernel.  Net-new on the command
+            # line (the reference's main never constructs this class).  Bad ids are reported after the loop (main).
+            scores = ops.similarity_scores(b.feats, b.img_idx, b.z_orig, b.z_knns, b.a_knns, b.answer_aids, bad_flag=self.sem_flag)
         else:
             scores = blackbox_scores(b.a_knns, b.answer_aids).contiguous()
         r = ops.ranking_loss(scores, gt, want_grad=False)
@@ -333,7 +338,7 @@ class Runner:
 
 
 TRAINABLE = ("NeuralModel", "LinearContext", "PairwiseLinearModel")
-SCORERS = TRAINABLE + ("RandomBaseline", "DistanceBaseline", "BlackBox", "SemanticBaseline")
+SCORERS = TRAINABLE + ("RandomBaseline", "DistanceBaseline", "BlackBox", "SemanticBaseline", "SimilarityModel")
 
 
 def synthetic_answer_embedding(n_answers, dim_a=2400, seed=2400):
@@ -373,7 +378,7 @@ def main(argv=None):
         res = r.evaluate(r.test if args.test else r.val)
         torch.cuda.synchronize()
         if r.sem_flag is not None:
-            ops.check_semantic_ids(r.sem_flag)
+            (ops.check_similarity_ids if r.baseline == "SimilarityModel" else ops.check_semantic_ids)(r.sem_flag)
         n = (r.test if args.test else r.val).N
         r.report("test" if args.test else "val", 1, res)
         r.log("{}: {} triplets in {:.2f} s ({:.0f} triplets/s)".format(r.baseline, n, time.time() - t0, n / (time.time() - t0)))

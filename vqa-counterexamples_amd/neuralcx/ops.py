@@ -7,6 +7,7 @@ hot path runs in libneuralcx_hip.so.  Reference surface these mirror:
   ranking_loss                           counterexamples.py:310,334 + recallAtK (counterexamples.py:501-506)
   adam_step                              torch.optim.Adam as used at counterexamples.py:275-276,339
   cosine_gram / semantic_scores          SemanticBaseline.set_answer_embedding / forward (vqa/models/cx.py:174-175,182-209)
+  similarity_scores                      SimilarityModel.forward (vqa/models/cx.py:496-518)
   pairlin_* / linctx_*                   PairwiseLinearModel / LinearContext forward and loss.backward() (cx.py:139-156,379-425)
   contrastive_*                          ContrastiveModel.forward / get_scores, ContrastiveLoss and loss.backward()
                                          (cx.py:428-487, contrastive.py:217-223,293-309)
@@ -366,6 +367,52 @@ def check_semantic_ids(bad_flag: Optional[torch.Tensor] = None, device=None) -> 
     if int(bad_flag.item()):
         bad_flag.zero_()
         raise IndexError("answer_aids outside [0, A) in a semantic_scores call")
+
+
+def similarity_scores(feats: torch.Tensor, img_idx: torch.Tensor, z_orig: torch.Tensor, z_knns: torch.Tensor, a_knns: torch.Tensor,
+                      aids: torch.Tensor, bad_flag: Optional[torch.Tensor] = None, want_parts: bool = False):
+    """The similarity scorer (ncx_similarity_scores; reference cx.py:496-518) on the current stream, no host sync:
+    feats [n_img, dv] feature table, img_idx [B, K + 1] its row ids (column 0 the original image), z_orig [B, dz], z_knns
+    [B, K, dz], a_knns [B, K, A] logits, aids [B] -> scores [B, K] = cos(v) + cos(z) + cross-entropy (higher = better), and with
+    want_parts the three terms [B, K, 3] as well: (scores, parts).  The rows are gathered by id inside the kernel.
+    A row id outside [0, n_img) or an answer id outside [0, A) leaves NaN in its question's row and sets `bad_flag` (default:
+    semantic_bad_flag(device)); check_similarity_ids raises the IndexError -- deferred, as for semantic_scores."""
+    if feats.dim() != 2 or img_idx.dim() != 2 or a_knns.dim() != 3:
+        raise ValueError("similarity_scores takes feats [n_img, dv], img_idx [B, K + 1], a_knns [B, K, A]; got %s, %s, %s"
+                         % (tuple(feats.shape), tuple(img_idx.shape), tuple(a_knns.shape)))
+    B, K, A = a_knns.shape
+    n_img, dv = feats.shape
+    if tuple(img_idx.shape) != (B, K + 1):
+        raise ValueError("img_idx must be [%d, %d], got %s" % (B, K + 1, tuple(img_idx.shape)))
+    if z_orig.dim() != 2 or z_orig.shape[0] != B or tuple(z_knns.shape) != (B, K, z_orig.shape[1]):
+        raise ValueError("z_orig must be [%d, dz] and z_knns [%d, %d, dz], got %s and %s" % (B, B, K, tuple(z_orig.shape), tuple(z_knns.shape)))
+    if tuple(aids.shape) != (B,):
+        raise ValueError("aids must be [%d], got %s" % (B, tuple(aids.shape)))
+    dev = a_knns.device
+    feats, z_orig, z_knns, a_knns = (t.float().contiguous() for t in (feats, z_orig, z_knns, a_knns))
+    img_idx, aids = img_idx.to(torch.int32).contiguous(), aids.to(torch.int32).contiguous()
+    if bad_flag is None:
+        bad_flag = semantic_bad_flag(dev)
+    scores = torch.empty(B, K, dtype=torch.float32, device=dev)
+    parts = torch.empty(B, K, 3, dtype=torch.float32, device=dev) if want_parts else None
+    _lib.check(_lib.lib().ncx_similarity_scores(_ptr(feats, torch.float32, "feats"), _ptr(img_idx, torch.int32, "img_idx"), n_img, dv,
+                                                _ptr(z_orig, torch.float32, "z_orig"), _ptr(z_knns, torch.float32, "z_knns"),
+                                                z_orig.shape[1], _ptr(a_knns, torch.float32, "a_knns"), _ptr(aids, torch.int32, "aids"),
+                                                A, B, K, C.c_void_p(scores.data_ptr()), _ptr(parts, torch.float32, "parts"),
+                                                _ptr(bad_flag, torch.int32, "bad_flag"), _stream()),
+               "ncx_similarity_scores")
+    return (scores, parts) if want_parts else scores
+
+
+def check_similarity_ids(bad_flag: Optional[torch.Tensor] = None, device=None) -> None:
+    """Raises IndexError (what the reference's indexing of the feature table and F.cross_entropy's target check raise) if a
+    similarity_scores call since the last check saw a feature row id outside [0, n_img) or an answer id outside [0, A);
+    clears the flag.  Synchronises with the flag's stream."""
+    if bad_flag is None:
+        bad_flag = semantic_bad_flag(device if device is not None else "cuda")
+    if int(bad_flag.item()):
+        bad_flag.zero_()
+        raise IndexError("feature row ids outside [0, n_img) or answer_aids outside [0, A) in a similarity_scores call")
 
 
 # ---- the trainable scorers LinearContext and PairwiseLinearModel (include/neuralcx.h) -----------------------------------------

@@ -12,6 +12,9 @@ reference's surface likewise; its cosine Gram and scorer run in the same library
 (cx.py:139-156) and `PairwiseLinearModel` (cx.py:379-425) keep the reference's constructor, submodule names and state_dict
 keys; their forward and backward run in the library through an autograd.Function, so the reference's loop with
 torch.optim.Adam trains them.  `ContrastiveModel` (cx.py:428-487), the model of the reference's second script contrastive.py, likewise.
+`SimilarityModel` (cx.py:490-518) has no parameters: its scorer is one HIP launch per batch (see its docstring).  Every name the
+reference's counterexamples.py imports from this module (counterexamples.py:30-32) exists here; `PairwiseModel` (cx.py:336-376) is
+the one without an implementation: its constructor raises.
 
 Deliberate differences from the reference (all supersets):
   * knn_size may be 1..64 (the reference asserts == 24, cx.py:226); config 5 of BASELINE.json uses 48;
@@ -213,6 +216,54 @@ class SemanticBaseline(CXModelBase):
                                      float(self.lam), bad_flag=flag)
         ops.check_semantic_ids(flag)            # (the reference reads its scores back to the host per batch as well)
         return scores.requires_grad_(True)      # cx.py:209
+
+
+class SimilarityModel(CXModelBase):
+    """Scores candidates by similarity to the original in image-feature and fusion space plus the VQA model's loss on the
+    original answer (reference cx.py:490-518; no parameters of its own):
+        scores[b, k] = cos(v_orig[b], v_knn[b, k]) + cos(z_orig[b], z_knn[b, k]) + cross_entropy(a_knns[b, k], answer_aids[b])
+    The whole scorer is one HIP launch per batch (ops.similarity_scores: the reference loops over the candidates in Python,
+    three torch ops each); z and a come from the HIP MUTAN path where it applies.  There is no CPU fallback: on a CPU device
+    `forward` raises.
+
+    Kept from the reference: the constructor, `dim_z`, the mutable `knn_size`, forward returning fp32 [B, knn_size] on the
+    inputs' device without requires_grad (cx.py:518), the cosine rule of F.cosine_similarity (each norm clamped at 1e-8: an
+    all-zero row scores 0), and state_dict keys (`vqa_model.*` only).  Deliberate differences (supersets):
+      * knn_size may be 1..64 (CXModelBase's assert ties it to the width of image_features, as in the reference);
+      * `trainable_vqa=True` is rejected (the reference detaches z and a here anyway: nothing would train);
+      * an answer id outside [0, A) raises IndexError (F.cross_entropy's target check aborts or raises, by device, in the
+        reference).
+    """
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        if self.trainable_vqa:
+            raise NotImplementedError("trainable_vqa=True is not supported by the HIP path (frozen VQA model only)")
+        self.dim_z = self.vqa_model.opt["fusion"]["dim_mm"]
+
+    def forward(self, image_features, question_wids, answer_aids):
+        if not image_features.is_cuda:
+            raise ops._lib.NcxError("SimilarityModel runs on the GPU: move the inputs and the model there (no CPU fallback)")
+        assert image_features.size(1) == self.knn_size + 1
+        B, K1 = image_features.size(0), self.knn_size + 1
+        _, z_orig, a_knns, z_knns, _ = self.vqa_forward(image_features, question_wids)
+        dev = image_features.device
+        feats = image_features.reshape(B * K1, -1).float().contiguous()       # the gathered block as the table, ids = arange
+        idx = torch.arange(B * K1, device=dev, dtype=torch.int32).view(B, K1)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        scores = ops.similarity_scores(feats, idx, z_orig, z_knns, a_knns, answer_aids.to(dev), bad_flag=flag)
+        ops.check_similarity_ids(flag)
+        return scores                            # cx.py:518 (a fresh tensor: no requires_grad)
+
+
+class PairwiseModel(CXModelBase):
+    """The reference's pairwise scorer (cx.py:336-376; `counterexamples.py --pairwise`, knn_size = 2) is outside the accelerated
+    path: the name exists so that the reference's import line (counterexamples.py:30-32) resolves against this package, and
+    constructing it says so."""
+
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError("PairwiseModel (--pairwise, knn_size = 2) is outside the accelerated path: it has no HIP "
+                                  "implementation; use the reference's vqa.models.cx for it")
 
 
 class NeuralModel(CXModelBase):
