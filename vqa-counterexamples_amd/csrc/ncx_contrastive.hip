@@ -21,7 +21,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "ncx_internal.h"
-#include "ncx_scorer_util.h"
 
 namespace ncx {
 
@@ -70,8 +69,8 @@ static CtLayout ct_layout(const ncx_contrastive_dims& d) {
     w.idx = take(M * 4); w.zall = take(M * d.dz * 4); w.h = take(M * CT_H * 4); w.dpre = take(M * CT_H * 4);
     w.per = take((size_t)d.B * 16);
     CtPtrs p{}; GemmPlan pl; size_t sb, t;
-    GemmArgs a = ct_gemm_h(d, p, &pl); sb = slab_need(a, pl);
-    a = ct_gemm_dw(d, p, &pl);         t = slab_need(a, pl); sb = t > sb ? t : sb;
+    GemmArgs a = ct_gemm_h(d, p, &pl); sb = gemm_slab_bytes(a, pl);
+    a = ct_gemm_dw(d, p, &pl);         t = gemm_slab_bytes(a, pl); sb = t > sb ? t : sb;
     w.slab = take(sb); w.slab_bytes = sb;
     w.total = o;
     return w;
@@ -208,7 +207,7 @@ extern "C" int ncx_contrastive_forward(const ncx_contrastive_dims* dp, const ncx
     NCX_HIP_TRY(hipGetLastError());
     GemmPlan pl;
     GemmArgs a = ct_gemm_h(d, q, &pl);
-    int rc = run_planned(a, FORM_NT, pl, (float*)(base + l.slab), l.slab_bytes, s); if (rc) return rc;
+    int rc = run_gemm_planned(a, FORM_NT, pl, (float*)(base + l.slab), l.slab_bytes, nullptr, s); if (rc) return rc;
     if (h_out) NCX_HIP_TRY(hipMemcpyAsync(h_out, q.h, (size_t)M * CT_H * 4, hipMemcpyDeviceToDevice, s));
     return NCX_OK;
 }
@@ -239,8 +238,7 @@ extern "C" int ncx_contrastive_loss(const ncx_contrastive_dims* dp, void* ws, si
     hipLaunchKernelGGL(k_ct_loss, dim3((unsigned)((dp->B + 3) / 4)), dim3(256), 0, s, (const float*)(base + l.h), dp->B, margin, scale, per, dist,
                        (float*)(base + l.dpre));
     NCX_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_colsum, dim3(4), dim3(256), 0, s, (const float*)per, 4ll, dp->B, losses4);
-    NCX_HIP_TRY(hipGetLastError());
+    NCX_HIP_TRY(colsum_rows((const float*)per, 4ll, dp->B, 4, losses4, s));
     return NCX_OK;
 }
 
@@ -266,8 +264,7 @@ extern "C" int ncx_contrastive_backward(const ncx_contrastive_dims* dp, const nc
     q.feats = in->feats; q.idx = (int*)(base + l.idx); q.zall = (float*)(base + l.zall); q.dpre = dpre; q.gW = gw;
     GemmPlan pl;
     GemmArgs a = ct_gemm_dw(d, q, &pl);
-    int rc = run_planned(a, FORM_TN, pl, (float*)(base + l.slab), l.slab_bytes, s); if (rc) return rc;
-    hipLaunchKernelGGL(k_colsum, dim3(CT_H), dim3(256), 0, s, (const float*)dpre, (long long)CT_H, (int)M, gb);
-    NCX_HIP_TRY(hipGetLastError());
+    int rc = run_gemm_planned(a, FORM_TN, pl, (float*)(base + l.slab), l.slab_bytes, nullptr, s); if (rc) return rc;
+    NCX_HIP_TRY(colsum_rows((const float*)dpre, (long long)CT_H, (int)M, CT_H, gb, s));
     return NCX_OK;
 }

@@ -1,0 +1,99 @@
+// ncx_diag.hip -- the diagnostics ABI: launch timing, in-kernel stamps, the WgMap self-check and the plan query.
+#include "ncx_driver.h"
+#include <stdlib.h>
+
+using namespace ncx;
+extern "C" {
+int ncx_profile_begin(uint32_t gemm_mask, int32_t max_launches) {
+    if (g_prof.on || gemm_mask == 0 || (gemm_mask >> U_COUNT) != 0 || max_launches < 1 || max_launches > 65536) return NCX_E_DIMS;
+    g_prof.ev = (hipEvent_t*)malloc(sizeof(hipEvent_t) * 2 * (size_t)max_launches);
+    g_prof.ids = (int*)malloc(sizeof(int) * (size_t)max_launches);
+    if (!g_prof.ev || !g_prof.ids) return NCX_E_NULL;
+    for (int i = 0; i < 2 * max_launches; ++i) NCX_HIP_TRY(hipEventCreate(&g_prof.ev[i]));
+    g_prof.mask = gemm_mask; g_prof.n = 0; g_prof.cap = max_launches; g_prof.on = true;
+    return NCX_OK;
+}
+
+int ncx_profile_end(float* ms, int32_t* ids, int32_t cap) {
+    if (!g_prof.on) return NCX_E_FLAGS;
+    int n = 0;
+    for (int i = 0; i < g_prof.n; ++i) {
+        if (hipEventSynchronize(g_prof.ev[2 * i + 1]) != hipSuccess) break;
+        float t = 0.f;
+        if (hipEventElapsedTime(&t, g_prof.ev[2 * i], g_prof.ev[2 * i + 1]) != hipSuccess) break;
+        if (n < cap) { if (ms) ms[n] = t; if (ids) ids[n] = g_prof.ids[i]; }
+        ++n;
+    }
+    for (int i = 0; i < 2 * g_prof.cap; ++i) (void)hipEventDestroy(g_prof.ev[i]);
+    free(g_prof.ev); free(g_prof.ids);
+    g_prof.ev = nullptr; g_prof.ids = nullptr; g_prof.on = false; g_prof.mask = 0; g_prof.n = 0; g_prof.cap = 0;
+    return n < cap ? n : cap;
+}
+
+int ncx_profile_stamps(unsigned long long* stamps, int64_t words) {
+    if ((stamps == nullptr) != (words == 0) || words < 0) return NCX_E_DIMS;
+    int dev = 0;
+    NCX_HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 16) return NCX_E_DIMS;
+    // armed for the CURRENT device only (the buffer lives there); disarm = pointer first, so no reader pairs the old pointer with 0 words
+    if (!stamps) { g_stamps[dev].ptr.store(nullptr, std::memory_order_release); g_stamps[dev].words.store(0, std::memory_order_release); }
+    else { g_stamps[dev].ptr.store(nullptr, std::memory_order_release); g_stamps[dev].words.store(words, std::memory_order_release);
+           g_stamps[dev].ptr.store(stamps, std::memory_order_release); }
+    return NCX_OK;
+}
+
+int ncx_wgmap_check(int32_t tiles_m, int32_t tiles_n, int32_t S) {
+    if (tiles_m < 1 || tiles_n < 1 || S < 1 || (long long)tiles_m * tiles_n * S > (1 << 24)) return NCX_E_DIMS;
+    const WgMap w{tiles_m, tiles_n, S};
+    const int total = tiles_m * tiles_n * S, count = w.count();
+    if (count < total) return 1;
+    unsigned char* seen = (unsigned char*)calloc((size_t)total, 1);
+    if (!seen) return NCX_E_NULL;
+    int bad = 0, nvalid = 0;
+    for (int lw = 0; lw < count && !bad; ++lw) {
+        int tm = -1, tn = -1, z = -1;
+        if (!w.decode(lw, tm, tn, z)) continue;
+        ++nvalid;
+        if (tm < 0 || tm >= tiles_m || tn < 0 || tn >= tiles_n || z < 0 || z >= S) { bad = 2; break; }
+        if (w.encode(tm, tn, z) != lw) { bad = 3; break; }
+        unsigned char& f = seen[((size_t)z * tiles_m + tm) * tiles_n + tn];
+        if (f) { bad = 4; break; }
+        f = 1;
+    }
+    if (!bad && nvalid != total) bad = 5;
+    free(seen);
+    return bad;
+}
+
+int ncx_plan_query(const ncx_dims* d, int32_t gemm_id, int32_t* out6) {
+    if (check_dims(d) != NCX_OK || !out6) return NCX_E_DIMS;
+    if (gemm_id == NCX_QUERY_DW1_ROUTE) {      // the routes of linear_1's weight gradient, from the predicates backward_impl launches by
+        const bool bf16 = d->flags & NCX_F_BF16;
+        const StepRoutes r = routes(*d);
+        out6[0] = r.km_form;
+        out6[1] = (bf16 ? r.tn8_shared : r.tn8) ? (r.tn8_x6 ? 2 : 1) : 0;
+        int grid = 0;
+        out6[2] = dw_tn8_pieces(*d, bf16 ? TN8_LIST_SHARED : TN8_LIST_MAIN, &grid);
+        out6[3] = grid;
+        out6[4] = r.dw1ak_on_tn8(km_defers_to_side_stream(*d, r)) ? 1 : 0;
+        out6[5] = TN8_MAX_SEG;
+        return NCX_OK;
+    }
+    if (gemm_id < 0 || gemm_id >= U_COUNT) return NCX_E_DIMS;
+    GemmUse u[U_COUNT];
+    list_uses(*d, routes(*d), u);
+    out6[0] = u[gemm_id].form; out6[1] = (int32_t)u[gemm_id].M; out6[2] = (int32_t)u[gemm_id].N;
+    out6[3] = (int32_t)u[gemm_id].ksteps; out6[4] = u[gemm_id].plan.cfg; out6[5] = u[gemm_id].plan.split;
+    // linear_1 / hidden-layer forward: the fused kernel of ncx_main.h (tile codes 5: 48x128, 6: 48x64 with the per-triplet fold)
+    const bool fast = (gemm_id == U_MAIN && main_fwd_dims_ok(*d)) || (gemm_id == U_FWD_L && hidden_fwd_dims_ok(*d) && !(d->flags & NCX_F_BF16));
+    if (fast) {
+        const long long M = (long long)d->B * d->K, T = u[gemm_id].ksteps;
+        const int sp = main_split(M, d->H, T);
+        const bool vfold = gemm_id == U_MAIN && (d->flags & NCX_F_V_MULT) && (d->K == 24 || (d->K == 48 && main_fold_rows(M, d->H) >= 96)) && d->dv % 32 == 0 && d->dv >= 64 && sp == 1;
+        const long long tiles96 = ((M + 95) / 96) * ((d->H + 127) / 128);
+        out6[4] = vfold ? (main_fold_rows(M, d->H) == 192 ? 8 : (main_fold_rows(M, d->H) == 96 || d->K == 48) ? 7 : 6) : (sp == 1 && tiles96 * 10 >= (long long)num_cus() * 9) ? CFG_96x128 : 5;
+        out6[5] = sp;
+    }
+    return NCX_OK;
+}
+}  // extern "C"

@@ -621,8 +621,6 @@ __global__ __launch_bounds__(TN8_T, 1) void k_dw_tn8_x6(const Tn8Args a) {
 
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
-static inline int tn8_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
-
 // NCX_F_X6: the launch runs on the bf16 matrix path with three-plane operands (k_dw_tn8_x6); the row-gather tables share LDS with six planes
 constexpr int TN6_MAX_B = 2048;
 bool dw_tn8_x6(const ncx_dims& d) { return (d.flags & NCX_F_X6) && d.B <= TN6_MAX_B && !hook_env("NCX_NO_X6"); }
@@ -646,7 +644,7 @@ static Tn8Plan tn8_plan(const ncx_dims& d, const Tn8Prob* p, int np, int n_al, i
     const int cus = num_cus(), tiles_m = d.H / TN8_BM;
     pl.grid = cus;
     if (n_al) {
-        pl.al_tiles = tiles_m * tn8_cdiv(p[0].N, TN8_BN);
+        pl.al_tiles = tiles_m * (int)cdiv(p[0].N, TN8_BN);
         const int steps = p[0].rows / TN8_BK;
         int S = cus / pl.al_tiles; if (S < 1) S = 1;
         while (S > 1 && steps / S < 8) --S;                        // at least 8 k-steps per chunk
@@ -656,13 +654,13 @@ static Tn8Plan tn8_plan(const ncx_dims& d, const Tn8Prob* p, int np, int n_al, i
     long long g = 0; int t0 = 0;
     for (int i = 0; i < TN8_MAX_PROB; ++i) { rest_tiles[i] = 0; rest_steps[i] = 1; rest_tile0[i] = 0; rest_pre[i] = 0; }
     for (int i = n_al; i < np; ++i) {
-        rest_tiles[i] = tiles_m * tn8_cdiv(p[i].N, TN8_BN); rest_steps[i] = p[i].rows / TN8_BK; rest_tile0[i] = t0; rest_pre[i] = (int)g;
+        rest_tiles[i] = tiles_m * (int)cdiv(p[i].N, TN8_BN); rest_steps[i] = p[i].rows / TN8_BK; rest_tile0[i] = t0; rest_pre[i] = (int)g;
         t0 += rest_tiles[i]; g += (long long)rest_tiles[i] * rest_steps[i];
     }
     for (int i = np; i <= TN8_MAX_PROB; ++i) rest_pre[i] = (int)g;
     for (int i = 0; i < n_al; ++i) rest_pre[i] = 0;
     pl.rest_tiles_total = t0;
-    pl.R = g > 0 ? tn8_cdiv(g, pl.grid) : 1;
+    pl.R = g > 0 ? (int)cdiv(g, pl.grid) : 1;
     pl.n_slots = pl.al_wgs + t0 + pl.grid;
     return pl;
 }
@@ -705,8 +703,8 @@ int dw_tn8_pieces(const ncx_dims& d, int list, int* grid) {
 }
 
 // Where a plan would need more pieces than the LDS table holds (wide H: many row tiles; the a_emb lesion: the long a_other block in the rest
-// sequence; K = 48), the products stay on the generic engine's grouped launch.  list_uses, ws_layout, dw_tn8_slab_bytes and backward_impl
-// all decide from these two predicates.
+// sequence; K = 48), the products stay on the generic engine's grouped launch.  routes() (ncx_plan.hip) caches their answers in StepRoutes:
+// list_uses, ws_layout and backward_impl read that struct, dw_tn8_slab_bytes asks here.
 bool dw_tn8_supported(const ncx_dims& d) {
     if ((d.flags & NCX_F_BF16) || !dw_tn8_shapes_ok(d)) return false;
     if (dw_tn8_pieces(d, TN8_LIST_MAIN, nullptr) > TN8_MAX_SEG) return false;
@@ -724,10 +722,10 @@ size_t dw_tn8_slab_bytes(const ncx_dims& d) {
     const int cus = num_cus(), tiles_m = d.H / TN8_BM;
     const bool aemb = d.flags & NCX_F_A_EMB, bf16 = d.flags & NCX_F_BF16;
     long long al_wgs = 0;
-    if (aemb && !bf16) { const int t = tiles_m * tn8_cdiv(d.A, TN8_BN); int S = cus / t; if (S < 1) S = 1; al_wgs = (long long)t * S; }
+    if (aemb && !bf16) { const int t = tiles_m * (int)cdiv(d.A, TN8_BN); int S = cus / t; if (S < 1) S = 1; al_wgs = (long long)t * S; }
     long long rest_tiles = 0;
     const int cols[7] = {(aemb || bf16) ? 0 : d.da, bf16 ? 0 : d.dz, bf16 ? 0 : pad_to(d.K + 1, 4), d.dv, d.dq, d.dz, d.da};
-    for (int i = 0; i < 7; ++i) if (cols[i]) rest_tiles += (long long)tiles_m * tn8_cdiv(cols[i], TN8_BN);
+    for (int i = 0; i < 7; ++i) if (cols[i]) rest_tiles += (long long)tiles_m * (int)cdiv(cols[i], TN8_BN);
     const long long grid = al_wgs > cus ? al_wgs : cus;
     return (size_t)(al_wgs + rest_tiles + grid) * TN8_BM * TN8_BN * 4;
 }
@@ -745,7 +743,7 @@ static int tn8_fill(const ncx_dims& d, const Tn8Prob* probs, int np, int n_al, b
     // (a backstop: the callers ask dw_tn8_supported / dw_tn8_shared_ok, which plan the same lists)
     if (tn8_piece_bound(pl, a.rest_steps, np, n_al) > TN8_MAX_SEG) return NCX_E_DIMS;
     a.np = np; a.n_al = n_al; a.H = d.H; a.tiles_m = d.H / TN8_BM; a.B = d.B;
-    a.S = pl.S; a.al_wgs = pl.al_wgs; a.al_tiles_n = n_al ? tn8_cdiv(probs[0].N, TN8_BN) : 0; a.R = pl.R;
+    a.S = pl.S; a.al_wgs = pl.al_wgs; a.al_tiles_n = n_al ? (int)cdiv(probs[0].N, TN8_BN) : 0; a.R = pl.R;
     a.do_al = do_al && n_al; a.do_rest = do_rest && np > n_al;
     a.slab = slab; a.n_slots = pl.n_slots;
     r.np = np; r.n_al = n_al; r.tiles_m = a.tiles_m; r.S = pl.S; r.al_wgs = pl.al_wgs; r.R = pl.R; r.do_al = a.do_al; r.do_rest = a.do_rest;

@@ -41,6 +41,16 @@ static inline SegOffsets seg_offsets(const ncx_dims& d) {
 struct GemmPlan { int cfg; int split; };   // split: aligned k-chunks per output tile (1 = none)
 GemmPlan plan_gemm(int form, long long M, long long N, long long ksteps, bool allow_96);
 int num_cus();
+static inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
+static inline long long ksteps(long long k) { return cdiv(k, GEMM_BK); }      // 32-deep reduction steps of a k extent
+// The GEMM driver (ncx_driver.hip) of every launch on the generic engine.  Problems whose a.split[i] is 0 take pl.split (callers
+// may preset per-problem splits); a split launch puts its partial tiles in `slab` (NCX_E_WORKSPACE when slab_bytes is short).
+// reduce_bias (nullable): applied by the epilogue or by the fix-up kernel.  Hook NCX_NO_FAST: the diagnostic tile path.
+__attribute__((visibility("hidden"))) size_t gemm_slab_bytes(GemmArgs a, const GemmPlan& pl);      // 0 when unsplit
+__attribute__((visibility("hidden"))) int run_gemm_planned(GemmArgs& a, int form, const GemmPlan& pl, float* slab, size_t slab_bytes,
+                                                           const float* reduce_bias, hipStream_t s);
+// ncx_scorers.hip: out[c] = sum over rows r < R of in[r * ld + c], c < cols, in a fixed order (k_colsum)
+__attribute__((visibility("hidden"))) hipError_t colsum_rows(const float* in, long long ld, int R, int cols, float* out, hipStream_t s);
 
 // Workspace partition (byte offsets from a 256-byte aligned base).  Saved-for-backward part first.
 struct WsLayout {

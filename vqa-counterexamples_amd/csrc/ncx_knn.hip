@@ -204,7 +204,7 @@ extern "C" int ncx_knn(const float* table, int32_t n, const float* queries, int3
         a.a[0] = x_plain(queries, dv, nq, dv); a.b[0] = x_plain(table, dv, n, dv); a.klen[0] = dv;
         a.out[0] = V; a.ldo[0] = n; a.n_cols[0] = n; a.split[0] = 1;
         a.epi.bias = halfneg;
-        GemmPlan pl = plan_gemm(FORM_NT, nq, n, (dv + GEMM_BK - 1) / GEMM_BK, true);
+        GemmPlan pl = plan_gemm(FORM_NT, nq, n, ksteps(dv), true);
         pl.split = 1;
         const int rc = run_gemm_nt(a, pl.cfg, s);
         if (rc) return rc;

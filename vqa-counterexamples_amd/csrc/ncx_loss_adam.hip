@@ -1,0 +1,116 @@
+// ncx_loss_adam.hip -- the two entry points every scorer shares: the listwise loss / rank (ncx_loss_rank) and the Adam update
+// (ncx_adam_step).
+#include "ncx_wave.h"
+
+namespace ncx {
+// Listwise softmax cross-entropy over the K candidates of a triplet + rank of the ground truth.
+// One wave per triplet, lane k holds score k (K <= 64).
+__global__ __launch_bounds__(256) void k_loss_rank(const float* __restrict__ scores, const int* __restrict__ gt,
+                                                   int B, int K, float scale, float* __restrict__ loss_rows,
+                                                   float* __restrict__ dscores, int* __restrict__ rank) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const float s = lane < K ? scores[(long long)b * K + lane] : -INFINITY;
+    const int g = gt[b];
+    const float m = wave_max(s);
+    const float e = lane < K ? __expf(s - m) : 0.f;
+    const float sum = wave_sum(e);
+    const float sg = __shfl(s, g, 64);
+    if (dscores && lane < K) dscores[(long long)b * K + lane] = (e / sum - (lane == g ? 1.f : 0.f)) * scale;
+    const bool ahead = lane < K && (s > sg || (s == sg && lane < g));
+    const unsigned long long bal = __ballot(ahead);
+    if (lane == 0) {
+        if (loss_rows) loss_rows[b] = (logf(sum) + m - sg) * scale;
+        if (rank) rank[b] = __popcll(bal);
+    }
+}
+
+// loss = sum(loss_rows); hits = {#rank<1, #rank<5}.  Single block: deterministic.
+__global__ __launch_bounds__(256) void k_loss_finish(const float* __restrict__ loss_rows, const int* __restrict__ rank,
+                                                     int B, float* __restrict__ loss, int* __restrict__ hits) {
+    __shared__ float sl[4];
+    __shared__ int s1[4], s5[4];
+    float acc = 0.f; int h1 = 0, h5 = 0;
+    for (int i = threadIdx.x; i < B; i += 256) {
+        if (loss_rows) acc += loss_rows[i];
+        if (rank) { const int rk = rank[i]; h1 += rk < 1; h5 += rk < 5; }
+    }
+    acc = wave_sum(acc);
+    h1 = (int)wave_sum((float)h1); h5 = (int)wave_sum((float)h5);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { sl[w] = acc; s1[w] = h1; s5[w] = h5; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (loss) loss[0] = sl[0] + sl[1] + sl[2] + sl[3];
+        if (hits) { hits[0] = s1[0] + s1[1] + s1[2] + s1[3]; hits[1] = s5[0] + s5[1] + s5[2] + s5[3]; }
+    }
+}
+
+// torch.optim.Adam (counterexamples.py:275-276): m = lerp(m, g, 1-b1); v = b2 v + (1-b2) g^2;
+// p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps).
+__global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                              float* __restrict__ v, size_t n, float step_size, float b1, float b2,
+                                              float eps, float inv_bc2_sqrt, float gscale) {
+    size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    const size_t stride = (size_t)gridDim.x * 256 * 4;
+    for (; i < n; i += stride) {
+        if (i + 3 < n) {
+            f32x4 pv = *(f32x4*)(p + i), gv = *(const f32x4*)(g + i), mv = *(f32x4*)(m + i), vv = *(f32x4*)(v + i);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float gj = gv[j] * gscale;
+                mv[j] = mv[j] + (gj - mv[j]) * (1.f - b1);
+                vv[j] = vv[j] * b2 + (1.f - b2) * gj * gj;
+                const float den = sqrtf(vv[j]) * inv_bc2_sqrt + eps;
+                pv[j] = pv[j] - step_size * (mv[j] / den);
+            }
+            *(f32x4*)(p + i) = pv; *(f32x4*)(m + i) = mv; *(f32x4*)(v + i) = vv;
+        } else {
+            for (size_t j = i; j < n; ++j) {
+                const float gj = g[j] * gscale;
+                const float mj = m[j] + (gj - m[j]) * (1.f - b1);
+                const float vj = v[j] * b2 + (1.f - b2) * gj * gj;
+                m[j] = mj; v[j] = vj;
+                p[j] = p[j] - step_size * (mj / (sqrtf(vj) * inv_bc2_sqrt + eps));
+            }
+        }
+    }
+}
+}  // namespace ncx
+
+using namespace ncx;
+extern "C" {
+int ncx_loss_rank(const float* scores, const int32_t* gt, int32_t B, int32_t K, float scale, float* loss_rows,
+                  float* loss, float* dscores, int32_t* rank, int32_t* hits, void* stream_) {
+    if (!scores || !gt) return NCX_E_NULL;
+    if (B < 1 || K < 1 || K > 64) return NCX_E_DIMS;
+    if ((loss && !loss_rows) || (hits && !rank)) return NCX_E_NULL;
+    hipStream_t s = (hipStream_t)stream_;
+    if (scale <= 0.f) scale = 1.f / (float)B;
+    hipLaunchKernelGGL(k_loss_rank, dim3((unsigned)cdiv(B, 4)), dim3(256), 0, s, scores, gt, B, K, scale, loss_rows, dscores, rank);
+    NCX_HIP_TRY(hipGetLastError());
+    if (loss || hits) {
+        hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(256), 0, s, (const float*)loss_rows, (const int*)rank, B, loss, hits);
+        NCX_HIP_TRY(hipGetLastError());
+    }
+    return NCX_OK;
+}
+
+int ncx_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, float lr,
+                  float beta1, float beta2, float eps, int32_t step, float grad_scale, void* stream_) {
+    if (!param || !grad || !exp_avg || !exp_avg_sq) return NCX_E_NULL;
+    if (step < 1 || n == 0) return NCX_E_DIMS;
+    if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return NCX_E_WORKSPACE;
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    const float step_size = (float)((double)lr / bc1);
+    const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+    size_t blocks = (n + 1023) / 1024;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_adam, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, param, grad, exp_avg, exp_avg_sq, n,
+                       step_size, beta1, beta2, eps, inv_bc2_sqrt, grad_scale);
+    NCX_HIP_TRY(hipGetLastError());
+    return NCX_OK;
+}
+}  // extern "C"

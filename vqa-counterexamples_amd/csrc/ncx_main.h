@@ -19,7 +19,7 @@
 // The k-step is ONE basic block, always (in-kernel stamps showed branches inside it costing 15 %: hipcc cannot interleave
 // MFMAs with loads / LDS stores across them).  What makes that possible:
 //   * ragged reduction extents need no code: the WEIGHT side of every segment is zero-padded to a multiple of 32 columns
-//     (ncx_api.hip packs padded copies of the slices that need it; Gt is allocated padded), the OPERAND side only has to
+//     (ncx_forward.hip packs padded copies of the slices that need it; Gt is allocated padded), the OPERAND side only has to
 //     be a multiple of 4 wide: its 16-byte loads are windows slid left to stay inside the row, so a window beyond the
 //     extent re-reads valid (finite) columns that meet zero weights;
 //   * rows beyond the matrix / the tile are clamped loads into spare LDS rows, never predicated;

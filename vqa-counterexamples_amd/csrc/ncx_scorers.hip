@@ -25,7 +25,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "ncx_internal.h"
-#include "ncx_scorer_util.h"
 
 namespace ncx {
 
@@ -125,10 +124,10 @@ static PlLayout pl_layout(const ncx_scorer_dims& d) {
     w.P = take(B * PL_H * 4); w.h = take(M * PL_H * 4); w.s = take(M * 4); w.dpre = take(M * PL_H * 4);
     w.dP = take(B * PL_H * 4); w.pw = take(B * PL_H * 4); w.pg = take(B * 4); w.dA = take(B * PL_DA * 4);
     PlPtrs p{}; GemmPlan pl; size_t sb = 0, t;
-    GemmArgs a = pl_gemm_p(d, p, &pl);   t = slab_need(a, pl); sb = t > sb ? t : sb;
-    a = pl_gemm_dwc(d, p, &pl);          t = slab_need(a, pl); sb = t > sb ? t : sb;
-    a = pl_gemm_dwq(d, p, &pl);          t = slab_need(a, pl); sb = t > sb ? t : sb;
-    a = pl_gemm_da(d, p, &pl);           t = slab_need(a, pl); sb = t > sb ? t : sb;
+    GemmArgs a = pl_gemm_p(d, p, &pl);   t = gemm_slab_bytes(a, pl); sb = t > sb ? t : sb;
+    a = pl_gemm_dwc(d, p, &pl);          t = gemm_slab_bytes(a, pl); sb = t > sb ? t : sb;
+    a = pl_gemm_dwq(d, p, &pl);          t = gemm_slab_bytes(a, pl); sb = t > sb ? t : sb;
+    a = pl_gemm_da(d, p, &pl);           t = gemm_slab_bytes(a, pl); sb = t > sb ? t : sb;
     w.slab = take(sb); w.slab_bytes = sb;
     w.total = o;
     return w;
@@ -202,7 +201,25 @@ __global__ __launch_bounds__(256) void k_pl_head(const float* __restrict__ dscor
     }
 }
 
-// (k_colsum, the fixed-order column sum: ncx_scorer_util.h)
+// out[c] = sum over rows r < R of in[r * ld + c]: one workgroup per column, each thread a fixed stride of rows, then a fixed
+// LDS tree (deterministic).  colsum_rows (ncx_internal.h) is its launcher: the contrastive path sums with it too.
+static __global__ __launch_bounds__(256) void k_colsum(const float* __restrict__ in, long long ld, int R, float* __restrict__ out) {
+    const int c = blockIdx.x, t = threadIdx.x;
+    __shared__ float red[256];
+    float acc = 0.f;
+    for (int r = t; r < R; r += 256) acc += in[(long long)r * ld + c];
+    red[t] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) red[t] += red[t + o];
+        __syncthreads();
+    }
+    if (t == 0) out[c] = red[0];
+}
+hipError_t colsum_rows(const float* in, long long ld, int R, int cols, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_colsum, dim3(cols), dim3(256), 0, s, in, ld, R, out);
+    return hipGetLastError();
+}
 
 // d answer_embedding: row a = sum of dA[b] over the b with aid_c[b] == a, b ascending; every row written.
 constexpr int DEMB_CHUNK = 1024;
@@ -259,8 +276,8 @@ static LcLayout lc_layout(const ncx_scorer_dims& d) {
     auto take = [&](size_t bytes) { const size_t r = o; o = align_up(o + bytes, 256); return r; };
     w.pad = take(d.K < 4 ? (size_t)d.B * 16 : 0);
     GemmPlan pl; size_t sb, t;
-    GemmArgs a = lc_gemm_fwd(d, nullptr, nullptr, nullptr, nullptr, &pl); sb = slab_need(a, pl);
-    a = lc_gemm_dw(d, nullptr, nullptr, d.K < 4 ? 4 : d.K, nullptr, &pl); t = slab_need(a, pl); sb = t > sb ? t : sb;
+    GemmArgs a = lc_gemm_fwd(d, nullptr, nullptr, nullptr, nullptr, &pl); sb = gemm_slab_bytes(a, pl);
+    a = lc_gemm_dw(d, nullptr, nullptr, d.K < 4 ? 4 : d.K, nullptr, &pl); t = gemm_slab_bytes(a, pl); sb = t > sb ? t : sb;
     w.slab = take(sb); w.slab_bytes = sb; w.total = o > 256 ? o : 256;      // (0 is the "unsupported dims" answer)
     return w;
 }
@@ -296,9 +313,9 @@ extern "C" int ncx_pairlin_forward(const ncx_scorer_dims* dp, const ncx_inputs* 
     NCX_HIP_TRY(hipGetLastError());
     GemmPlan pl;
     GemmArgs a = pl_gemm_p(d, q, &pl);
-    int rc = run_planned(a, FORM_NT, pl, (float*)(base + w.slab), w.slab_bytes, s); if (rc) return rc;
+    int rc = run_gemm_planned(a, FORM_NT, pl, (float*)(base + w.slab), w.slab_bytes, nullptr, s); if (rc) return rc;
     a = pl_gemm_h(d, q, &pl);
-    rc = run_planned(a, FORM_NT, pl, (float*)(base + w.slab), w.slab_bytes, s); if (rc) return rc;
+    rc = run_gemm_planned(a, FORM_NT, pl, (float*)(base + w.slab), w.slab_bytes, nullptr, s); if (rc) return rc;
     hipLaunchKernelGGL(k_pl_score, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, (const float*)q.h, p->w_out, p->b_out, M,
                        (float*)(base + w.s), scores);
     NCX_HIP_TRY(hipGetLastError());
@@ -326,19 +343,16 @@ extern "C" int ncx_pairlin_backward(const ncx_scorer_dims* dp, const ncx_inputs*
     hipLaunchKernelGGL(k_pl_head, dim3(d.B), dim3(256), 0, s, dscores, (const float*)(base + w.s), (const float*)q.h, p->w_out, d.K,
                        q.dpre, q.dP, pw, pg);
     NCX_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_colsum, dim3(PL_H), dim3(256), 0, s, (const float*)q.dP, (long long)PL_H, d.B, g->b);
-    NCX_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_colsum, dim3(PL_H), dim3(256), 0, s, (const float*)pw, (long long)PL_H, d.B, g->w_out);
-    NCX_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_colsum, dim3(1), dim3(256), 0, s, (const float*)pg, 1ll, d.B, g->b_out);
-    NCX_HIP_TRY(hipGetLastError());
+    NCX_HIP_TRY(colsum_rows((const float*)q.dP, (long long)PL_H, d.B, PL_H, g->b, s));
+    NCX_HIP_TRY(colsum_rows((const float*)pw, (long long)PL_H, d.B, PL_H, g->w_out, s));
+    NCX_HIP_TRY(colsum_rows((const float*)pg, 1ll, d.B, 1, g->b_out, s));
     GemmPlan pl;
     GemmArgs a = pl_gemm_dwc(d, q, &pl);
-    int rc = run_planned(a, FORM_TN, pl, (float*)(base + w.slab), w.slab_bytes, s); if (rc) return rc;
+    int rc = run_gemm_planned(a, FORM_TN, pl, (float*)(base + w.slab), w.slab_bytes, nullptr, s); if (rc) return rc;
     a = pl_gemm_dwq(d, q, &pl);
-    rc = run_planned(a, FORM_TN, pl, (float*)(base + w.slab), w.slab_bytes, s); if (rc) return rc;
+    rc = run_gemm_planned(a, FORM_TN, pl, (float*)(base + w.slab), w.slab_bytes, nullptr, s); if (rc) return rc;
     a = pl_gemm_da(d, q, &pl);
-    rc = run_planned(a, FORM_NN, pl, (float*)(base + w.slab), w.slab_bytes, s); if (rc) return rc;
+    rc = run_gemm_planned(a, FORM_NN, pl, (float*)(base + w.slab), w.slab_bytes, nullptr, s); if (rc) return rc;
     hipLaunchKernelGGL(k_pl_demb, dim3(d.A), dim3(256), 0, s, (const float*)q.dA, q.aid, d.B, g->answer_embedding);
     NCX_HIP_TRY(hipGetLastError());
     return NCX_OK;
@@ -357,7 +371,7 @@ extern "C" int ncx_linctx_forward(const ncx_scorer_dims* dp, const float* z_knns
     if (ws_bytes < l.total || ((uintptr_t)ws & 255)) return NCX_E_WORKSPACE;
     GemmPlan pl;
     GemmArgs a = lc_gemm_fwd(*dp, z_knns, w, b, scores, &pl);
-    return run_planned(a, FORM_NT, pl, (float*)((char*)ws + l.slab), l.slab_bytes, (hipStream_t)stream_);
+    return run_gemm_planned(a, FORM_NT, pl, (float*)((char*)ws + l.slab), l.slab_bytes, nullptr, (hipStream_t)stream_);
 }
 
 extern "C" int ncx_linctx_backward(const ncx_scorer_dims* dp, const float* z_knns, const float* dscores, void* ws, size_t ws_bytes,
@@ -378,8 +392,7 @@ extern "C" int ncx_linctx_backward(const ncx_scorer_dims* dp, const float* z_knn
     }
     GemmPlan pl;
     GemmArgs a = lc_gemm_dw(d, z_knns, ds, ld, gw, &pl);
-    int rc = run_planned(a, FORM_TN, pl, (float*)((char*)ws + l.slab), l.slab_bytes, s); if (rc) return rc;
-    hipLaunchKernelGGL(k_colsum, dim3(d.K), dim3(256), 0, s, dscores, (long long)d.K, d.B, gb);
-    NCX_HIP_TRY(hipGetLastError());
+    int rc = run_gemm_planned(a, FORM_TN, pl, (float*)((char*)ws + l.slab), l.slab_bytes, nullptr, s); if (rc) return rc;
+    NCX_HIP_TRY(colsum_rows(dscores, (long long)d.K, d.B, d.K, gb, s));
     return NCX_OK;
 }

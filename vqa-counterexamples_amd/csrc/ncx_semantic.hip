@@ -206,7 +206,7 @@ extern "C" int ncx_cosine_gram(const float* emb, int32_t A, int32_t da, void* ws
         GemmArgs a{}; a.mode = MODE_CHAIN; a.nseg = 1; a.M = A;
         a.a[0] = x_plain(en + c0, ldp, A, w); a.b[0] = x_plain(en + c0, ldp, A, w); a.klen[0] = w;
         a.out[0] = gram; a.ldo[0] = A; a.n_cols[0] = A; a.split[0] = 1;
-        GemmPlan pl = plan_gemm(FORM_NT, A, A, (w + GEMM_BK - 1) / GEMM_BK, true);
+        GemmPlan pl = plan_gemm(FORM_NT, A, A, ksteps(w), true);
         pl.split = 1;
         const int rc = run_gemm_nt(a, pl.cfg, s);
         if (rc) return rc;
