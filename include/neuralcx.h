@@ -267,6 +267,30 @@ int ncx_vqa_forward(const ncx_dims* d, const float* feats, const int32_t* img_id
                     const ncx_mutan_params* m, void* workspace, size_t workspace_bytes,
                     float* z_orig, float* z_knns, float* a_knns, float* a_orig, void* stream);
 
+/* ---- the frozen MLB producer: the reference factory's second no-attention model (vqa/models/utils.py:7) ----
+ * Replaces CXModelBase.vqa_forward (vqa/models/cx.py:64-104) for the MLBNoAtt model (vqa/models/noatt.py:38-46) in eval mode:
+ * MLBFusion.forward (vqa/models/fusion.py:31-50: linear_v / linear_q + activation, hadamard product) and
+ * AbstractNoAtt._classif (vqa/models/noatt.py:24-29: optional activation, linear_classif) on the original + K candidate images:
+ *   x_q = act_q(q Wq^T + bq) once per question;  x_v = act_v(feats[img_idx] Wv^T + bv);  z = x_q * x_v;  a = act_c(z) Wc^T + bc
+ * z_orig / z_knns are z BEFORE the classifier's activation, as the reference returns them (cx.py:94-104).  The image gather
+ * is folded into linear_v and x_v is never stored: the product, the row split and act_c(z) happen in that GEMM's epilogue. */
+typedef struct ncx_mlb_params {
+    const float* wv;  const float* bv;    /* fusion.linear_v.weight [dh, dv], .bias [dh]                         */
+    const float* wq;  const float* bq;    /* fusion.linear_q.weight [dh, dq], .bias [dh]                         */
+    const float* wc;  const float* bc;    /* linear_classif.weight [A, dh], .bias [A]                            */
+    int32_t dh;                           /* fusion.dim_h; must equal d->dz                                      */
+    int32_t act_v, act_q, act_c;          /* activation_v / activation_q / classif.activation: 0 none, 2 tanh    */
+} ncx_mlb_params;
+
+/* 0 for invalid dims or parameters (as ncx_vqa_workspace_bytes). */
+size_t ncx_mlb_workspace_bytes(const ncx_dims* d, const ncx_mlb_params* m);
+
+/* z_orig [B,dh], z_knns [B,K,dh], a_knns [B,K,A] (logits), a_orig [B,A] (nullable: its B rows are multiplied only on request).
+ * Uses d->B, K, dv, dq, dz (== m->dh), A, n_img only.  Status codes and workspace rules of ncx_vqa_forward; no allocation. */
+int ncx_mlb_forward(const ncx_dims* d, const float* feats, const int32_t* img_idx, const float* q_emb,
+                    const ncx_mlb_params* m, void* workspace, size_t workspace_bytes,
+                    float* z_orig, float* z_knns, float* a_knns, float* a_orig, void* stream);
+
 /* ---- brute-force k nearest neighbours of feature rows --------------------------------------
  * Replaces knn.py:41-58 of the reference (sklearn NearestNeighbors(n_neighbors=k).fit(table).kneighbors(queries),
  * brute force, euclidean).  For each of the nq query rows: the k rows of `table` [n, dv] with the smallest

@@ -29,6 +29,7 @@ if HERE not in sys.path:
 
 import counterexamples as cxcli                                   # noqa: E402  (Runner: data loading, checkpoints, logging)
 from neuralcx import dp, ops                                      # noqa: E402
+from vqa.models.fusion import out_dim as fusion_out_dim          # noqa: E402
 from neuralcx.contrastive import ContrastiveEngine, sample_positions, triple_img_idx, triple_z   # noqa: E402
 
 RECALL_KEY = "contrastive/recall"
@@ -87,7 +88,7 @@ class ContrastiveRunner(cxcli.Runner):
         random.seed(42); torch.manual_seed(42); torch.cuda.manual_seed(42)
         fus = options["model"]["fusion"]
         self.K = 24                                                      # contrastive.py:270
-        self.engine = ContrastiveEngine(dv=fus["dim_v"], dz=fus["dim_mm"], A=options["vqa"]["nans"], lr=options["optim"]["lr"],
+        self.engine = ContrastiveEngine(dv=fus["dim_v"], dz=fusion_out_dim(fus), A=options["vqa"]["nans"], lr=options["optim"]["lr"],
                                         device=self.dev)
         self.engine.init_parameters(seed=42)
         self.gb = options["optim"]["batch_size"]

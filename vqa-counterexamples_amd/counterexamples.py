@@ -43,6 +43,7 @@ from neuralcx.engine import NeuralCXEngine        # noqa: E402
 from neuralcx.scorers import LinearContextEngine, PairwiseLinearEngine        # noqa: E402
 from neuralcx.synth import SyntheticCX            # noqa: E402
 from neuralcx import formats                      # noqa: E402
+from vqa.models.fusion import out_dim as fusion_out_dim        # noqa: E402
 
 
 def build_parser():
@@ -110,13 +111,13 @@ class Runner:
         fus = options["model"]["fusion"]
         self.K = 24
         if args.cx_model == "PairwiseLinearModel":          # counterexamples.py:268-270 (cx.py:379-425)
-            self.engine = PairwiseLinearEngine(K=self.K, dv=fus["dim_v"], dq=fus["dim_q"], dz=fus["dim_mm"], A=options["vqa"]["nans"],
+            self.engine = PairwiseLinearEngine(K=self.K, dv=fus["dim_v"], dq=fus["dim_q"], dz=fusion_out_dim(fus), A=options["vqa"]["nans"],
                                                lr=options["optim"]["lr"], device=self.dev, world_size=self.world)
         elif args.cx_model == "LinearContext":              # counterexamples.py:233-235 (cx.py:139-156)
-            self.engine = LinearContextEngine(K=self.K, dz=fus["dim_mm"], lr=options["optim"]["lr"], device=self.dev,
+            self.engine = LinearContextEngine(K=self.K, dz=fusion_out_dim(fus), lr=options["optim"]["lr"], device=self.dev,
                                               world_size=self.world)
         else:
-            self.engine = NeuralCXEngine(K=self.K, dv=fus["dim_v"], dq=fus["dim_q"], dz=fus["dim_mm"], da=2400,
+            self.engine = NeuralCXEngine(K=self.K, dv=fus["dim_v"], dq=fus["dim_q"], dz=fusion_out_dim(fus), da=2400,
                                          A=options["vqa"]["nans"], H=cx["dim_h"], L=cx["n_layers"], drop_p=cx["drop_p"],
                                          lr=options["optim"]["lr"], device=self.dev,
                                          spec={k: cx.get(k, True) for k in ("v_mult", "v_dist", "v_rank", "a_emb")},
@@ -137,7 +138,7 @@ class Runner:
     def load_synthetic(self):
         a = self.args
         fus = self.opt["model"]["fusion"]
-        kw = dict(K=self.K, dv=fus["dim_v"], dq=fus["dim_q"], dz=fus["dim_mm"], A=self.opt["vqa"]["nans"], device=self.dev)
+        kw = dict(K=self.K, dv=fus["dim_v"], dq=fus["dim_q"], dz=fusion_out_dim(fus), A=self.opt["vqa"]["nans"], device=self.dev)
         n_tr = 1024 if a.dev_mode else a.syn_train
         self.train = SyntheticCX(n_triplets=n_tr, n_img=a.syn_images, seed=1234, **kw)
         self.val = SyntheticCX(n_triplets=a.syn_val, n_img=a.syn_images, seed=4321, feats=self.train.feats, **kw)
@@ -174,7 +175,8 @@ class Runner:
         self.vqa.eval()                                                                      # cx.py:73-80 (frozen)
         for p_ in self.vqa.parameters():
             p_.requires_grad_(False)
-        self.mutan = ops.MutanWeights(self.vqa) if isinstance(self.vqa, models.MutanNoAtt) else None
+        # the HIP producer's weights object: MutanWeights or (MLBNoAtt) MlbWeights; ops.vqa_forward dispatches on it
+        self.mutan = ops.vqa_weights(self.vqa) if isinstance(self.vqa, (models.MutanNoAtt, models.MLBNoAtt)) else None
         self._torch_vqa = None if self.mutan is not None else CXModelBase(self.vqa, self.K)
         emb = None
         if opt["cx_model"].get("pretrained_emb"):

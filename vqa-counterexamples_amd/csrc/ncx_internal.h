@@ -111,8 +111,11 @@ struct MainArgs {
     float* dist_out; long long ld_dist;
     unsigned long long* stamps;      // diagnostics (tools/mb/mb_main.hip): 16 words per workgroup of s_memtime / s_memrealtime stamps; NULL in the library
     int x6;                          // NCX_F_X6: the plain / softmax segments of the 192 x 64 fold form on the bf16 matrix path with three-plane operands
+    float* t_out; float* t_out0;     // main_forward_mlb only (nullable): t = tanh(z) of the rows that go to out / epi.out0, leading dimension N
 };
 int main_forward(MainArgs& a, hipStream_t s);
+// The MLB producer's x_v product (ncx_mlb.hip): one MK_GATHER segment with the EPI_MLB epilogue of ncx_main.h
+int main_forward_mlb(MainArgs& a, hipStream_t s);
 // k-split of a problem for the fused forward kernel (48 x 128 tiles): 1 when its tiles already give every CU a workgroup,
 // else as many k-chunks as keep all workgroups resident at once (two per CU), at least 8 k-steps each.  T: k-steps of the whole chain.
 int main_split(long long M, long long N, long long T);
@@ -161,6 +164,8 @@ int dw_tn8(const ncx_dims& d, const Tn8Prob* probs, int np, int n_al, bool do_al
 // ncx_mutan.hip: the rank-R fusion of the MUTAN producer as ONE product per question against an effective weight tile built on the fly
 bool mutan_fold_supported(const ncx_dims& d, const ncx_mutan_params& m);
 int mutan_fold(const ncx_dims& d, const ncx_mutan_params& m, const float* xv, const float* hq, float* z_orig, float* z_knns, hipStream_t s);
+// ncx_vqa.hip: dst[r][0 .. cols) = src[r][0 .. cols), dst[r][cols .. ldd) = 0 (weight rows zero-padded to whole 32-column k-steps for ncx_main.h)
+__attribute__((visibility("hidden"))) hipError_t pad_rows(const float* src, long long ld_src, int cols, float* dst, int ldd, int rows, hipStream_t s);
 WsLayout ws_layout(const ncx_dims& d);
 __host__ __device__ static inline int pad_to(int x, int m) { return (x + m - 1) / m * m; }
 // The fused forward kernel (ncx_main.h) takes operands whose widths are multiples of 4 (16-byte windows, no straddling);

@@ -47,6 +47,7 @@ template <int BM_, int BN_, int WGM_, int WGN_, int DEPTH_, int OCC_, int T_ = M
 struct MainCfg {
     static constexpr int BM = BM_, BN = BN_, WGM = WGM_, WGN = WGN_, DEPTH = DEPTH_, OCC = OCC_, T = T_;
     static constexpr bool X6 = X6_;
+    static constexpr int EPI = 0;                                   // which epilogue the kernel is compiled with (EPI_MLB: WithMlbEpi below)
     static constexpr int RP = T / 8;                                // tile rows per loader pass (8 threads x 16 bytes per 32-float row)
     static constexpr int BM_LDS = (BM + RP - 1) / RP * RP;        // A rows held in LDS (a multiple of the loader pass)
     static constexpr int LDS6 = 2 * 3 * (BM_LDS + BN) * MF6_P;      // X6: [2 buffers][3 planes][A rows | W rows][MF6_P]
@@ -56,6 +57,14 @@ struct MainCfg {
     static constexpr int LDS_FOLD = BM % 96 == 0 ? 2 * (32 * (T / 64) + 128) * MF_P * 4   // MK_VFOLD, one triplet per wave: A 32 rows per wave, W_k | W_m 2 x 64 rows
                                                  : 2 * (80 + 2 * 64) * MF_P * 4;          // MK_VFOLD on 48-row tiles: A 80 rows, two effective weight tiles
 };
+
+// EPI_MLB (the MLB producer's x_v product, ncx_mlb.hip; MLBFusion.forward, vqa/models/fusion.py:31-50): after bias and activation the
+// value is multiplied by the question's x_q row (epi.fold_mul[(r / (K + 1)) * epi.ld_fold + n]), the product z is row-split
+// (epi.rowsplit_g = K + 1: image 0 of a question -> epi.out0, images 1 .. K -> out) and, when args.t_out is set, t = tanh(z) is stored
+// beside it in the same pass (t_out0 / t_out, leading dimension N): the classifier's plain operand.  A compile-time choice: the
+// other instantiations keep their code.
+enum { EPI_STD = 0, EPI_MLB = 1 };
+template <class CFG> struct WithMlbEpi : CFG { static constexpr int EPI = EPI_MLB; };
 
 typedef const __attribute__((address_space(1))) float* gfptr;      // global address space: global_load, never flat_load
 typedef const __attribute__((address_space(1))) int* giptr;
@@ -1096,6 +1105,25 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
                 v[jj] = x;
             }
         }
+        if constexpr (CFG::EPI == EPI_MLB) {
+            // (split == 1, host-checked)  z = act(acc + bias) * x_q[question]; rows -> z_orig / z_knns; t = tanh(z) beside it
+            const int g = e.rowsplit_g, b = r / g, jr = r - b * g;
+            const f32x4 xq = win(e.fold_mul + (long long)b * e.ld_fold, nl, sh);
+            v *= xq;
+            const long long ro = jr == 0 ? (long long)b : (long long)b * (g - 1) + jr - 1;
+            float* oz = (jr == 0 ? e.out0 + ro * e.ldo0 : args.out + ro * args.ldo) + n;
+            if (n + 3 < N) *(f32x4u*)oz = v;
+            else { oz[0] = v[0]; if (n + 1 < N) oz[1] = v[1]; if (n + 2 < N) oz[2] = v[2]; }
+            if (args.t_out) {
+                float* ot = (jr == 0 ? args.t_out0 : args.t_out) + ro * N + n;
+                f32x4 t;
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) t[jj] = tanhf(v[jj]);
+                if (n + 3 < N) *(f32x4u*)ot = t;
+                else { ot[0] = t[0]; if (n + 1 < N) ot[1] = t[1]; if (n + 2 < N) ot[2] = t[2]; }
+            }
+            continue;
+        }
         float* o = dst + (long long)r * ldd + n;
         if (n + 3 < N) *(f32x4u*)o = v;
         else { o[0] = v[0]; if (n + 1 < N) o[1] = v[1]; if (n + 2 < N) o[2] = v[2]; }
@@ -1159,6 +1187,12 @@ static inline int launch_main_fwd(MainArgs& a, hipStream_t s) {
     auto is = [&](std::initializer_list<int> ks) { if ((int)ks.size() != a.nseg) return false; int i = 0; for (int k : ks) if (a.seg[i++].kind != k) return false; return true; };
     constexpr int G = MK_GATHER, X = MK_GATHER_MUL, P = MK_PLAIN, S = MK_SOFTMAX;
     constexpr int V = MK_VFOLD;
+    if constexpr (CFG::EPI == EPI_MLB) {     // the MLB producer's x_v: one gathered segment, unsplit, every epilogue operand present
+        if (!is({G}) || a.split > 1 || a.dist_out || a.N < 4 || !a.epi.bias || !a.epi.fold_mul || a.epi.rowsplit_g < 2 || !a.epi.out0 ||
+            !a.out || (a.t_out && !a.t_out0))
+            return NCX_E_FLAGS;
+        return launch_main_fwd_seq<CFG, false, G>(a, s);
+    } else {
     if (a.seg[0].kind == V) {                // the per-triplet fold of the two v segments: its own tile shape
         if constexpr (CFG::BM == 48 && CFG::BN == 64 && CFG::WGM == 1 && CFG::DEPTH == 2) {
             if (a.split > 1 || a.seg[0].klen % MF_BK || a.seg[0].klen < 2 * MF_BK || !a.epi.rowadd || a.epi.rowdiv != 24) return NCX_E_FLAGS;
@@ -1203,6 +1237,7 @@ static inline int launch_main_fwd(MainArgs& a, hipStream_t s) {
     if (is({G, P, P, P}))    return launch_main_fwd_seq<CFG, false, G, P, P, P>(a, s);
     if (is({P, P}))          return launch_main_fwd_seq<CFG, false, P, P>(a, s);
     return NCX_E_FLAGS;
+    }
     }
 }
 

@@ -47,6 +47,13 @@ int main_forward(MainArgs& a, hipStream_t s) {
     return launch_main_fwd<MainCfg0>(a, s);
 }
 
+// x_v of the MLB producer: 96 x 128 tiles, one workgroup per CU, once they fill the chip (12 800 x 1200 at B = 512: 1340 tiles), else 48 x 128
+int main_forward_mlb(MainArgs& a, hipStream_t s) {
+    const long long tiles96 = (long long)((a.M + 95) / 96) * ((a.N + 127) / 128);
+    if (tiles96 * 10 >= (long long)num_cus() * 9) return launch_main_fwd<WithMlbEpi<MainCfg2>>(a, s);
+    return launch_main_fwd<WithMlbEpi<MainCfg0>>(a, s);
+}
+
 // ... with the experiment hooks and the K = 48 rule applied: the form main_forward takes
 int main_fold_rows_eff(long long M, long long N, int rowdiv) {
     int rows = main_fold_rows(M, N);

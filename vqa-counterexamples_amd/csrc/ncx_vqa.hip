@@ -13,6 +13,14 @@ __global__ __launch_bounds__(256) void k_pad_rows(const float* __restrict__ src,
     const int r = (int)(i / ldd), c = (int)(i - (long long)r * ldd);
     dst[i] = c < cols ? src[(long long)r * lds_ + c] : 0.f;
 }
+}  // extern "C"
+namespace ncx {
+hipError_t pad_rows(const float* src, long long ld_src, int cols, float* dst, int ldd, int rows, hipStream_t s) {
+    hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)cdiv((long long)rows * ldd, 256)), dim3(256), 0, s, src, ld_src, cols, dst, ldd, rows);
+    return hipGetLastError();
+}
+}  // namespace ncx
+extern "C" {
 static VqaLayout vqa_layout(const ncx_dims& d, const ncx_mutan_params& m, GemmPlan* plans /*[5]*/) {
     VqaLayout w{};
     size_t off = 0;
@@ -122,8 +130,7 @@ int ncx_vqa_forward(const ncx_dims* dp, const float* feats, const int32_t* img_i
         if (d.dz % 32) {
             float* wcp = (float*)(ws + w.wcp);
             const int ldd = pad_to(d.dz, 32);
-            hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)cdiv((long long)d.A * ldd, 256)), dim3(256), 0, s, m.wc, (long long)d.dz, d.dz, wcp, ldd, d.A);
-            NCX_HIP_TRY(hipGetLastError());
+            NCX_HIP_TRY(pad_rows(m.wc, (long long)d.dz, d.dz, wcp, ldd, d.A, s));
             wc = wcp; ldw = ldd;
         }
         MainArgs a{}; a.M = d.B * d.K; a.N = d.A; a.nseg = 1;

@@ -19,7 +19,7 @@ NCX_F_BF16 = 16       # BASELINE configs[4]: bf16 operands for the two dominant 
 
 EXPORTS = ("ncx_input_size", "ncx_workspace_bytes", "ncx_forward", "ncx_forward_phase", "ncx_loss_rank", "ncx_backward", "ncx_backward_phase",
            "ncx_adam_step", "ncx_version", "ncx_profile_begin", "ncx_profile_end", "ncx_plan_query",
-           "ncx_vqa_workspace_bytes", "ncx_vqa_forward", "ncx_knn_workspace_bytes", "ncx_knn", "ncx_cosine_gram_workspace_bytes", "ncx_cosine_gram", "ncx_semantic_scores",
+           "ncx_vqa_workspace_bytes", "ncx_vqa_forward", "ncx_mlb_workspace_bytes", "ncx_mlb_forward", "ncx_knn_workspace_bytes", "ncx_knn", "ncx_cosine_gram_workspace_bytes", "ncx_cosine_gram", "ncx_semantic_scores",
            "ncx_similarity_scores",
            "ncx_ws_region", "ncx_wgmap_check",
            "ncx_comm_unique_id", "ncx_comm_create", "ncx_comm_destroy", "ncx_allreduce", "ncx_train_tail", "ncx_profile_stamps",
@@ -56,6 +56,11 @@ class NcxGrads(C.Structure):
 class NcxMutanParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("wv", "bv", "wq", "bq", "whv", "bhv", "whq", "bhq", "wc", "bc")] + \
                [(n, C.c_int32) for n in ("dhv", "dhq", "R", "act_v", "act_q")]
+
+
+class NcxMlbParams(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("wv", "bv", "wq", "bq", "wc", "bc")] + \
+               [(n, C.c_int32) for n in ("dh", "act_v", "act_q", "act_c")]
 
 
 class NcxScorerDims(C.Structure):
@@ -129,6 +134,11 @@ def lib():
     L.ncx_vqa_workspace_bytes.argtypes = [C.POINTER(NcxDims), C.POINTER(NcxMutanParams)]
     L.ncx_vqa_forward.restype = C.c_int
     L.ncx_vqa_forward.argtypes = [C.POINTER(NcxDims), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NcxMutanParams), C.c_void_p,
+                                  C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ncx_mlb_workspace_bytes.restype = C.c_size_t
+    L.ncx_mlb_workspace_bytes.argtypes = [C.POINTER(NcxDims), C.POINTER(NcxMlbParams)]
+    L.ncx_mlb_forward.restype = C.c_int
+    L.ncx_mlb_forward.argtypes = [C.POINTER(NcxDims), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NcxMlbParams), C.c_void_p,
                                   C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ncx_knn_workspace_bytes.restype = C.c_size_t
     L.ncx_knn_workspace_bytes.argtypes = [C.c_int32, C.c_int32]

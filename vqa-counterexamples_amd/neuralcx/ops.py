@@ -22,7 +22,7 @@ import os
 
 from . import _lib
 from ._lib import (NCX_F_A_EMB, NCX_F_ALL, NCX_F_V_DIST, NCX_F_V_MULT, NCX_F_V_RANK, NcxDims, NcxGrads,
-                   NcxInputs, NcxMutanParams, NcxParams)
+                   NcxInputs, NcxMlbParams, NcxMutanParams, NcxParams)
 
 PARAM_FIELDS = ("answer_embedding", "w1", "b1", "w2", "b2", "w3", "b3", "w_out", "b_out")
 # state_dict names of the reference (vqa/models/cx.py:240-257) -> C ABI field
@@ -275,17 +275,56 @@ class MutanWeights:
         return m
 
 
-def vqa_forward(feats: torch.Tensor, img_idx: torch.Tensor, q_emb: torch.Tensor, mw: MutanWeights, want_a_orig=False, ws=None):
-    """HIP replacement of CXModelBase.vqa_forward below the question encoder (cx.py:64-104).
+class MlbWeights:
+    """Frozen MLBNoAtt parameters as ncx_mlb_forward wants them (contiguous fp32: fusion.linear_v / linear_q, linear_classif).
+    Built once per model; rebuild after loading a checkpoint.  Activations in {none, tanh}; a fusion block without dim_v or dim_q
+    (the reference then passes that input through, fusion.py:33-47) is refused."""
+    WS_BYTES, FORWARD = "ncx_mlb_workspace_bytes", "ncx_mlb_forward"
+
+    def __init__(self, vqa_model):
+        f, opt = vqa_model.fusion, vqa_model.opt["fusion"]
+        for k in ("dim_v", "dim_q", "dim_h"):
+            if k not in opt:
+                raise _lib.NcxError("ncx_mlb_forward needs fusion.%s (a block that passes an input through is not supported)" % k)
+        act = {None: 0, "tanh": 2}
+        acts = (opt.get("activation_v"), opt.get("activation_q"), vqa_model.opt.get("classif", {}).get("activation"))
+        for name, a in zip(("fusion.activation_v", "fusion.activation_q", "classif.activation"), acts):
+            if a not in act:
+                raise _lib.NcxError("ncx_mlb_forward supports %s in {none, tanh}, got %r" % (name, a))
+        c = lambda t: t.detach().float().contiguous()
+        self.t = dict(wv=c(f.linear_v.weight), bv=c(f.linear_v.bias), wq=c(f.linear_q.weight), bq=c(f.linear_q.bias),
+                      wc=c(vqa_model.linear_classif.weight), bc=c(vqa_model.linear_classif.bias))
+        self.dz = opt["dim_h"]
+        self.A = self.t["wc"].shape[0]
+        self.act_v, self.act_q, self.act_c = (act[a] for a in acts)
+
+    def c_struct(self):
+        m = NcxMlbParams()
+        for k, v in self.t.items():
+            setattr(m, k, _ptr(v, torch.float32, k))
+        m.dh, m.act_v, m.act_q, m.act_c = self.dz, self.act_v, self.act_q, self.act_c
+        return m
+
+
+def vqa_weights(vqa_model):
+    """The weights object of the HIP producer for a frozen no-attention VQA model: MlbWeights for an MLB fusion, else MutanWeights."""
+    from vqa.models.fusion import MLBFusion
+    return MlbWeights(vqa_model) if isinstance(vqa_model.fusion, MLBFusion) else MutanWeights(vqa_model)
+
+
+def vqa_forward(feats: torch.Tensor, img_idx: torch.Tensor, q_emb: torch.Tensor, mw, want_a_orig=False, ws=None):
+    """HIP replacement of CXModelBase.vqa_forward below the question encoder (cx.py:64-104), for the producer `mw`
+    belongs to (MutanWeights: ncx_vqa_forward; MlbWeights: ncx_mlb_forward).
     -> (a_orig or None, z_orig [B,dz], a_knns [B,K,A], z_knns [B,K,dz])."""
     B, K1 = img_idx.shape
     d = NcxDims()
     d.B, d.K, d.dv, d.dq, d.dz, d.da, d.A, d.H, d.L = B, K1 - 1, feats.shape[1], q_emb.shape[1], mw.dz, 4, mw.A, 4, 1
     d.n_img = feats.shape[0]
     m = mw.c_struct()
-    need = _lib.lib().ncx_vqa_workspace_bytes(C.byref(d), C.byref(m))
+    ws_name, fwd_name = getattr(mw, "WS_BYTES", "ncx_vqa_workspace_bytes"), getattr(mw, "FORWARD", "ncx_vqa_forward")
+    need = getattr(_lib.lib(), ws_name)(C.byref(d), C.byref(m))
     if need == 0:
-        raise _lib.NcxError("ncx_vqa_workspace_bytes: invalid dims")
+        raise _lib.NcxError("%s: invalid dims" % ws_name)
     if ws is None or ws.numel() < need + 256:
         ws = torch.empty(need + 256, dtype=torch.uint8, device=feats.device)
     dev = feats.device
@@ -293,10 +332,10 @@ def vqa_forward(feats: torch.Tensor, img_idx: torch.Tensor, q_emb: torch.Tensor,
     a_k = torch.empty(B, K1 - 1, mw.A, device=dev)
     a_o = torch.empty(B, mw.A, device=dev) if want_a_orig else None
     p, n = _ws_ptr(ws)
-    _lib.check(_lib.lib().ncx_vqa_forward(C.byref(d), _ptr(feats, torch.float32, "feats"), _ptr(img_idx, torch.int32, "img_idx"),
-                                          _ptr(q_emb, torch.float32, "q_emb"), C.byref(m), p, n, C.c_void_p(z_o.data_ptr()),
-                                          C.c_void_p(z_k.data_ptr()), C.c_void_p(a_k.data_ptr()),
-                                          C.c_void_p(a_o.data_ptr()) if a_o is not None else None, _stream()), "ncx_vqa_forward")
+    _lib.check(getattr(_lib.lib(), fwd_name)(C.byref(d), _ptr(feats, torch.float32, "feats"), _ptr(img_idx, torch.int32, "img_idx"),
+                                             _ptr(q_emb, torch.float32, "q_emb"), C.byref(m), p, n, C.c_void_p(z_o.data_ptr()),
+                                             C.c_void_p(z_k.data_ptr()), C.c_void_p(a_k.data_ptr()),
+                                             C.c_void_p(a_o.data_ptr()) if a_o is not None else None, _stream()), fwd_name)
     return a_o, z_o, a_k, z_k
 
 

@@ -33,6 +33,8 @@ import torch.nn as nn
 
 from neuralcx import ops
 
+from .fusion import out_dim as fusion_out_dim
+
 DIM_A = 2400      # cx.py:235
 
 
@@ -69,16 +71,17 @@ class CXModelBase(nn.Module):
         self.knn_size = knn_size
 
     def _hip_vqa_ok(self, image_features):
-        from .noatt import MutanNoAtt
-        return (isinstance(self.vqa_model, MutanNoAtt) and image_features.is_cuda and not self.trainable_vqa
+        from .noatt import MLBNoAtt, MutanNoAtt
+        return (isinstance(self.vqa_model, (MutanNoAtt, MLBNoAtt)) and image_features.is_cuda and not self.trainable_vqa
                 and getattr(self, "use_hip_vqa", True))
 
     @torch.no_grad()
     def vqa_forward(self, image_features, question_wids):
         """Frozen VQA model on the original + K candidate images -> a_orig, z_orig, a_knns, z_knns, q_emb
-        (same outputs as cx.py:64-104).  For MutanNoAtt on the GPU everything below the question encoder runs in
+        (same outputs as cx.py:64-104).  For MutanNoAtt and MLBNoAtt on the GPU everything below the question encoder runs in
         the HIP library (ncx_vqa_forward: gather + linear_v + tanh, R-term fusion folded in one chained GEMM,
-        classifier); otherwise plain PyTorch.  Either way the question branch is computed once per question
+        classifier; ncx_mlb_forward: gather + linear_v + tanh + hadamard product in one launch, classifier); otherwise plain
+        PyTorch (also with use_hip_vqa = False).  Either way the question branch is computed once per question
         (the reference duplicates q K+1 times first, cx.py:83-87)."""
         assert image_features.size(1) == self.knn_size + 1
         B, K1 = image_features.size(0), self.knn_size + 1
@@ -96,11 +99,11 @@ class CXModelBase(nn.Module):
         return (a[:, 0].contiguous(), z[:, 0].contiguous(), a[:, 1:].contiguous(), z[:, 1:].contiguous(), q_emb)
 
     def _hip_vqa_forward(self, image_features, q_emb, want_a_orig):
-        """ncx_vqa_forward on the MUTAN weights of this module (stacked once per device)."""
+        """ncx_vqa_forward / ncx_mlb_forward on the frozen weights of this module (packed once per device)."""
         B, K1 = image_features.size(0), self.knn_size + 1
         mw = self.__dict__.get("_mutan_weights")
         if mw is None or mw.t["wv"].device != image_features.device:
-            mw = ops.MutanWeights(self.vqa_model)
+            mw = ops.vqa_weights(self.vqa_model)
             self.__dict__["_mutan_weights"] = mw
         feats = image_features.reshape(B * K1, -1).float().contiguous()
         idx = torch.arange(B * K1, device=feats.device, dtype=torch.int32).view(B, K1)
@@ -154,7 +157,7 @@ class SemanticBaseline(CXModelBase):
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
-        self.dim_z = self.vqa_model.opt["fusion"]["dim_mm"]
+        self.dim_z = fusion_out_dim(self.vqa_model.opt["fusion"])
         self.emb = None
         self.lam = 0.5                     # cx.py:171 (default)
         self.__dict__["_grams"] = {}       # device -> device Gram of self.emb (not module state: checkpoints stay vqa_model.*)
@@ -239,7 +242,7 @@ class SimilarityModel(CXModelBase):
         super().__init__(*args, **kwargs)
         if self.trainable_vqa:
             raise NotImplementedError("trainable_vqa=True is not supported by the HIP path (frozen VQA model only)")
-        self.dim_z = self.vqa_model.opt["fusion"]["dim_mm"]
+        self.dim_z = fusion_out_dim(self.vqa_model.opt["fusion"])
 
     def forward(self, image_features, question_wids, answer_aids):
         if not image_features.is_cuda:
@@ -278,7 +281,7 @@ class NeuralModel(CXModelBase):
             raise ValueError("n_layers must be 1, 2 or 3")
         self.model_spec = dict(model_spec)
         fus = self.vqa_model.opt["fusion"]
-        self.dim_v, self.dim_q, self.dim_z = fus["dim_v"], fus["dim_q"], fus["dim_mm"]
+        self.dim_v, self.dim_q, self.dim_z = fus["dim_v"], fus["dim_q"], fusion_out_dim(fus)
         self.ans_size = len(self.vqa_model.vocab_answers)
         self.dim_a = DIM_A
         self.dim_h, self.n_layers, self.drop_p = dim_h, n_layers, drop_p
@@ -466,7 +469,7 @@ class LinearContext(_TrainableScorer):
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
-        self.dim_z = self.vqa_model.opt["fusion"]["dim_mm"]
+        self.dim_z = fusion_out_dim(self.vqa_model.opt["fusion"])
         self.linear = nn.Linear(self.knn_size * self.dim_z, self.knn_size)
 
     def forward(self, image_features, question_wids, answer_aids):
@@ -488,7 +491,7 @@ class PairwiseLinearModel(_TrainableScorer):
         super().__init__(*args, **kwargs)
         assert self.knn_size == 24                              # cx.py:384
         fus = self.vqa_model.opt["fusion"]
-        self.dim_v, self.dim_q, self.dim_z = fus["dim_v"], fus["dim_q"], fus["dim_mm"]
+        self.dim_v, self.dim_q, self.dim_z = fus["dim_v"], fus["dim_q"], fusion_out_dim(fus)
         self.dim_h = ops.PAIRLIN_H
         self.dim_a = ops.PAIRLIN_H
         self.answer_embedding = nn.Embedding(len(self.vqa_model.vocab_answers), self.dim_a)
@@ -548,7 +551,7 @@ class ContrastiveModel(CXModelBase):
         if self.trainable_vqa:
             raise NotImplementedError("trainable_vqa=True is not supported by the HIP path (frozen VQA model only)")
         fus = self.vqa_model.opt["fusion"]
-        self.dim_v, self.dim_q, self.dim_z = fus["dim_v"], fus["dim_q"], fus["dim_mm"]
+        self.dim_v, self.dim_q, self.dim_z = fus["dim_v"], fus["dim_q"], fusion_out_dim(fus)
         self.dim_h = ops.CONTRASTIVE_H
         self.dim_a = ops.CONTRASTIVE_H
         self.answer_embedding = nn.Embedding(len(self.vqa_model.vocab_answers), self.dim_a)

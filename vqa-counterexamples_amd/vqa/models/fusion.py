@@ -1,10 +1,44 @@
-"""MUTAN fusion (Ben-younes et al.), the producer of the multimodal vector z consumed by NeuralCX.
-Same arithmetic and state_dict keys as the reference's MutanFusion (vqa/models/fusion.py:53-121):
+"""The fusions of the two no-attention VQA models, the producers of the multimodal vector z consumed by NeuralCX.
+MutanFusion (Ben-younes et al.): same arithmetic and state_dict keys as the reference's (vqa/models/fusion.py:53-121):
 tanh(linear_v(v)), tanh(linear_q(q)), R rank-1 terms linear_hv_i(x_v) * linear_hq_i(x_q), summed.
-Plain PyTorch-ROCm (hipBLASLt under torch): SURVEY 8 marks it "next" (f1), not part of the HIP hot path."""
+MLBFusion (Kim et al.): the reference's (vqa/models/fusion.py:16-50): act(linear_v(v)) * act(linear_q(q)).
+These modules are the plain PyTorch-ROCm statement (the torch path of CXModelBase.vqa_forward and the yardstick of the tests);
+on the GPU the frozen models run in the HIP library (ncx_vqa_forward / ncx_mlb_forward)."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+
+def out_dim(fusion_opt):
+    """Width of z, the fusion block's output: dim_mm (MUTAN) when the block has it, else dim_h (MLB).  The reference's scorers read
+    opt['fusion']['dim_mm'] and would raise KeyError on an MLB config (cx.py:168,228); accepting both is a deliberate superset."""
+    if "dim_mm" in fusion_opt:
+        return fusion_opt["dim_mm"]
+    if "dim_h" in fusion_opt:
+        return fusion_opt["dim_h"]
+    raise KeyError("fusion options have neither dim_mm nor dim_h")
+
+
+class MLBFusion(nn.Module):
+    """x_mm = act_q(linear_q(q)) * act_v(linear_v(v)) (reference fusion.py:16-50; parameter names linear_v.*, linear_q.*).  A block without
+    dim_v / dim_q passes that input through, as the reference does."""
+
+    def __init__(self, opt):
+        super().__init__()
+        self.opt = opt
+        if "dim_v" in opt:
+            self.linear_v = nn.Linear(opt["dim_v"], opt["dim_h"])
+        if "dim_q" in opt:
+            self.linear_q = nn.Linear(opt["dim_q"], opt["dim_h"])
+
+    def _embed(self, x, name):
+        if "dim_" + name not in self.opt:
+            return x
+        x = getattr(self, "linear_" + name)(F.dropout(x, p=self.opt["dropout_" + name], training=self.training))
+        return getattr(torch, self.opt["activation_" + name])(x) if "activation_" + name in self.opt else x
+
+    def forward(self, input_v, input_q):
+        return torch.mul(self._embed(input_q, "q"), self._embed(input_v, "v"))
 
 
 class MutanFusion(nn.Module):

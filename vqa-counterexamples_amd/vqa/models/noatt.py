@@ -1,4 +1,4 @@
-"""No-attention VQA model used as the frozen feature producer of NeuralCX (reference: vqa/models/noatt.py:9-58).
+"""No-attention VQA models used as the frozen feature producer of NeuralCX (reference: vqa/models/noatt.py:9-58).
 Exposes what vqa.models.cx needs: .seq2vec, ._fusion(v, q), ._classif(z), .opt['fusion'], .vocab_answers."""
 import torch.nn as nn
 import torch.nn.functional as F
@@ -6,16 +6,16 @@ import torch.nn.functional as F
 from . import fusion, seq2vec
 
 
-class MutanNoAtt(nn.Module):
+class AbstractNoAtt(nn.Module):
+    """seq2vec + a fusion (set by the subclass) + the classifier over fusion.dim_h (reference noatt.py:9-35)."""
+
     def __init__(self, opt=None, vocab_words=(), vocab_answers=()):
         super().__init__()
         opt = opt or {}
-        opt["fusion"]["dim_h"] = opt["fusion"]["dim_mm"]
         self.opt, self.vocab_words, self.vocab_answers = opt, vocab_words, vocab_answers
         self.num_classes = len(vocab_answers)
-        self.seq2vec = seq2vec.factory(vocab_words, opt["seq2vec"], dim_q=opt["fusion"]["dim_q"])
+        self.seq2vec = seq2vec.factory(vocab_words, opt["seq2vec"], dim_q=opt["fusion"].get("dim_q", 2400))
         self.linear_classif = nn.Linear(opt["fusion"]["dim_h"], self.num_classes)
-        self.fusion = fusion.MutanFusion(opt["fusion"])
 
     def _fusion(self, input_v, input_q):
         return self.fusion(input_v, input_q)
@@ -28,3 +28,20 @@ class MutanNoAtt(nn.Module):
 
     def forward(self, input_v, input_q):
         return self._classif(self._fusion(input_v, self.seq2vec(input_q)))
+
+
+class MutanNoAtt(AbstractNoAtt):
+    def __init__(self, opt=None, vocab_words=(), vocab_answers=()):
+        opt = opt or {}
+        opt["fusion"]["dim_h"] = opt["fusion"]["dim_mm"]
+        super().__init__(opt, vocab_words, vocab_answers)
+        self.fusion = fusion.MutanFusion(opt["fusion"])
+
+
+class MLBNoAtt(AbstractNoAtt):
+    """The reference's MLBNoAtt (vqa/models/noatt.py:38-46): MLBFusion + (classif.activation) + linear_classif over fusion.dim_h.
+    state_dict keys: seq2vec.*, linear_classif.*, fusion.linear_v.*, fusion.linear_q.*."""
+
+    def __init__(self, opt=None, vocab_words=(), vocab_answers=()):
+        super().__init__(opt, vocab_words, vocab_answers)
+        self.fusion = fusion.MLBFusion(self.opt["fusion"])

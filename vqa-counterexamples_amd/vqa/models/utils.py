@@ -3,9 +3,9 @@ reference's nn.DataParallel wrapper (immediately unwrapped by counterexamples.py
 data_parallel=True is accepted and ignored."""
 import copy
 
-from .noatt import MutanNoAtt
+from .noatt import MLBNoAtt, MutanNoAtt
 
-_REGISTRY = {"MutanNoAtt": MutanNoAtt}
+_REGISTRY = {"MutanNoAtt": MutanNoAtt, "MLBNoAtt": MLBNoAtt}
 model_names = sorted(_REGISTRY)
 
 
