@@ -340,6 +340,36 @@ int ncx_similarity_scores(const float* feats, const int32_t* img_idx, int32_t n_
                           float* scores /*[B,K]*/, float* parts /*[B,K,3] v_cos|z_cos|xent, nullable*/,
                           int32_t* bad_id_flag, void* stream);
 
+/* ---- the question encoder (reference vqa/models/seq2vec.py; GRUEncoder: nn.Embedding -> one-layer nn.GRU -> last valid step) -----
+ * Forward only (the encoder is frozen wherever the counterexample path calls it); eval mode (no dropout).  Semantics, gate order r, z, n
+ * as torch.nn.GRU:
+ *   len_b = max(1, #{t : wids[b, t] != 0})          process_lengths (seq2vec.py:11-17) for right-padded questions
+ *   x_t = E[wids[b, t]]                              row 0 of E is read like any other row
+ *   r = s(W_ir x + b_ir + W_hr h + b_hr);  z = s(W_iz x + b_iz + W_hz h + b_hz);  n = tanh(W_in x + b_in + r (W_hn h + b_hn))
+ *   h' = (1 - z) n + z h, h_0 = 0;   q[b] = h after step len_b - 1          select_last (seq2vec.py:19-25)
+ * A row is advanced only while t < len_b: the rows are ordered by length on the device and step t multiplies the n_t = #{len_b > t}
+ * longest rows (one launch per step, always issued; nothing is read back).  The input projection E[wid] . W_ih^T rides in the same
+ * launch, for the valid (row, t) pairs only.  No atomics, no inter-workgroup wait: bit-identical from run to run.
+ * Unlike the rest of the ABI these four return -1 for ANY invalid argument (NULL pointer, dimension out of range, short or misaligned
+ * buffer); 1 <= T <= 64, B, V1, dim_emb, dim_q >= 1.
+ *
+ * ncx_gru_pack takes the role of the encoder's construction in factory (seq2vec.py:79-97): nn.GRU's weight_ih_l0 [3 dim_q, dim_emb],
+ * weight_hh_l0 [3 dim_q, dim_q], bias_ih_l0, bias_hh_l0 [3 dim_q] (gate blocks r | z | n) -> `packed` (ncx_gru_packed_bytes, 16-byte
+ * aligned), once per weight set:
+ *   W [ceil(dim_q / 32)][3 gates][32 units][kp] | bias [ceil(dim_q / 32)][6: ir iz in hr hz hn][32 units],  kp = pad32(dim_emb) + pad32(dim_q)
+ *   W row (j, g, u) = W_i{g}[32 j + u, :] zero-padded to pad32(dim_emb), then W_h{g}[32 j + u, :] zero-padded to pad32(dim_q)
+ * so a workgroup's 96 weight rows are the r, z and n rows of the SAME 32 hidden units and the gate arithmetic runs from registers. */
+size_t ncx_gru_packed_bytes(int32_t dim_emb, int32_t dim_q);                               /* 0 for invalid dims */
+int ncx_gru_pack(const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, int32_t dim_emb, int32_t dim_q,
+                 float* packed, void* stream);
+/* Workspace of ncx_gru_encode (256-byte aligned: the length plan and the two h buffers); 0 for invalid dims. */
+size_t ncx_gru_workspace_bytes(int32_t B, int32_t T, int32_t dim_emb, int32_t dim_q);
+/* Takes the role of process_lengths + the GRU + select_last (seq2vec.py:11-25) in the encoder's forward: wids [B, T] int32, right-padded
+ * with 0; E [V1, dim_emb] the embedding table; q_out [B, dim_q] in the input row order.  A word id outside [0, V1) is never used as an
+ * address (it is clamped; that row's output is meaningless) and *bad_id_flag is set to 1 (never cleared here; the caller zeroes it). */
+int ncx_gru_encode(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t dim_emb, int32_t dim_q,
+                   const float* packed, void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream);
+
 /* ---- the trainable scorers LinearContext and PairwiseLinearModel (reference vqa/models/cx.py:139-156, 379-425) ---------
  * Both train with the library's loss (ncx_loss_rank) and optimiser (ncx_adam_step): forward -> scores, ncx_loss_rank ->
  * dscores, backward -> gradients (the reference's loop, counterexamples.py:330-339).  Neither model has dropout.

@@ -78,6 +78,7 @@ def build_parser():
     p.add_argument("--syn_images", type=int, default=82783)
     p.add_argument("--max_steps", type=int, default=-1, help="stop an epoch early (smoke runs)")
     p.add_argument("--no_vqa_cache", action="store_true", help="produce q / z / answer logits per batch instead of once per split")
+    p.add_argument("--no_hip_seq2vec", action="store_true", help="run the question encoder in PyTorch instead of the HIP library (GRUEncoder.use_hip = False)")
     p.add_argument("--bf16", action="store_true", help="bf16 operands on the two dominant GEMMs (fp32 accumulate / master weights)")
     p.add_argument("--x6", action="store_true", help="NCX_F_X6: the three big fp32 products on the bf16 matrix cores with three-plane fp32-grade operands (same results to fp32 rounding; not the default)")
     p.add_argument("--path_trainset", type=str, default=None, help="overrides vqa.path_trainset of the YAML")
@@ -173,6 +174,8 @@ class Runner:
             else:
                 self.log("Warning: no VQA checkpoint at '{}' (continuing with the untrained VQA model)".format(ck))
         self.vqa.eval()                                                                      # cx.py:73-80 (frozen)
+        if a.no_hip_seq2vec and hasattr(self.vqa.seq2vec, "use_hip"):
+            self.vqa.seq2vec.use_hip = False
         for p_ in self.vqa.parameters():
             p_.requires_grad_(False)
         # the HIP producer's weights object: MutanWeights or (MLBNoAtt) MlbWeights; ops.vqa_forward dispatches on it
@@ -201,6 +204,7 @@ class Runner:
                 seen.add(id(ds))
                 nbytes = ds.cache_vqa_outputs(lambda img_idx, wids, ds=ds: self._vqa_outputs(ds, img_idx, wids))
                 self.log("=> cached VQA outputs of the {} split: {} examples, {:.2f} GB".format(name, ds.N, nbytes / 1e9))
+            ops.check_gru_ids(device=self.dev)      # a word id outside the vocabulary (nn.Embedding raises there): one sync, after the caches
 
     def set_semantic_embedding(self, emb):
         """SemanticBaseline.set_answer_embedding (cx.py:173-175): the cosine Gram, built once on the device."""

@@ -21,6 +21,7 @@ EXPORTS = ("ncx_input_size", "ncx_workspace_bytes", "ncx_forward", "ncx_forward_
            "ncx_adam_step", "ncx_version", "ncx_profile_begin", "ncx_profile_end", "ncx_plan_query",
            "ncx_vqa_workspace_bytes", "ncx_vqa_forward", "ncx_mlb_workspace_bytes", "ncx_mlb_forward", "ncx_knn_workspace_bytes", "ncx_knn", "ncx_cosine_gram_workspace_bytes", "ncx_cosine_gram", "ncx_semantic_scores",
            "ncx_similarity_scores",
+           "ncx_gru_packed_bytes", "ncx_gru_pack", "ncx_gru_workspace_bytes", "ncx_gru_encode",
            "ncx_ws_region", "ncx_wgmap_check",
            "ncx_comm_unique_id", "ncx_comm_create", "ncx_comm_destroy", "ncx_allreduce", "ncx_train_tail", "ncx_profile_stamps",
            "ncx_pairlin_workspace_bytes", "ncx_pairlin_forward", "ncx_pairlin_backward",
@@ -155,6 +156,15 @@ def lib():
     L.ncx_similarity_scores.restype = C.c_int
     L.ncx_similarity_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ncx_gru_packed_bytes.restype = C.c_size_t
+    L.ncx_gru_packed_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.ncx_gru_pack.restype = C.c_int
+    L.ncx_gru_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.ncx_gru_workspace_bytes.restype = C.c_size_t
+    L.ncx_gru_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    L.ncx_gru_encode.restype = C.c_int
+    L.ncx_gru_encode.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                 C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ncx_ws_region.restype = C.c_int
     L.ncx_ws_region.argtypes = [C.POINTER(NcxDims), C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.ncx_profile_begin.restype = C.c_int

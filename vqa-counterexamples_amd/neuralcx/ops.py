@@ -454,6 +454,136 @@ def check_similarity_ids(bad_flag: Optional[torch.Tensor] = None, device=None) -
         raise IndexError("feature row ids outside [0, n_img) or answer_aids outside [0, A) in a similarity_scores call")
 
 
+# ---- the question encoder (include/neuralcx.h: ncx_gru_*) -----------------------------------------------------------------------
+GRU_UNITS = 32          # hidden units per workgroup of the step kernel: the packed layout's block (csrc/ncx_gru.hip)
+
+
+def _pad32(n: int) -> int:
+    return (n + 31) // 32 * 32
+
+
+def gru_pack_layout(w_ih: torch.Tensor, w_hh: torch.Tensor, b_ih: torch.Tensor, b_hh: torch.Tensor) -> torch.Tensor:
+    """The packed layout of ncx_gru_pack restated with tensor ops (any device; not on the product path: GruWeights packs device
+    weights with the kernel, this is what a test or a host without the kernel compares against):
+    W [nj][3][32][kp] | bias [nj][6: ir iz in hr hz hn][32], kp = pad32(dim_emb) + pad32(dim_q), zero padded."""
+    dim_q, dim_emb = w_hh.shape[1], w_ih.shape[1]
+    kx, nj = _pad32(dim_emb), (dim_q + GRU_UNITS - 1) // GRU_UNITS
+    W = torch.zeros(nj * GRU_UNITS, 3, kx + _pad32(dim_q), dtype=torch.float32, device=w_ih.device)
+    W[:dim_q, :, :dim_emb] = w_ih.detach().float().view(3, dim_q, dim_emb).transpose(0, 1)
+    W[:dim_q, :, kx:kx + dim_q] = w_hh.detach().float().view(3, dim_q, dim_q).transpose(0, 1)
+    b = torch.zeros(nj * GRU_UNITS, 6, dtype=torch.float32, device=w_ih.device)
+    b[:dim_q, :3] = b_ih.detach().float().view(3, dim_q).t()
+    b[:dim_q, 3:] = b_hh.detach().float().view(3, dim_q).t()
+    W = W.view(nj, GRU_UNITS, 3, -1).transpose(1, 2)
+    b = b.view(nj, GRU_UNITS, 6).transpose(1, 2)
+    return torch.cat([W.reshape(-1), b.reshape(-1)])
+
+
+def gru_unpack_layout(packed: torch.Tensor, dim_emb: int, dim_q: int):
+    """-> (w_ih [3 dim_q, dim_emb], w_hh [3 dim_q, dim_q], b_ih [3 dim_q], b_hh [3 dim_q]) read back out of the packed layout."""
+    kx, nj = _pad32(dim_emb), (dim_q + GRU_UNITS - 1) // GRU_UNITS
+    kp = kx + _pad32(dim_q)
+    nw = nj * 3 * GRU_UNITS * kp
+    W = packed[:nw].view(nj, 3, GRU_UNITS, kp).transpose(1, 2).reshape(nj * GRU_UNITS, 3, kp)[:dim_q]
+    b = packed[nw:].view(nj, 6, GRU_UNITS).transpose(1, 2).reshape(nj * GRU_UNITS, 6)[:dim_q]
+    return (W[:, :, :dim_emb].transpose(0, 1).reshape(3 * dim_q, dim_emb), W[:, :, kx:kx + dim_q].transpose(0, 1).reshape(3 * dim_q, dim_q),
+            b[:, :3].t().reshape(-1), b[:, 3:].t().reshape(-1))
+
+
+class GruWeights:
+    """A GRUEncoder's frozen parameters as ncx_gru_encode wants them: the embedding table E [V + 1, dim_emb] (the parameter itself
+    when it is contiguous fp32) and the GRU's weights in the packed layout (ncx_gru_pack on the device; for a CPU encoder the same
+    layout from gru_pack_layout, which only inspection and tests use: gru_encode refuses host tensors).  Built once per weight set;
+    GRUEncoder rebuilds it when a parameter changes."""
+
+    def __init__(self, encoder):
+        g = encoder.gru
+        if not isinstance(g, torch.nn.GRU) or g.num_layers != 1 or g.bidirectional or not g.bias or not g.batch_first:
+            raise _lib.NcxError("ncx_gru_encode takes a one-layer unidirectional batch_first nn.GRU with biases")
+        E = encoder.embedding.weight.detach()
+        ws = [p.detach() for p in (g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0)]
+        if any(t.dtype != torch.float32 for t in [E] + ws):
+            raise _lib.NcxError("ncx_gru_encode takes fp32 parameters")
+        self.E = E.contiguous()
+        self.V1, self.dim_emb = self.E.shape
+        self.dim_q = g.hidden_size
+        nbytes = _lib.lib().ncx_gru_packed_bytes(self.dim_emb, self.dim_q)
+        if nbytes == 0:
+            raise _lib.NcxError("ncx_gru_pack: dims out of range (dim_emb %d, dim_q %d)" % (self.dim_emb, self.dim_q))
+        if self.E.is_cuda:
+            ws = [t.contiguous() for t in ws]
+            self.packed = torch.empty(nbytes // 4, dtype=torch.float32, device=self.E.device)
+            with torch.cuda.device(self.E.device):
+                _lib.check(_lib.lib().ncx_gru_pack(*[_ptr(t, torch.float32, "gru weight") for t in ws], self.dim_emb, self.dim_q,
+                                                   C.c_void_p(self.packed.data_ptr()), _stream()), "ncx_gru_pack")
+        else:
+            self.packed = gru_pack_layout(*ws)
+            assert self.packed.numel() * 4 == nbytes
+        self.t = {"E": self.E, "packed": self.packed}
+
+    def unpack(self):
+        return gru_unpack_layout(self.packed, self.dim_emb, self.dim_q)
+
+
+def gru_weights(encoder) -> GruWeights:
+    """The weights object of the HIP question encoder for a GRUEncoder (vqa/models/seq2vec.py)."""
+    return GruWeights(encoder)
+
+
+_GRU_FLAGS: Dict[torch.device, torch.Tensor] = {}
+
+
+def gru_bad_flag(device) -> torch.Tensor:
+    """The per-device int32 flag ncx_gru_encode sets on a word id outside [0, V + 1) (sticky until checked)."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    f = _GRU_FLAGS.get(device)
+    if f is None:
+        f = _GRU_FLAGS[device] = torch.zeros(1, dtype=torch.int32, device=device)
+    return f
+
+
+def gru_encode(wids: torch.Tensor, gw: GruWeights, bad_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The question encoder (ncx_gru_encode; GRUEncoder.forward in eval mode) on the current stream, no host sync: wids [B, T] word
+    ids right-padded with 0 -> q [B, dim_q], the hidden state after each question's last word.  Padded steps are not computed.
+    A word id outside [0, V + 1) is never used as an address; it sets `bad_flag` (default: gru_bad_flag(device)) and
+    check_gru_ids raises the IndexError -- deferred, as for semantic_scores."""
+    if wids.dim() != 2:
+        raise ValueError("wids must be [B, T], got %s" % (tuple(wids.shape),))
+    if wids.is_floating_point():
+        raise TypeError("wids must be an integer tensor, got %s" % wids.dtype)
+    B, T = wids.shape
+    if B < 1 or not 1 <= T <= 64:
+        raise ValueError("gru_encode takes B >= 1 questions of 1 <= T <= 64 steps, got [%d, %d]" % (B, T))
+    dev = wids.device
+    if gw.packed.device != dev:
+        raise _lib.NcxError("wids are on %s, the encoder's weights on %s" % (dev, gw.packed.device))
+    wids = wids.to(torch.int32).contiguous()
+    if bad_flag is None:
+        bad_flag = gru_bad_flag(dev)
+    n = _lib.lib().ncx_gru_workspace_bytes(B, T, gw.dim_emb, gw.dim_q)
+    if n == 0:
+        raise _lib.NcxError("ncx_gru_workspace_bytes: dims out of range")
+    ws = torch.empty(n + 256, dtype=torch.uint8, device=dev)
+    p, n = _ws_ptr(ws)
+    q = torch.empty(B, gw.dim_q, dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().ncx_gru_encode(_ptr(wids, torch.int32, "wids"), B, T, _ptr(gw.E, torch.float32, "E"), gw.V1, gw.dim_emb, gw.dim_q,
+                                         _ptr(gw.packed, torch.float32, "packed"), p, n, C.c_void_p(q.data_ptr()),
+                                         _ptr(bad_flag, torch.int32, "bad_flag"), _stream()), "ncx_gru_encode")
+    return q
+
+
+def check_gru_ids(bad_flag: Optional[torch.Tensor] = None, device=None) -> None:
+    """Raises IndexError (what nn.Embedding raises for such an id) if a gru_encode call since the last check saw a word id outside
+    [0, V + 1); clears the flag.  Synchronises with the flag's stream."""
+    if bad_flag is None:
+        bad_flag = gru_bad_flag(device if device is not None else "cuda")
+    if int(bad_flag.item()):
+        bad_flag.zero_()
+        raise IndexError("question_wids outside [0, V + 1) in a gru_encode call")
+
+
 # ---- the trainable scorers LinearContext and PairwiseLinearModel (include/neuralcx.h) -----------------------------------------
 PAIRLIN_H = 300                     # dim_h = dim_a = 300 in the reference (cx.py:391-392)
 PAIRLIN_FIELDS = ("answer_embedding", "w", "b", "w_out", "b_out")

@@ -110,8 +110,12 @@ class CXModelBase(nn.Module):
         return ops.vqa_forward(feats, idx, q_emb.float().contiguous(), mw, want_a_orig=want_a_orig)
 
     def refresh_vqa_weights(self):
-        """Call after loading a VQA checkpoint: the stacked MUTAN weights of the HIP path are cached."""
+        """Call after loading a VQA checkpoint: the stacked MUTAN weights of the HIP path are cached (and the packed weights of
+        the HIP question encoder, which would also notice the change on their own)."""
         self.__dict__.pop("_mutan_weights", None)
+        enc = getattr(self.vqa_model, "seq2vec", None)
+        if hasattr(enc, "drop_hip_weights"):
+            enc.drop_hip_weights()
 
     def forward(self, image_features, question_wids, answer_aids):
         raise NotImplementedError

@@ -6,13 +6,43 @@ import torch.nn as nn
 
 
 class GRUEncoder(nn.Module):
+    """nn.Embedding -> nn.GRU -> the hidden state after the last word.  On a CUDA device, when no gradient can be wanted and dropout
+    is inert, forward runs in the HIP library (ops.gru_encode: padded steps are skipped); `use_hip = False` keeps it in PyTorch."""
+    use_hip = True
+
     def __init__(self, vocab_words, dim_q=2400, dim_emb=620, dropout=0.25):
         super().__init__()
         self.embedding = nn.Embedding(len(vocab_words) + 1, dim_emb, padding_idx=0)
         self.gru = nn.GRU(dim_emb, dim_q, batch_first=True)
         self.dropout = nn.Dropout(dropout)
 
+    def _hip_ok(self, wids):
+        if not (self.use_hip and wids.is_cuda and wids.dim() == 2 and 1 <= wids.shape[1] <= 64 and wids.shape[0] >= 1):
+            return False
+        if self.training and self.dropout.p > 0:
+            return False
+        params = list(self.parameters())
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            return False
+        return all(p.dtype == torch.float32 and p.device == wids.device for p in params)
+
+    def _hip_weights(self):
+        """ops.GruWeights of the current parameters; repacked when a parameter moved or was written to (load_state_dict, .to(),
+        an optimizer step) -- data_ptr and the in-place version counter of every parameter are the key."""
+        from neuralcx import ops
+        key = tuple((p.data_ptr(), p._version) for p in self.parameters())
+        hit = self.__dict__.get("_hip_gru")
+        if hit is None or hit[0] != key:
+            hit = self.__dict__["_hip_gru"] = (key, ops.gru_weights(self))
+        return hit[1]
+
+    def drop_hip_weights(self):
+        self.__dict__.pop("_hip_gru", None)
+
     def forward(self, wids):
+        if self._hip_ok(wids):
+            from neuralcx import ops
+            return ops.gru_encode(wids, self._hip_weights())
         x = self.embedding(wids)
         out, _ = self.gru(x)
         last = (wids > 0).sum(1).clamp(min=1) - 1            # last valid step (right padding)
