@@ -297,7 +297,16 @@ int ncx_mlb_forward(const ncx_dims* d, const float* feats, const int32_t* img_id
  * euclidean distance, ascending (ties by row index), as out_idx [nq, k] int64 and out_dist [nq, k] fp32.
  * One call handles one block of queries; the workspace holds -|x_j|^2/2 for the table (computed when
  * norms_ready == 0, reusable by later calls with the same table and workspace) and the nq x n product block.
- * 1 <= k <= min(n, 120); dv >= 4. */
+ * 1 <= k <= min(n, 120); dv >= 4.
+ * PRECONDITION: every element of table and queries is finite (neuralcx.knn.knn checks it; the C ABI does not).
+ * Precision: the k + 8 candidates are chosen on the fp32 products V = q.x_j - |x_j|^2/2 and ranked exactly (fp64), so the
+ * exact squared distance of a returned row exceeds the true k-th one by at most
+ *   tau = 4 (dv + 2) 2^-24 max_j (sum_t |q_t x_jt| + |x_j|^2 / 2)      (0 where the gaps between neighbours exceed tau).
+ * Status: two int32 words at byte ncx_knn_status_offset(n) of the workspace, zeroed by a call with norms_ready == 0 and
+ * sticky over the calls that follow it.  Word 0 != 0: some query row kept more distinct products in one bin than the
+ * candidate buffer holds after the last refinement level; word 1 != 0: a product was not finite.  Either way that
+ * call's output is not to be used; the caller reads the words after its last block (one readback per table). */
+size_t ncx_knn_status_offset(int32_t n);
 size_t ncx_knn_workspace_bytes(int32_t n, int32_t block_rows);
 int ncx_knn(const float* table, int32_t n, const float* queries, int32_t nq, int32_t dv, int32_t k,
             int32_t norms_ready, void* workspace, size_t workspace_bytes, int64_t* out_idx, float* out_dist,

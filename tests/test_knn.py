@@ -86,7 +86,8 @@ def test_knn_full_width_rows_vs_sklearn_and_properties():
 
 @pytest.mark.gpu
 def test_knn_mass_ties():
-    """All-identical rows (zero vectors) and k close to the table size: every distance is 0, indices are distinct."""
+    """All-identical rows (zero vectors), far more of them than the candidate buffer holds: every distance is 0, indices are
+    distinct, and the lowest row indices win."""
     from neuralcx.knn import knn
     x = np.zeros((1500, 64), np.float32)
     x[:40] = _table(5, 40, 64)
@@ -94,6 +95,7 @@ def test_knn_mass_ties():
     idx, dist = idx.cpu().numpy(), dist.cpu().numpy()
     assert all(len(set(r)) == 30 for r in idx) and idx.min() >= 0 and idx.max() < 1500
     assert np.all(dist[40:] == 0.0) and np.all(idx[40:] >= 40)
+    assert np.array_equal(idx[40:], np.tile(np.arange(40, 70), (1460, 1)))
     ref = np.sqrt(((x[:40, None, :] - x[None, :, :]) ** 2).sum(-1))
     assert np.allclose(np.sort(ref, axis=1)[:, :30], dist[:40], atol=1e-5)
 

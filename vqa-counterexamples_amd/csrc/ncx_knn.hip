@@ -6,9 +6,11 @@
 //   1. halfneg[j] = -|x_j|^2 / 2                                         (k_knn_halfnorm, once per table)
 //   2. V[i][j]    = q_i . x_j - |x_j|^2 / 2   for a block of queries      (the NT GEMM engine, bias = halfneg)
 //                   |q_i - x_j|^2 = |q_i|^2 - 2 V[i][j]: per query, the k nearest rows are the k LARGEST V
-//   3. per query row: linear-histogram select of the k+8 largest V (3 coalesced passes over the row), then the
-//      candidates' distances are recomputed exactly as sum (q - x)^2 (no cancellation), sorted by (distance, index)
-//      and the first k are written.                                       (k_knn_select, one workgroup per query)
+//   3. per query row: linear-histogram select of the k+8 largest V by (V, index) (3 coalesced passes over the row; more
+//      only when a bin must be refined), then the candidates' distances are recomputed exactly as sum (q - x)^2 (no
+//      cancellation), sorted by (distance, index) and the first k are written.   (k_knn_select, one workgroup per query)
+// Precision contract (DESIGN f4): a returned row's exact d2 exceeds the true k-th d2 by at most
+//   tau = 4 (dv + 2) 2^-24 max_j (sum_t |q_t x_jt| + |x_j|^2 / 2); input must be finite.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "ncx_internal.h"
@@ -20,7 +22,9 @@ constexpr int KNN_CAP = 1024;        // candidate buffer (elements at or above t
 constexpr int KNN_MAXK = 128;        // k + margin
 constexpr int KNN_LEVELS = 3;
 
-__global__ __launch_bounds__(256) void k_knn_halfnorm(const float* __restrict__ x, int n, int dv, float* __restrict__ halfneg) {
+__global__ __launch_bounds__(256) void k_knn_halfnorm(const float* __restrict__ x, int n, int dv, float* __restrict__ halfneg,
+                                                      int* __restrict__ status) {
+    if (blockIdx.x == 0 && threadIdx.x < 2) status[threadIdx.x] = 0;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= n) return;
     const float* p = x + (long long)row * dv;
@@ -30,34 +34,36 @@ __global__ __launch_bounds__(256) void k_knn_halfnorm(const float* __restrict__ 
     if (lane == 0) halfneg[row] = -0.5f * s;
 }
 
-struct KnnLevel { float lo, scale; int b; };
+// Status word of a table's workspace (see ncx_knn_status_offset in neuralcx.h): cleared by k_knn_halfnorm, set by k_knn_select.
+// Each word is only ever stored as 1 (plain stores from any workgroup: no atomics, no ordering needed).
+constexpr int KNN_ST_EXHAUSTED = 0;  // word 0: distinct products still overflow the candidate buffer after the last level
+constexpr int KNN_ST_NONFINITE = 1;  // word 1: a product row is not finite (the input was not, or its products overflow fp32)
 
-// membership of v in the candidate set defined by the refinement levels: bin above the chosen one at the first level
-// where it differs, or inside the chosen bin at every level.  Same float expressions as the histogram pass.
+// bin of v in a histogram of [lo, lo + KNN_BINS / scale): monotone in v, clamped at both ends
 __device__ inline int knn_bin(float v, float lo, float scale) {
     const float f = (v - lo) * scale;
     int b = (int)f;
     return b < 0 ? 0 : b > KNN_BINS - 1 ? KNN_BINS - 1 : b;
 }
-// returns +1 above, 0 inside the chosen bins of all `nl` levels, -1 below
-__device__ inline int knn_classify(float v, const KnnLevel* lv, int nl) {
-    for (int l = 0; l < nl; ++l) {
-        const int b = knn_bin(v, lv[l].lo, lv[l].scale);
-        if (b > lv[l].b) return 1;
-        if (b < lv[l].b) return -1;
-    }
-    return 0;
+// +1 above, 0 inside, -1 below the chosen bin of the last level.  That level's members are the values inside [lo, hi]; knn_bin
+// is monotone, so everything above hi is above the bin and everything below lo is below it.
+__device__ inline int knn_classify(float v, float lo, float hi, float scale, int chosen) {
+    if (v > hi) return 1;
+    if (v < lo) return -1;
+    const int b = knn_bin(v, lo, scale);
+    return b > chosen ? 1 : b < chosen ? -1 : 0;
 }
 
 __global__ __launch_bounds__(256) void k_knn_select(const float* __restrict__ V, long long ldv, const float* __restrict__ table,
                                                     const float* __restrict__ queries, int n, int dv, int k, int kc,
-                                                    long long* __restrict__ out_idx, float* __restrict__ out_dist) {
+                                                    long long* __restrict__ out_idx, float* __restrict__ out_dist,
+                                                    int* __restrict__ status) {
     __shared__ int hist[KNN_BINS];
     __shared__ float cand_v[KNN_CAP];
     __shared__ int cand_j[KNN_CAP];
-    __shared__ float red_a[4], red_b[4];
-    __shared__ KnnLevel lv[KNN_LEVELS];
-    __shared__ int s_nl, s_count, s_count_in, s_done, s_above_total, s_chosen;
+    __shared__ float red_a[4], red_b[4], red_c[4];
+    __shared__ int s_count, s_count_in, s_done, s_above_total, s_chosen;
+    __shared__ int s_wcnt[2][4];
     __shared__ float top_v[KNN_MAXK];
     __shared__ int top_j[KNN_MAXK];
     __shared__ double top_d[KNN_MAXK];
@@ -66,26 +72,31 @@ __global__ __launch_bounds__(256) void k_knn_select(const float* __restrict__ V,
     const float* row = V + q * ldv;
 
     // pass 1: range of the row
-    float mx = -INFINITY, mn = INFINITY;
-    for (int j = tid; j < n; j += 256) { const float v = row[j]; mx = fmaxf(mx, v); mn = fminf(mn, v); }
-    for (int o = 32; o > 0; o >>= 1) { mx = fmaxf(mx, __shfl_xor(mx, o)); mn = fminf(mn, __shfl_xor(mn, o)); }
-    if (lane == 0) { red_a[wave] = mx; red_b[wave] = mn; }
-    if (tid == 0) { s_nl = 0; s_done = 0; s_above_total = 0; }
+    float mx = -INFINITY, mn = INFINITY, nf = 0.f;                 // nf: v - v is 0 for a finite v, NaN otherwise
+    for (int j = tid; j < n; j += 256) { const float v = row[j]; mx = fmaxf(mx, v); mn = fminf(mn, v); nf += v - v; }
+    for (int o = 32; o > 0; o >>= 1) { mx = fmaxf(mx, __shfl_xor(mx, o)); mn = fminf(mn, __shfl_xor(mn, o)); nf += __shfl_xor(nf, o); }
+    if (lane == 0) { red_a[wave] = mx; red_b[wave] = mn; red_c[wave] = nf; }
+    if (tid == 0) { s_done = 0; s_above_total = 0; s_chosen = 0; }
+    if (tid < KNN_MAXK) { top_v[tid] = 0.f; top_j[tid] = 0; }       // a non-finite row may leave ranks unfilled: never an address
     __syncthreads();
     mx = fmaxf(fmaxf(red_a[0], red_a[1]), fmaxf(red_a[2], red_a[3]));
     mn = fminf(fminf(red_b[0], red_b[1]), fminf(red_b[2], red_b[3]));
+    if (tid == 0 && (red_c[0] + red_c[1]) + (red_c[2] + red_c[3]) != 0.f) status[KNN_ST_NONFINITE] = 1;
 
-    // refinement levels: histogram of the elements still undecided, pick the bin holding the kc-th largest
-    float lo = mn, hi = mx;
+    // refinement levels: histogram of the members (values inside [lo, hi]), pick the bin holding the kc-th largest.  A bin whose
+    // members do not fit the buffer's tie region is refined over the smallest and largest of ITS MEMBERS (a reduction over the
+    // row, run only then): each level narrows the real value range, wherever the row's minimum lies.
+    float lo = mn, hi = mx, scale = 0.f;
+    bool fits = true;
     for (int level = 0; level < KNN_LEVELS; ++level) {
         for (int b = tid; b < KNN_BINS; b += 256) hist[b] = 0;
         const float range = hi - lo;
-        const float scale = range > 0.f ? (float)KNN_BINS / range : 0.f;
+        // a refined range can be a few denormal steps wide: keep the scale finite, so that (lo - lo) * scale is 0, never 0 * inf
+        scale = range > 0.f ? fminf((float)KNN_BINS / range, 3.402823466e38f) : 0.f;
         __syncthreads();
-        const int nl = s_nl;
         for (int j = tid; j < n; j += 256) {
             const float v = row[j];
-            if (knn_classify(v, lv, nl) == 0) atomicAdd(&hist[knn_bin(v, lo, scale)], 1);
+            if (v >= lo && v <= hi) atomicAdd(&hist[knn_bin(v, lo, scale)], 1);
         }
         __syncthreads();
         if (wave == 0) {
@@ -104,38 +115,78 @@ __global__ __launch_bounds__(256) void k_knn_select(const float* __restrict__ V,
                     acc += h;
                 }
                 s_chosen = chosen;
-                lv[nl].lo = lo; lv[nl].scale = scale; lv[nl].b = chosen;
-                s_nl = nl + 1;
-                // stop when the chosen bin's elements fit the buffer's tie region (elements above it number < kc)
-                if (hist[chosen] <= KNN_CAP - kc || scale == 0.f || level == KNN_LEVELS - 1) s_done = 1;
-                else s_above_total += acc;
+                // stop when the chosen bin's members fit the buffer's tie region (elements above it number < kc)
+                if (hist[chosen] <= KNN_CAP - kc) s_done = 1;
+                else s_above_total += acc;                      // read by the next level, if the bin is refined
             }
         }
         __syncthreads();
         if (s_done) break;
-        // refine inside the chosen bin: its value range, slightly widened (clamped bins absorb the rounding)
-        const float w = range / (float)KNN_BINS;
-        const float nlo = lo + w * (float)s_chosen - 1e-6f * fabsf(lo + w * (float)s_chosen);
-        const float nhi = lo + w * (float)(s_chosen + 1) + 1e-6f * fabsf(lo + w * (float)(s_chosen + 1));
-        lo = nlo; hi = nhi;
+        // the chosen bin's members do not fit: their smallest and largest value
+        const int chosen = s_chosen;
+        float bmx = -INFINITY, bmn = INFINITY;
+        for (int j = tid; j < n; j += 256) {
+            const float v = row[j];
+            if (v >= lo && v <= hi && knn_bin(v, lo, scale) == chosen) { bmx = fmaxf(bmx, v); bmn = fminf(bmn, v); }
+        }
+        for (int o = 32; o > 0; o >>= 1) { bmx = fmaxf(bmx, __shfl_xor(bmx, o)); bmn = fminf(bmn, __shfl_xor(bmn, o)); }
+        if (lane == 0) { red_a[wave] = bmx; red_b[wave] = bmn; }
         __syncthreads();
+        bmx = fmaxf(fmaxf(red_a[0], red_a[1]), fmaxf(red_a[2], red_a[3]));
+        bmn = fminf(fminf(red_b[0], red_b[1]), fminf(red_b[2], red_b[3]));
+        __syncthreads();                                        // red_a / red_b are written again by the next level
+        // one value (exact ties: the lowest row indices are kept below), or no level left for distinct ones: never a guess
+        if (!(bmn < bmx) || level == KNN_LEVELS - 1) {
+            if (bmn < bmx && tid == 0) status[KNN_ST_EXHAUSTED] = 1;
+            fits = false;
+            break;
+        }
+        lo = bmn; hi = bmx;
     }
 
-    // pass 3: collect everything above the chosen bins (from the front of the buffer) and inside them (from the back:
-    // when more elements tie inside the last bin than the buffer holds, the overflow never displaces the ones above)
+    // pass 3: collect everything above the chosen bin (from the front of the buffer) and inside it (from the back, so that
+    // the in-bin elements never displace the ones above).  When the in-bin members fit, their slots come in arrival order: the
+    // set is complete and the rank sort below orders it.  When they do not (ties), the first KNN_CAP - kc of them BY ROW INDEX
+    // are kept: a block scan over each stride of 256 rows, j ascending.
     if (tid == 0) { s_count = 0; s_count_in = 0; }
     __syncthreads();
     {
-        const int nl = s_nl;
-        for (int j = tid; j < n; j += 256) {
-            const float v = row[j];
-            const int cls = knn_classify(v, lv, nl);
-            if (cls > 0) {
-                const int slot = atomicAdd(&s_count, 1);
-                if (slot < KNN_CAP) { cand_v[slot] = v; cand_j[slot] = j; }
-            } else if (cls == 0) {
-                const int slot = KNN_CAP - 1 - atomicAdd(&s_count_in, 1);
-                if (slot >= kc) { cand_v[slot] = v; cand_j[slot] = j; }      // above-elements number < kc <= slot
+        const int chosen = s_chosen;
+        if (fits) {
+            for (int j = tid; j < n; j += 256) {
+                const float v = row[j];
+                const int cls = knn_classify(v, lo, hi, scale, chosen);
+                if (cls > 0) {
+                    const int slot = atomicAdd(&s_count, 1);
+                    if (slot < KNN_CAP) { cand_v[slot] = v; cand_j[slot] = j; }
+                } else if (cls == 0) {
+                    const int slot = KNN_CAP - 1 - atomicAdd(&s_count_in, 1);
+                    if (slot >= kc) { cand_v[slot] = v; cand_j[slot] = j; }      // above-elements number < kc <= slot
+                }
+            }
+        } else {
+            int base = 0;                                                        // in-bin members before this stride (uniform)
+            for (int j0 = 0, it = 0; j0 < n && base < KNN_CAP - kc; j0 += 256, ++it) {
+                const int j = j0 + tid;
+                const float v = j < n ? row[j] : 0.f;
+                const int cls = j < n ? knn_classify(v, lo, hi, scale, chosen) : -1;
+                const unsigned long long in = __ballot(cls == 0);
+                if (lane == 0) s_wcnt[it & 1][wave] = __popcll(in);
+                __syncthreads();                                                 // two buffers: one barrier per stride
+                int before = base + __popcll(in & ((1ull << lane) - 1ull));
+                for (int w = 0; w < 4; ++w) { const int c = s_wcnt[it & 1][w]; if (w < wave) before += c; base += c; }
+                if (cls == 0) {
+                    const int slot = KNN_CAP - 1 - before;
+                    if (slot >= kc) { cand_v[slot] = v; cand_j[slot] = j; }
+                }
+            }
+            if (tid == 0) s_count_in = base;
+            for (int j = tid; j < n; j += 256) {                                 // the elements above: fewer than kc, any order
+                const float v = row[j];
+                if (knn_classify(v, lo, hi, scale, chosen) > 0) {
+                    const int slot = atomicAdd(&s_count, 1);
+                    if (slot < KNN_CAP) { cand_v[slot] = v; cand_j[slot] = j; }
+                }
             }
         }
     }
@@ -181,9 +232,12 @@ __global__ __launch_bounds__(256) void k_knn_select(const float* __restrict__ V,
 
 using namespace ncx;
 
+// workspace: halfneg [n] | status words (256 B) | V [block_rows, n]
+extern "C" size_t ncx_knn_status_offset(int32_t n) { return n < 1 ? 0 : align_up((size_t)n * 4, 256); }
+
 extern "C" size_t ncx_knn_workspace_bytes(int32_t n, int32_t block_rows) {
     if (n < 1 || block_rows < 1) return 0;
-    return align_up((size_t)n * 4, 256) + (size_t)block_rows * (size_t)n * 4 + 256;
+    return align_up((size_t)n * 4, 256) + 256 + (size_t)block_rows * (size_t)n * 4;
 }
 
 extern "C" int ncx_knn(const float* table, int32_t n, const float* queries, int32_t nq, int32_t dv, int32_t k,
@@ -194,9 +248,10 @@ extern "C" int ncx_knn(const float* table, int32_t n, const float* queries, int3
     if (workspace_bytes < ncx_knn_workspace_bytes(n, nq) || ((uintptr_t)workspace & 255)) return NCX_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream_;
     float* halfneg = (float*)workspace;
-    float* V = (float*)((char*)workspace + align_up((size_t)n * 4, 256));
+    int* status = (int*)((char*)workspace + ncx_knn_status_offset(n));
+    float* V = (float*)((char*)status + 256);
     if (!norms_ready) {
-        hipLaunchKernelGGL(k_knn_halfnorm, dim3((n + 3) / 4), dim3(256), 0, s, table, n, dv, halfneg);
+        hipLaunchKernelGGL(k_knn_halfnorm, dim3((n + 3) / 4), dim3(256), 0, s, table, n, dv, halfneg, status);
         NCX_HIP_TRY(hipGetLastError());
     }
     {
@@ -211,7 +266,7 @@ extern "C" int ncx_knn(const float* table, int32_t n, const float* queries, int3
     }
     const int kc = k + 8 < n ? k + 8 : n;
     hipLaunchKernelGGL(k_knn_select, dim3(nq), dim3(256), 0, s, (const float*)V, (long long)n, table, queries, n, dv, k, kc,
-                       (long long*)out_idx, out_dist);
+                       (long long*)out_idx, out_dist, status);
     NCX_HIP_TRY(hipGetLastError());
     return NCX_OK;
 }
