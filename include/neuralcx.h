@@ -460,6 +460,57 @@ int ncx_contrastive_loss(const ncx_contrastive_dims* d, void* workspace, size_t 
 int ncx_contrastive_backward(const ncx_contrastive_dims* d, const ncx_inputs* in, void* workspace, size_t workspace_bytes,
                              const float* dh, float* gw, float* gb, void* stream);
 
+/* ---- training the MutanNoAtt VQA model (reference train.py:136-145, vqa/lib/engine.py:6-56) -------------------------------------
+ * The fusion and classifier of MutanNoAtt in TRAINING mode, one image per question (row b reads feats[img_idx[b]]; an id outside
+ * [0, n_img) is clamped), with the stashes its backward needs; the cross-entropy head; the backward.  The question encoder stays
+ * outside: q_emb comes in, d loss / d q_emb goes out on request (torch autograd carries it into the encoder).  Supported model:
+ * what ncx_mutan_params expresses (activation_v / activation_q in {none, tanh}, no activation_hv / _hq / _mm, no
+ * classif.activation, dropout_hv = dropout_hq = 0): every MutanNoAtt YAML of the reference.  The optimiser is ncx_adam_step.
+ * Dims: B >= 1; dv, dq, dz, A, dhv, dhq >= 4; 1 <= R <= 10; 0 <= p < 1.  Status codes as the rest of the ABI, checked before any
+ * launch; no allocation, no atomics, no host read-back; bit-identical from run to run. */
+typedef struct ncx_vqa_train_dims {
+    int32_t B, dv, dq, dz, A, n_img;
+    float   p_v, p_q, p_c;     /* fusion.dropout_v, fusion.dropout_q (fusion.py:82,88), classif.dropout on z (noatt.py:27)        */
+    int32_t dropout_mode;      /* 0 off (the eval forward), 1 counter-based generator keyed by `seed` (layer ids 1 v, 2 q, 3 z;
+                                  element index row * width + column; oracle/ncx_oracle.py:dropout_keep_mask), 2 explicit masks  */
+    int32_t want_dq;           /* backward also writes d loss / d q_emb                                                         */
+    int32_t pad_;
+    uint64_t seed;
+} ncx_vqa_train_dims;
+typedef struct ncx_mutan_grads {          /* shapes of ncx_mutan_params' tensors; OVERWRITTEN by ncx_vqa_train_backward */
+    float* wv;  float* bv;  float* wq;  float* bq;  float* whv; float* bhv; float* whq; float* bhq; float* wc;  float* bc;
+} ncx_mutan_grads;
+/* Workspace of the forward / backward pair (256-byte aligned); 0 for invalid dims or an unsupported activation.  R, dhv, dhq,
+ * act_v, act_q are read from `m` (its pointers are not). */
+size_t ncx_vqa_train_workspace_bytes(const ncx_vqa_train_dims* d, const ncx_mutan_params* m);
+/* Replaces model(input_visual, input_question) of the train step (engine.py:22) below seq2vec: MutanFusion.forward
+ * (fusion.py:78-121) and AbstractNoAtt._classif (noatt.py:24-29) with F.dropout active.  logits [B, A]; z [B, dz] is the fusion
+ * output before the classifier's dropout.  masks (dropout_mode 2 only, else nullable): keep masks as 0 / 1 floats,
+ * [B, dv] | [B, dq] | [B, dz] back to back; a kept element is scaled by 1 / (1 - p).  dropout_mode 0 is the eval forward. */
+int ncx_vqa_train_forward(const ncx_vqa_train_dims* d, const float* feats, const int32_t* img_idx, const float* q_emb,
+                          const ncx_mutan_params* m, const float* masks, void* workspace, size_t workspace_bytes,
+                          float* logits, float* z, void* stream);
+/* Replaces nn.CrossEntropyLoss()(output, target) (train.py:136, engine.py:24), its gradient, and utils.accuracy(topk=(1, 5))
+ * (vqa/lib/utils.py:23-38) as hit COUNTS:
+ *   loss[1] = scale sum_b (logsumexp(logits[b]) - logits[b][target[b]])            scale = 1 / B when scale <= 0   (nullable)
+ *   dlogits [B, A] = (softmax - onehot) scale                                                                        (nullable)
+ *   hits_top1[1], hits_top5[1] = #{b : rank_b < 1}, #{b : rank_b < 5}, rank_b = #{c : x_c > x_t} + #{c < t : x_c == x_t}   (nullable)
+ * rows: [2 B] words of scratch (the per-example terms; the sums over b are taken from it in a fixed order by one workgroup).
+ * A target outside [0, A) is never used as an address: that example contributes 0 to every output, its dlogits row is 0 and
+ * *bad_flag is set to 1 (never cleared here; the caller zeroes it). */
+int ncx_ce_loss(const float* logits, const int32_t* target, int32_t B, int32_t A, float scale, float* loss, float* dlogits,
+                int32_t* hits_top1, int32_t* hits_top5, int32_t* bad_flag, float* rows, void* stream);
+/* Replaces loss.backward() (engine.py:36) for the tensors of ncx_mutan_params: every field of `g` is overwritten; dq_emb [B, dq]
+ * = d loss / d q_emb when d->want_dq (else nullable).  No gradient is taken with respect to the image features.  Reads what the
+ * forward left in the workspace: same dims, params, masks and workspace. */
+int ncx_vqa_train_backward(const ncx_vqa_train_dims* d, const ncx_mutan_params* m, const float* masks, void* workspace,
+                           size_t workspace_bytes, const float* dlogits, const ncx_mutan_grads* g, float* dq_emb, void* stream);
+/* Diagnostics / tests: byte offset and size of the tensors the forward dropped, valid after ncx_vqa_train_forward. */
+#define NCX_VT_WS_VD 1   /* drop_v(feats[img_idx]) [B, dv] */
+#define NCX_VT_WS_QD 2   /* drop_q(q_emb)          [B, dq] */
+#define NCX_VT_WS_ZC 3   /* drop_c(z)              [B, dz] */
+int ncx_vqa_train_ws_region(const ncx_vqa_train_dims* d, const ncx_mutan_params* m, int32_t which, size_t* offset, size_t* bytes);
+
 /* ---- diagnostics (bench.py / tests only; the only process-global state, off by default) --------------
  * GEMM ids: 0 Gt = W1[:,a_other].E^T, 1 Sh (shared segments), 2 MAIN (candidate segments, the dominant
  * forward kernel), 3 hidden layer l>=2 forward, 4 dW1 candidate columns (+dGt; the dominant backward

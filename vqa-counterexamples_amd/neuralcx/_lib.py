@@ -27,7 +27,8 @@ EXPORTS = ("ncx_input_size", "ncx_workspace_bytes", "ncx_forward", "ncx_forward_
            "ncx_pairlin_workspace_bytes", "ncx_pairlin_forward", "ncx_pairlin_backward",
            "ncx_linctx_workspace_bytes", "ncx_linctx_forward", "ncx_linctx_backward",
            "ncx_contrastive_workspace_bytes", "ncx_contrastive_forward", "ncx_contrastive_distances", "ncx_contrastive_loss",
-           "ncx_contrastive_backward")
+           "ncx_contrastive_backward",
+           "ncx_vqa_train_workspace_bytes", "ncx_vqa_train_forward", "ncx_ce_loss", "ncx_vqa_train_backward", "ncx_vqa_train_ws_region")
 
 
 class NcxDims(C.Structure):
@@ -57,6 +58,15 @@ class NcxGrads(C.Structure):
 class NcxMutanParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("wv", "bv", "wq", "bq", "whv", "bhv", "whq", "bhq", "wc", "bc")] + \
                [(n, C.c_int32) for n in ("dhv", "dhq", "R", "act_v", "act_q")]
+
+
+class NcxMutanGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("wv", "bv", "wq", "bq", "whv", "bhv", "whq", "bhq", "wc", "bc")]
+
+
+class NcxVqaTrainDims(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "dv", "dq", "dz", "A", "n_img")] + [(n, C.c_float) for n in ("p_v", "p_q", "p_c")] + \
+               [("dropout_mode", C.c_int32), ("want_dq", C.c_int32), ("pad_", C.c_int32), ("seed", C.c_uint64)]
 
 
 class NcxMlbParams(C.Structure):
@@ -211,6 +221,19 @@ def lib():
     L.ncx_contrastive_backward.restype = C.c_int
     L.ncx_contrastive_backward.argtypes = [P_CD, C.POINTER(NcxInputs), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p]
+    P_VT, P_MP = C.POINTER(NcxVqaTrainDims), C.POINTER(NcxMutanParams)
+    L.ncx_vqa_train_workspace_bytes.restype = C.c_size_t
+    L.ncx_vqa_train_workspace_bytes.argtypes = [P_VT, P_MP]
+    L.ncx_vqa_train_forward.restype = C.c_int
+    L.ncx_vqa_train_forward.argtypes = [P_VT, C.c_void_p, C.c_void_p, C.c_void_p, P_MP, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]
+    L.ncx_ce_loss.restype = C.c_int
+    L.ncx_ce_loss.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 7
+    L.ncx_vqa_train_backward.restype = C.c_int
+    L.ncx_vqa_train_backward.argtypes = [P_VT, P_MP, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(NcxMutanGrads), C.c_void_p,
+                                         C.c_void_p]
+    L.ncx_vqa_train_ws_region.restype = C.c_int
+    L.ncx_vqa_train_ws_region.argtypes = [P_VT, P_MP, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     _lib = L
     return L
 

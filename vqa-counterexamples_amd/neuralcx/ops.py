@@ -267,6 +267,17 @@ class MutanWeights:
         self.A = self.t["wc"].shape[0]
         self.act_v, self.act_q = act[opt.get("activation_v")], act[opt.get("activation_q")]
 
+    @classmethod
+    def from_tensors(cls, t: Dict[str, torch.Tensor], R: int, act_v: int = 2, act_q: int = 2):
+        """The same object around caller-owned tensors in the stacked layout (the VQA trainer's flat buffer views: a model
+        trained there feeds vqa_forward without re-stacking)."""
+        self = cls.__new__(cls)
+        self.t = dict(t)
+        self.dhv, self.dhq, self.R = t["wv"].shape[0], t["wq"].shape[0], int(R)
+        self.A, self.dz = t["wc"].shape
+        self.act_v, self.act_q = int(act_v), int(act_q)
+        return self
+
     def c_struct(self):
         m = NcxMutanParams()
         for k, v in self.t.items():
@@ -765,6 +776,111 @@ def contrastive_backward(d, batch: Batch, ws: torch.Tensor, gw: torch.Tensor, gb
     s.feats = _ptr(batch.feats, torch.float32, "feats")
     _lib.check(_lib.lib().ncx_contrastive_backward(C.byref(d), C.byref(s), p, n, _ptr(dh, torch.float32, "dh"), _ptr(gw, torch.float32, "gw"),
                                                    _ptr(gb, torch.float32, "gb"), _stream()), "ncx_contrastive_backward")
+
+
+# ---- training the MutanNoAtt VQA model (include/neuralcx.h: ncx_vqa_train_*, ncx_ce_loss) ---------------------------------
+MUTAN_FIELDS = ("wv", "bv", "wq", "bq", "whv", "bhv", "whq", "bhq", "wc", "bc")
+VT_WS_VD, VT_WS_QD, VT_WS_ZC = 1, 2, 3
+VT_LAYERS = dict(v=1, q=2, z=3)          # layer ids of the counter-based dropout generator
+
+
+def mutan_shapes(dv, dq, dhv, dhq, dz, R, A):
+    """Field -> shape of the stacked MutanNoAtt layout (MutanWeights / ncx_mutan_params), in flat-buffer order."""
+    return dict(wv=(dhv, dv), bv=(dhv,), wq=(dhq, dq), bq=(dhq,), whv=(R * dz, dhv), bhv=(R * dz,), whq=(R * dz, dhq), bhq=(R * dz,),
+                wc=(A, dz), bc=(A,))
+
+
+def vqa_train_dims(B, dv, dq, dz, A, n_img, p=(0.0, 0.0, 0.0), dropout_mode=0, seed=0, want_dq=False) -> _lib.NcxVqaTrainDims:
+    d = _lib.NcxVqaTrainDims()
+    d.B, d.dv, d.dq, d.dz, d.A, d.n_img = int(B), int(dv), int(dq), int(dz), int(A), int(n_img)
+    d.p_v, d.p_q, d.p_c = (float(x) for x in p)
+    d.dropout_mode, d.want_dq, d.seed = int(dropout_mode), int(bool(want_dq)), int(seed) & 0xFFFFFFFFFFFFFFFF
+    return d
+
+
+def vqa_train_workspace(d, mw, device) -> torch.Tensor:
+    m = mw.c_struct()
+    need = _lib.lib().ncx_vqa_train_workspace_bytes(C.byref(d), C.byref(m))
+    if need == 0:
+        raise _lib.NcxError("ncx_vqa_train_workspace_bytes: unsupported dims or activation")
+    return torch.empty(need + 256, dtype=torch.uint8, device=device)
+
+
+def vqa_train_forward(d, feats, img_idx, q_emb, mw, ws, masks=None):
+    """Training-mode fusion + classifier (ncx_vqa_train_forward) -> (logits [B, A], z [B, dz]); the stashes stay in ws."""
+    m = mw.c_struct()
+    logits = torch.empty(d.B, d.A, dtype=torch.float32, device=feats.device)
+    z = torch.empty(d.B, d.dz, dtype=torch.float32, device=feats.device)
+    p, n = _ws_ptr(ws)
+    _lib.check(_lib.lib().ncx_vqa_train_forward(C.byref(d), _ptr(feats, torch.float32, "feats"), _ptr(img_idx, torch.int32, "img_idx"),
+                                                _ptr(q_emb, torch.float32, "q_emb"), C.byref(m), _ptr(masks, torch.float32, "masks"), p, n,
+                                                C.c_void_p(logits.data_ptr()), C.c_void_p(z.data_ptr()), _stream()), "ncx_vqa_train_forward")
+    return logits, z
+
+
+def vqa_train_backward(d, mw, ws, dlogits, grads: Dict[str, torch.Tensor], masks=None):
+    """Every gradient of MUTAN_FIELDS into `grads` (overwritten); -> d loss / d q_emb [B, dq] when d.want_dq, else None."""
+    m = mw.c_struct()
+    g = _lib.NcxMutanGrads()
+    for k in MUTAN_FIELDS:
+        setattr(g, k, _ptr(grads[k], torch.float32, "grad " + k))
+    dq = torch.empty(d.B, d.dq, dtype=torch.float32, device=dlogits.device) if d.want_dq else None
+    p, n = _ws_ptr(ws)
+    _lib.check(_lib.lib().ncx_vqa_train_backward(C.byref(d), C.byref(m), _ptr(masks, torch.float32, "masks"), p, n,
+                                                 _ptr(dlogits, torch.float32, "dlogits"), C.byref(g), _ptr(dq, torch.float32, "dq_emb"),
+                                                 _stream()), "ncx_vqa_train_backward")
+    return dq
+
+
+def vqa_train_ws_view(d, mw, ws, which) -> torch.Tensor:
+    """The tensor the forward dropped (VT_WS_VD / _QD / _ZC) as a [B, width] view of the workspace (tests, diagnostics)."""
+    m = mw.c_struct()
+    off, nb = C.c_size_t(), C.c_size_t()
+    _lib.check(_lib.lib().ncx_vqa_train_ws_region(C.byref(d), C.byref(m), which, C.byref(off), C.byref(nb)), "ncx_vqa_train_ws_region")
+    pad = (-ws.data_ptr()) % 256
+    return ws[pad + off.value: pad + off.value + nb.value].view(torch.float32).view(d.B, -1)
+
+
+_VQA_FLAGS: Dict[torch.device, torch.Tensor] = {}
+
+
+def vqa_bad_flag(device) -> torch.Tensor:
+    """The per-device int32 flag ncx_ce_loss sets on a target outside [0, A) (sticky until checked)."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    f = _VQA_FLAGS.get(device)
+    if f is None:
+        f = _VQA_FLAGS[device] = torch.zeros(1, dtype=torch.int32, device=device)
+    return f
+
+
+def ce_loss(logits: torch.Tensor, target: torch.Tensor, scale: float = 0.0, want_grad: bool = True, bad_flag=None):
+    """Mean cross-entropy, its gradient and the top-1 / top-5 hit counts (ncx_ce_loss) on the current stream, no host sync.
+    -> dict(loss [1], dlogits [B, A] or None, hits1 [1] int32, hits5 [1] int32).  scale <= 0: 1 / B."""
+    B, A = logits.shape
+    dev = logits.device
+    if bad_flag is None:
+        bad_flag = vqa_bad_flag(dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    hits = torch.empty(2, dtype=torch.int32, device=dev)
+    rows = torch.empty(2 * B, dtype=torch.float32, device=dev)
+    dlogits = torch.empty(B, A, dtype=torch.float32, device=dev) if want_grad else None
+    _lib.check(_lib.lib().ncx_ce_loss(_ptr(logits, torch.float32, "logits"), _ptr(target, torch.int32, "target"), B, A, float(scale),
+                                      C.c_void_p(loss.data_ptr()), _ptr(dlogits, torch.float32, "dlogits"), C.c_void_p(hits.data_ptr()),
+                                      C.c_void_p(hits.data_ptr() + 4), _ptr(bad_flag, torch.int32, "bad_flag"), C.c_void_p(rows.data_ptr()),
+                                      _stream()), "ncx_ce_loss")
+    return dict(loss=loss, dlogits=dlogits, hits1=hits[0:1], hits5=hits[1:2])
+
+
+def check_vqa_targets(bad_flag: Optional[torch.Tensor] = None, device=None) -> None:
+    """Raises IndexError (nn.CrossEntropyLoss raises there) if a ce_loss call since the last check saw a target outside [0, A);
+    clears the flag.  Synchronises with the flag's stream."""
+    if bad_flag is None:
+        bad_flag = vqa_bad_flag(device if device is not None else "cuda")
+    if int(bad_flag.item()):
+        bad_flag.zero_()
+        raise IndexError("target outside [0, A) in a ce_loss call")
 
 
 class WorkspacePool:

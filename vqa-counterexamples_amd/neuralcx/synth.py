@@ -10,6 +10,7 @@ The ground truth is PLANTED so that ranking is learnable: the probability of can
 counterexample falls with its feature distance to the original image and with its neighbour rank (as in
 the real data, where the distance baseline reaches R@5 = 44 %: README.md:39 of the reference).
 """
+import math
 from typing import Optional
 
 import numpy as np
@@ -73,3 +74,50 @@ class SyntheticCX:
         a_k = torch.randn(B, K, self.A, generator=g, device=self.device) * 2.0
         b = Batch(self.feats, self.img_idx.index_select(0, sel), q, z_o, z_k, a_k, self.answer_aids.index_select(0, sel))
         return b, self.gt.index_select(0, sel)
+
+
+class SyntheticVQA:
+    """Synthetic VQA training data (there are no datasets offline): a resident feature table [n_img, dv], right-padded question word
+    ids [N, T] with their lengths, one image row per question, and answers drawn from a HIDDEN teacher -- a small MUTAN over the image
+    row and a bag-of-words question vector -- so that the task is learnable from (image, question).  Seeded; everything lives on
+    `device`.  The first n_train examples are the train split, the rest the val split."""
+
+    def __init__(self, n_examples=8192, n_img=1024, dv=2048, vocab=1000, T=26, A=2000, seed=1234, device="cuda:0", val_fraction=0.125,
+                 teacher_dim=64, teacher_R=2, temperature=0.5):
+        self.N, self.n_img, self.dv, self.vocab, self.T, self.A, self.seed = n_examples, n_img, dv, vocab, T, A, seed
+        self.device = torch.device(device)
+        g = torch.Generator(device="cpu").manual_seed(seed)
+        feats = torch.randn(n_img, dv, generator=g).abs_() * 0.45
+        img = torch.randint(0, n_img, (n_examples,), generator=g)
+        lengths = torch.randint(3, T + 1, (n_examples,), generator=g)
+        wids = torch.randint(1, vocab + 1, (n_examples, T), generator=g)
+        wids = wids * (torch.arange(T)[None, :] < lengths[:, None])
+        # the teacher: x_v = tanh(Wv v), x_q = tanh(mean word vector), z = sum_r (Hv_r x_v) * (Hq_r x_q), answer ~ softmax(Wc z / temperature)
+        h = teacher_dim
+        E = torch.randn(vocab + 1, h, generator=g); E[0] = 0
+        Wv = torch.randn(h, dv, generator=g) / math.sqrt(dv) * 3
+        Hv = torch.randn(teacher_R, h, h, generator=g) / math.sqrt(h) * 2
+        Hq = torch.randn(teacher_R, h, h, generator=g) / math.sqrt(h) * 2
+        Wc = torch.randn(A, h, generator=g) / math.sqrt(h) * 4
+        xv = torch.tanh((feats - feats.mean(0, keepdim=True))[img] @ Wv.t())
+        xq = torch.tanh(E[wids].sum(1) / lengths[:, None].float().sqrt())
+        z = sum((xv @ Hv[r].t()) * (xq @ Hq[r].t()) for r in range(teacher_R))
+        prob = torch.softmax(z @ Wc.t() / temperature, 1)
+        aid = torch.multinomial(prob, 1, generator=g)[:, 0]
+        self.feats = feats.to(self.device)
+        self.img_idx = img.to(torch.int32).to(self.device)
+        self.question_wids = wids.to(self.device)
+        self.lengths = lengths.to(self.device)
+        self.answer_aids = aid.to(torch.int32).to(self.device)
+        self.n_train = n_examples - int(n_examples * val_fraction)
+        self.vocab_words = ["w%d" % i for i in range(vocab)]
+        self.vocab_answers = ["a%d" % i for i in range(A)]
+
+    def split(self, name):
+        """-> (first id, count) of the 'train' / 'val' split"""
+        return (0, self.n_train) if name == "train" else (self.n_train, self.N - self.n_train)
+
+    def batch(self, sel: torch.Tensor):
+        """sel: int64 example ids -> (img_idx [B] int32, question_wids [B, T] int64, answer_aids [B] int32), all on the device"""
+        sel = sel.to(self.device)
+        return self.img_idx.index_select(0, sel), self.question_wids.index_select(0, sel), self.answer_aids.index_select(0, sel)

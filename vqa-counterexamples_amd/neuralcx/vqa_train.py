@@ -1,0 +1,199 @@
+"""Training the MutanNoAtt VQA model (reference train.py:136-145, vqa/lib/engine.py:6-56): the producer of the
+best_model.pth.tar the counterexample pipeline loads.
+
+MutanTrainFunction is the differentiable fusion + classifier (ncx_vqa_train_forward / _backward) for a caller that keeps torch
+autograd around it -- the module route of vqa.models.noatt.MutanNoAtt (`use_hip_train`), where the question encoder trains under
+autograd from the d loss / d q_emb the backward returns.  VqaTrainEngine is the whole step in HIP on flat buffers: forward,
+cross-entropy (ncx_ce_loss), backward, Adam (ncx_adam_step), for a frozen or externally trained encoder.
+"""
+import math
+from typing import Dict, Optional
+
+import torch
+
+from . import ops
+from .engine import FlatParams
+
+ACT_CODE = {None: 0, "tanh": 2}
+
+
+def route_for(opt) -> str:
+    """"hip" when the MutanNoAtt options `opt` are the model ncx_vqa_train_* supports, else "torch path: <why>".  Reads the
+    options only (never touches the library)."""
+    f = opt.get("fusion", {})
+    for k in ("activation_hv", "activation_hq", "activation_mm"):
+        if k in f:
+            return "torch path: fusion.%s is not supported in HIP" % k
+    for k in ("activation_v", "activation_q"):
+        if f.get(k) not in ACT_CODE:
+            return "torch path: fusion.%s = %r (HIP supports none / tanh)" % (k, f.get(k))
+    for k in ("dropout_hv", "dropout_hq"):
+        if float(f.get(k, 0.0)) > 0:
+            return "torch path: fusion.%s > 0 is not supported in HIP" % k
+    if "activation" in opt.get("classif", {}):
+        return "torch path: classif.activation is not supported in HIP"
+    for k in ("dim_v", "dim_q", "dim_hv", "dim_hq", "dim_mm", "R"):
+        if k not in f:
+            return "torch path: fusion.%s is missing" % k
+    if not 1 <= int(f["R"]) <= 10:
+        return "torch path: fusion.R outside 1..10"
+    return "hip"
+
+
+def dropouts(opt):
+    return (float(opt["fusion"].get("dropout_v", 0.0)), float(opt["fusion"].get("dropout_q", 0.0)), float(opt["classif"].get("dropout", 0.0)))
+
+
+class MutanTrainFunction(torch.autograd.Function):
+    """logits = classif(fusion(feats[img_idx], q_emb)) with the ten parameter tensors in the stacked MutanWeights layout
+    (ops.MUTAN_FIELDS order).  Gradients: the parameters, and q_emb when it requires grad.  cfg = (R, act_v, act_q, (p_v, p_q,
+    p_c), seed, training): dropout runs on the counter-based generator under `seed` when training."""
+
+    @staticmethod
+    def forward(ctx, feats, img_idx, q_emb, wv, bv, wq, bq, whv, bhv, whq, bhq, wc, bc, cfg):
+        R, act_v, act_q, p, seed, training = cfg
+        t = {k: x.detach().float().contiguous() for k, x in zip(ops.MUTAN_FIELDS, (wv, bv, wq, bq, whv, bhv, whq, bhq, wc, bc))}
+        mw = ops.MutanWeights.from_tensors(t, R, act_v, act_q)
+        mode = 1 if training and any(x > 0 for x in p) else 0
+        d = ops.vqa_train_dims(img_idx.shape[0], feats.shape[1], q_emb.shape[1], mw.dz, mw.A, feats.shape[0], p=p if mode else (0, 0, 0),
+                               dropout_mode=mode, seed=seed, want_dq=ctx.needs_input_grad[2])
+        ws = ops.vqa_train_workspace(d, mw, feats.device)
+        logits, z = ops.vqa_train_forward(d, feats.detach().float().contiguous(), img_idx, q_emb.detach().float().contiguous(), mw, ws)
+        ctx.hip = (d, mw, ws)
+        ctx.z = z
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        d, mw, ws = ctx.hip
+        grads = {k: torch.empty_like(v) for k, v in mw.t.items()}
+        dq = ops.vqa_train_backward(d, mw, ws, dlogits.float().contiguous(), grads)
+        return (None, None, dq) + tuple(grads[k] for k in ops.MUTAN_FIELDS) + (None,)
+
+
+def module_forward(model, input_v: torch.Tensor, q_emb: torch.Tensor) -> torch.Tensor:
+    """The HIP route of MutanNoAtt.forward below seq2vec: the rows of input_v are the feature table, the index the identity."""
+    f, opt = model.fusion, model.opt
+    idx = torch.arange(input_v.shape[0], dtype=torch.int32, device=input_v.device)
+    seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if model.training else 0      # torch's CPU generator: torch.manual_seed reproduces it
+    cfg = (int(opt["fusion"]["R"]), ACT_CODE[opt["fusion"].get("activation_v")], ACT_CODE[opt["fusion"].get("activation_q")],
+           dropouts(opt), seed, bool(model.training))
+    return MutanTrainFunction.apply(input_v, idx, q_emb, f.linear_v.weight, f.linear_v.bias, f.linear_q.weight, f.linear_q.bias,
+                                    torch.cat([l.weight for l in f.list_linear_hv]), torch.cat([l.bias for l in f.list_linear_hv]),
+                                    torch.cat([l.weight for l in f.list_linear_hq]), torch.cat([l.bias for l in f.list_linear_hq]),
+                                    model.linear_classif.weight, model.linear_classif.bias, cfg)
+
+
+class VqaTrainEngine:
+    """One flat parameter buffer, one flat gradient buffer (both in the stacked MutanWeights layout) and two Adam state buffers.
+    state_dict keys are the reference's (fusion.linear_v.*, fusion.list_linear_hv.{i}.* as row views of the stacked block,
+    linear_classif.*); seq2vec.* entries are carried through untouched."""
+
+    def __init__(self, dv=2048, dq=2400, dhv=360, dhq=360, dz=360, R=10, A=2000, activation_v="tanh", activation_q="tanh",
+                 dropout=(0.5, 0.5, 0.5), lr=1e-4, device="cuda:0", seed=0):
+        self.cfg = dict(dv=dv, dq=dq, dhv=dhv, dhq=dhq, dz=dz, R=R, A=A)
+        self.act_v, self.act_q = ACT_CODE[activation_v], ACT_CODE[activation_q]
+        self.dropout, self.lr, self.seed = tuple(float(x) for x in dropout), lr, int(seed)
+        self.device = torch.device(device)
+        self.params = FlatParams(ops.mutan_shapes(dv, dq, dhv, dhq, dz, R, A), self.device)
+        self.grads = self.params.like()
+        self.exp_avg = torch.zeros_like(self.params.flat)
+        self.exp_avg_sq = torch.zeros_like(self.params.flat)
+        self.step_count = 0
+        self.seq2vec_state: Dict[str, torch.Tensor] = {}
+        self._ws, self._ws_key = None, None
+
+    @classmethod
+    def from_options(cls, opt, num_answers, **kw):
+        r = route_for(opt)
+        if r != "hip":
+            raise ops._lib.NcxError("VqaTrainEngine: " + r)
+        f = opt["fusion"]
+        return cls(dv=f["dim_v"], dq=f["dim_q"], dhv=f["dim_hv"], dhq=f["dim_hq"], dz=f["dim_mm"], R=f["R"], A=num_answers,
+                   activation_v=f.get("activation_v"), activation_q=f.get("activation_q"), dropout=dropouts(opt), **kw)
+
+    # ---- parameters ----------------------------------------------------------------------------------------
+    def _named_views(self) -> Dict[str, torch.Tensor]:
+        v, dz, R = self.params.views, self.cfg["dz"], self.cfg["R"]
+        out = {"fusion.linear_v.weight": v["wv"], "fusion.linear_v.bias": v["bv"], "fusion.linear_q.weight": v["wq"], "fusion.linear_q.bias": v["bq"]}
+        for name, w, b in (("hv", "whv", "bhv"), ("hq", "whq", "bhq")):
+            for i in range(R):
+                out["fusion.list_linear_%s.%d.weight" % (name, i)] = v[w][i * dz:(i + 1) * dz]
+                out["fusion.list_linear_%s.%d.bias" % (name, i)] = v[b][i * dz:(i + 1) * dz]
+        out["linear_classif.weight"], out["linear_classif.bias"] = v["wc"], v["bc"]
+        return out
+
+    def init_parameters(self, seed=42):
+        """nn.Linear's default: weight and bias U(+-1/sqrt(fan_in)), from a seed."""
+        g = torch.Generator(device="cpu").manual_seed(seed)
+        for n, v in self._named_views().items():
+            fan_in = v.shape[1] if v.dim() == 2 else self._named_views()[n.replace("bias", "weight")].shape[1]
+            v.copy_((torch.rand(v.shape, generator=g) * 2 - 1) / math.sqrt(fan_in))
+
+    def state_dict(self, views=False):
+        sd = {n: (v if views else v.detach().clone()) for n, v in self._named_views().items()}
+        sd.update({k: v for k, v in self.seq2vec_state.items()})
+        return sd
+
+    def load_state_dict(self, sd, strict=True):
+        mine = self._named_views()
+        extra = [k for k in sd if k not in mine and not k.startswith("seq2vec.")]
+        missing = [k for k in mine if k not in sd]
+        if strict and (extra or missing):
+            raise KeyError("load_state_dict: missing %s, unexpected %s" % (missing, extra))
+        for k, v in mine.items():
+            if k in sd:
+                v.copy_(torch.as_tensor(sd[k]).to(self.device))
+        self.seq2vec_state = {k: torch.as_tensor(v).detach().clone() for k, v in sd.items() if k.startswith("seq2vec.")}
+
+    def optimizer_state(self):
+        return {"exp_avg": self.exp_avg.detach().cpu(), "exp_avg_sq": self.exp_avg_sq.detach().cpu(), "step": self.step_count,
+                "numel": self.params.numel}
+
+    def load_optimizer_state(self, st):
+        if st["numel"] != self.params.numel:
+            raise ValueError("optimizer state of another model (%d vs %d parameters)" % (st["numel"], self.params.numel))
+        self.exp_avg.copy_(st["exp_avg"].to(self.device)); self.exp_avg_sq.copy_(st["exp_avg_sq"].to(self.device))
+        self.step_count = int(st["step"])
+
+    def mutan_weights(self, flat: Optional[FlatParams] = None) -> ops.MutanWeights:
+        """The SAME buffers in the form the frozen producer takes (ops.vqa_forward): nothing is re-stacked."""
+        return ops.MutanWeights.from_tensors((flat or self.params).views, self.cfg["R"], self.act_v, self.act_q)
+
+    # ---- steps ---------------------------------------------------------------------------------------------
+    def _dims(self, feats, B, mode, seed, want_dq):
+        c = self.cfg
+        d = ops.vqa_train_dims(B, c["dv"], c["dq"], c["dz"], c["A"], feats.shape[0], p=self.dropout if mode else (0, 0, 0), dropout_mode=mode,
+                               seed=seed, want_dq=want_dq)
+        key = (B, feats.shape[0])
+        if self._ws_key != key:
+            self._ws = ops.vqa_train_workspace(d, self.mutan_weights(), self.device)
+            self._ws_key = key
+        return d
+
+    def forward_backward(self, feats, img_idx, q_emb, target, want_dq=False, masks=None, train=True):
+        """forward + loss + backward into self.grads; -> dict(loss, hits1, hits5, logits, dq_emb).  No host sync."""
+        mode = 2 if masks is not None else (1 if train and any(p > 0 for p in self.dropout) else 0)
+        d = self._dims(feats, img_idx.shape[0], mode, self.seed * 1000003 + self.step_count, want_dq)
+        mw = self.mutan_weights()
+        logits, z = ops.vqa_train_forward(d, feats, img_idx, q_emb, mw, self._ws, masks=masks)
+        r = ops.ce_loss(logits, target)
+        dq = ops.vqa_train_backward(d, mw, self._ws, r["dlogits"], self.grads.views, masks=masks)
+        return dict(loss=r["loss"], hits1=r["hits1"], hits5=r["hits5"], logits=logits, dq_emb=dq)
+
+    def train_step(self, feats, img_idx, q_emb, target, want_dq=False, masks=None):
+        """One optimisation step (engine.py:22-37).  Returns device tensors: loss [1], hits1 / hits5 [1] (counts; acc = 100 hits / B)."""
+        self.step_count += 1
+        r = self.forward_backward(feats, img_idx, q_emb, target, want_dq=want_dq, masks=masks)
+        ops.adam_step(self.params.flat, self.grads.flat, self.exp_avg, self.exp_avg_sq, self.step_count, lr=self.lr)
+        return r
+
+    def evaluate(self, feats, img_idx, q_emb, target):
+        """Eval forward + loss + hit counts (engine.py:59-100), dropout off."""
+        d = self._dims(feats, img_idx.shape[0], 0, 0, False)
+        logits, z = ops.vqa_train_forward(d, feats, img_idx, q_emb, self.mutan_weights(), self._ws)
+        r = ops.ce_loss(logits, target, want_grad=False)
+        return dict(loss=r["loss"], hits1=r["hits1"], hits5=r["hits5"], logits=logits, z=z)
+
+    def check_targets(self):
+        ops.check_vqa_targets(device=self.device)

@@ -1,0 +1,270 @@
+"""Trains the MutanNoAtt VQA model: the producer of <logs.dir_logs>/best_model.pth.tar, the checkpoint counterexamples.py and
+contrastive.py load with pretrained_vqa.
+
+Keeps the reference's flags where they apply (train.py:20-67), its loop (vqa/lib/engine.py:6-100: CrossEntropyLoss, Adam over the
+parameters that require grad, acc1 / acc5) and its checkpoint files (train.py:290-367: <dir_logs>/{ckpt,best}_{info,model,optim}
+.pth.tar, best by val acc1, --resume ckpt|best).  Data: what counterexamples.py already reads (pickle_old/*.pickle and the
+feature tables through neuralcx.formats; each example is its original image, question_wids and answer_aid) or --synthetic.
+
+Three routes:
+  --freeze_seq2vec          q_emb is computed ONCE per split by the (frozen) question encoder and kept resident; the whole step is HIP
+                            (neuralcx.vqa_train.VqaTrainEngine: forward, cross-entropy, backward, Adam).
+  (default)                 the module route: MutanNoAtt.use_hip_train = True, the fusion and classifier run in HIP inside torch
+                            autograd, the encoder trains under autograd, torch.optim.Adam steps.
+  --no_hip                  the same loop on the plain PyTorch modules (also runs on a CPU).
+"""
+import argparse
+import json
+import os
+import shutil
+import sys
+import time
+
+import torch
+import torch.nn as nn
+import yaml
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+
+from vqa import models                                       # noqa: E402
+from vqa.lib import utils                                    # noqa: E402
+
+CKPT_PARTS = ("info", "model", "optim")
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="Train / evaluate the MutanNoAtt VQA model", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument("--path_opt", default=os.path.join(HERE, "options", "vqa2", "mutan_noatt_train.yaml"), type=str)
+    p.add_argument("--dir_logs", type=str, help="dir logs")
+    p.add_argument("--st_dropout", type=float)
+    p.add_argument("--st_fixed_emb", default=None, type=utils.str2bool, help="do not backprop into the word embedding")
+    p.add_argument("-lr", "--learning_rate", type=float, help="initial learning rate")
+    p.add_argument("-b", "--batch_size", type=int, help="mini-batch size")
+    p.add_argument("--epochs", type=int, help="number of total epochs to run")
+    p.add_argument("--start_epoch", default=0, type=int, help="manual epoch number (useful on restarts)")
+    p.add_argument("--resume", default="", type=str, help="ckpt | best: resume <dir_logs>/<resume>_{info,model,optim}.pth.tar")
+    p.add_argument("--save_model", default=True, type=utils.str2bool, help="save model and optim state")
+    p.add_argument("-e", "--evaluate", dest="evaluate", action="store_true", help="evaluate on the validation set and exit")
+    p.add_argument("--print_freq", "-p", default=10, type=int, help="print frequency")
+    # net-new
+    p.add_argument("--synthetic", action="store_true", help="synthetic data (neuralcx.synth.SyntheticVQA): no datasets offline")
+    p.add_argument("--syn_examples", type=int, default=8192)
+    p.add_argument("--syn_images", type=int, default=1024)
+    p.add_argument("--syn_vocab", type=int, default=1000)
+    p.add_argument("--path_trainset", type=str, default=None, help="overrides vqa.path_trainset of the YAML")
+    p.add_argument("--path_features", type=str, default=None, help="overrides coco.path_features of the YAML")
+    p.add_argument("--freeze_seq2vec", action="store_true", help="freeze the question encoder: q_emb once per split, the whole step in HIP")
+    p.add_argument("--no_hip", action="store_true", help="the plain PyTorch modules (no HIP library; runs on a CPU too)")
+    p.add_argument("--seed", type=int, default=1337)
+    return p
+
+
+def load_options(args):
+    options = {"logs": {"dir_logs": args.dir_logs},
+               "model": {"seq2vec": {"dropout": args.st_dropout, "fixed_emb": args.st_fixed_emb}},
+               "optim": {"lr": args.learning_rate, "batch_size": args.batch_size, "epochs": args.epochs}}
+    with open(args.path_opt) as f:
+        from_yaml = yaml.safe_load(f)
+    return utils.update_values(options, from_yaml)
+
+
+def ckpt_paths(dir_logs, tag):
+    """train.py:293-298 / 333-335: <dir_logs>/<tag>_{info,model,optim}.pth.tar, tag in {ckpt, best}"""
+    return {part: os.path.join(dir_logs, "%s_%s.pth.tar" % (tag, part)) for part in CKPT_PARTS}
+
+
+class _Split:
+    def __init__(self, feats, img_idx, wids, aids):
+        self.feats, self.img_idx, self.wids, self.aids = feats, img_idx, wids, aids
+        self.N = img_idx.shape[0]
+        self.q_emb = None
+
+
+def load_data(args, opt, dev):
+    """-> (train split, val split, vocab_words, vocab_answers)"""
+    if args.synthetic:
+        from neuralcx.synth import SyntheticVQA
+        s = SyntheticVQA(n_examples=args.syn_examples, n_img=args.syn_images, dv=opt["model"]["fusion"]["dim_v"], vocab=args.syn_vocab,
+                         T=opt["vqa"].get("maxlength", 26), A=opt["vqa"]["nans"], seed=1234, device=dev)
+        n = s.n_train
+        return (_Split(s.feats, s.img_idx[:n], s.question_wids[:n], s.answer_aids[:n]),
+                _Split(s.feats, s.img_idx[n:], s.question_wids[n:], s.answer_aids[n:]), s.vocab_words, s.vocab_answers)
+    from neuralcx import formats
+    vqa_dir = args.path_trainset or opt["vqa"].get("path_trainset")
+    feat_dir = args.path_features or opt["coco"].get("path_features")
+    if not vqa_dir or not feat_dir:
+        raise SystemExit("real-data mode needs vqa.path_trainset and coco.path_features (YAML or --path_trainset / --path_features)")
+    pk = lambda fn: formats.load_cx_pickle(os.path.join(vqa_dir, "pickle_old", fn))
+    trainset, valset = pk("trainset_augmented.pickle"), pk("valset_augmented_small.pickle")
+    tr = formats.CXDeviceDataset(trainset, formats.load_feature_table(feat_dir, "train"), dev)
+    va = formats.CXDeviceDataset(valset, formats.load_feature_table(feat_dir, "val"), dev)
+    mk = lambda d: _Split(d.feats, d.img_idx[:, 0].contiguous(), d.question_wids, d.answer_aids)       # the original image of each example
+    return mk(tr), mk(va), trainset["vocab_words"], trainset["vocab_answers"]
+
+
+class Trainer:
+    def __init__(self, args, opt):
+        self.args, self.opt = args, opt
+        cuda = torch.cuda.is_available()
+        if not cuda and not args.no_hip:
+            raise SystemExit("train.py: the HIP routes need an MI355X (use --no_hip for the PyTorch modules)")
+        self.dev = torch.device("cuda:0" if cuda else "cpu")
+        torch.manual_seed(args.seed)
+        self.train, self.val, vw, va = load_data(args, opt, self.dev)
+        self.model = models.factory(opt["model"], vw, va, cuda=cuda, data_parallel=False)
+        self.lr, self.B = opt["optim"]["lr"], opt["optim"]["batch_size"]
+        self.freeze = args.freeze_seq2vec
+        from neuralcx import vqa_train
+        self.route = "torch path: --no_hip" if args.no_hip else vqa_train.route_for(opt["model"])
+        self.hip = self.route == "hip"
+        self.engine = None
+        if self.freeze or opt["model"]["seq2vec"].get("fixed_emb"):
+            for n, p_ in self.model.seq2vec.named_parameters():
+                if self.freeze or "embedding" in n:
+                    p_.requires_grad_(False)
+        if self.hip and self.freeze:
+            self.engine = vqa_train.VqaTrainEngine.from_options(opt["model"], len(va), lr=self.lr, device=self.dev, seed=args.seed)
+            self.engine.load_state_dict(self.model.state_dict())          # nn.Linear's init under --seed; seq2vec.* carried through
+        else:
+            self.model.use_hip_train = self.hip
+            self.optim = torch.optim.Adam([p_ for p_ in self.model.parameters() if p_.requires_grad], self.lr)     # train.py:143-144
+            self.criterion = nn.CrossEntropyLoss()
+        self.best_acc1, self.history = 0.0, []
+        print("=> route: %s%s" % ("hip" if self.hip else self.route, " (engine: whole step in HIP)" if self.engine else ""), flush=True)
+
+    # ---- data ------------------------------------------------------------------------------------------------
+    def q_emb_of(self, split):
+        """--freeze_seq2vec: the encoder's output for a whole split, computed once (eval mode: its dropout is off) and kept resident."""
+        if split.q_emb is None:
+            self.model.seq2vec.eval()
+            with torch.no_grad():
+                split.q_emb = torch.cat([self.model.seq2vec(split.wids[i:i + 2048]).float() for i in range(0, split.N, 2048)]).contiguous()
+        return split.q_emb
+
+    # ---- steps -----------------------------------------------------------------------------------------------
+    def _step(self, split, sel, train):
+        idx, aids = split.img_idx.index_select(0, sel), split.aids.index_select(0, sel)
+        if self.engine is not None:
+            q = self.q_emb_of(split).index_select(0, sel)
+            r = self.engine.train_step(split.feats, idx, q, aids) if train else self.engine.evaluate(split.feats, idx, q, aids)
+            return r["loss"][0], r["hits1"][0].float(), r["hits5"][0].float()
+        v = split.feats.index_select(0, idx.long())
+        wids = split.wids.index_select(0, sel)
+        with torch.set_grad_enabled(train):
+            if self.freeze:                                       # (torch path only: the HIP route with a frozen encoder is the engine)
+                logits = self.model._classif(self.model._fusion(v, self.q_emb_of(split).index_select(0, sel)))
+            else:
+                logits = self.model(v, wids)
+            loss = self.criterion(logits, aids.long())
+        if train:
+            self.optim.zero_grad()
+            loss.backward()
+            self.optim.step()
+        top = logits.detach().topk(min(5, logits.shape[1]), 1).indices                       # utils.accuracy (vqa/lib/utils.py:23-38), as counts
+        hit = top == aids.long()[:, None]
+        return loss.detach(), hit[:, :1].sum().float(), hit.sum().float()
+
+    def run_epoch(self, epoch):
+        torch.manual_seed(self.args.seed * 7919 + epoch)          # shuffle + torch dropout: an epoch depends on (seed, epoch, state) only
+        if self.engine is None:
+            self.model.train()
+            if self.freeze:
+                self.model.seq2vec.eval()
+        perm = torch.randperm(self.train.N).to(self.dev)
+        tot = torch.zeros(3, device=self.dev)
+        t0, n = time.time(), 0
+        for i, s in enumerate(range(0, self.train.N, self.B)):
+            sel = perm[s:s + self.B]
+            loss, h1, h5 = self._step(self.train, sel, True)
+            tot += torch.stack([loss * sel.numel(), h1, h5])
+            n += sel.numel()
+            if self.args.print_freq > 0 and (i + 1) % self.args.print_freq == 0:
+                l, a1, a5 = (tot / n).tolist()
+                print("Epoch: [%d][%d/%d] loss %.4f acc1 %.2f acc5 %.2f (%.1f ex/s)" % (epoch, i + 1, -(-self.train.N // self.B), l, 100 * a1, 100 * a5,
+                                                                                       n / (time.time() - t0)), flush=True)
+        l, a1, a5 = (tot / n).tolist()
+        return dict(loss=l, acc1=100 * a1, acc5=100 * a5)
+
+    def evaluate(self):
+        if self.engine is None:
+            self.model.eval()
+        tot, n = torch.zeros(3, device=self.dev), 0
+        for s in range(0, self.val.N, self.B):
+            sel = torch.arange(s, min(s + self.B, self.val.N), device=self.dev)
+            loss, h1, h5 = self._step(self.val, sel, False)
+            tot += torch.stack([loss * sel.numel(), h1, h5])
+            n += sel.numel()
+        if self.engine is not None:
+            self.engine.check_targets()
+        l, a1, a5 = (tot / max(n, 1)).tolist()
+        return dict(loss=l, acc1=100 * a1, acc5=100 * a5)
+
+    # ---- checkpoints (train.py:290-367) -------------------------------------------------------------------------
+    def state_dict(self):
+        sd = self.engine.state_dict() if self.engine is not None else self.model.state_dict()
+        return {k: v.detach().cpu() for k, v in sd.items()}
+
+    def save(self, dir_logs, info, is_best):
+        os.makedirs(dir_logs, exist_ok=True)
+        ck, best = ckpt_paths(dir_logs, "ckpt"), ckpt_paths(dir_logs, "best")
+        with open(os.path.join(dir_logs, "logger.json"), "w") as f:
+            json.dump(self.history, f)
+        torch.save(info, ck["info"])
+        parts = ["info"]
+        if self.args.save_model:
+            torch.save(self.state_dict(), ck["model"])
+            torch.save(self.engine.optimizer_state() if self.engine is not None else self.optim.state_dict(), ck["optim"])
+            parts += ["model", "optim"]
+        else:
+            print("Warning train.py: checkpoint not saved")
+        if is_best:
+            for part in parts:
+                shutil.copyfile(ck[part], best[part])
+
+    def load(self, dir_logs, tag):
+        pth = ckpt_paths(dir_logs, tag)
+        info = torch.load(pth["info"]) if os.path.isfile(pth["info"]) else {}
+        if os.path.isfile(pth["model"]):
+            sd = torch.load(pth["model"], map_location=self.dev)
+            if self.engine is not None:
+                self.engine.load_state_dict(sd)
+            self.model.load_state_dict(sd)
+        else:
+            print("Warning train.py: no model checkpoint found at '%s'" % pth["model"])
+        if os.path.isfile(pth["optim"]):
+            st = torch.load(pth["optim"], map_location="cpu")
+            self.engine.load_optimizer_state(st) if self.engine is not None else self.optim.load_state_dict(st)
+        self.best_acc1 = float(info.get("best_acc1", 0.0))
+        self.history = list(info.get("history", []))
+        print("=> loaded checkpoint '%s' (epoch %d, best_acc1 %.4f)" % (tag, info.get("epoch", 0), self.best_acc1))
+        return int(info.get("epoch", 0))
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    opt = load_options(args)
+    dir_logs = opt["logs"]["dir_logs"]
+    t = Trainer(args, opt)
+    start = args.start_epoch
+    if args.resume:
+        start = t.load(dir_logs, args.resume)
+    if args.evaluate:
+        val = t.evaluate()
+        print("Val: loss %.4f acc1 %.2f acc5 %.2f" % (val["loss"], val["acc1"], val["acc5"]), flush=True)
+        return dict(val=val, history=t.history, trainer=t)
+    for epoch in range(start + 1, opt["optim"]["epochs"] + 1):
+        tr = t.run_epoch(epoch)
+        val = t.evaluate()
+        print("Epoch %d: train loss %.4f acc1 %.2f | val loss %.4f acc1 %.2f acc5 %.2f" % (epoch, tr["loss"], tr["acc1"], val["loss"], val["acc1"],
+                                                                                      val["acc5"]), flush=True)
+        t.history.append(dict(epoch=epoch, train=tr, val=val))
+        is_best = val["acc1"] >= t.best_acc1                      # (>=: the first epoch always writes best_*)
+        t.best_acc1 = max(t.best_acc1, val["acc1"])
+        t.save(dir_logs, dict(epoch=epoch, best_acc1=t.best_acc1, history=t.history, route=t.route, options=opt), is_best)
+    return dict(history=t.history, trainer=t)
+
+
+if __name__ == "__main__":
+    main()

@@ -31,11 +31,23 @@ class AbstractNoAtt(nn.Module):
 
 
 class MutanNoAtt(AbstractNoAtt):
+    """`use_hip_train = True` (set by a caller; never by default) routes forward's fusion + classifier through the HIP library's
+    differentiable step (neuralcx.vqa_train.MutanTrainFunction) when the input is a dense [B, dim_v] CUDA tensor and the options
+    are the supported model; seq2vec stays in PyTorch and trains under autograd."""
+    use_hip_train = False
+
     def __init__(self, opt=None, vocab_words=(), vocab_answers=()):
         opt = opt or {}
         opt["fusion"]["dim_h"] = opt["fusion"]["dim_mm"]
         super().__init__(opt, vocab_words, vocab_answers)
         self.fusion = fusion.MutanFusion(opt["fusion"])
+
+    def forward(self, input_v, input_q):
+        if self.use_hip_train and input_v.is_cuda and input_v.dim() == 2:
+            from neuralcx import vqa_train
+            if vqa_train.route_for(self.opt) == "hip":
+                return vqa_train.module_forward(self, input_v, self.seq2vec(input_q))
+        return super().forward(input_v, input_q)
 
 
 class MLBNoAtt(AbstractNoAtt):
