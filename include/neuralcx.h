@@ -511,6 +511,33 @@ int ncx_vqa_train_backward(const ncx_vqa_train_dims* d, const ncx_mutan_params* 
 #define NCX_VT_WS_ZC 3   /* drop_c(z)              [B, dz] */
 int ncx_vqa_train_ws_region(const ncx_vqa_train_dims* d, const ncx_mutan_params* m, int32_t which, size_t* offset, size_t* bytes);
 
+/* ---- training the MLBNoAtt VQA model: the sibling of the block above for the factory's second no-attention model ------------------
+ * The fusion and classifier of MLBNoAtt in TRAINING mode (MLBFusion.forward vqa/models/fusion.py:31-50, AbstractNoAtt._classif
+ * vqa/models/noatt.py:24-29), one image per question (row b reads feats[img_idx[b]]; an id outside [0, n_img) is clamped):
+ *   vd = drop_v(feats[img_idx])   qd = drop_q(q_emb)   x_v = act_v(vd Wv^T + bv)   x_q = act_q(qd Wq^T + bq)          [B, dh]
+ *   z = x_q * x_v (returned: the fusion output, BEFORE act_c)   t = act_c(z)   tc = drop_c(t)   logits = tc Wc^T + bc   [B, A]
+ * Every activation in {none, tanh} (0 / 2), classif.activation included.  Takes ncx_vqa_train_dims with d->dz == m->dh (else
+ * NCX_E_DIMS) and its dropout modes: layer ids 1 (v), 2 (q), 3 (the classifier's input); explicit masks [B, dv] | [B, dq] | [B, dh].
+ * The loss is ncx_ce_loss, the optimiser ncx_adam_step.  Dims: B >= 1; dv, dq, dh, A >= 4; 0 <= p < 1.  Status codes as the rest
+ * of the ABI, checked before any launch; no allocation, no atomics, no host read-back; bit-identical from run to run. */
+typedef struct ncx_mlb_grads {            /* shapes of ncx_mlb_params' tensors; OVERWRITTEN by ncx_mlb_train_backward */
+    float* wv;  float* bv;  float* wq;  float* bq;  float* wc;  float* bc;
+} ncx_mlb_grads;
+/* Workspace of the forward / backward pair (256-byte aligned); 0 for invalid dims or an unsupported activation.  dh and the
+ * activation codes are read from `m` (its pointers are not). */
+size_t ncx_mlb_train_workspace_bytes(const ncx_vqa_train_dims* d, const ncx_mlb_params* m);
+/* logits [B, A]; z [B, dh].  masks: dropout_mode 2 only, else nullable.  dropout_mode 0 is the eval forward.  x_v, x_q, t and the
+ * dropped tensors stay in the workspace for the backward. */
+int ncx_mlb_train_forward(const ncx_vqa_train_dims* d, const float* feats, const int32_t* img_idx, const float* q_emb,
+                          const ncx_mlb_params* m, const float* masks, void* workspace, size_t workspace_bytes,
+                          float* logits, float* z, void* stream);
+/* Every field of `g` is overwritten; dq_emb [B, dq] = d loss / d q_emb when d->want_dq (else nullable).  No gradient is taken with
+ * respect to the image features.  Reads what the forward left in the workspace: same dims, params, masks and workspace. */
+int ncx_mlb_train_backward(const ncx_vqa_train_dims* d, const ncx_mlb_params* m, const float* masks, void* workspace,
+                           size_t workspace_bytes, const float* dlogits, const ncx_mlb_grads* g, float* dq_emb, void* stream);
+/* which: NCX_VT_WS_VD, NCX_VT_WS_QD, NCX_VT_WS_ZC (here tc = drop_c(act_c(z)) [B, dh]); valid after ncx_mlb_train_forward. */
+int ncx_mlb_train_ws_region(const ncx_vqa_train_dims* d, const ncx_mlb_params* m, int32_t which, size_t* offset, size_t* bytes);
+
 /* ---- diagnostics (bench.py / tests only; the only process-global state, off by default) --------------
  * GEMM ids: 0 Gt = W1[:,a_other].E^T, 1 Sh (shared segments), 2 MAIN (candidate segments, the dominant
  * forward kernel), 3 hidden layer l>=2 forward, 4 dW1 candidate columns (+dGt; the dominant backward

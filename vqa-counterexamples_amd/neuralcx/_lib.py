@@ -28,7 +28,8 @@ EXPORTS = ("ncx_input_size", "ncx_workspace_bytes", "ncx_forward", "ncx_forward_
            "ncx_linctx_workspace_bytes", "ncx_linctx_forward", "ncx_linctx_backward",
            "ncx_contrastive_workspace_bytes", "ncx_contrastive_forward", "ncx_contrastive_distances", "ncx_contrastive_loss",
            "ncx_contrastive_backward",
-           "ncx_vqa_train_workspace_bytes", "ncx_vqa_train_forward", "ncx_ce_loss", "ncx_vqa_train_backward", "ncx_vqa_train_ws_region")
+           "ncx_vqa_train_workspace_bytes", "ncx_vqa_train_forward", "ncx_ce_loss", "ncx_vqa_train_backward", "ncx_vqa_train_ws_region",
+           "ncx_mlb_train_workspace_bytes", "ncx_mlb_train_forward", "ncx_mlb_train_backward", "ncx_mlb_train_ws_region")
 
 
 class NcxDims(C.Structure):
@@ -72,6 +73,10 @@ class NcxVqaTrainDims(C.Structure):
 class NcxMlbParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("wv", "bv", "wq", "bq", "wc", "bc")] + \
                [(n, C.c_int32) for n in ("dh", "act_v", "act_q", "act_c")]
+
+
+class NcxMlbGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("wv", "bv", "wq", "bq", "wc", "bc")]
 
 
 class NcxScorerDims(C.Structure):
@@ -234,6 +239,17 @@ def lib():
                                          C.c_void_p]
     L.ncx_vqa_train_ws_region.restype = C.c_int
     L.ncx_vqa_train_ws_region.argtypes = [P_VT, P_MP, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    P_LP = C.POINTER(NcxMlbParams)
+    L.ncx_mlb_train_workspace_bytes.restype = C.c_size_t
+    L.ncx_mlb_train_workspace_bytes.argtypes = [P_VT, P_LP]
+    L.ncx_mlb_train_forward.restype = C.c_int
+    L.ncx_mlb_train_forward.argtypes = [P_VT, C.c_void_p, C.c_void_p, C.c_void_p, P_LP, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]
+    L.ncx_mlb_train_backward.restype = C.c_int
+    L.ncx_mlb_train_backward.argtypes = [P_VT, P_LP, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(NcxMlbGrads), C.c_void_p,
+                                         C.c_void_p]
+    L.ncx_mlb_train_ws_region.restype = C.c_int
+    L.ncx_mlb_train_ws_region.argtypes = [P_VT, P_LP, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     _lib = L
     return L
 

@@ -309,6 +309,16 @@ class MlbWeights:
         self.A = self.t["wc"].shape[0]
         self.act_v, self.act_q, self.act_c = (act[a] for a in acts)
 
+    @classmethod
+    def from_tensors(cls, t: Dict[str, torch.Tensor], act_v: int = 2, act_q: int = 2, act_c: int = 2):
+        """The same object around caller-owned tensors (the MLB trainer's flat buffer views: a model trained there feeds
+        vqa_forward without a copy).  Activation codes: 0 none, 2 tanh."""
+        self = cls.__new__(cls)
+        self.t = dict(t)
+        self.A, self.dz = t["wc"].shape
+        self.act_v, self.act_q, self.act_c = int(act_v), int(act_q), int(act_c)
+        return self
+
     def c_struct(self):
         m = NcxMlbParams()
         for k, v in self.t.items():
@@ -798,47 +808,91 @@ def vqa_train_dims(B, dv, dq, dz, A, n_img, p=(0.0, 0.0, 0.0), dropout_mode=0, s
     return d
 
 
-def vqa_train_workspace(d, mw, device) -> torch.Tensor:
+def _train_workspace(sym, d, mw, device) -> torch.Tensor:
     m = mw.c_struct()
-    need = _lib.lib().ncx_vqa_train_workspace_bytes(C.byref(d), C.byref(m))
+    need = getattr(_lib.lib(), sym)(C.byref(d), C.byref(m))
     if need == 0:
-        raise _lib.NcxError("ncx_vqa_train_workspace_bytes: unsupported dims or activation")
+        raise _lib.NcxError("%s: unsupported dims or activation" % sym)
     return torch.empty(need + 256, dtype=torch.uint8, device=device)
 
 
-def vqa_train_forward(d, feats, img_idx, q_emb, mw, ws, masks=None):
-    """Training-mode fusion + classifier (ncx_vqa_train_forward) -> (logits [B, A], z [B, dz]); the stashes stay in ws."""
+def _train_forward(sym, d, feats, img_idx, q_emb, mw, ws, masks):
     m = mw.c_struct()
     logits = torch.empty(d.B, d.A, dtype=torch.float32, device=feats.device)
     z = torch.empty(d.B, d.dz, dtype=torch.float32, device=feats.device)
     p, n = _ws_ptr(ws)
-    _lib.check(_lib.lib().ncx_vqa_train_forward(C.byref(d), _ptr(feats, torch.float32, "feats"), _ptr(img_idx, torch.int32, "img_idx"),
-                                                _ptr(q_emb, torch.float32, "q_emb"), C.byref(m), _ptr(masks, torch.float32, "masks"), p, n,
-                                                C.c_void_p(logits.data_ptr()), C.c_void_p(z.data_ptr()), _stream()), "ncx_vqa_train_forward")
+    _lib.check(getattr(_lib.lib(), sym)(C.byref(d), _ptr(feats, torch.float32, "feats"), _ptr(img_idx, torch.int32, "img_idx"),
+                                        _ptr(q_emb, torch.float32, "q_emb"), C.byref(m), _ptr(masks, torch.float32, "masks"), p, n,
+                                        C.c_void_p(logits.data_ptr()), C.c_void_p(z.data_ptr()), _stream()), sym)
     return logits, z
+
+
+def _train_backward(sym, grads_cls, fields, d, mw, ws, dlogits, grads, masks):
+    m = mw.c_struct()
+    g = grads_cls()
+    for k in fields:
+        setattr(g, k, _ptr(grads[k], torch.float32, "grad " + k))
+    dq = torch.empty(d.B, d.dq, dtype=torch.float32, device=dlogits.device) if d.want_dq else None
+    p, n = _ws_ptr(ws)
+    _lib.check(getattr(_lib.lib(), sym)(C.byref(d), C.byref(m), _ptr(masks, torch.float32, "masks"), p, n,
+                                        _ptr(dlogits, torch.float32, "dlogits"), C.byref(g), _ptr(dq, torch.float32, "dq_emb"), _stream()), sym)
+    return dq
+
+
+def _train_ws_view(sym, d, mw, ws, which) -> torch.Tensor:
+    m = mw.c_struct()
+    off, nb = C.c_size_t(), C.c_size_t()
+    _lib.check(getattr(_lib.lib(), sym)(C.byref(d), C.byref(m), which, C.byref(off), C.byref(nb)), sym)
+    pad = (-ws.data_ptr()) % 256
+    return ws[pad + off.value: pad + off.value + nb.value].view(torch.float32).view(d.B, -1)
+
+
+def vqa_train_workspace(d, mw, device) -> torch.Tensor:
+    return _train_workspace("ncx_vqa_train_workspace_bytes", d, mw, device)
+
+
+def vqa_train_forward(d, feats, img_idx, q_emb, mw, ws, masks=None):
+    """Training-mode fusion + classifier (ncx_vqa_train_forward) -> (logits [B, A], z [B, dz]); the stashes stay in ws."""
+    return _train_forward("ncx_vqa_train_forward", d, feats, img_idx, q_emb, mw, ws, masks)
 
 
 def vqa_train_backward(d, mw, ws, dlogits, grads: Dict[str, torch.Tensor], masks=None):
     """Every gradient of MUTAN_FIELDS into `grads` (overwritten); -> d loss / d q_emb [B, dq] when d.want_dq, else None."""
-    m = mw.c_struct()
-    g = _lib.NcxMutanGrads()
-    for k in MUTAN_FIELDS:
-        setattr(g, k, _ptr(grads[k], torch.float32, "grad " + k))
-    dq = torch.empty(d.B, d.dq, dtype=torch.float32, device=dlogits.device) if d.want_dq else None
-    p, n = _ws_ptr(ws)
-    _lib.check(_lib.lib().ncx_vqa_train_backward(C.byref(d), C.byref(m), _ptr(masks, torch.float32, "masks"), p, n,
-                                                 _ptr(dlogits, torch.float32, "dlogits"), C.byref(g), _ptr(dq, torch.float32, "dq_emb"),
-                                                 _stream()), "ncx_vqa_train_backward")
-    return dq
+    return _train_backward("ncx_vqa_train_backward", _lib.NcxMutanGrads, MUTAN_FIELDS, d, mw, ws, dlogits, grads, masks)
 
 
 def vqa_train_ws_view(d, mw, ws, which) -> torch.Tensor:
     """The tensor the forward dropped (VT_WS_VD / _QD / _ZC) as a [B, width] view of the workspace (tests, diagnostics)."""
-    m = mw.c_struct()
-    off, nb = C.c_size_t(), C.c_size_t()
-    _lib.check(_lib.lib().ncx_vqa_train_ws_region(C.byref(d), C.byref(m), which, C.byref(off), C.byref(nb)), "ncx_vqa_train_ws_region")
-    pad = (-ws.data_ptr()) % 256
-    return ws[pad + off.value: pad + off.value + nb.value].view(torch.float32).view(d.B, -1)
+    return _train_ws_view("ncx_vqa_train_ws_region", d, mw, ws, which)
+
+
+# ---- training the MLBNoAtt VQA model (include/neuralcx.h: ncx_mlb_train_*): the same dims struct, loss and optimiser ----------
+MLB_FIELDS = ("wv", "bv", "wq", "bq", "wc", "bc")
+MlbGrads = _lib.NcxMlbGrads
+
+
+def mlb_shapes(dv, dq, dh, A):
+    """Field -> shape of the MLBNoAtt layout (MlbWeights / ncx_mlb_params), in flat-buffer order."""
+    return dict(wv=(dh, dv), bv=(dh,), wq=(dh, dq), bq=(dh,), wc=(A, dh), bc=(A,))
+
+
+def mlb_train_workspace(d, mw, device) -> torch.Tensor:
+    return _train_workspace("ncx_mlb_train_workspace_bytes", d, mw, device)
+
+
+def mlb_train_forward(d, feats, img_idx, q_emb, mw, ws, masks=None):
+    """Training-mode MLB fusion + classifier (ncx_mlb_train_forward) -> (logits [B, A], z [B, dh] before classif.activation)."""
+    return _train_forward("ncx_mlb_train_forward", d, feats, img_idx, q_emb, mw, ws, masks)
+
+
+def mlb_train_backward(d, mw, ws, dlogits, grads: Dict[str, torch.Tensor], masks=None):
+    """Every gradient of MLB_FIELDS into `grads` (overwritten); -> d loss / d q_emb [B, dq] when d.want_dq, else None."""
+    return _train_backward("ncx_mlb_train_backward", MlbGrads, MLB_FIELDS, d, mw, ws, dlogits, grads, masks)
+
+
+def mlb_train_ws_region(d, mw, ws, which) -> torch.Tensor:
+    """The tensor the forward dropped (VT_WS_VD / _QD; VT_WS_ZC: drop_c(act_c(z))) as a [B, width] view of the workspace."""
+    return _train_ws_view("ncx_mlb_train_ws_region", d, mw, ws, which)
 
 
 _VQA_FLAGS: Dict[torch.device, torch.Tensor] = {}

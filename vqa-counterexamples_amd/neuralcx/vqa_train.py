@@ -1,10 +1,12 @@
-"""Training the MutanNoAtt VQA model (reference train.py:136-145, vqa/lib/engine.py:6-56): the producer of the
-best_model.pth.tar the counterexample pipeline loads.
+"""Training the no-attention VQA models, MutanNoAtt and MLBNoAtt (reference train.py:136-145, vqa/lib/engine.py:6-56): the producers
+of the best_model.pth.tar the counterexample pipeline loads.
 
 MutanTrainFunction is the differentiable fusion + classifier (ncx_vqa_train_forward / _backward) for a caller that keeps torch
 autograd around it -- the module route of vqa.models.noatt.MutanNoAtt (`use_hip_train`), where the question encoder trains under
 autograd from the d loss / d q_emb the backward returns.  VqaTrainEngine is the whole step in HIP on flat buffers: forward,
-cross-entropy (ncx_ce_loss), backward, Adam (ncx_adam_step), for a frozen or externally trained encoder.
+cross-entropy (ncx_ce_loss), backward, Adam (ncx_adam_step), for a frozen or externally trained encoder.  MlbTrainFunction,
+mlb_module_forward and MlbTrainEngine are the same three for MLBNoAtt (ncx_mlb_train_forward / _backward); the two engines share
+everything but their parameter layout.
 """
 import math
 from typing import Dict, Optional
@@ -84,18 +86,73 @@ def module_forward(model, input_v: torch.Tensor, q_emb: torch.Tensor) -> torch.T
                                     model.linear_classif.weight, model.linear_classif.bias, cfg)
 
 
-class VqaTrainEngine:
-    """One flat parameter buffer, one flat gradient buffer (both in the stacked MutanWeights layout) and two Adam state buffers.
-    state_dict keys are the reference's (fusion.linear_v.*, fusion.list_linear_hv.{i}.* as row views of the stacked block,
-    linear_classif.*); seq2vec.* entries are carried through untouched."""
+def mlb_route_for(opt) -> str:
+    """"hip" when the MLBNoAtt options `opt` are the model ncx_mlb_train_* supports, else "torch path: <why>".  Reads the options
+    only (never touches the library)."""
+    f = opt.get("fusion", {})
+    for k in ("dim_v", "dim_q", "dim_h"):
+        if k not in f:
+            return "torch path: fusion.%s is missing" % k
+    for where, a in (("fusion.activation_v", f.get("activation_v")), ("fusion.activation_q", f.get("activation_q")),
+                     ("classif.activation", opt.get("classif", {}).get("activation"))):
+        if a not in ACT_CODE:
+            return "torch path: %s = %r (HIP supports none / tanh)" % (where, a)
+    return "hip"
 
-    def __init__(self, dv=2048, dq=2400, dhv=360, dhq=360, dz=360, R=10, A=2000, activation_v="tanh", activation_q="tanh",
-                 dropout=(0.5, 0.5, 0.5), lr=1e-4, device="cuda:0", seed=0):
-        self.cfg = dict(dv=dv, dq=dq, dhv=dhv, dhq=dhq, dz=dz, R=R, A=A)
-        self.act_v, self.act_q = ACT_CODE[activation_v], ACT_CODE[activation_q]
+
+def mlb_acts(opt):
+    return (ACT_CODE[opt["fusion"].get("activation_v")], ACT_CODE[opt["fusion"].get("activation_q")],
+            ACT_CODE[opt.get("classif", {}).get("activation")])
+
+
+class MlbTrainFunction(torch.autograd.Function):
+    """logits = classif(fusion(feats[img_idx], q_emb)) of MLBNoAtt with the six parameter tensors in ops.MLB_FIELDS order.
+    Gradients: the parameters, and q_emb when it requires grad.  cfg = ((act_v, act_q, act_c), (p_v, p_q, p_c), seed, training):
+    dropout runs on the counter-based generator under `seed` when training."""
+
+    @staticmethod
+    def forward(ctx, feats, img_idx, q_emb, wv, bv, wq, bq, wc, bc, cfg):
+        acts, p, seed, training = cfg
+        t = {k: x.detach().float().contiguous() for k, x in zip(ops.MLB_FIELDS, (wv, bv, wq, bq, wc, bc))}
+        mw = ops.MlbWeights.from_tensors(t, *acts)
+        mode = 1 if training and any(x > 0 for x in p) else 0
+        d = ops.vqa_train_dims(img_idx.shape[0], feats.shape[1], q_emb.shape[1], mw.dz, mw.A, feats.shape[0], p=p if mode else (0, 0, 0),
+                               dropout_mode=mode, seed=seed, want_dq=ctx.needs_input_grad[2])
+        ws = ops.mlb_train_workspace(d, mw, feats.device)
+        logits, z = ops.mlb_train_forward(d, feats.detach().float().contiguous(), img_idx, q_emb.detach().float().contiguous(), mw, ws)
+        ctx.hip = (d, mw, ws)
+        ctx.z = z
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        d, mw, ws = ctx.hip
+        grads = {k: torch.empty_like(v) for k, v in mw.t.items()}
+        dq = ops.mlb_train_backward(d, mw, ws, dlogits.float().contiguous(), grads)
+        return (None, None, dq) + tuple(grads[k] for k in ops.MLB_FIELDS) + (None,)
+
+
+def mlb_module_forward(model, input_v: torch.Tensor, q_emb: torch.Tensor) -> torch.Tensor:
+    """The HIP route of MLBNoAtt.forward below seq2vec: the rows of input_v are the feature table, the index the identity."""
+    f, opt = model.fusion, model.opt
+    idx = torch.arange(input_v.shape[0], dtype=torch.int32, device=input_v.device)
+    seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if model.training else 0      # torch's CPU generator: torch.manual_seed reproduces it
+    cfg = (mlb_acts(opt), dropouts(opt), seed, bool(model.training))
+    return MlbTrainFunction.apply(input_v, idx, q_emb, f.linear_v.weight, f.linear_v.bias, f.linear_q.weight, f.linear_q.bias,
+                                  model.linear_classif.weight, model.linear_classif.bias, cfg)
+
+
+class _TrainEngine:
+    """What the two engines share: one flat parameter buffer, one flat gradient buffer (both in the layout of the model's weights
+    object) and two Adam state buffers; the reference's state_dict keys over views of the flat buffer, seq2vec.* entries carried
+    through untouched; the step.  A subclass gives the layout (the shapes it hands to _setup), the names (_named_views), the weights object (_weights)
+    and the three operators (_OPS)."""
+    _OPS = None            # (workspace, forward, backward) of neuralcx.ops
+
+    def _setup(self, shapes, dropout, lr, device, seed):
         self.dropout, self.lr, self.seed = tuple(float(x) for x in dropout), lr, int(seed)
         self.device = torch.device(device)
-        self.params = FlatParams(ops.mutan_shapes(dv, dq, dhv, dhq, dz, R, A), self.device)
+        self.params = FlatParams(shapes, self.device)
         self.grads = self.params.like()
         self.exp_avg = torch.zeros_like(self.params.flat)
         self.exp_avg_sq = torch.zeros_like(self.params.flat)
@@ -103,26 +160,7 @@ class VqaTrainEngine:
         self.seq2vec_state: Dict[str, torch.Tensor] = {}
         self._ws, self._ws_key = None, None
 
-    @classmethod
-    def from_options(cls, opt, num_answers, **kw):
-        r = route_for(opt)
-        if r != "hip":
-            raise ops._lib.NcxError("VqaTrainEngine: " + r)
-        f = opt["fusion"]
-        return cls(dv=f["dim_v"], dq=f["dim_q"], dhv=f["dim_hv"], dhq=f["dim_hq"], dz=f["dim_mm"], R=f["R"], A=num_answers,
-                   activation_v=f.get("activation_v"), activation_q=f.get("activation_q"), dropout=dropouts(opt), **kw)
-
     # ---- parameters ----------------------------------------------------------------------------------------
-    def _named_views(self) -> Dict[str, torch.Tensor]:
-        v, dz, R = self.params.views, self.cfg["dz"], self.cfg["R"]
-        out = {"fusion.linear_v.weight": v["wv"], "fusion.linear_v.bias": v["bv"], "fusion.linear_q.weight": v["wq"], "fusion.linear_q.bias": v["bq"]}
-        for name, w, b in (("hv", "whv", "bhv"), ("hq", "whq", "bhq")):
-            for i in range(R):
-                out["fusion.list_linear_%s.%d.weight" % (name, i)] = v[w][i * dz:(i + 1) * dz]
-                out["fusion.list_linear_%s.%d.bias" % (name, i)] = v[b][i * dz:(i + 1) * dz]
-        out["linear_classif.weight"], out["linear_classif.bias"] = v["wc"], v["bc"]
-        return out
-
     def init_parameters(self, seed=42):
         """nn.Linear's default: weight and bias U(+-1/sqrt(fan_in)), from a seed."""
         g = torch.Generator(device="cpu").manual_seed(seed)
@@ -156,10 +194,6 @@ class VqaTrainEngine:
         self.exp_avg.copy_(st["exp_avg"].to(self.device)); self.exp_avg_sq.copy_(st["exp_avg_sq"].to(self.device))
         self.step_count = int(st["step"])
 
-    def mutan_weights(self, flat: Optional[FlatParams] = None) -> ops.MutanWeights:
-        """The SAME buffers in the form the frozen producer takes (ops.vqa_forward): nothing is re-stacked."""
-        return ops.MutanWeights.from_tensors((flat or self.params).views, self.cfg["R"], self.act_v, self.act_q)
-
     # ---- steps ---------------------------------------------------------------------------------------------
     def _dims(self, feats, B, mode, seed, want_dq):
         c = self.cfg
@@ -167,7 +201,7 @@ class VqaTrainEngine:
                                seed=seed, want_dq=want_dq)
         key = (B, feats.shape[0])
         if self._ws_key != key:
-            self._ws = ops.vqa_train_workspace(d, self.mutan_weights(), self.device)
+            self._ws = self._OPS[0](d, self._weights(), self.device)
             self._ws_key = key
         return d
 
@@ -175,10 +209,10 @@ class VqaTrainEngine:
         """forward + loss + backward into self.grads; -> dict(loss, hits1, hits5, logits, dq_emb).  No host sync."""
         mode = 2 if masks is not None else (1 if train and any(p > 0 for p in self.dropout) else 0)
         d = self._dims(feats, img_idx.shape[0], mode, self.seed * 1000003 + self.step_count, want_dq)
-        mw = self.mutan_weights()
-        logits, z = ops.vqa_train_forward(d, feats, img_idx, q_emb, mw, self._ws, masks=masks)
+        mw = self._weights()
+        logits, z = self._OPS[1](d, feats, img_idx, q_emb, mw, self._ws, masks=masks)
         r = ops.ce_loss(logits, target)
-        dq = ops.vqa_train_backward(d, mw, self._ws, r["dlogits"], self.grads.views, masks=masks)
+        dq = self._OPS[2](d, mw, self._ws, r["dlogits"], self.grads.views, masks=masks)
         return dict(loss=r["loss"], hits1=r["hits1"], hits5=r["hits5"], logits=logits, dq_emb=dq)
 
     def train_step(self, feats, img_idx, q_emb, target, want_dq=False, masks=None):
@@ -191,9 +225,78 @@ class VqaTrainEngine:
     def evaluate(self, feats, img_idx, q_emb, target):
         """Eval forward + loss + hit counts (engine.py:59-100), dropout off."""
         d = self._dims(feats, img_idx.shape[0], 0, 0, False)
-        logits, z = ops.vqa_train_forward(d, feats, img_idx, q_emb, self.mutan_weights(), self._ws)
+        logits, z = self._OPS[1](d, feats, img_idx, q_emb, self._weights(), self._ws)
         r = ops.ce_loss(logits, target, want_grad=False)
         return dict(loss=r["loss"], hits1=r["hits1"], hits5=r["hits5"], logits=logits, z=z)
 
     def check_targets(self):
         ops.check_vqa_targets(device=self.device)
+
+
+class VqaTrainEngine(_TrainEngine):
+    """The MutanNoAtt trainer: buffers in the stacked MutanWeights layout.  state_dict keys are the reference's (fusion.linear_v.*,
+    fusion.list_linear_hv.{i}.* as row views of the stacked block, linear_classif.*)."""
+    _OPS = (ops.vqa_train_workspace, ops.vqa_train_forward, ops.vqa_train_backward)
+
+    def __init__(self, dv=2048, dq=2400, dhv=360, dhq=360, dz=360, R=10, A=2000, activation_v="tanh", activation_q="tanh",
+                 dropout=(0.5, 0.5, 0.5), lr=1e-4, device="cuda:0", seed=0):
+        self.cfg = dict(dv=dv, dq=dq, dhv=dhv, dhq=dhq, dz=dz, R=R, A=A)
+        self.act_v, self.act_q = ACT_CODE[activation_v], ACT_CODE[activation_q]
+        self._setup(ops.mutan_shapes(dv, dq, dhv, dhq, dz, R, A), dropout, lr, device, seed)
+
+    @classmethod
+    def from_options(cls, opt, num_answers, **kw):
+        r = route_for(opt)
+        if r != "hip":
+            raise ops._lib.NcxError("VqaTrainEngine: " + r)
+        f = opt["fusion"]
+        return cls(dv=f["dim_v"], dq=f["dim_q"], dhv=f["dim_hv"], dhq=f["dim_hq"], dz=f["dim_mm"], R=f["R"], A=num_answers,
+                   activation_v=f.get("activation_v"), activation_q=f.get("activation_q"), dropout=dropouts(opt), **kw)
+
+    def _named_views(self) -> Dict[str, torch.Tensor]:
+        v, dz, R = self.params.views, self.cfg["dz"], self.cfg["R"]
+        out = {"fusion.linear_v.weight": v["wv"], "fusion.linear_v.bias": v["bv"], "fusion.linear_q.weight": v["wq"], "fusion.linear_q.bias": v["bq"]}
+        for name, w, b in (("hv", "whv", "bhv"), ("hq", "whq", "bhq")):
+            for i in range(R):
+                out["fusion.list_linear_%s.%d.weight" % (name, i)] = v[w][i * dz:(i + 1) * dz]
+                out["fusion.list_linear_%s.%d.bias" % (name, i)] = v[b][i * dz:(i + 1) * dz]
+        out["linear_classif.weight"], out["linear_classif.bias"] = v["wc"], v["bc"]
+        return out
+
+    def mutan_weights(self, flat: Optional[FlatParams] = None) -> ops.MutanWeights:
+        """The SAME buffers in the form the frozen producer takes (ops.vqa_forward): nothing is re-stacked."""
+        return ops.MutanWeights.from_tensors((flat or self.params).views, self.cfg["R"], self.act_v, self.act_q)
+
+    _weights = mutan_weights
+
+
+class MlbTrainEngine(_TrainEngine):
+    """The MLBNoAtt trainer: buffers in the MlbWeights layout.  state_dict keys are the reference's (fusion.linear_v.*,
+    fusion.linear_q.*, linear_classif.*)."""
+    _OPS = (ops.mlb_train_workspace, ops.mlb_train_forward, ops.mlb_train_backward)
+
+    def __init__(self, dv=2048, dq=2400, dh=1200, A=2000, activation_v="tanh", activation_q="tanh", activation_c="tanh",
+                 dropout=(0.5, 0.5, 0.5), lr=1e-4, device="cuda:0", seed=0):
+        self.cfg = dict(dv=dv, dq=dq, dz=dh, A=A)
+        self.act_v, self.act_q, self.act_c = ACT_CODE[activation_v], ACT_CODE[activation_q], ACT_CODE[activation_c]
+        self._setup(ops.mlb_shapes(dv, dq, dh, A), dropout, lr, device, seed)
+
+    @classmethod
+    def from_options(cls, opt, num_answers, **kw):
+        r = mlb_route_for(opt)
+        if r != "hip":
+            raise ops._lib.NcxError("MlbTrainEngine: " + r)
+        f = opt["fusion"]
+        return cls(dv=f["dim_v"], dq=f["dim_q"], dh=f["dim_h"], A=num_answers, activation_v=f.get("activation_v"),
+                   activation_q=f.get("activation_q"), activation_c=opt.get("classif", {}).get("activation"), dropout=dropouts(opt), **kw)
+
+    def _named_views(self) -> Dict[str, torch.Tensor]:
+        v = self.params.views
+        return {"fusion.linear_v.weight": v["wv"], "fusion.linear_v.bias": v["bv"], "fusion.linear_q.weight": v["wq"],
+                "fusion.linear_q.bias": v["bq"], "linear_classif.weight": v["wc"], "linear_classif.bias": v["bc"]}
+
+    def mlb_weights(self, flat: Optional[FlatParams] = None) -> ops.MlbWeights:
+        """The SAME buffers in the form the frozen producer takes (ops.vqa_forward -> ncx_mlb_forward): nothing is copied."""
+        return ops.MlbWeights.from_tensors((flat or self.params).views, self.act_v, self.act_q, self.act_c)
+
+    _weights = mlb_weights

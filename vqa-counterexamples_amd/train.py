@@ -1,5 +1,5 @@
-"""Trains the MutanNoAtt VQA model: the producer of <logs.dir_logs>/best_model.pth.tar, the checkpoint counterexamples.py and
-contrastive.py load with pretrained_vqa.
+"""Trains a no-attention VQA model (model.arch: MutanNoAtt, the default YAML, or MLBNoAtt): the producer of
+<logs.dir_logs>/best_model.pth.tar, the checkpoint counterexamples.py and contrastive.py load with pretrained_vqa.
 
 Keeps the reference's flags where they apply (train.py:20-67), its loop (vqa/lib/engine.py:6-100: CrossEntropyLoss, Adam over the
 parameters that require grad, acc1 / acc5) and its checkpoint files (train.py:290-367: <dir_logs>/{ckpt,best}_{info,model,optim}
@@ -8,8 +8,8 @@ feature tables through neuralcx.formats; each example is its original image, que
 
 Three routes:
   --freeze_seq2vec          q_emb is computed ONCE per split by the (frozen) question encoder and kept resident; the whole step is HIP
-                            (neuralcx.vqa_train.VqaTrainEngine: forward, cross-entropy, backward, Adam).
-  (default)                 the module route: MutanNoAtt.use_hip_train = True, the fusion and classifier run in HIP inside torch
+                            (neuralcx.vqa_train.VqaTrainEngine, MlbTrainEngine for MLBNoAtt: forward, cross-entropy, backward, Adam).
+  (default)                 the module route: the model's use_hip_train = True, the fusion and classifier run in HIP inside torch
                             autograd, the encoder trains under autograd, torch.optim.Adam steps.
   --no_hip                  the same loop on the plain PyTorch modules (also runs on a CPU).
 """
@@ -35,7 +35,7 @@ CKPT_PARTS = ("info", "model", "optim")
 
 
 def build_parser():
-    p = argparse.ArgumentParser(description="Train / evaluate the MutanNoAtt VQA model", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p = argparse.ArgumentParser(description="Train / evaluate a no-attention VQA model (MutanNoAtt, MLBNoAtt)", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument("--path_opt", default=os.path.join(HERE, "options", "vqa2", "mutan_noatt_train.yaml"), type=str)
     p.add_argument("--dir_logs", type=str, help="dir logs")
     p.add_argument("--st_dropout", type=float)
@@ -117,7 +117,9 @@ class Trainer:
         self.lr, self.B = opt["optim"]["lr"], opt["optim"]["batch_size"]
         self.freeze = args.freeze_seq2vec
         from neuralcx import vqa_train
-        self.route = "torch path: --no_hip" if args.no_hip else vqa_train.route_for(opt["model"])
+        mlb = opt["model"].get("arch") == "MLBNoAtt"
+        route_for, engine_cls = (vqa_train.mlb_route_for, vqa_train.MlbTrainEngine) if mlb else (vqa_train.route_for, vqa_train.VqaTrainEngine)
+        self.route = "torch path: --no_hip" if args.no_hip else route_for(opt["model"])
         self.hip = self.route == "hip"
         self.engine = None
         if self.freeze or opt["model"]["seq2vec"].get("fixed_emb"):
@@ -125,7 +127,7 @@ class Trainer:
                 if self.freeze or "embedding" in n:
                     p_.requires_grad_(False)
         if self.hip and self.freeze:
-            self.engine = vqa_train.VqaTrainEngine.from_options(opt["model"], len(va), lr=self.lr, device=self.dev, seed=args.seed)
+            self.engine = engine_cls.from_options(opt["model"], len(va), lr=self.lr, device=self.dev, seed=args.seed)
             self.engine.load_state_dict(self.model.state_dict())          # nn.Linear's init under --seed; seq2vec.* carried through
         else:
             self.model.use_hip_train = self.hip

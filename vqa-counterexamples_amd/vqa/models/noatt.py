@@ -52,8 +52,18 @@ class MutanNoAtt(AbstractNoAtt):
 
 class MLBNoAtt(AbstractNoAtt):
     """The reference's MLBNoAtt (vqa/models/noatt.py:38-46): MLBFusion + (classif.activation) + linear_classif over fusion.dim_h.
-    state_dict keys: seq2vec.*, linear_classif.*, fusion.linear_v.*, fusion.linear_q.*."""
+    state_dict keys: seq2vec.*, linear_classif.*, fusion.linear_v.*, fusion.linear_q.*.
+    `use_hip_train = True` (set by a caller; never by default) routes forward's fusion + classifier through
+    neuralcx.vqa_train.MlbTrainFunction under the conditions of MutanNoAtt.forward."""
+    use_hip_train = False
 
     def __init__(self, opt=None, vocab_words=(), vocab_answers=()):
         super().__init__(opt, vocab_words, vocab_answers)
         self.fusion = fusion.MLBFusion(self.opt["fusion"])
+
+    def forward(self, input_v, input_q):
+        if self.use_hip_train and input_v.is_cuda and input_v.dim() == 2:
+            from neuralcx import vqa_train
+            if vqa_train.mlb_route_for(self.opt) == "hip":
+                return vqa_train.mlb_module_forward(self, input_v, self.seq2vec(input_q))
+        return super().forward(input_v, input_q)
