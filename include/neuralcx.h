@@ -379,6 +379,45 @@ size_t ncx_gru_workspace_bytes(int32_t B, int32_t T, int32_t dim_emb, int32_t di
 int ncx_gru_encode(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t dim_emb, int32_t dim_q,
                    const float* packed, void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream);
 
+/* ---- training the question encoder: backward through time (csrc/ncx_gru_train.hip) -------------------------------------------------
+ * Takes the role of torch autograd through GRUEncoder.forward -- nn.Embedding, nn.GRU and the last-step selection (the stand-in for the
+ * encoder the reference builds in factory, seq2vec.py:79-97, and selects from in process_lengths + select_last, seq2vec.py:11-25); torch
+ * walks all T steps of every row forward and backward, these entries walk the valid (row, t) pairs only.  len_b, the sorted row order
+ * (perm) and n_t as above; for t from len_b - 1 down to 0, on the rows still inside their question:
+ *   dh_t = [t == len_b - 1] dq_out[b] + (what step t + 1 sends back)
+ *   dn = dh (1 - z);  dz = dh (h_{t-1} - n);  h_{-1} = 0
+ *   da_n = dn (1 - n^2);  da_z = dz z (1 - z);  da_r = da_n hn r (1 - r);  da_hn = da_n r        hn = W_hn h_{t-1} + b_hn
+ *   dh_{t-1} = dh z + [da_r | da_z | da_hn] . W_hh
+ *   dGx_t = [da_r | da_z | da_n] -> dW_ih, db_ih, dX_t = dGx_t . W_ih;   dGh_t = [da_r | da_z | da_hn] -> dW_hh (t >= 1 only), db_hh
+ * A row whose question is empty still takes its one step over wids[b, 0] = 0 and its gradients count; a zero id inside a question is
+ * stepped over like any word.  dE[0] is ZERO whatever read E[0] in the forward (nn.Embedding(padding_idx=0): torch's embedding backward
+ * skips that row); every other row of dE is the sum of dX_t[b] over the valid pairs with that word id.  Where no recurrent product ran
+ * (all lengths 1, or T == 1) dW_hh is exactly 0.  No atomics: bit-identical from run to run.  Like the four entries above these return
+ * -1 for ANY invalid argument.
+ *
+ * Workspace of one training step (256-byte aligned; 0 for invalid dims): the length plan, the word id of every valid pair, and the stash,
+ * laid out [T][B] in the plan's sorted row order: h_t [dim_q]; the gates r | z | n | hn [4][dqp]; the gate gradients da_r | da_z | da_n |
+ * da_hn [4][dqp] (dqp = pad32(dim_q), pad columns zero); two dh buffers [B][dim_q]; dX [T][B][dim_emb]. */
+size_t ncx_gru_train_workspace_bytes(int32_t B, int32_t T, int32_t dim_emb, int32_t dim_q);
+/* The backward's extra packed operands: weight_hh_l0 and weight_ih_l0 (seq2vec.py:79-97, as for ncx_gru_pack) with the contraction over the
+ * 3 dim_q gate rows, once per weight set (16-byte aligned; ncx_gru_packed_t_bytes is 0 for invalid dims):
+ *   WhhT [pad64(dim_q)][3 dqp] | WihT [pad64(dim_emb)][3 dqp],  WhhT[j][g dqp + u] = W_hh[g dim_q + u][j],  WihT[c][g dqp + u] = W_ih[g dim_q + u][c]
+ * zero where u >= dim_q or the row does not exist. */
+size_t ncx_gru_packed_t_bytes(int32_t dim_emb, int32_t dim_q);
+int ncx_gru_pack_t(const float* w_ih, const float* w_hh, int32_t dim_emb, int32_t dim_q, float* packed_t, void* stream);
+/* ncx_gru_encode's arguments, plan and step kernel (seq2vec.py:11-25), the kernel instantiated with a flag that also writes h_t, r, z, n and
+ * hn of every valid (row, t) pair to the stash.  q_out is bit-identical to ncx_gru_encode's for the same inputs. */
+int ncx_gru_train_forward(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t dim_emb, int32_t dim_q,
+                          const float* packed, void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream);
+/* Takes the role of loss.backward() below q = seq2vec(wids) (torch's GRU, embedding and index backward).  `workspace` as the forward of
+ * the same wids left it; dq_out [B, dim_q] in the input row order.  Outputs in torch's layouts: dW_ih [3 dim_q, dim_emb], dW_hh [3 dim_q,
+ * dim_q], db_ih, db_hh [3 dim_q], dE [V1, dim_emb] (every row written).  dE == NULL: a fixed embedding (--st_fixed_emb), the dX product
+ * and the scatter are skipped and the other four gradients are unchanged.  A word id outside [0, V1) was flagged by the forward; here it
+ * is never used as an address either (its pair reads a clamped row of E and is left out of the dE sums). */
+int ncx_gru_train_backward(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t dim_emb, int32_t dim_q,
+                           const float* packed_t, void* workspace, size_t workspace_bytes, const float* dq_out,
+                           float* dW_ih, float* dW_hh, float* db_ih, float* db_hh, float* dE /*nullable*/, void* stream);
+
 /* ---- the trainable scorers LinearContext and PairwiseLinearModel (reference vqa/models/cx.py:139-156, 379-425) ---------
  * Both train with the library's loss (ncx_loss_rank) and optimiser (ncx_adam_step): forward -> scores, ncx_loss_rank ->
  * dscores, backward -> gradients (the reference's loop, counterexamples.py:330-339).  Neither model has dropout.

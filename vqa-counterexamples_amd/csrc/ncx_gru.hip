@@ -17,15 +17,12 @@
 //               with the r, z and n weight rows of THOSE units side by side (the packed layout), keeps W_in x and W_hn h in separate
 //               accumulators, and its epilogue does the gate arithmetic from registers, writes h_t (double buffered) and
 //               q[perm[row]] when t == len_row - 1.
-#include "ncx_internal.h"
+#include "ncx_gru.h"
 
 using namespace ncx;
 
 namespace {
-constexpr int GRU_BM = 64;        // rows (questions) per workgroup
-constexpr int GRU_BU = 32;        // hidden units per workgroup (x 3 gates = 96 weight rows)
 constexpr int GRU_P = GEMM_BK + 4;   // LDS pitch of a 32-deep k-step (conflict-free ds_read_b64 fragments, ncx_gemm.h)
-constexpr int GRU_MAX_T = 64;
 constexpr int GRU_TILE_ROWS = GRU_BM + 3 * GRU_BU;
 
 struct GruPacked { int kx, kp, nj; size_t w_floats, floats; };
@@ -101,10 +98,13 @@ __global__ __launch_bounds__(256) void k_gru_plan(const int* __restrict__ wids, 
     }
 }
 
+// KEEP (the training forward, ncx_gru_train.hip): the same step; the epilogue also leaves r, z, n and hn = W_hn h + b_hn of every valid
+// (row, t) pair in the stash, and the host hands it h_{t-1} / h_t of the [T][B] stash instead of the two alternating buffers.
+template <bool KEEP>
 __global__ __launch_bounds__(256) void k_gru_step(const int* __restrict__ wids, int T, int t, const float* __restrict__ E, int V1, int dim_emb, int dim_q,
                                                   const float* __restrict__ packed, const int* __restrict__ perm, const int* __restrict__ lens,
                                                   const int* __restrict__ n_t, const float* __restrict__ h_prev, float* __restrict__ h_next,
-                                                  float* __restrict__ q, int tiles_m, int total) {
+                                                  float* __restrict__ q, int tiles_m, int total, GruKeep<KEEP> keep) {
     __shared__ __attribute__((aligned(16))) float lds[2][GRU_TILE_ROWS * GRU_P];
     // workgroup ids are dealt round-robin over the 8 XCDs: consecutive work items (the row tiles of one unit tile, which share its
     // weight rows) go to the same XCD's L2
@@ -215,17 +215,40 @@ __global__ __launch_bounds__(256) void k_gru_step(const int* __restrict__ wids, 
             const float hn = (1.f - z) * n + z * hp;
             h_next[(size_t)row * dim_q + unit] = hn;
             if (t == lens[row] - 1) q[(size_t)perm[row] * dim_q + unit] = hn;
+            if constexpr (KEEP) {
+                float* g = keep.gates + ((size_t)t * keep.B + row) * (4 * (size_t)keep.dqp) + unit;
+                g[0] = r; g[keep.dqp] = z; g[2 * keep.dqp] = n; g[3 * keep.dqp] = acc_nh[i][e] + b_hn;
+            }
         }
 }
 
-extern "C" {
-struct GruLayout { size_t perm, lens, lens_tmp, n_t, h0, h1, total; };
-
-static bool gru_dims_ok(long long B, long long T, long long dim_emb, long long dim_q) {
+namespace ncx {
+bool gru_dims_ok(long long B, long long T, long long dim_emb, long long dim_q) {
     if (B < 1 || T < 1 || T > GRU_MAX_T || dim_emb < 1 || dim_q < 1) return false;
     if (B * T >= (1ll << 31) || dim_emb >= (1 << 24) || dim_q >= (1 << 24)) return false;
     return cdiv(B, GRU_BM) * cdiv(dim_q, GRU_BU) < (1ll << 28);        // the step launch's grid
 }
+
+// ncx_gru_encode's plan and T step launches with the KEEP instantiation: h_t goes to hstash [T][B][dim_q], the gates to `gates`
+int gru_forward_keep(const int32_t* wids, int B, int T, const float* E, int V1, int dim_emb, int dim_q, const float* packed, const GruPlan& p,
+                     float* hstash, float* gates, float* q_out, int32_t* bad_id_flag, hipStream_t s) {
+    hipLaunchKernelGGL(k_gru_plan, dim3(1), dim3(256), 0, s, wids, B, T, V1, p.perm, p.lens, p.lens_tmp, p.n_t, (int*)bad_id_flag);
+    NCX_HIP_TRY(hipGetLastError());
+    const int tiles_m = (int)cdiv(B, GRU_BM), total = tiles_m * (int)cdiv(dim_q, GRU_BU);
+    const unsigned grid = (unsigned)(8 * cdiv(total, 8));
+    const GruKeep<true> keep{gates, B, pad_to(dim_q, GEMM_BK)};
+    const size_t hs = (size_t)B * dim_q;
+    for (int t = 0; t < T; ++t) {
+        hipLaunchKernelGGL(k_gru_step<true>, dim3(grid), dim3(256), 0, s, wids, T, t, E, V1, dim_emb, dim_q, packed, p.perm, p.lens, p.n_t,
+                           t > 0 ? hstash + (t - 1) * hs : hstash, hstash + t * hs, q_out, tiles_m, total, keep);
+        NCX_HIP_TRY(hipGetLastError());
+    }
+    return NCX_OK;
+}
+}  // namespace ncx
+
+extern "C" {
+struct GruLayout { size_t perm, lens, lens_tmp, n_t, h0, h1, total; };
 
 static GruLayout gru_layout(int B, int dim_q) {
     GruLayout w{};
@@ -271,8 +294,8 @@ int ncx_gru_encode(const int32_t* wids, int32_t B, int32_t T, const float* E, in
     const int tiles_m = (int)cdiv(B, GRU_BM), total = tiles_m * (int)cdiv(dim_q, GRU_BU);
     const unsigned grid = (unsigned)(8 * cdiv(total, 8));
     for (int t = 0; t < T; ++t) {              // every step is launched: how many rows it has is known on the device only
-        hipLaunchKernelGGL(k_gru_step, dim3(grid), dim3(256), 0, s, wids, T, t, E, V1, dim_emb, dim_q, packed, perm, lens, n_t,
-                           h[(t + 1) & 1], h[t & 1], q_out, tiles_m, total);
+        hipLaunchKernelGGL(k_gru_step<false>, dim3(grid), dim3(256), 0, s, wids, T, t, E, V1, dim_emb, dim_q, packed, perm, lens, n_t,
+                           h[(t + 1) & 1], h[t & 1], q_out, tiles_m, total, GruKeep<false>{});
         NCX_HIP_TRY(hipGetLastError());
     }
     return NCX_OK;

@@ -605,6 +605,129 @@ def check_gru_ids(bad_flag: Optional[torch.Tensor] = None, device=None) -> None:
         raise IndexError("question_wids outside [0, V + 1) in a gru_encode call")
 
 
+# ---- training the question encoder (include/neuralcx.h: ncx_gru_train_*, ncx_gru_pack_t) -----------------------------------------
+GRU_T_ROWS = 64         # output columns per workgroup of the backward's products: the rows of the transposed pack come in whole tiles
+
+
+def _pad64(n: int) -> int:
+    return (n + GRU_T_ROWS - 1) // GRU_T_ROWS * GRU_T_ROWS
+
+
+def gru_pack_t_layout(w_ih: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
+    """The layout of ncx_gru_pack_t restated with tensor ops (any device; what a test compares the kernel against): the contraction
+    runs over the 3 dim_q gate rows, WhhT [pad64(dim_q)][3 dqp] | WihT [pad64(dim_emb)][3 dqp], WhhT[j][g dqp + u] = w_hh[g dim_q + u][j],
+    WihT[c][g dqp + u] = w_ih[g dim_q + u][c], dqp = pad32(dim_q), zero padded."""
+    dim_q, dim_emb = w_hh.shape[1], w_ih.shape[1]
+    dqp = _pad32(dim_q)
+    out = []
+    for w, n in ((w_hh, dim_q), (w_ih, dim_emb)):
+        t = torch.zeros(_pad64(n), 3, dqp, dtype=torch.float32, device=w.device)
+        t[:n, :, :dim_q] = w.detach().float().view(3, dim_q, n).permute(2, 0, 1)
+        out.append(t.reshape(-1))
+    return torch.cat(out)
+
+
+def gru_unpack_t_layout(packed_t: torch.Tensor, dim_emb: int, dim_q: int):
+    """-> (w_ih [3 dim_q, dim_emb], w_hh [3 dim_q, dim_q]) read back out of the transposed pack."""
+    dqp = _pad32(dim_q)
+    nh = _pad64(dim_q) * 3 * dqp
+    hh = packed_t[:nh].view(_pad64(dim_q), 3, dqp)[:dim_q, :, :dim_q].permute(1, 2, 0).reshape(3 * dim_q, dim_q)
+    ih = packed_t[nh:].view(_pad64(dim_emb), 3, dqp)[:dim_emb, :, :dim_q].permute(1, 2, 0).reshape(3 * dim_q, dim_emb)
+    return ih, hh
+
+
+class GruTrainWeights:
+    """One weight set of the trainable encoder as ncx_gru_train_forward / _backward want it: E, the forward's pack (ncx_gru_pack) and
+    the backward's transposed pack (ncx_gru_pack_t).  Built from the five tensors, on their device."""
+
+    def __init__(self, E, w_ih, w_hh, b_ih, b_hh):
+        ts = [t.detach() for t in (E, w_ih, w_hh, b_ih, b_hh)]
+        if any(t.dtype != torch.float32 for t in ts):
+            raise _lib.NcxError("ncx_gru_train_* take fp32 parameters")
+        E, w_ih, w_hh, b_ih, b_hh = (t.contiguous() for t in ts)
+        if E.dim() != 2 or w_ih.dim() != 2 or w_hh.dim() != 2 or w_ih.shape[1] != E.shape[1] or w_hh.shape[0] != 3 * w_hh.shape[1] or \
+                w_ih.shape[0] != w_hh.shape[0] or tuple(b_ih.shape) != (w_hh.shape[0],) or tuple(b_hh.shape) != (w_hh.shape[0],):
+            raise ValueError("gru_train_weights takes E [V + 1, de], w_ih [3 dq, de], w_hh [3 dq, dq], b_ih, b_hh [3 dq]; got %s"
+                             % ([tuple(t.shape) for t in ts],))
+        self.E = E
+        self.V1, self.dim_emb = E.shape
+        self.dim_q = w_hh.shape[1]
+        L = _lib.lib()
+        n, nt = L.ncx_gru_packed_bytes(self.dim_emb, self.dim_q), L.ncx_gru_packed_t_bytes(self.dim_emb, self.dim_q)
+        if n == 0 or nt == 0:
+            raise _lib.NcxError("ncx_gru_pack_t: dims out of range (dim_emb %d, dim_q %d)" % (self.dim_emb, self.dim_q))
+        self.packed = torch.empty(n // 4, dtype=torch.float32, device=E.device)
+        self.packed_t = torch.empty(nt // 4, dtype=torch.float32, device=E.device)
+        with torch.cuda.device(E.device):
+            _lib.check(L.ncx_gru_pack(*[_ptr(t, torch.float32, "gru weight") for t in (w_ih, w_hh, b_ih, b_hh)], self.dim_emb, self.dim_q,
+                                      C.c_void_p(self.packed.data_ptr()), _stream()), "ncx_gru_pack")
+            _lib.check(L.ncx_gru_pack_t(_ptr(w_ih, torch.float32, "w_ih"), _ptr(w_hh, torch.float32, "w_hh"), self.dim_emb, self.dim_q,
+                                        C.c_void_p(self.packed_t.data_ptr()), _stream()), "ncx_gru_pack_t")
+
+
+def gru_train_weights(E, w_ih, w_hh, b_ih, b_hh) -> GruTrainWeights:
+    return GruTrainWeights(E, w_ih, w_hh, b_ih, b_hh)
+
+
+def _gru_train_args(wids: torch.Tensor, gw: GruTrainWeights, what: str):
+    if wids.dim() != 2:
+        raise ValueError("wids must be [B, T], got %s" % (tuple(wids.shape),))
+    if wids.is_floating_point():
+        raise TypeError("wids must be an integer tensor, got %s" % wids.dtype)
+    B, T = wids.shape
+    if B < 1 or not 1 <= T <= 64:
+        raise ValueError("%s takes B >= 1 questions of 1 <= T <= 64 steps, got [%d, %d]" % (what, B, T))
+    if gw.packed.device != wids.device:
+        raise _lib.NcxError("wids are on %s, the encoder's weights on %s" % (wids.device, gw.packed.device))
+    return B, T, wids.to(torch.int32).contiguous()
+
+
+def gru_train_workspace(B: int, T: int, gw: GruTrainWeights, device) -> torch.Tensor:
+    """The workspace of one training step (ncx_gru_train_workspace_bytes): the length plan and the stash the backward needs."""
+    n = _lib.lib().ncx_gru_train_workspace_bytes(B, T, gw.dim_emb, gw.dim_q)
+    if n == 0:
+        raise _lib.NcxError("ncx_gru_train_workspace_bytes: dims out of range")
+    return torch.empty(n + 256, dtype=torch.uint8, device=device)
+
+
+def gru_train_forward(wids: torch.Tensor, gw: GruTrainWeights, ws: torch.Tensor, bad_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ncx_gru_train_forward: gru_encode's q (bit for bit), with the stash of the valid (row, t) pairs left in `ws`."""
+    B, T, wids = _gru_train_args(wids, gw, "gru_train_forward")
+    if bad_flag is None:
+        bad_flag = gru_bad_flag(wids.device)
+    p, n = _ws_ptr(ws)
+    q = torch.empty(B, gw.dim_q, dtype=torch.float32, device=wids.device)
+    _lib.check(_lib.lib().ncx_gru_train_forward(_ptr(wids, torch.int32, "wids"), B, T, _ptr(gw.E, torch.float32, "E"), gw.V1, gw.dim_emb,
+                                                gw.dim_q, _ptr(gw.packed, torch.float32, "packed"), p, n, C.c_void_p(q.data_ptr()),
+                                                _ptr(bad_flag, torch.int32, "bad_flag"), _stream()), "ncx_gru_train_forward")
+    return q
+
+
+def gru_train_backward(wids: torch.Tensor, gw: GruTrainWeights, ws: torch.Tensor, dq_out: torch.Tensor, want_dE: bool = True,
+                       dE: Optional[torch.Tensor] = None) -> Dict[str, Optional[torch.Tensor]]:
+    """ncx_gru_train_backward on the workspace gru_train_forward left for the same wids: dq_out [B, dim_q] -> {"w_ih", "w_hh", "b_ih",
+    "b_hh", "E"} in torch's layouts; "E" is None when want_dE is off (a fixed embedding).  `dE`: a caller's [V + 1, dim_emb] buffer."""
+    B, T, wids = _gru_train_args(wids, gw, "gru_train_backward")
+    if tuple(dq_out.shape) != (B, gw.dim_q):
+        raise ValueError("dq_out must be [%d, %d], got %s" % (B, gw.dim_q, tuple(dq_out.shape)))
+    dev = wids.device
+    g = {"w_ih": torch.empty(3 * gw.dim_q, gw.dim_emb, dtype=torch.float32, device=dev),
+         "w_hh": torch.empty(3 * gw.dim_q, gw.dim_q, dtype=torch.float32, device=dev),
+         "b_ih": torch.empty(3 * gw.dim_q, dtype=torch.float32, device=dev), "b_hh": torch.empty(3 * gw.dim_q, dtype=torch.float32, device=dev),
+         "E": None}
+    if want_dE:
+        g["E"] = dE if dE is not None else torch.empty(gw.V1, gw.dim_emb, dtype=torch.float32, device=dev)
+        if tuple(g["E"].shape) != (gw.V1, gw.dim_emb):
+            raise ValueError("dE must be [%d, %d], got %s" % (gw.V1, gw.dim_emb, tuple(g["E"].shape)))
+    p, n = _ws_ptr(ws)
+    _lib.check(_lib.lib().ncx_gru_train_backward(_ptr(wids, torch.int32, "wids"), B, T, _ptr(gw.E, torch.float32, "E"), gw.V1, gw.dim_emb,
+                                                 gw.dim_q, _ptr(gw.packed_t, torch.float32, "packed_t"), p, n,
+                                                 _ptr(dq_out.float().contiguous(), torch.float32, "dq_out"),
+                                                 *[_ptr(g[k], torch.float32, "d" + k) for k in ("w_ih", "w_hh", "b_ih", "b_hh", "E")], _stream()),
+               "ncx_gru_train_backward")
+    return g
+
+
 # ---- the trainable scorers LinearContext and PairwiseLinearModel (include/neuralcx.h) -----------------------------------------
 PAIRLIN_H = 300                     # dim_h = dim_a = 300 in the reference (cx.py:391-392)
 PAIRLIN_FIELDS = ("answer_embedding", "w", "b", "w_out", "b_out")

@@ -73,6 +73,38 @@ class MutanTrainFunction(torch.autograd.Function):
         return (None, None, dq) + tuple(grads[k] for k in ops.MUTAN_FIELDS) + (None,)
 
 
+class GruTrainFunction(torch.autograd.Function):
+    """q = the hidden state after each question's last word (GRUEncoder below its dropout) through ncx_gru_train_forward / _backward.
+    Inputs: wids, E, w_ih, w_hh, b_ih, b_hh and the encoder module, on which the packs are cached (keyed on data_ptr / _version of the
+    five tensors, like GRUEncoder._hip_weights: rebuilt after an optimizer step).  Gradients: the five tensors; None for E when it does
+    not require grad (a fixed embedding: the dX product is skipped)."""
+
+    @staticmethod
+    def weights(module, tensors):
+        key = tuple((t.data_ptr(), t._version) for t in tensors)
+        hit = module.__dict__.get("_hip_gru_train") if module is not None else None
+        if hit is None or hit[0] != key:
+            hit = (key, ops.gru_train_weights(*tensors))
+            if module is not None:
+                module.__dict__["_hip_gru_train"] = hit
+        return hit[1]
+
+    @staticmethod
+    def forward(ctx, wids, E, w_ih, w_hh, b_ih, b_hh, module=None):
+        gw = GruTrainFunction.weights(module, (E, w_ih, w_hh, b_ih, b_hh))
+        ws = ops.gru_train_workspace(wids.shape[0], wids.shape[1], gw, wids.device)
+        q = ops.gru_train_forward(wids, gw, ws)
+        ctx.hip = (wids, gw, ws)
+        return q
+
+    @staticmethod
+    def backward(ctx, dq):
+        wids, gw, ws = ctx.hip
+        g = ops.gru_train_backward(wids, gw, ws, dq, want_dE=ctx.needs_input_grad[1])
+        ctx.hip = None                                            # the stash is the step's largest buffer: let go of it here
+        return None, g["E"], g["w_ih"], g["w_hh"], g["b_ih"], g["b_hh"], None
+
+
 def module_forward(model, input_v: torch.Tensor, q_emb: torch.Tensor) -> torch.Tensor:
     """The HIP route of MutanNoAtt.forward below seq2vec: the rows of input_v are the feature table, the index the identity."""
     f, opt = model.fusion, model.opt

@@ -10,7 +10,8 @@ Three routes:
   --freeze_seq2vec          q_emb is computed ONCE per split by the (frozen) question encoder and kept resident; the whole step is HIP
                             (neuralcx.vqa_train.VqaTrainEngine, MlbTrainEngine for MLBNoAtt: forward, cross-entropy, backward, Adam).
   (default)                 the module route: the model's use_hip_train = True, the fusion and classifier run in HIP inside torch
-                            autograd, the encoder trains under autograd, torch.optim.Adam steps.
+                            autograd, the encoder trains under autograd, torch.optim.Adam steps.  With --hip_seq2vec_train the encoder's
+                            forward and backward through time run in HIP too (GRUEncoder.use_hip_train, neuralcx.vqa_train.GruTrainFunction).
   --no_hip                  the same loop on the plain PyTorch modules (also runs on a CPU).
 """
 import argparse
@@ -56,6 +57,7 @@ def build_parser():
     p.add_argument("--path_trainset", type=str, default=None, help="overrides vqa.path_trainset of the YAML")
     p.add_argument("--path_features", type=str, default=None, help="overrides coco.path_features of the YAML")
     p.add_argument("--freeze_seq2vec", action="store_true", help="freeze the question encoder: q_emb once per split, the whole step in HIP")
+    p.add_argument("--hip_seq2vec_train", action="store_true", help="default route only: train the question encoder in HIP as well (backward through time)")
     p.add_argument("--no_hip", action="store_true", help="the plain PyTorch modules (no HIP library; runs on a CPU too)")
     p.add_argument("--seed", type=int, default=1337)
     return p
@@ -108,6 +110,10 @@ class Trainer:
     def __init__(self, args, opt):
         self.args, self.opt = args, opt
         cuda = torch.cuda.is_available()
+        if args.hip_seq2vec_train and args.no_hip:
+            raise SystemExit("train.py: --hip_seq2vec_train trains the encoder in HIP; it cannot be combined with --no_hip")
+        if args.hip_seq2vec_train and args.freeze_seq2vec:
+            raise SystemExit("train.py: --hip_seq2vec_train has nothing to train under --freeze_seq2vec")
         if not cuda and not args.no_hip:
             raise SystemExit("train.py: the HIP routes need an MI355X (use --no_hip for the PyTorch modules)")
         self.dev = torch.device("cuda:0" if cuda else "cpu")
@@ -131,10 +137,16 @@ class Trainer:
             self.engine.load_state_dict(self.model.state_dict())          # nn.Linear's init under --seed; seq2vec.* carried through
         else:
             self.model.use_hip_train = self.hip
+            self.hip_seq2vec = bool(args.hip_seq2vec_train and self.hip and hasattr(type(self.model.seq2vec), "use_hip_train"))
+            if args.hip_seq2vec_train and not self.hip_seq2vec:
+                raise SystemExit("train.py: --hip_seq2vec_train needs the HIP route and the GRU encoder (%s)" % self.route)
+            if self.hip_seq2vec:
+                self.model.seq2vec.use_hip_train = True
             self.optim = torch.optim.Adam([p_ for p_ in self.model.parameters() if p_.requires_grad], self.lr)     # train.py:143-144
             self.criterion = nn.CrossEntropyLoss()
         self.best_acc1, self.history = 0.0, []
-        print("=> route: %s%s" % ("hip" if self.hip else self.route, " (engine: whole step in HIP)" if self.engine else ""), flush=True)
+        print("=> route: %s%s%s" % ("hip" if self.hip else self.route, " (engine: whole step in HIP)" if self.engine else "",
+                                    " (question encoder: HIP forward + backward through time)" if getattr(self, "hip_seq2vec", False) else ""), flush=True)
 
     # ---- data ------------------------------------------------------------------------------------------------
     def q_emb_of(self, split):

@@ -7,8 +7,11 @@ import torch.nn as nn
 
 class GRUEncoder(nn.Module):
     """nn.Embedding -> nn.GRU -> the hidden state after the last word.  On a CUDA device, when no gradient can be wanted and dropout
-    is inert, forward runs in the HIP library (ops.gru_encode: padded steps are skipped); `use_hip = False` keeps it in PyTorch."""
+    is inert, forward runs in the HIP library (ops.gru_encode: padded steps are skipped); `use_hip = False` keeps it in PyTorch.
+    `use_hip_train = True` (off by default) also trains it there: a CUDA fp32 module called with grad mode on and a parameter that
+    requires grad runs neuralcx.vqa_train.GruTrainFunction (forward with a stash, backward through time); its dropout stays in torch."""
     use_hip = True
+    use_hip_train = False
 
     def __init__(self, vocab_words, dim_q=2400, dim_emb=620, dropout=0.25):
         super().__init__()
@@ -38,11 +41,24 @@ class GRUEncoder(nn.Module):
 
     def drop_hip_weights(self):
         self.__dict__.pop("_hip_gru", None)
+        self.__dict__.pop("_hip_gru_train", None)
+
+    def _hip_train_ok(self, wids):
+        if not (self.use_hip_train and wids.is_cuda and wids.dim() == 2 and 1 <= wids.shape[1] <= 64 and wids.shape[0] >= 1):
+            return False
+        params = list(self.parameters())
+        if not (torch.is_grad_enabled() and any(p.requires_grad for p in params)):
+            return False
+        return all(p.dtype == torch.float32 and p.device == wids.device for p in params)
 
     def forward(self, wids):
         if self._hip_ok(wids):
             from neuralcx import ops
             return ops.gru_encode(wids, self._hip_weights())
+        if self._hip_train_ok(wids):
+            from neuralcx.vqa_train import GruTrainFunction
+            g = self.gru
+            return self.dropout(GruTrainFunction.apply(wids, self.embedding.weight, g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0, self))
         x = self.embedding(wids)
         out, _ = self.gru(x)
         last = (wids > 0).sum(1).clamp(min=1) - 1            # last valid step (right padding)
