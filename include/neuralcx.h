@@ -418,6 +418,36 @@ int ncx_gru_train_backward(const int32_t* wids, int32_t B, int32_t T, const floa
                            const float* packed_t, void* workspace, size_t workspace_bytes, const float* dq_out,
                            float* dW_ih, float* dW_hh, float* db_ih, float* db_hh, float* dE /*nullable*/, void* stream);
 
+/* ---- the two-layer LSTM question encoder: seq2vec arch `2-lstm` (csrc/ncx_lstm.hip) ------------------------------------------------
+ * Takes the role of TwoLSTM.forward in eval mode (seq2vec.py:48-76).  Forward only; gate order i, f, g, o as torch.nn.LSTM:
+ *   len_b = #{t : wids[b, t] != 0}, and T when that is 0      process_lengths (seq2vec.py:11-14); select_last's index len_b - 1 = -1 is the
+ *                                                             LAST step (seq2vec.py:16-25), so an all-padding row runs T steps on E[0]
+ *   x_t = tanh(E[wids[b, t]])                                 seq2vec.py:63-64; row 0 of E is read like any other row
+ *   layer l in {0, 1}:  [i f g o] = W_ih^l x + b_ih^l + W_hh^l h + b_hh^l;  c' = s(f) c + s(i) tanh(g);  h' = s(o) tanh(c');  h_0 = c_0 = 0
+ *   layer 1's x_t is layer 0's h_t                            seq2vec.py:65, 70
+ *   q[b] = [h^0 | h^1] after step len_b - 1                   seq2vec.py:66, 71, 75
+ * The recurrence runs over TIME.  The reference builds its nn.LSTMs without batch_first and feeds them [B, T, emb], so as written it runs
+ * over the batch axis and a question's vector depends on its place in the batch; the parameters' names and shapes are the same either way.
+ * A row is advanced only while t < len_b (length plan as ncx_gru_encode).  Launch s in [0, T] runs layer 0 at step s and layer 1 at step
+ * s - 1 side by side: T + 2 launches with the plan, nothing read back, no atomics, no inter-workgroup wait, bit-identical from run to run.
+ * Like the ncx_gru_* entries these return -1 for ANY invalid argument; emb, H, B, V1 >= 1, 1 <= T <= 64.
+ *
+ * ncx_lstm2_pack takes the role of TwoLSTM's construction in factory (seq2vec.py:86-89): rnn_0's weight_ih_l0 [4 H, emb], weight_hh_l0
+ * [4 H, H], bias_ih_l0, bias_hh_l0 [4 H] and rnn_1's ([4 H, H] both) -> `packed` (ncx_lstm2_packed_bytes, 16-byte aligned), once per
+ * weight set:  layer 0 | layer 1,  layer l = W [ceil(H / 32)][4 gates][32 units][kp_l] | bias [ceil(H / 32)][4][32 units]
+ *   kp_0 = pad32(emb) + pad32(H), kp_1 = 2 pad32(H);  W row (j, g, u) = W_ih[g H + 32 j + u, :] zero-padded, then W_hh[g H + 32 j + u, :]
+ *   zero-padded;  bias (j, g, u) = b_ih[g H + 32 j + u] + b_hh[g H + 32 j + u] (one fp32 addition) */
+size_t ncx_lstm2_packed_bytes(int32_t emb, int32_t H);                                     /* 0 for invalid dims */
+int ncx_lstm2_pack(const float* w_ih0, const float* w_hh0, const float* b_ih0, const float* b_hh0, const float* w_ih1, const float* w_hh1,
+                   const float* b_ih1, const float* b_hh1, int32_t emb, int32_t H, float* packed, void* stream);
+/* Workspace of ncx_lstm2_encode (256-byte aligned: the length plan, two h buffers and the cell state per layer); 0 for invalid dims. */
+size_t ncx_lstm2_workspace_bytes(int32_t B, int32_t T, int32_t emb, int32_t H);
+/* Takes the role of process_lengths, both nn.LSTMs and select_last (seq2vec.py:11-25, 61-76): wids [B, T] int32; E [V1, emb] the embedding
+ * table; q_out [B, 2 H] in the input row order.  q_out does not depend on what the workspace held.  A word id outside [0, V1) is never
+ * used as an address (clamped; that row's output is meaningless) and *bad_id_flag is set to 1, as by ncx_gru_encode. */
+int ncx_lstm2_encode(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t emb, int32_t H, const float* packed,
+                     void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream);
+
 /* ---- the trainable scorers LinearContext and PairwiseLinearModel (reference vqa/models/cx.py:139-156, 379-425) ---------
  * Both train with the library's loss (ncx_loss_rank) and optimiser (ncx_adam_step): forward -> scores, ncx_loss_rank ->
  * dscores, backward -> gradients (the reference's loop, counterexamples.py:330-339).  Neither model has dropout.

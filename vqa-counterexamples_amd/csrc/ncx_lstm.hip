@@ -1,0 +1,331 @@
+// ncx_lstm.hip -- the two-layer LSTM question encoder (TwoLSTM in eval mode: tanh(embedding) -> LSTM -> LSTM -> both layers' hidden
+// state at the last valid step, side by side): ncx_lstm2_packed_bytes, ncx_lstm2_pack, ncx_lstm2_workspace_bytes, ncx_lstm2_encode.
+// Forward only.
+//
+// Reference: vqa/models/seq2vec.py -- process_lengths + select_last (11-25), TwoLSTM (48-76), factory's `2-lstm` branch (86-89).
+// Semantics, gate order i, f, g, o as torch.nn.LSTM, the recurrence over TIME (batch_first; DESIGN 5n on why not as written):
+//   len_b = #{t : wids[b, t] != 0}, and T when that is 0 (select_last's index -1);  x_t = tanh(E[wids[b, t]])  (row 0 is read like any row)
+//   layer l:  [i f g o] = W_ih x + b_ih + W_hh h + b_hh;  c' = s(f) c + s(i) tanh(g);  h' = s(o) tanh(c');  h_0 = c_0 = 0;  layer 1's x is layer 0's h'
+//   q[b] = [h^0 | h^1] after step len_b - 1
+// Plan (T + 2 launches, nothing read back, no inter-workgroup wait, no atomics):
+//   k_lstm_plan  one workgroup: k_gru_plan (ncx_gru.hip) with the length rule above.  A kernel of its own so that the GRU encoder's object
+//                code does not change with this file.
+//   k_lstm_step  launch s in [0, T]: layer 0 at step s (s < T) and layer 1 at step s - 1 (s >= 1) as two ranges of workgroup ids -- a
+//                wavefront: both read only what launch s - 1 wrote.  A layer's step is the GEMM [x_t | h_{t-1}][0:n_t) . [W_ih | W_hh]^T on
+//                v_mfma_f32_16x16x4_f32 (step 0 stops after the x columns: h_0 = 0).  A workgroup owns 64 rows x 32 hidden units with the
+//                i, f, g, o weight rows of THOSE units side by side; one accumulator per gate (x and h share it); the epilogue does the cell
+//                arithmetic from registers, updates c in place, writes h_t (double buffered) and q[perm[row]] when t == len_row - 1.
+//                Layer 0 gathers E[wid] on the load side and takes tanh on the way from registers to LDS.
+#include "ncx_gru.h"
+
+using namespace ncx;
+
+namespace {
+// LDS rows are one 32-deep k-step with no padding; the 16-byte quad q of tile row r sits at quad q ^ ((r >> 1) & 7).  A 32-lane half
+// of a ds_read_b64 fragment read (16 rows, one logical quad, two 8-byte halves) then covers all 64 banks once, as the padded pitch
+// of 36 (ncx_gru.hip) does, and the two buffers take 48 KB instead of 54: three workgroups fit a CU's LDS, not two.
+constexpr int LSTM_P = GEMM_BK;
+constexpr int LSTM_BM = GRU_BM, LSTM_BU = GRU_BU, LSTM_MAX_T = GRU_MAX_T;
+constexpr int LSTM_TILE_ROWS = LSTM_BM + 4 * LSTM_BU;
+
+// packed = layer 0 | layer 1;  layer l = W [nj][4 gates][32 units][kp_l] | bias [nj][4][32 units] (b_ih + b_hh)
+struct LstmPacked { int kx[2], kp[2], nj; size_t w_floats[2], off[2], floats; };
+__host__ __device__ inline LstmPacked lstm_packed(int emb, int H) {
+    LstmPacked p;
+    p.nj = (H + LSTM_BU - 1) / LSTM_BU;
+    size_t off = 0;
+    for (int l = 0; l < 2; ++l) {
+        p.kx[l] = pad_to(l ? H : emb, GEMM_BK); p.kp[l] = p.kx[l] + pad_to(H, GEMM_BK);
+        p.w_floats[l] = (size_t)p.nj * 4 * LSTM_BU * p.kp[l];
+        p.off[l] = off; off += p.w_floats[l] + (size_t)p.nj * 4 * LSTM_BU;
+    }
+    p.floats = off;
+    return p;
+}
+
+struct LstmW { const float* w_ih; const float* w_hh; const float* b_ih; const float* b_hh; };
+
+struct LstmStep {
+    const int* wids; const float* E; const float* packed; const int* perm; const int* lens; const int* n_t;
+    float* h[2][2];      // [layer][t & 1]: h_t of the rows [0, n_t), sorted row order, [B][H]
+    float* c[2];         // [layer]: the cell state, [B][H], updated in place
+    float* q;            // [B][2 H], input row order
+    int T, V1, emb, H, tiles_m, total, grid1;
+};
+}  // namespace
+
+// row (j, g, u) of layer l = W_ih^l[g H + 32 j + u, :] zero-padded to whole k-steps, then W_hh^l[g H + 32 j + u, :] likewise; units beyond H
+// are zero rows
+__global__ __launch_bounds__(256) void k_lstm_pack(LstmW w0, LstmW w1, int emb, int H, float* __restrict__ packed) {
+    const LstmPacked p = lstm_packed(emb, H);
+    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.floats) return;
+    const int l = i >= p.off[1];
+    const LstmW w = l ? w1 : w0;
+    const int in = l ? H : emb, kx = p.kx[l], kp = p.kp[l];
+    const size_t o = i - p.off[l];
+    float v = 0.f;
+    if (o < p.w_floats[l]) {
+        const size_t row = o / kp;
+        const int c = (int)(o - row * kp);
+        const int u = (int)(row % LSTM_BU), g = (int)(row / LSTM_BU % 4), unit = (int)(row / (4 * LSTM_BU)) * LSTM_BU + u;
+        if (unit < H) {
+            if (c < kx) { if (c < in) v = w.w_ih[((size_t)g * H + unit) * in + c]; }
+            else if (c - kx < H) v = w.w_hh[((size_t)g * H + unit) * H + (c - kx)];
+        }
+    } else {
+        const size_t b = o - p.w_floats[l];
+        const int u = (int)(b % LSTM_BU), g = (int)(b / LSTM_BU % 4), unit = (int)(b / (4 * LSTM_BU)) * LSTM_BU + u;
+        if (unit < H) v = w.b_ih[(size_t)g * H + unit] + w.b_hh[(size_t)g * H + unit];
+    }
+    packed[i] = v;
+}
+
+// One workgroup.  lens_tmp [B] is scratch; perm / lens [B] come out in sorted order (length descending, input order inside a length).
+__global__ __launch_bounds__(256) void k_lstm_plan(const int* __restrict__ wids, int B, int T, int V1, int* __restrict__ perm, int* __restrict__ lens,
+                                                   int* __restrict__ lens_tmp, int* __restrict__ n_t, int* __restrict__ bad) {
+    __shared__ int cnt[LSTM_MAX_T + 2], start[LSTM_MAX_T + 2], sbad;
+    const int tid = threadIdx.x;
+    if (tid == 0) sbad = 0;
+    __syncthreads();
+    bool oob = false;
+    for (int b = tid; b < B; b += 256) {
+        int n = 0;
+        for (int t = 0; t < T; ++t) {
+            const int w = wids[(size_t)b * T + t];
+            oob |= w < 0 || w >= V1;
+            n += w != 0;
+        }
+        lens_tmp[b] = n > 0 ? n : T;           // all padding: select_last indexes step -1, the LAST one
+    }
+    if (oob) sbad = 1;
+    __syncthreads();
+    if (tid == 0 && sbad) *bad = 1;
+    const int L = tid + 1;                     // thread L - 1 owns the rows of length L
+    if (L <= T) {
+        int c = 0;
+        for (int b = 0; b < B; ++b) c += lens_tmp[b] == L;
+        cnt[L] = c;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int run = 0;
+        for (int l = T; l >= 1; --l) { start[l] = run; run += cnt[l]; n_t[l - 1] = run; }   // n_t[t] = #{len >= t + 1}
+    }
+    __syncthreads();
+    if (L <= T) {
+        int pos = start[L];
+        for (int b = 0; b < B; ++b)
+            if (lens_tmp[b] == L) { perm[pos] = b; lens[pos] = L; ++pos; }
+    }
+}
+
+// grid = (layers of this launch) x grid1; workgroups [0, grid1) run layer `layer_base`, [grid1, 2 grid1) layer 1
+__global__ __launch_bounds__(256) void k_lstm_step(LstmStep a, int s, int layer_base) {
+    __shared__ __attribute__((aligned(16))) float lds[2][LSTM_TILE_ROWS * LSTM_P];
+    const int second = (int)blockIdx.x >= a.grid1;
+    const int layer = layer_base + second, bid = (int)blockIdx.x - second * a.grid1;
+    const int t = s - layer;
+    // workgroup ids are dealt round-robin over the 8 XCDs (grid1 is a multiple of 8): the row tiles of one unit tile, which share its
+    // weight rows, go to the same XCD's L2
+    const int per = (a.total + 7) >> 3;
+    const int w = (bid & 7) * per + (bid >> 3);
+    if (w >= a.total) return;
+    const int nt = a.n_t[t];
+    const int j = w / a.tiles_m, m0 = (w - j * a.tiles_m) * LSTM_BM;
+    if (m0 >= nt) return;                      // (uniform: before any barrier)
+
+    const int H = a.H, in = layer ? H : a.emb;
+    // (the two layers' entries of lstm_packed by selects: a runtime index into that struct would cost a private copy of it)
+    const int kx = pad_to(in, GEMM_BK), kp = kx + pad_to(H, GEMM_BK);
+    const size_t blk = (size_t)((H + LSTM_BU - 1) / LSTM_BU) * 4 * LSTM_BU;                // weight rows of a layer = floats of its bias block
+    const size_t w_floats = blk * kp;
+    const float* packed = a.packed + (layer ? blk * (pad_to(a.emb, GEMM_BK) + pad_to(H, GEMM_BK)) + blk : 0);
+    // (selects, not indexing: a runtime index into the argument struct would cost a private copy of it)
+    float* const hl0 = layer ? a.h[1][0] : a.h[0][0];
+    float* const hl1 = layer ? a.h[1][1] : a.h[0][1];
+    const float* h_prev = (t & 1) ? hl0 : hl1;
+    float* h_next = (t & 1) ? hl1 : hl0;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 15, lk = lane >> 4;
+    const int wr = wave >> 1, wu = wave & 1;   // wave tile: rows 32 wr .. + 32, units 16 wu .. + 16
+    const int c4 = 4 * (tid & 7), lr = tid >> 3;
+    const int sc4 = 4 * ((tid & 7) ^ ((lr >> 1) & 7));                       // where the loader's quad goes in its LDS rows (lr + 32 i)
+
+    // loader: thread owns column quad c4 of tile rows lr + 32 i (2 of the A tile, 4 of the weight tile)
+    const float* xptr[2]; const float* hptr[2]; const float* bptr[4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int row = min(m0 + lr + 32 * i, nt - 1);                       // rows beyond n_t: clamped here, never stored
+        if (layer == 0) {
+            int wid = a.wids[(size_t)a.perm[row] * a.T + t];
+            wid = min(max(wid, 0), a.V1 - 1);                                // an id out of range is never an address (k_lstm_plan flags it)
+            xptr[i] = a.E + (size_t)wid * a.emb;
+        } else {
+            xptr[i] = ((t & 1) ? a.h[0][1] : a.h[0][0]) + (size_t)row * H;                       // layer 0's h_t, written by the previous launch
+        }
+        hptr[i] = h_prev + (size_t)row * H;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bptr[i] = packed + ((size_t)j * 4 * LSTM_BU + lr + 32 * i) * kp + c4;
+    const int nx = kx / GEMM_BK, ns = nx + (t > 0 ? (kp - kx) / GEMM_BK : 0);
+
+    f32x4 va[2], vb[4];
+    auto issue = [&](int ks) __attribute__((always_inline)) {
+        const bool ish = ks >= nx;
+        const int k = (ish ? ks - nx : ks) * GEMM_BK + c4, cols = ish ? H : in;
+        if (k - c4 + GEMM_BK <= cols) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) va[i] = *(const f32x4u*)((ish ? hptr[i] : xptr[i]) + k);
+        } else {                               // the ragged last k-step of a segment: guarded, zero filled
+#pragma unroll
+            for (int i = 0; i < 2; ++i) va[i] = load4(ish ? hptr[i] : xptr[i], k, cols);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) vb[i] = *(const f32x4*)(bptr[i] + ks * GEMM_BK);
+    };
+    auto store = [&](int buf, int ks) __attribute__((always_inline)) {
+        if (layer == 0 && ks < nx) {           // x = tanh(E[wid]); tanh(0) = 0 keeps the zero fill
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) va[i][e] = tanhf(va[i][e]);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) *(f32x4*)(&lds[buf][(lr + 32 * i) * LSTM_P + sc4]) = va[i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) *(f32x4*)(&lds[buf][(LSTM_BM + lr + 32 * i) * LSTM_P + sc4]) = vb[i];
+    };
+
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[4][2] = {{zero, zero}, {zero, zero}, {zero, zero}, {zero, zero}};     // [gate i f g o][row half]
+    // MFMA (tt, e) takes k = 8 tt + 2 lk + e from lane group lk for both operands (ncx_gemm.h): logical quad 2 tt + (lk >> 1) of a
+    // fragment row, whose swizzle key is (li >> 1) & 7 (every fragment starts at a multiple of 16 rows)
+    int co[GEMM_BK / 8];
+#pragma unroll
+    for (int tt = 0; tt < GEMM_BK / 8; ++tt) co[tt] = 4 * ((2 * tt + (lk >> 1)) ^ ((li >> 1) & 7)) + ((2 * lk) & 3);
+    auto compute = [&](int buf) __attribute__((always_inline)) {
+        const float* pa = &lds[buf][(32 * wr + li) * LSTM_P];
+        const float* pb = &lds[buf][(LSTM_BM + 16 * wu + li) * LSTM_P];
+#pragma unroll
+        for (int tt = 0; tt < GEMM_BK / 8; ++tt) {
+            const f32x2 a0 = *(const f32x2*)(pa + co[tt]), a1 = *(const f32x2*)(pa + 16 * LSTM_P + co[tt]);
+            f32x2 b[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) b[g] = *(const f32x2*)(pb + g * LSTM_BU * LSTM_P + co[tt]);
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    acc[g][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[e], b[g][e], acc[g][0], 0, 0, 0);
+                    acc[g][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[e], b[g][e], acc[g][1], 0, 0, 0);
+                }
+        }
+    };
+
+    // register-staged double-buffered LDS, one barrier per k-step: the loads of step ks + 1 fly over the MFMAs of step ks
+    issue(0); store(0, 0);
+    __syncthreads();
+    int buf = 0;
+    for (int ks = 0; ks < ns; ++ks) {
+        const bool more = ks + 1 < ns;
+        if (more) issue(ks + 1);
+        compute(buf);
+        if (more) store(buf ^ 1, ks + 1);
+        __syncthreads();
+        buf ^= 1;
+    }
+
+    // epilogue: C layout col = lane & 15 (unit), row = 4 (lane >> 4) + reg
+    const int ul = 16 * wu + li, unit = j * LSTM_BU + ul;
+    if (unit >= H) return;
+    const float* bias = packed + w_floats + (size_t)j * 4 * LSTM_BU + ul;
+    const float b_i = bias[0], b_f = bias[LSTM_BU], b_g = bias[2 * LSTM_BU], b_o = bias[3 * LSTM_BU];
+    float* cbuf = layer ? a.c[1] : a.c[0];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int row = m0 + 32 * wr + 16 * i + 4 * lk + e;
+            if (row >= nt) continue;
+            const size_t at = (size_t)row * H + unit;
+            const float gi = 1.f / (1.f + expf(-(acc[0][i][e] + b_i)));
+            const float gf = 1.f / (1.f + expf(-(acc[1][i][e] + b_f)));
+            const float gg = tanhf(acc[2][i][e] + b_g);
+            const float go = 1.f / (1.f + expf(-(acc[3][i][e] + b_o)));
+            const float cp = t > 0 ? cbuf[at] : 0.f;                         // step 0 never reads the workspace
+            const float cn = gf * cp + gi * gg;
+            const float hn = go * tanhf(cn);
+            cbuf[at] = cn;
+            h_next[at] = hn;
+            if (t == a.lens[row] - 1) a.q[(size_t)a.perm[row] * (2 * (size_t)H) + (size_t)layer * H + unit] = hn;
+        }
+}
+
+extern "C" {
+struct Lstm2Layout { size_t perm, lens, lens_tmp, n_t, h[2][2], c[2], total; };
+
+static bool lstm2_dims_ok(long long B, long long T, long long emb, long long H) {
+    // gru_dims_ok bounds B T, the widths and one layer's grid; the launch holds two layers
+    return gru_dims_ok(B, T, emb, H) && 2 * 8 * cdiv(cdiv(B, LSTM_BM) * cdiv(H, LSTM_BU), 8) < (1ll << 30);
+}
+
+static Lstm2Layout lstm2_layout(int B, int H) {
+    Lstm2Layout w{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+    w.perm = take((size_t)B * 4); w.lens = take((size_t)B * 4); w.lens_tmp = take((size_t)B * 4); w.n_t = take(LSTM_MAX_T * 4);
+    for (int l = 0; l < 2; ++l) {
+        w.h[l][0] = take((size_t)B * H * 4); w.h[l][1] = take((size_t)B * H * 4); w.c[l] = take((size_t)B * H * 4);
+    }
+    w.total = off;
+    return w;
+}
+
+size_t ncx_lstm2_packed_bytes(int32_t emb, int32_t H) {
+    if (!lstm2_dims_ok(1, 1, emb, H)) return 0;
+    return lstm_packed(emb, H).floats * 4;
+}
+
+size_t ncx_lstm2_workspace_bytes(int32_t B, int32_t T, int32_t emb, int32_t H) {
+    if (!lstm2_dims_ok(B, T, emb, H)) return 0;
+    return lstm2_layout(B, H).total;
+}
+
+int ncx_lstm2_pack(const float* w_ih0, const float* w_hh0, const float* b_ih0, const float* b_hh0, const float* w_ih1, const float* w_hh1,
+                   const float* b_ih1, const float* b_hh1, int32_t emb, int32_t H, float* packed, void* stream) {
+    if (!w_ih0 || !w_hh0 || !b_ih0 || !b_hh0 || !w_ih1 || !w_hh1 || !b_ih1 || !b_hh1 || !packed || ((uintptr_t)packed & 15)) return -1;
+    if (!lstm2_dims_ok(1, 1, emb, H)) return -1;
+    const size_t n = lstm_packed(emb, H).floats;
+    if (cdiv((long long)n, 256) >= (1ll << 31)) return -1;
+    hipLaunchKernelGGL(k_lstm_pack, dim3((unsigned)cdiv((long long)n, 256)), dim3(256), 0, (hipStream_t)stream, LstmW{w_ih0, w_hh0, b_ih0, b_hh0},
+                       LstmW{w_ih1, w_hh1, b_ih1, b_hh1}, emb, H, packed);
+    NCX_HIP_TRY(hipGetLastError());
+    return NCX_OK;
+}
+
+int ncx_lstm2_encode(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t emb, int32_t H, const float* packed,
+                     void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream) {
+    if (!wids || !E || !packed || !workspace || !q_out || !bad_id_flag) return -1;
+    if (!lstm2_dims_ok(B, T, emb, H) || V1 < 1 || ((uintptr_t)packed & 15)) return -1;
+    const Lstm2Layout w = lstm2_layout(B, H);
+    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    LstmStep a{};
+    a.wids = wids; a.E = E; a.packed = packed;
+    a.perm = (int*)(ws + w.perm); a.lens = (int*)(ws + w.lens); a.n_t = (int*)(ws + w.n_t);
+    for (int l = 0; l < 2; ++l) { a.h[l][0] = (float*)(ws + w.h[l][0]); a.h[l][1] = (float*)(ws + w.h[l][1]); a.c[l] = (float*)(ws + w.c[l]); }
+    a.q = q_out; a.T = T; a.V1 = V1; a.emb = emb; a.H = H;
+    a.tiles_m = (int)cdiv(B, LSTM_BM); a.total = a.tiles_m * (int)cdiv(H, LSTM_BU); a.grid1 = (int)(8 * cdiv(a.total, 8));
+    hipLaunchKernelGGL(k_lstm_plan, dim3(1), dim3(256), 0, st, wids, B, T, V1, (int*)a.perm, (int*)a.lens, (int*)(ws + w.lens_tmp), (int*)a.n_t,
+                       (int*)bad_id_flag);
+    NCX_HIP_TRY(hipGetLastError());
+    for (int s = 0; s <= T; ++s) {             // every launch is issued: how many rows a step has is known on the device only
+        const int layers = (s < T) + (s >= 1);
+        hipLaunchKernelGGL(k_lstm_step, dim3((unsigned)(layers * a.grid1)), dim3(256), 0, st, a, s, s < T ? 0 : 1);
+        NCX_HIP_TRY(hipGetLastError());
+    }
+    return NCX_OK;
+}
+}  // extern "C"

@@ -605,6 +605,117 @@ def check_gru_ids(bad_flag: Optional[torch.Tensor] = None, device=None) -> None:
         raise IndexError("question_wids outside [0, V + 1) in a gru_encode call")
 
 
+# ---- the two-layer LSTM question encoder (include/neuralcx.h: ncx_lstm2_*) ----------------------------------------------------------
+LSTM_KEYS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+
+
+def _lstm_layer_layout(w_ih, w_hh, b_ih, b_hh):
+    H, n_in = w_hh.shape[1], w_ih.shape[1]
+    kx, nj = _pad32(n_in), (H + GRU_UNITS - 1) // GRU_UNITS
+    W = torch.zeros(nj * GRU_UNITS, 4, kx + _pad32(H), dtype=torch.float32, device=w_ih.device)
+    W[:H, :, :n_in] = w_ih.detach().float().view(4, H, n_in).transpose(0, 1)
+    W[:H, :, kx:kx + H] = w_hh.detach().float().view(4, H, H).transpose(0, 1)
+    b = torch.zeros(nj * GRU_UNITS, 4, dtype=torch.float32, device=w_ih.device)
+    b[:H] = (b_ih.detach().float() + b_hh.detach().float()).view(4, H).t()
+    return torch.cat([W.view(nj, GRU_UNITS, 4, -1).transpose(1, 2).reshape(-1), b.view(nj, GRU_UNITS, 4).transpose(1, 2).reshape(-1)])
+
+
+def lstm_pack_layout(layer0, layer1) -> torch.Tensor:
+    """The packed layout of ncx_lstm2_pack restated with tensor ops (any device; what a test compares the kernel against).  layer0 and
+    layer1 are (w_ih, w_hh, b_ih, b_hh) of rnn_0 and rnn_1, gate blocks i | f | g | o:
+    layer 0 | layer 1, layer l = W [nj][4][32][kp_l] | bias [nj][4][32] (b_ih + b_hh), kp_l = pad32(in_l) + pad32(H), zero padded."""
+    return torch.cat([_lstm_layer_layout(*layer0), _lstm_layer_layout(*layer1)])
+
+
+def lstm_unpack_layout(packed: torch.Tensor, emb: int, H: int):
+    """-> ((w_ih, w_hh, b) of layer 0, (w_ih, w_hh, b) of layer 1) read back out of the packed layout; b = b_ih + b_hh [4 H]."""
+    nj, out, off = (H + GRU_UNITS - 1) // GRU_UNITS, [], 0
+    for n_in in (emb, H):
+        kx = _pad32(n_in)
+        kp = kx + _pad32(H)
+        nw, nb = nj * 4 * GRU_UNITS * kp, nj * 4 * GRU_UNITS
+        W = packed[off:off + nw].view(nj, 4, GRU_UNITS, kp).transpose(1, 2).reshape(nj * GRU_UNITS, 4, kp)[:H]
+        b = packed[off + nw:off + nw + nb].view(nj, 4, GRU_UNITS).transpose(1, 2).reshape(nj * GRU_UNITS, 4)[:H]
+        out.append((W[:, :, :n_in].transpose(0, 1).reshape(4 * H, n_in), W[:, :, kx:kx + H].transpose(0, 1).reshape(4 * H, H), b.t().reshape(-1)))
+        off += nw + nb
+    return tuple(out)
+
+
+class LstmWeights:
+    """A TwoLSTM's frozen parameters as ncx_lstm2_encode wants them: the embedding table E [V + 1, emb] (the parameter itself when it
+    is contiguous fp32; tanh is taken in the kernel's loader) and both layers' weights in the packed layout (ncx_lstm2_pack on the device;
+    for a CPU encoder lstm_pack_layout, for inspection and tests only).  Built once per weight set; TwoLSTM rebuilds it when a
+    parameter changes."""
+
+    def __init__(self, encoder):
+        r0, r1 = encoder.rnn_0, encoder.rnn_1
+        for r in (r0, r1):
+            if not isinstance(r, torch.nn.LSTM) or r.num_layers != 1 or r.bidirectional or not r.bias or not r.batch_first or r.proj_size:
+                raise _lib.NcxError("ncx_lstm2_encode takes two one-layer unidirectional batch_first nn.LSTMs with biases")
+        if r0.hidden_size != r1.hidden_size or r1.input_size != r0.hidden_size:
+            raise _lib.NcxError("ncx_lstm2_encode takes rnn_1 = LSTM(H -> H) on rnn_0 = LSTM(emb -> H)")
+        E = encoder.embedding.weight.detach()
+        ws = [getattr(r, k).detach() for r in (r0, r1) for k in LSTM_KEYS]
+        if any(t.dtype != torch.float32 for t in [E] + ws):
+            raise _lib.NcxError("ncx_lstm2_encode takes fp32 parameters")
+        self.E = E.contiguous()
+        self.V1, self.emb = self.E.shape
+        self.H = r0.hidden_size
+        if r0.input_size != self.emb:
+            raise _lib.NcxError("rnn_0 takes %d inputs, the embedding gives %d" % (r0.input_size, self.emb))
+        nbytes = _lib.lib().ncx_lstm2_packed_bytes(self.emb, self.H)
+        if nbytes == 0:
+            raise _lib.NcxError("ncx_lstm2_pack: dims out of range (emb %d, H %d)" % (self.emb, self.H))
+        if self.E.is_cuda:
+            ws = [t.contiguous() for t in ws]
+            self.packed = torch.empty(nbytes // 4, dtype=torch.float32, device=self.E.device)
+            with torch.cuda.device(self.E.device):
+                _lib.check(_lib.lib().ncx_lstm2_pack(*[_ptr(t, torch.float32, "lstm weight") for t in ws], self.emb, self.H,
+                                                     C.c_void_p(self.packed.data_ptr()), _stream()), "ncx_lstm2_pack")
+        else:
+            self.packed = lstm_pack_layout(ws[:4], ws[4:])
+            assert self.packed.numel() * 4 == nbytes
+        self.t = {"E": self.E, "packed": self.packed}
+
+    def unpack(self):
+        return lstm_unpack_layout(self.packed, self.emb, self.H)
+
+
+def lstm_weights(encoder) -> LstmWeights:
+    """The weights object of the HIP question encoder for a TwoLSTM (vqa/models/seq2vec.py)."""
+    return LstmWeights(encoder)
+
+
+def lstm_encode(wids: torch.Tensor, lw: LstmWeights, bad_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The two-layer LSTM question encoder (ncx_lstm2_encode; TwoLSTM.forward in eval mode) on the current stream, no host sync: wids
+    [B, T] -> q [B, 2 H], layer 0's and layer 1's hidden state after each question's last word.  len = the number of nonzero ids, T for
+    an all-padding row; padded steps are not computed.  A word id outside [0, V + 1) is never used as an address; it sets `bad_flag`
+    (default: gru_bad_flag(device), the flag check_gru_ids reads)."""
+    if wids.dim() != 2:
+        raise ValueError("wids must be [B, T], got %s" % (tuple(wids.shape),))
+    if wids.is_floating_point():
+        raise TypeError("wids must be an integer tensor, got %s" % wids.dtype)
+    B, T = wids.shape
+    if B < 1 or not 1 <= T <= 64:
+        raise ValueError("lstm_encode takes B >= 1 questions of 1 <= T <= 64 steps, got [%d, %d]" % (B, T))
+    dev = wids.device
+    if lw.packed.device != dev:
+        raise _lib.NcxError("wids are on %s, the encoder's weights on %s" % (dev, lw.packed.device))
+    wids = wids.to(torch.int32).contiguous()
+    if bad_flag is None:
+        bad_flag = gru_bad_flag(dev)
+    n = _lib.lib().ncx_lstm2_workspace_bytes(B, T, lw.emb, lw.H)
+    if n == 0:
+        raise _lib.NcxError("ncx_lstm2_workspace_bytes: dims out of range")
+    ws = torch.empty(n + 256, dtype=torch.uint8, device=dev)
+    p, n = _ws_ptr(ws)
+    q = torch.empty(B, 2 * lw.H, dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().ncx_lstm2_encode(_ptr(wids, torch.int32, "wids"), B, T, _ptr(lw.E, torch.float32, "E"), lw.V1, lw.emb, lw.H,
+                                           _ptr(lw.packed, torch.float32, "packed"), p, n, C.c_void_p(q.data_ptr()),
+                                           _ptr(bad_flag, torch.int32, "bad_flag"), _stream()), "ncx_lstm2_encode")
+    return q
+
+
 # ---- training the question encoder (include/neuralcx.h: ncx_gru_train_*, ncx_gru_pack_t) -----------------------------------------
 GRU_T_ROWS = 64         # output columns per workgroup of the backward's products: the rows of the transposed pack come in whole tiles
 
