@@ -448,6 +448,46 @@ size_t ncx_lstm2_workspace_bytes(int32_t B, int32_t T, int32_t emb, int32_t H);
 int ncx_lstm2_encode(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t emb, int32_t H, const float* packed,
                      void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream);
 
+/* ---- training the two-layer LSTM question encoder: backward through time (csrc/ncx_lstm_train.hip) ----------------------------------
+ * Take the role of torch autograd through TwoLSTM.forward below its dropout (seq2vec.py:48-76: tanh(embedding), rnn_0, rnn_1, and the
+ * selection of process_lengths + select_last, seq2vec.py:11-25); torch walks all T steps of every row forward and backward, these entries
+ * walk the valid (row, t) pairs only.  len_b, the sorted row order (perm) and n_t as ncx_lstm2_encode; per layer l, for t from len_b - 1
+ * down to 0, on the rows still inside their question:
+ *   dh^l_t = [t == len_b - 1] dq_out[b, l H : (l + 1) H] + da^l_{t+1} . W_hh^l  (+ da^1_t . W_ih^1 when l == 0)
+ *   dc_t   = dc_{t+1} f_{t+1} + dh_t o_t (1 - tanh(c_t)^2)
+ *   da_o = dh_t tanh(c_t) o (1 - o);  da_i = dc_t g i (1 - i);  da_g = dc_t i (1 - g^2);  da_f = dc_t c_{t-1} f (1 - f)      c_{-1} = 0
+ *   dW_ih^l = sum da^l_t^T x^l_t;  dW_hh^l = sum_{t >= 1} da^l_t^T h^l_{t-1};  db_ih^l = db_hh^l = sum da^l_t
+ *   dX_t = da^0_t . W_ih^0;  dE[w] = (sum over the valid pairs with id w of dX_t) (1 - tanh(E[w])^2)
+ * An all-padding row runs its T steps on E[0] and its weight gradients count; a zero id inside a question is stepped over like any word.
+ * dE[0] is ZERO whatever read E[0] in the forward (nn.Embedding(padding_idx=0)).  Where no recurrent product ran (all lengths 1, or
+ * T == 1) dW_hh^0 and dW_hh^1 are exactly 0; dW_ih^1 is not.  No atomics: bit-identical from run to run.  -1 for ANY invalid argument;
+ * emb, H, B, V1 >= 1, 1 <= T <= 64.
+ *
+ * Workspace of one training step (256-byte aligned; 0 for invalid dims): the length plan, the word id of every valid pair, and per layer
+ * the stash, laid out [T][B] in the plan's sorted row order: h_t [H]; c_t [H]; the gates i | f | g | o [4][Hp]; the gate gradients da_i |
+ * da_f | da_g | da_o [4][Hp] (Hp = pad32(H), pad columns zero); dc_t f_t [B][H]; and dX [T][B][emb]. */
+size_t ncx_lstm2_train_workspace_bytes(int32_t B, int32_t T, int32_t emb, int32_t H);
+/* The backward's packed operands: rnn_0's weight_ih_l0, weight_hh_l0 and rnn_1's (seq2vec.py:86-89, as for ncx_lstm2_pack) with the
+ * contraction over the 4 H gate rows contiguous, once per weight set (16-byte aligned; ncx_lstm2_packed_t_bytes is 0 for invalid dims):
+ *   P0 [pad64(H)][8 Hp] | P1 [pad64(H)][4 Hp] | PX [pad64(emb)][4 Hp]
+ *   P0[j][g Hp + u] = W_hh^0[g H + u][j],  P0[j][4 Hp + g Hp + u] = W_ih^1[g H + u][j],  P1[j][g Hp + u] = W_hh^1[g H + u][j],
+ *   PX[c][g Hp + u] = W_ih^0[g H + u][c];  zero where u >= H or the row does not exist. */
+size_t ncx_lstm2_packed_t_bytes(int32_t emb, int32_t H);
+int ncx_lstm2_pack_t(const float* w_ih0, const float* w_hh0, const float* w_ih1, const float* w_hh1, int32_t emb, int32_t H, float* packed_t,
+                     void* stream);
+/* ncx_lstm2_encode's arguments, plan and step kernel (seq2vec.py:11-25, 61-76), the kernel instantiated with a flag that also writes h_t, c_t
+ * and the four activated gates of every valid (row, t) pair of both layers to the stash.  q_out is bit-identical to ncx_lstm2_encode's. */
+int ncx_lstm2_train_forward(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t emb, int32_t H, const float* packed,
+                            void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream);
+/* Takes the role of loss.backward() below q = seq2vec(wids) (torch's LSTM, tanh, embedding and index backward; seq2vec.py:61-76).
+ * `workspace` as the forward of the same wids left it; dq_out [B, 2 H] in the input row order.  Outputs in torch's layouts: dW_ih0 [4 H,
+ * emb], dW_hh0, dW_ih1, dW_hh1 [4 H, H], the four db [4 H], dE [V1, emb]; every element of every output is written.  dE == NULL: a fixed
+ * embedding, the dX product and the scatter are skipped and the other eight gradients are unchanged.  A word id outside [0, V1) was
+ * flagged by the forward; here it is never used as an address either (its pair reads a clamped row of E and is left out of the dE sums). */
+int ncx_lstm2_train_backward(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t emb, int32_t H, const float* packed_t,
+                             void* workspace, size_t workspace_bytes, const float* dq_out, float* dW_ih0, float* dW_hh0, float* db_ih0,
+                             float* db_hh0, float* dW_ih1, float* dW_hh1, float* db_ih1, float* db_hh1, float* dE /*nullable*/, void* stream);
+
 /* ---- the trainable scorers LinearContext and PairwiseLinearModel (reference vqa/models/cx.py:139-156, 379-425) ---------
  * Both train with the library's loss (ncx_loss_rank) and optimiser (ncx_adam_step): forward -> scores, ncx_loss_rank ->
  * dscores, backward -> gradients (the reference's loop, counterexamples.py:330-339).  Neither model has dropout.

@@ -1,6 +1,6 @@
 // ncx_lstm.hip -- the two-layer LSTM question encoder (TwoLSTM in eval mode: tanh(embedding) -> LSTM -> LSTM -> both layers' hidden
 // state at the last valid step, side by side): ncx_lstm2_packed_bytes, ncx_lstm2_pack, ncx_lstm2_workspace_bytes, ncx_lstm2_encode.
-// Forward only.
+// The training forward (ncx_lstm_train.hip) is the same step kernel with KEEP = true.
 //
 // Reference: vqa/models/seq2vec.py -- process_lengths + select_last (11-25), TwoLSTM (48-76), factory's `2-lstm` branch (86-89).
 // Semantics, gate order i, f, g, o as torch.nn.LSTM, the recurrence over TIME (batch_first; DESIGN 5n on why not as written):
@@ -16,7 +16,7 @@
 //                i, f, g, o weight rows of THOSE units side by side; one accumulator per gate (x and h share it); the epilogue does the cell
 //                arithmetic from registers, updates c in place, writes h_t (double buffered) and q[perm[row]] when t == len_row - 1.
 //                Layer 0 gathers E[wid] on the load side and takes tanh on the way from registers to LDS.
-#include "ncx_gru.h"
+#include "ncx_lstm.h"
 
 using namespace ncx;
 
@@ -25,7 +25,6 @@ namespace {
 // of a ds_read_b64 fragment read (16 rows, one logical quad, two 8-byte halves) then covers all 64 banks once, as the padded pitch
 // of 36 (ncx_gru.hip) does, and the two buffers take 48 KB instead of 54: three workgroups fit a CU's LDS, not two.
 constexpr int LSTM_P = GEMM_BK;
-constexpr int LSTM_BM = GRU_BM, LSTM_BU = GRU_BU, LSTM_MAX_T = GRU_MAX_T;
 constexpr int LSTM_TILE_ROWS = LSTM_BM + 4 * LSTM_BU;
 
 // packed = layer 0 | layer 1;  layer l = W [nj][4 gates][32 units][kp_l] | bias [nj][4][32 units] (b_ih + b_hh)
@@ -121,7 +120,10 @@ __global__ __launch_bounds__(256) void k_lstm_plan(const int* __restrict__ wids,
 }
 
 // grid = (layers of this launch) x grid1; workgroups [0, grid1) run layer `layer_base`, [grid1, 2 grid1) layer 1
-__global__ __launch_bounds__(256) void k_lstm_step(LstmStep a, int s, int layer_base) {
+// KEEP (the training forward, ncx_lstm_train.hip): the same step; h_{t-1} / c_{t-1} are read from and h_t / c_t written to the [T][B]
+// stash instead of the alternating buffers, and the epilogue also leaves the four activated gates of every valid (row, t) pair there.
+template <bool KEEP>
+__global__ __launch_bounds__(256) void k_lstm_step(LstmStep a, int s, int layer_base, LstmKeep<KEEP> keep) {
     __shared__ __attribute__((aligned(16))) float lds[2][LSTM_TILE_ROWS * LSTM_P];
     const int second = (int)blockIdx.x >= a.grid1;
     const int layer = layer_base + second, bid = (int)blockIdx.x - second * a.grid1;
@@ -146,6 +148,11 @@ __global__ __launch_bounds__(256) void k_lstm_step(LstmStep a, int s, int layer_
     float* const hl1 = layer ? a.h[1][1] : a.h[0][1];
     const float* h_prev = (t & 1) ? hl0 : hl1;
     float* h_next = (t & 1) ? hl1 : hl0;
+    if constexpr (KEEP) {
+        const size_t hs = (size_t)keep.B * a.H;
+        float* const hst = layer ? keep.h1 : keep.h0;
+        h_prev = hst + (size_t)(t > 0 ? t - 1 : 0) * hs; h_next = hst + (size_t)t * hs;
+    }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lk = lane >> 4;
     const int wr = wave >> 1, wu = wave & 1;   // wave tile: rows 32 wr .. + 32, units 16 wu .. + 16
@@ -162,7 +169,8 @@ __global__ __launch_bounds__(256) void k_lstm_step(LstmStep a, int s, int layer_
             wid = min(max(wid, 0), a.V1 - 1);                                // an id out of range is never an address (k_lstm_plan flags it)
             xptr[i] = a.E + (size_t)wid * a.emb;
         } else {
-            xptr[i] = ((t & 1) ? a.h[0][1] : a.h[0][0]) + (size_t)row * H;                       // layer 0's h_t, written by the previous launch
+            if constexpr (KEEP) xptr[i] = keep.h0 + ((size_t)t * keep.B + row) * H;
+            else xptr[i] = ((t & 1) ? a.h[0][1] : a.h[0][0]) + (size_t)row * H;                  // layer 0's h_t, written by the previous launch
         }
         hptr[i] = h_prev + (size_t)row * H;
     }
@@ -242,6 +250,12 @@ __global__ __launch_bounds__(256) void k_lstm_step(LstmStep a, int s, int layer_
     const float* bias = packed + w_floats + (size_t)j * 4 * LSTM_BU + ul;
     const float b_i = bias[0], b_f = bias[LSTM_BU], b_g = bias[2 * LSTM_BU], b_o = bias[3 * LSTM_BU];
     float* cbuf = layer ? a.c[1] : a.c[0];
+    const float* cprev = cbuf;
+    if constexpr (KEEP) {
+        const size_t hs = (size_t)keep.B * H;
+        float* const cst = layer ? keep.c1 : keep.c0;
+        cprev = cst + (size_t)(t > 0 ? t - 1 : 0) * hs; cbuf = cst + (size_t)t * hs;
+    }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -253,22 +267,56 @@ __global__ __launch_bounds__(256) void k_lstm_step(LstmStep a, int s, int layer_
             const float gf = 1.f / (1.f + expf(-(acc[1][i][e] + b_f)));
             const float gg = tanhf(acc[2][i][e] + b_g);
             const float go = 1.f / (1.f + expf(-(acc[3][i][e] + b_o)));
-            const float cp = t > 0 ? cbuf[at] : 0.f;                         // step 0 never reads the workspace
+            const float cp = t > 0 ? cprev[at] : 0.f;                        // step 0 never reads the workspace
             const float cn = gf * cp + gi * gg;
             const float hn = go * tanhf(cn);
             cbuf[at] = cn;
             h_next[at] = hn;
             if (t == a.lens[row] - 1) a.q[(size_t)a.perm[row] * (2 * (size_t)H) + (size_t)layer * H + unit] = hn;
+            if constexpr (KEEP) {
+                float* g = (layer ? keep.g1 : keep.g0) + ((size_t)t * keep.B + row) * (4 * (size_t)keep.Hp) + unit;
+                g[0] = gi; g[keep.Hp] = gf; g[2 * keep.Hp] = gg; g[3 * keep.Hp] = go;
+            }
         }
 }
 
-extern "C" {
-struct Lstm2Layout { size_t perm, lens, lens_tmp, n_t, h[2][2], c[2], total; };
-
-static bool lstm2_dims_ok(long long B, long long T, long long emb, long long H) {
+namespace ncx {
+bool lstm2_dims_ok(long long B, long long T, long long emb, long long H) {
     // gru_dims_ok bounds B T, the widths and one layer's grid; the launch holds two layers
     return gru_dims_ok(B, T, emb, H) && 2 * 8 * cdiv(cdiv(B, LSTM_BM) * cdiv(H, LSTM_BU), 8) < (1ll << 30);
 }
+
+static LstmStep lstm2_step_args(const int32_t* wids, int B, int T, const float* E, int V1, int emb, int H, const float* packed, const Lstm2Plan& p,
+                                float* q_out) {
+    LstmStep a{};
+    a.wids = wids; a.E = E; a.packed = packed; a.perm = p.perm; a.lens = p.lens; a.n_t = p.n_t;
+    a.q = q_out; a.T = T; a.V1 = V1; a.emb = emb; a.H = H;
+    a.tiles_m = (int)cdiv(B, LSTM_BM); a.total = a.tiles_m * (int)cdiv(H, LSTM_BU); a.grid1 = (int)(8 * cdiv(a.total, 8));
+    return a;
+}
+
+// the plan and the T + 1 wavefront launches; KEEP: into the stash
+template <bool KEEP>
+static int lstm2_run(const int32_t* wids, int B, int T, int V1, const Lstm2Plan& p, const LstmStep& a, const LstmKeep<KEEP>& keep, int32_t* bad_id_flag,
+                     hipStream_t st) {
+    hipLaunchKernelGGL(k_lstm_plan, dim3(1), dim3(256), 0, st, wids, B, T, V1, p.perm, p.lens, p.lens_tmp, p.n_t, (int*)bad_id_flag);
+    NCX_HIP_TRY(hipGetLastError());
+    for (int s = 0; s <= T; ++s) {             // every launch is issued: how many rows a step has is known on the device only
+        const int layers = (s < T) + (s >= 1);
+        hipLaunchKernelGGL(k_lstm_step<KEEP>, dim3((unsigned)(layers * a.grid1)), dim3(256), 0, st, a, s, s < T ? 0 : 1, keep);
+        NCX_HIP_TRY(hipGetLastError());
+    }
+    return NCX_OK;
+}
+
+int lstm2_forward_keep(const int32_t* wids, int B, int T, const float* E, int V1, int emb, int H, const float* packed, const Lstm2Plan& p,
+                       const LstmKeep<true>& keep, float* q_out, int32_t* bad_id_flag, hipStream_t s) {
+    return lstm2_run<true>(wids, B, T, V1, p, lstm2_step_args(wids, B, T, E, V1, emb, H, packed, p, q_out), keep, bad_id_flag, s);
+}
+}  // namespace ncx
+
+extern "C" {
+struct Lstm2Layout { size_t perm, lens, lens_tmp, n_t, h[2][2], c[2], total; };
 
 static Lstm2Layout lstm2_layout(int B, int H) {
     Lstm2Layout w{};
@@ -310,22 +358,10 @@ int ncx_lstm2_encode(const int32_t* wids, int32_t B, int32_t T, const float* E, 
     if (!lstm2_dims_ok(B, T, emb, H) || V1 < 1 || ((uintptr_t)packed & 15)) return -1;
     const Lstm2Layout w = lstm2_layout(B, H);
     if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) return -1;
-    hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    LstmStep a{};
-    a.wids = wids; a.E = E; a.packed = packed;
-    a.perm = (int*)(ws + w.perm); a.lens = (int*)(ws + w.lens); a.n_t = (int*)(ws + w.n_t);
+    const Lstm2Plan p{(int*)(ws + w.perm), (int*)(ws + w.lens), (int*)(ws + w.lens_tmp), (int*)(ws + w.n_t)};
+    LstmStep a = lstm2_step_args(wids, B, T, E, V1, emb, H, packed, p, q_out);
     for (int l = 0; l < 2; ++l) { a.h[l][0] = (float*)(ws + w.h[l][0]); a.h[l][1] = (float*)(ws + w.h[l][1]); a.c[l] = (float*)(ws + w.c[l]); }
-    a.q = q_out; a.T = T; a.V1 = V1; a.emb = emb; a.H = H;
-    a.tiles_m = (int)cdiv(B, LSTM_BM); a.total = a.tiles_m * (int)cdiv(H, LSTM_BU); a.grid1 = (int)(8 * cdiv(a.total, 8));
-    hipLaunchKernelGGL(k_lstm_plan, dim3(1), dim3(256), 0, st, wids, B, T, V1, (int*)a.perm, (int*)a.lens, (int*)(ws + w.lens_tmp), (int*)a.n_t,
-                       (int*)bad_id_flag);
-    NCX_HIP_TRY(hipGetLastError());
-    for (int s = 0; s <= T; ++s) {             // every launch is issued: how many rows a step has is known on the device only
-        const int layers = (s < T) + (s >= 1);
-        hipLaunchKernelGGL(k_lstm_step, dim3((unsigned)(layers * a.grid1)), dim3(256), 0, st, a, s, s < T ? 0 : 1);
-        NCX_HIP_TRY(hipGetLastError());
-    }
-    return NCX_OK;
+    return lstm2_run<false>(wids, B, T, V1, p, a, LstmKeep<false>{}, bad_id_flag, (hipStream_t)stream);
 }
 }  // extern "C"

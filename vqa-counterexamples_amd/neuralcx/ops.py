@@ -839,6 +839,140 @@ def gru_train_backward(wids: torch.Tensor, gw: GruTrainWeights, ws: torch.Tensor
     return g
 
 
+# ---- training the two-layer LSTM question encoder (include/neuralcx.h: ncx_lstm2_train_*, ncx_lstm2_pack_t) ------------------------
+LSTM_GRADS = ("w_ih0", "w_hh0", "b_ih0", "b_hh0", "w_ih1", "w_hh1", "b_ih1", "b_hh1")
+
+
+def _lstm_t_block(w: torch.Tensor, H: int) -> torch.Tensor:
+    """w [4 H, n] -> [pad64(n)][4][Hp] with [j][g][u] = w[g H + u][j], zero padded."""
+    n = w.shape[1]
+    t = torch.zeros(_pad64(n), 4, _pad32(H), dtype=torch.float32, device=w.device)
+    t[:n, :, :H] = w.detach().float().view(4, H, n).permute(2, 0, 1)
+    return t
+
+
+def lstm_pack_t_layout(w_ih0: torch.Tensor, w_hh0: torch.Tensor, w_ih1: torch.Tensor, w_hh1: torch.Tensor) -> torch.Tensor:
+    """The layout of ncx_lstm2_pack_t restated with tensor ops (any device; what a test compares the kernel against): the contraction
+    runs over the 4 H gate rows, P0 [pad64(H)][8 Hp] | P1 [pad64(H)][4 Hp] | PX [pad64(emb)][4 Hp], P0[j] = W_hh^0[:, j] then W_ih^1[:, j],
+    P1[j] = W_hh^1[:, j], PX[c] = W_ih^0[:, c], each as [4 gates][Hp], Hp = pad32(H), zero padded."""
+    H = w_hh0.shape[1]
+    p0 = torch.cat([_lstm_t_block(w_hh0, H), _lstm_t_block(w_ih1, H)], 1)
+    return torch.cat([p0.reshape(-1), _lstm_t_block(w_hh1, H).reshape(-1), _lstm_t_block(w_ih0, H).reshape(-1)])
+
+
+def lstm_unpack_t_layout(packed_t: torch.Tensor, emb: int, H: int):
+    """-> (w_ih0 [4 H, emb], w_hh0, w_ih1, w_hh1 [4 H, H]) read back out of the transposed pack."""
+    Hp, rh, rx = _pad32(H), _pad64(H), _pad64(emb)
+    n0, n1 = rh * 8 * Hp, rh * 4 * Hp
+    back = lambda t, n: t[:n, :, :H].permute(1, 2, 0).reshape(4 * H, n)
+    p0 = packed_t[:n0].view(rh, 8, Hp)
+    p1 = packed_t[n0:n0 + n1].view(rh, 4, Hp)
+    px = packed_t[n0 + n1:].view(rx, 4, Hp)
+    return back(px, emb), back(p0[:, :4], H), back(p0[:, 4:], H), back(p1, H)
+
+
+class LstmTrainWeights:
+    """One weight set of the trainable TwoLSTM as ncx_lstm2_train_forward / _backward want it: E, the forward's pack (ncx_lstm2_pack) and the
+    backward's transposed pack (ncx_lstm2_pack_t).  Built from E and the eight tensors (rnn_0's w_ih, w_hh, b_ih, b_hh, then rnn_1's), on
+    their device."""
+
+    def __init__(self, E, *ws):
+        if len(ws) != 8:
+            raise ValueError("lstm_train_weights takes E and eight tensors (w_ih, w_hh, b_ih, b_hh of rnn_0, then of rnn_1), got %d" % len(ws))
+        ts = [t.detach() for t in (E,) + tuple(ws)]
+        if any(t.dtype != torch.float32 for t in ts):
+            raise _lib.NcxError("ncx_lstm2_train_* take fp32 parameters")
+        E, w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1 = ts = [t.contiguous() for t in ts]
+        H = w_hh0.shape[1] if w_hh0.dim() == 2 else -1
+        ok = E.dim() == 2 and w_ih0.dim() == 2 and tuple(w_ih0.shape) == (4 * H, E.shape[1]) and \
+            all(tuple(t.shape) == (4 * H, H) for t in (w_hh0, w_ih1, w_hh1)) and all(tuple(t.shape) == (4 * H,) for t in (b_ih0, b_hh0, b_ih1, b_hh1))
+        if not ok:
+            raise ValueError("lstm_train_weights takes E [V + 1, emb], w_ih0 [4 H, emb], w_hh0, w_ih1, w_hh1 [4 H, H] and four biases [4 H]; got %s"
+                             % ([tuple(t.shape) for t in ts],))
+        self.E = E
+        self.V1, self.emb = E.shape
+        self.H = H
+        L = _lib.lib()
+        n, nt = L.ncx_lstm2_packed_bytes(self.emb, self.H), L.ncx_lstm2_packed_t_bytes(self.emb, self.H)
+        if n == 0 or nt == 0:
+            raise _lib.NcxError("ncx_lstm2_pack_t: dims out of range (emb %d, H %d)" % (self.emb, self.H))
+        self.packed = torch.empty(n // 4, dtype=torch.float32, device=E.device)
+        self.packed_t = torch.empty(nt // 4, dtype=torch.float32, device=E.device)
+        with torch.cuda.device(E.device):
+            _lib.check(L.ncx_lstm2_pack(*[_ptr(t, torch.float32, "lstm weight") for t in ts[1:]], self.emb, self.H,
+                                        C.c_void_p(self.packed.data_ptr()), _stream()), "ncx_lstm2_pack")
+            _lib.check(L.ncx_lstm2_pack_t(*[_ptr(t, torch.float32, "lstm weight") for t in (w_ih0, w_hh0, w_ih1, w_hh1)], self.emb, self.H,
+                                          C.c_void_p(self.packed_t.data_ptr()), _stream()), "ncx_lstm2_pack_t")
+
+
+def lstm_train_weights(E, *ws) -> LstmTrainWeights:
+    return LstmTrainWeights(E, *ws)
+
+
+def _lstm_train_args(wids: torch.Tensor, lw: LstmTrainWeights, what: str):
+    if wids.dim() != 2:
+        raise ValueError("wids must be [B, T], got %s" % (tuple(wids.shape),))
+    if wids.is_floating_point():
+        raise TypeError("wids must be an integer tensor, got %s" % wids.dtype)
+    B, T = wids.shape
+    if B < 1 or not 1 <= T <= 64:
+        raise ValueError("%s takes B >= 1 questions of 1 <= T <= 64 steps, got [%d, %d]" % (what, B, T))
+    if lw.packed.device != wids.device:
+        raise _lib.NcxError("wids are on %s, the encoder's weights on %s" % (wids.device, lw.packed.device))
+    return B, T, wids.to(torch.int32).contiguous()
+
+
+def lstm_train_workspace(B: int, T: int, lw: LstmTrainWeights, device) -> torch.Tensor:
+    """The workspace of one training step (ncx_lstm2_train_workspace_bytes): the length plan and the stash the backward needs."""
+    n = _lib.lib().ncx_lstm2_train_workspace_bytes(B, T, lw.emb, lw.H)
+    if n == 0:
+        raise _lib.NcxError("ncx_lstm2_train_workspace_bytes: dims out of range")
+    return torch.empty(n + 256, dtype=torch.uint8, device=device)
+
+
+def lstm_train_forward(wids: torch.Tensor, lw: LstmTrainWeights, ws: torch.Tensor, bad_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ncx_lstm2_train_forward: lstm_encode's q [B, 2 H] (bit for bit), with the stash of the valid (row, t) pairs left in `ws`."""
+    B, T, wids = _lstm_train_args(wids, lw, "lstm_train_forward")
+    if bad_flag is None:
+        bad_flag = gru_bad_flag(wids.device)
+    p, n = _ws_ptr(ws)
+    q = torch.empty(B, 2 * lw.H, dtype=torch.float32, device=wids.device)
+    _lib.check(_lib.lib().ncx_lstm2_train_forward(_ptr(wids, torch.int32, "wids"), B, T, _ptr(lw.E, torch.float32, "E"), lw.V1, lw.emb, lw.H,
+                                                  _ptr(lw.packed, torch.float32, "packed"), p, n, C.c_void_p(q.data_ptr()),
+                                                  _ptr(bad_flag, torch.int32, "bad_flag"), _stream()), "ncx_lstm2_train_forward")
+    return q
+
+
+def lstm_train_backward(wids: torch.Tensor, lw: LstmTrainWeights, ws: torch.Tensor, dq_out: torch.Tensor, want_dE: bool = True,
+                        dE: Optional[torch.Tensor] = None, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, Optional[torch.Tensor]]:
+    """ncx_lstm2_train_backward on the workspace lstm_train_forward left for the same wids: dq_out [B, 2 H] -> {LSTM_GRADS..., "E"} in
+    torch's layouts; "E" is None when want_dE is off (a fixed embedding).  `dE`: a caller's [V + 1, emb] buffer; `out`: caller's buffers
+    for the eight weight gradients."""
+    B, T, wids = _lstm_train_args(wids, lw, "lstm_train_backward")
+    if tuple(dq_out.shape) != (B, 2 * lw.H):
+        raise ValueError("dq_out must be [%d, %d], got %s" % (B, 2 * lw.H, tuple(dq_out.shape)))
+    dev = wids.device
+    shape = {"w_ih0": (4 * lw.H, lw.emb), "w_hh0": (4 * lw.H, lw.H), "w_ih1": (4 * lw.H, lw.H), "w_hh1": (4 * lw.H, lw.H)}
+    g = {k: torch.empty(shape.get(k, (4 * lw.H,)), dtype=torch.float32, device=dev) for k in LSTM_GRADS}
+    if out is not None:
+        for k in LSTM_GRADS:
+            if tuple(out[k].shape) != tuple(g[k].shape):
+                raise ValueError("d%s must be %s, got %s" % (k, tuple(g[k].shape), tuple(out[k].shape)))
+            g[k] = out[k]
+    g["E"] = None
+    if want_dE:
+        g["E"] = dE if dE is not None else torch.empty(lw.V1, lw.emb, dtype=torch.float32, device=dev)
+        if tuple(g["E"].shape) != (lw.V1, lw.emb):
+            raise ValueError("dE must be [%d, %d], got %s" % (lw.V1, lw.emb, tuple(g["E"].shape)))
+    p, n = _ws_ptr(ws)
+    _lib.check(_lib.lib().ncx_lstm2_train_backward(_ptr(wids, torch.int32, "wids"), B, T, _ptr(lw.E, torch.float32, "E"), lw.V1, lw.emb, lw.H,
+                                                   _ptr(lw.packed_t, torch.float32, "packed_t"), p, n,
+                                                   _ptr(dq_out.float().contiguous(), torch.float32, "dq_out"),
+                                                   *[_ptr(g[k], torch.float32, "d" + k) for k in LSTM_GRADS + ("E",)], _stream()),
+               "ncx_lstm2_train_backward")
+    return g
+
+
 # ---- the trainable scorers LinearContext and PairwiseLinearModel (include/neuralcx.h) -----------------------------------------
 PAIRLIN_H = 300                     # dim_h = dim_a = 300 in the reference (cx.py:391-392)
 PAIRLIN_FIELDS = ("answer_embedding", "w", "b", "w_out", "b_out")

@@ -105,6 +105,38 @@ class GruTrainFunction(torch.autograd.Function):
         return None, g["E"], g["w_ih"], g["w_hh"], g["b_ih"], g["b_hh"], None
 
 
+class LstmTrainFunction(torch.autograd.Function):
+    """q = [h^0 | h^1] after each question's last word (TwoLSTM below its dropout) through ncx_lstm2_train_forward / _backward.
+    Inputs: wids, E, rnn_0's w_ih, w_hh, b_ih, b_hh, rnn_1's four and the encoder module, on which the packs are cached (keyed on
+    data_ptr / _version of the nine tensors, like GruTrainFunction: rebuilt after an optimizer step).  Gradients: the nine tensors;
+    None for E when it does not require grad (a fixed embedding: the dX product is skipped)."""
+
+    @staticmethod
+    def weights(module, tensors):
+        key = tuple((t.data_ptr(), t._version) for t in tensors)
+        hit = module.__dict__.get("_hip_lstm_train") if module is not None else None
+        if hit is None or hit[0] != key:
+            hit = (key, ops.lstm_train_weights(*tensors))
+            if module is not None:
+                module.__dict__["_hip_lstm_train"] = hit
+        return hit[1]
+
+    @staticmethod
+    def forward(ctx, wids, E, w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1, module=None):
+        lw = LstmTrainFunction.weights(module, (E, w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1))
+        ws = ops.lstm_train_workspace(wids.shape[0], wids.shape[1], lw, wids.device)
+        q = ops.lstm_train_forward(wids, lw, ws)
+        ctx.hip = (wids, lw, ws)
+        return q
+
+    @staticmethod
+    def backward(ctx, dq):
+        wids, lw, ws = ctx.hip
+        g = ops.lstm_train_backward(wids, lw, ws, dq, want_dE=ctx.needs_input_grad[1])
+        ctx.hip = None                                            # the stash is the step's largest buffer: let go of it here
+        return (None, g["E"]) + tuple(g[k] for k in ops.LSTM_GRADS) + (None,)
+
+
 def module_forward(model, input_v: torch.Tensor, q_emb: torch.Tensor) -> torch.Tensor:
     """The HIP route of MutanNoAtt.forward below seq2vec: the rows of input_v are the feature table, the index the identity."""
     f, opt = model.fusion, model.opt

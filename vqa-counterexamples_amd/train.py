@@ -11,7 +11,8 @@ Three routes:
                             (neuralcx.vqa_train.VqaTrainEngine, MlbTrainEngine for MLBNoAtt: forward, cross-entropy, backward, Adam).
   (default)                 the module route: the model's use_hip_train = True, the fusion and classifier run in HIP inside torch
                             autograd, the encoder trains under autograd, torch.optim.Adam steps.  With --hip_seq2vec_train the encoder's
-                            forward and backward through time run in HIP too (GRUEncoder.use_hip_train, neuralcx.vqa_train.GruTrainFunction).
+                            forward and backward through time run in HIP too (GRUEncoder.use_hip_train, neuralcx.vqa_train.GruTrainFunction);
+                            --hip_2lstm_train is the same for the 2-lstm encoder (TwoLSTM.use_hip_bptt, neuralcx.vqa_train.LstmTrainFunction).
   --no_hip                  the same loop on the plain PyTorch modules (also runs on a CPU).
 """
 import argparse
@@ -58,6 +59,7 @@ def build_parser():
     p.add_argument("--path_features", type=str, default=None, help="overrides coco.path_features of the YAML")
     p.add_argument("--freeze_seq2vec", action="store_true", help="freeze the question encoder: q_emb once per split, the whole step in HIP")
     p.add_argument("--hip_seq2vec_train", action="store_true", help="default route only: train the question encoder in HIP as well (backward through time)")
+    p.add_argument("--hip_2lstm_train", action="store_true", help="default route only: train the 2-lstm question encoder (TwoLSTM) in HIP as well (backward through time)")
     p.add_argument("--no_hip", action="store_true", help="the plain PyTorch modules (no HIP library; runs on a CPU too)")
     p.add_argument("--seed", type=int, default=1337)
     return p
@@ -114,6 +116,14 @@ class Trainer:
             raise SystemExit("train.py: --hip_seq2vec_train trains the encoder in HIP; it cannot be combined with --no_hip")
         if args.hip_seq2vec_train and args.freeze_seq2vec:
             raise SystemExit("train.py: --hip_seq2vec_train has nothing to train under --freeze_seq2vec")
+        if args.hip_2lstm_train and args.no_hip:
+            raise SystemExit("train.py: --hip_2lstm_train trains the encoder in HIP; it cannot be combined with --no_hip")
+        if args.hip_2lstm_train and args.freeze_seq2vec:
+            raise SystemExit("train.py: --hip_2lstm_train has nothing to train under --freeze_seq2vec")
+        s2v = opt["model"]["seq2vec"]
+        if args.hip_2lstm_train and not (s2v.get("arch") == "2-lstm" and "hidden_size" in s2v):       # seq2vec.factory's TwoLSTM branch
+            raise SystemExit("train.py: --hip_2lstm_train needs the 2-lstm encoder (seq2vec: {arch: 2-lstm, hidden_size: ...}); this YAML builds %r"
+                             % s2v.get("arch", "skipthoughts"))
         if not cuda and not args.no_hip:
             raise SystemExit("train.py: the HIP routes need an MI355X (use --no_hip for the PyTorch modules)")
         self.dev = torch.device("cuda:0" if cuda else "cpu")
@@ -139,14 +149,22 @@ class Trainer:
             self.model.use_hip_train = self.hip
             self.hip_seq2vec = bool(args.hip_seq2vec_train and self.hip and hasattr(type(self.model.seq2vec), "use_hip_train"))
             if args.hip_seq2vec_train and not self.hip_seq2vec:
-                raise SystemExit("train.py: --hip_seq2vec_train needs the HIP route and the GRU encoder (%s)" % self.route)
+                raise SystemExit("train.py: --hip_seq2vec_train needs the HIP route and the GRU encoder (%s); the 2-lstm encoder trains in HIP "
+                                 "with --hip_2lstm_train" % self.route)
             if self.hip_seq2vec:
                 self.model.seq2vec.use_hip_train = True
+            self.hip_2lstm = bool(args.hip_2lstm_train and self.hip and isinstance(self.model.seq2vec, models.seq2vec.TwoLSTM))
+            if args.hip_2lstm_train and not self.hip_2lstm:
+                raise SystemExit("train.py: --hip_2lstm_train needs the HIP route and the TwoLSTM encoder (%s)" % self.route)
+            if self.hip_2lstm:
+                self.model.seq2vec.use_hip_bptt = True
             self.optim = torch.optim.Adam([p_ for p_ in self.model.parameters() if p_.requires_grad], self.lr)     # train.py:143-144
             self.criterion = nn.CrossEntropyLoss()
         self.best_acc1, self.history = 0.0, []
         print("=> route: %s%s%s" % ("hip" if self.hip else self.route, " (engine: whole step in HIP)" if self.engine else "",
-                                    " (question encoder: HIP forward + backward through time)" if getattr(self, "hip_seq2vec", False) else ""), flush=True)
+                                    " (question encoder: HIP forward + backward through time)" if getattr(self, "hip_seq2vec", False) else
+                                    " (2-lstm question encoder: HIP forward + backward through time, --hip_2lstm_train)" if getattr(self, "hip_2lstm", False)
+                                    else ""), flush=True)
 
     # ---- data ------------------------------------------------------------------------------------------------
     def q_emb_of(self, split):

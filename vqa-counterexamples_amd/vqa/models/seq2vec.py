@@ -80,8 +80,12 @@ class TwoLSTM(nn.Module):
     over time, batch_first=True; that flag changes no parameter name or shape.
 
     On a CUDA device in eval mode, when no gradient can be wanted, forward runs in the HIP library (ops.lstm_encode: padded steps are
-    skipped, the two layers run as a wavefront); `use_hip = False` keeps it in PyTorch.  It trains under torch autograd."""
+    skipped, the two layers run as a wavefront); `use_hip = False` keeps it in PyTorch.  It trains under torch autograd, unless
+    `use_hip_bptt = True` (off by default; train.py --hip_2lstm_train): then a CUDA fp32 module called with grad mode on and a parameter
+    that requires grad runs neuralcx.vqa_train.LstmTrainFunction (forward with a stash, backward through time); its dropout stays in
+    torch, on the two halves in the torch path's order."""
     use_hip = True
+    use_hip_bptt = False
     p_drop = 0.3
 
     def __init__(self, vocab_words, emb_size, hidden_size):
@@ -112,11 +116,29 @@ class TwoLSTM(nn.Module):
 
     def drop_hip_weights(self):
         self.__dict__.pop("_hip_lstm", None)
+        self.__dict__.pop("_hip_lstm_train", None)
+
+    def _hip_bptt_ok(self, wids):
+        if not (self.use_hip_bptt and wids.is_cuda and wids.dim() == 2 and 1 <= wids.shape[1] <= 64 and wids.shape[0] >= 1):
+            return False
+        params = list(self.parameters())
+        if not (torch.is_grad_enabled() and any(p.requires_grad for p in params)):
+            return False
+        return all(p.dtype == torch.float32 and p.device == wids.device for p in params)
 
     def forward(self, wids):
         if self._hip_ok(wids):
             from neuralcx import ops
             return ops.lstm_encode(wids, self._hip_weights())
+        if self._hip_bptt_ok(wids):
+            from neuralcx.vqa_train import LstmTrainFunction
+            r0, r1, H = self.rnn_0, self.rnn_1, self.hidden_size
+            q = LstmTrainFunction.apply(wids, self.embedding.weight, r0.weight_ih_l0, r0.weight_hh_l0, r0.bias_ih_l0, r0.bias_hh_l0,
+                                        r1.weight_ih_l0, r1.weight_hh_l0, r1.bias_ih_l0, r1.bias_hh_l0, self)
+            # each half as a contiguous [B, H] tensor, vec_0 first: under one seed the masks are the torch path's
+            vec_0 = F.dropout(q[:, :H].contiguous(), p=self.p_drop, training=self.training)
+            vec_1 = F.dropout(q[:, H:].contiguous(), p=self.p_drop, training=self.training)
+            return torch.cat((vec_0, vec_1), 1)
         B, T = wids.shape
         n = (wids != 0).sum(1)
         last = torch.where(n > 0, n, torch.full_like(n, T)) - 1  # select_last's index len - 1; -1 is step T - 1
