@@ -1,9 +1,9 @@
 """Recipes of the GRU encoder's edge cases: shapes OFF the six that tests/test_gru_gpu.py and tests/test_gru_train_gpu.py share.  Plain
 data and numpy; tests/test_gru_edges_cpu.py checks what the table claims, tests/test_gru_edges_gpu.py runs the kernels on them.
 
-The kernels' constants the cases are placed around (csrc/ncx_gru.hip, csrc/ncx_gru_train.hip): 32-deep k-steps (dqp = dim_q rounded up
+The kernels' constants the cases are placed around (csrc/ncx_rnn.h, csrc/ncx_rnn.hip, csrc/ncx_gru.hip, csrc/ncx_gru_train.hip): 32-deep k-steps (dqp = dim_q rounded up
 to 32, kx likewise for dim_emb), 64-row x 32-unit step tiles, 64 x 64 sweep / dX tiles, 128 x 64 weight-gradient tiles over the 3 dqp
-gate rows, 256 threads in the one-workgroup length plan, GRU_MAX_T = 64, 1024 columns per pass of the embedding gradient.
+gate rows, 256 threads in the one-workgroup length plan, RNN_MAX_T = 64, 1024 columns per pass of the embedding gradient.
 
 `long` asks for every length 0 .. 64 several times over in B = 300 rows: 65 lengths fit four times (260 rows), not five (325), so each
 length is planted four times and the remaining 40 rows are uniform 1 .. 64."""
@@ -19,7 +19,7 @@ CASES = {"unit":   (1,     1,     2,   2),    # smallest legal dims; every guard
          "over64": (65,    65,    65,  4),    # one past the 64-column and the 64-row tiles
          "narrow": (5,     20,    3,   4),    # dqp = 32 < the 64-wide sweep tile; 3 dqp = 96 < the 128-row weight-gradient tile
          "wide_e": (1030,  12,    4,   3),    # the embedding gradient's second 1024-column pass; 17 dX column tiles
-         "long":   (6,     24,    300, 64),   # T = GRU_MAX_T; B > 256 (a second trip of the plan's row loop); n_t falls at every step
+         "long":   (6,     24,    300, 64),   # T = RNN_MAX_T; B > 256 (a second trip of the plan's row loop); n_t falls at every step
          "steps":  (10,    40,    65,  12)}   # n_t = 65, 64, 32, 0: one over / exactly on the row tile, on the k-step, then empty steps before T
 
 
@@ -83,7 +83,7 @@ def make(name, seed=SEED):
 
 
 def plan(wids):
-    """The device plan restated: (lens, perm, n_t) -- rows sorted by length descending, input order inside a length (k_gru_plan)."""
+    """The device plan restated: (lens, perm, n_t) -- rows sorted by length descending, input order inside a length (k_rnn_plan)."""
     from gru_ref import lengths
     lens = lengths(wids)
     perm = np.argsort(-lens, kind="stable")

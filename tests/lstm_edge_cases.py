@@ -2,9 +2,9 @@
 planted nonzero counts and the 2-lstm length rule (an all-padding row runs T steps, not one).  Plain data and numpy;
 tests/test_lstm_edges_cpu.py checks what the table claims, tests/test_lstm_edges_gpu.py runs the kernels on them.
 
-The kernels' constants the cases are placed around (csrc/ncx_lstm.hip, csrc/ncx_lstm_train.hip) are the GRU's, so no case moved: 32-deep
+The kernels' constants the cases are placed around (csrc/ncx_rnn.h, csrc/ncx_rnn.hip, csrc/ncx_lstm.hip, csrc/ncx_lstm_train.hip) are the GRU's, so no case moved: 32-deep
 k-steps (Hp = H rounded up to 32, kx likewise for emb), 64-row x 32-unit step tiles, 64 x 64 sweep / dX tiles, 128 x 64 weight-gradient
-tiles, 256 threads in the one-workgroup length plan, LSTM_MAX_T = 64, 1024 columns per pass of the embedding gradient.  One difference:
+tiles, 256 threads in the one-workgroup length plan, RNN_MAX_T = 64, 1024 columns per pass of the embedding gradient.  One difference:
 the weight-gradient tiles run over the 4 Hp gate rows, always a whole number of 128-row tiles, so `over64` has no ragged row tile there
 (the GRU's 3 dqp = 288 had); its 65 columns still give a second, one-column tile."""
 import numpy as np
@@ -19,7 +19,7 @@ from lstm_ref import lengths
 #  over64    65     65   65   4     one past the 64-column and the 64-row tiles; the all-padding row 64 sorts to the front
 #  narrow    5      20   3    4     Hp = 32 < the 64-wide sweep tile; 4 Hp = 128: one weight-gradient row tile
 #  wide_e    1030   12   4    3     the embedding gradient's second 1024-column pass; 17 dX column tiles; tanh in the dW_ih0 loader on a ragged tile
-#  long      6      24   300  64    T = LSTM_MAX_T; B > 256 (a second trip of the plan's row loop); n_t falls at every step
+#  long      6      24   300  64    T = RNN_MAX_T; B > 256 (a second trip of the plan's row loop); n_t falls at every step
 #  steps     10     40   65   12    n_t = 65, 64, 32, 0: one over / exactly on the row tile, on the k-step, then empty steps before T
 
 
@@ -39,7 +39,7 @@ def make(name, seed=SEED):
 
 
 def plan(wids):
-    """The device plan restated: (lens, perm, n_t) -- rows sorted by length descending, input order inside a length (k_lstm_plan)."""
+    """The device plan restated: (lens, perm, n_t) -- rows sorted by length descending, input order inside a length (k_rnn_plan)."""
     lens = lengths(wids)
     perm = np.argsort(-lens, kind="stable")
     n_t = np.array([(lens > t).sum() for t in range(wids.shape[1])])

@@ -8,8 +8,9 @@
 //   r = s(W_ir x + b_ir + W_hr h + b_hr);  z = s(W_iz x + b_iz + W_hz h + b_hz);  n = tanh(W_in x + b_in + r (W_hn h + b_hn))
 //   h' = (1 - z) n + z h,  h_0 = 0;  q[b] = h after step len_b - 1
 // Plan (T + 1 launches, nothing read back, no inter-workgroup wait, no atomics):
-//   k_gru_plan  one workgroup: id range check, len_b, a stable counting sort of the rows by length (descending) -> perm, and
-//               n_t = #{b : len_b > t}: the active rows of step t are the prefix [0, n_t) of the sorted order.
+//   k_rnn_plan  (ncx_rnn.hip, shared with the LSTM encoder; an all-padding row has length 1) one workgroup: id range check, len_b, a
+//               stable counting sort of the rows by length (descending) -> perm, and n_t = #{b : len_b > t}: the active rows of step t
+//               are the prefix [0, n_t) of the sorted order.
 //   k_gru_step  once per time step t, always launched; it reads n_t from memory and workgroups beyond it exit.  One launch is the
 //               GEMM  [x_t | h_{t-1}][0:n_t) . [W_ih | W_hh]^T  (K = dim_emb + dim_q; step 0 stops after the x columns: h_0 = 0) on
 //               v_mfma_f32_16x16x4_f32, the rows of E gathered by word id on the load side, so the input projection is computed
@@ -23,14 +24,14 @@ using namespace ncx;
 
 namespace {
 constexpr int GRU_P = GEMM_BK + 4;   // LDS pitch of a 32-deep k-step (conflict-free ds_read_b64 fragments, ncx_gemm.h)
-constexpr int GRU_TILE_ROWS = GRU_BM + 3 * GRU_BU;
+constexpr int GRU_TILE_ROWS = RNN_BM + 3 * RNN_BU;
 
 struct GruPacked { int kx, kp, nj; size_t w_floats, floats; };
 __host__ __device__ inline GruPacked gru_packed(int dim_emb, int dim_q) {
     GruPacked p;
-    p.kx = pad_to(dim_emb, GEMM_BK); p.kp = p.kx + pad_to(dim_q, GEMM_BK); p.nj = (dim_q + GRU_BU - 1) / GRU_BU;
-    p.w_floats = (size_t)p.nj * 3 * GRU_BU * p.kp;
-    p.floats = p.w_floats + (size_t)p.nj * 6 * GRU_BU;
+    p.kx = pad_to(dim_emb, GEMM_BK); p.kp = p.kx + pad_to(dim_q, GEMM_BK); p.nj = (dim_q + RNN_BU - 1) / RNN_BU;
+    p.w_floats = (size_t)p.nj * 3 * RNN_BU * p.kp;
+    p.floats = p.w_floats + (size_t)p.nj * 6 * RNN_BU;
     return p;
 }
 }  // namespace
@@ -46,56 +47,17 @@ __global__ __launch_bounds__(256) void k_gru_pack(const float* __restrict__ w_ih
     if (i < p.w_floats) {
         const size_t row = i / p.kp;
         const int c = (int)(i - row * p.kp);
-        const int u = (int)(row % GRU_BU), g = (int)(row / GRU_BU % 3), unit = (int)(row / (3 * GRU_BU)) * GRU_BU + u;
+        const int u = (int)(row % RNN_BU), g = (int)(row / RNN_BU % 3), unit = (int)(row / (3 * RNN_BU)) * RNN_BU + u;
         if (unit < dim_q) {
             if (c < p.kx) { if (c < dim_emb) v = w_ih[((size_t)g * dim_q + unit) * dim_emb + c]; }
             else if (c - p.kx < dim_q) v = w_hh[((size_t)g * dim_q + unit) * dim_q + (c - p.kx)];
         }
     } else {
         const size_t b = i - p.w_floats;
-        const int u = (int)(b % GRU_BU), g = (int)(b / GRU_BU % 6), unit = (int)(b / (6 * GRU_BU)) * GRU_BU + u;
+        const int u = (int)(b % RNN_BU), g = (int)(b / RNN_BU % 6), unit = (int)(b / (6 * RNN_BU)) * RNN_BU + u;
         if (unit < dim_q) v = g < 3 ? b_ih[(size_t)g * dim_q + unit] : b_hh[(size_t)(g - 3) * dim_q + unit];
     }
     packed[i] = v;
-}
-
-// One workgroup.  lens_tmp [B] is scratch; perm / lens [B] come out in sorted order (length descending, input order inside a length).
-__global__ __launch_bounds__(256) void k_gru_plan(const int* __restrict__ wids, int B, int T, int V1, int* __restrict__ perm, int* __restrict__ lens,
-                                                  int* __restrict__ lens_tmp, int* __restrict__ n_t, int* __restrict__ bad) {
-    __shared__ int cnt[GRU_MAX_T + 2], start[GRU_MAX_T + 2], sbad;
-    const int tid = threadIdx.x;
-    if (tid == 0) sbad = 0;
-    __syncthreads();
-    bool oob = false;
-    for (int b = tid; b < B; b += 256) {
-        int n = 0;
-        for (int t = 0; t < T; ++t) {
-            const int w = wids[(size_t)b * T + t];
-            oob |= w < 0 || w >= V1;
-            n += w != 0;
-        }
-        lens_tmp[b] = n > 1 ? n : 1;
-    }
-    if (oob) sbad = 1;
-    __syncthreads();
-    if (tid == 0 && sbad) *bad = 1;
-    const int L = tid + 1;                     // thread L - 1 owns the rows of length L
-    if (L <= T) {
-        int c = 0;
-        for (int b = 0; b < B; ++b) c += lens_tmp[b] == L;
-        cnt[L] = c;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int run = 0;
-        for (int l = T; l >= 1; --l) { start[l] = run; run += cnt[l]; n_t[l - 1] = run; }   // n_t[t] = #{len >= t + 1}
-    }
-    __syncthreads();
-    if (L <= T) {
-        int pos = start[L];
-        for (int b = 0; b < B; ++b)
-            if (lens_tmp[b] == L) { perm[pos] = b; lens[pos] = L; ++pos; }
-    }
 }
 
 // KEEP (the training forward, ncx_gru_train.hip): the same step; the epilogue also leaves r, z, n and hn = W_hn h + b_hn of every valid
@@ -112,7 +74,7 @@ __global__ __launch_bounds__(256) void k_gru_step(const int* __restrict__ wids, 
     const int w = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
     if (w >= total) return;
     const int nt = n_t[t];
-    const int j = w / tiles_m, m0 = (w - j * tiles_m) * GRU_BM;
+    const int j = w / tiles_m, m0 = (w - j * tiles_m) * RNN_BM;
     if (m0 >= nt) return;                      // (uniform: before any barrier)
 
     const GruPacked pk = gru_packed(dim_emb, dim_q);
@@ -127,12 +89,12 @@ __global__ __launch_bounds__(256) void k_gru_step(const int* __restrict__ wids, 
     for (int i = 0; i < 2; ++i) {
         const int row = min(m0 + lr + 32 * i, nt - 1);                       // rows beyond n_t: clamped here, never stored
         int wid = wids[(size_t)perm[row] * T + t];
-        wid = min(max(wid, 0), V1 - 1);                                      // an id out of range is never an address (k_gru_plan flags it)
+        wid = min(max(wid, 0), V1 - 1);                                      // an id out of range is never an address (k_rnn_plan flags it)
         xptr[i] = E + (size_t)wid * dim_emb;
         hptr[i] = h_prev + (size_t)row * dim_q;
     }
 #pragma unroll
-    for (int i = 0; i < 3; ++i) bptr[i] = packed + ((size_t)j * 3 * GRU_BU + lr + 32 * i) * pk.kp + c4;
+    for (int i = 0; i < 3; ++i) bptr[i] = packed + ((size_t)j * 3 * RNN_BU + lr + 32 * i) * pk.kp + c4;
     const int nx = pk.kx / GEMM_BK, ns = nx + (t > 0 ? (pk.kp - pk.kx) / GEMM_BK : 0);
 
     f32x4 va[2], vb[3];
@@ -153,7 +115,7 @@ __global__ __launch_bounds__(256) void k_gru_step(const int* __restrict__ wids, 
 #pragma unroll
         for (int i = 0; i < 2; ++i) *(f32x4*)(&lds[buf][(lr + 32 * i) * GRU_P + c4]) = va[i];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) *(f32x4*)(&lds[buf][(GRU_BM + lr + 32 * i) * GRU_P + c4]) = vb[i];
+        for (int i = 0; i < 3; ++i) *(f32x4*)(&lds[buf][(RNN_BM + lr + 32 * i) * GRU_P + c4]) = vb[i];
     };
 
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -161,12 +123,12 @@ __global__ __launch_bounds__(256) void k_gru_step(const int* __restrict__ wids, 
     // MFMA (tt, e) takes k = 8 tt + 2 lk + e from lane group lk for both operands (ncx_gemm.h)
     auto compute = [&](int buf, bool ish) __attribute__((always_inline)) {
         const float* pa = &lds[buf][(32 * wr + li) * GRU_P + 2 * lk];
-        const float* pb = &lds[buf][(GRU_BM + 16 * wu + li) * GRU_P + 2 * lk];
+        const float* pb = &lds[buf][(RNN_BM + 16 * wu + li) * GRU_P + 2 * lk];
 #pragma unroll
         for (int tt = 0; tt < GEMM_BK / 8; ++tt) {
             const f32x2 a0 = *(const f32x2*)(pa + 8 * tt), a1 = *(const f32x2*)(pa + 16 * GRU_P + 8 * tt);
-            const f32x2 br = *(const f32x2*)(pb + 8 * tt), bz = *(const f32x2*)(pb + GRU_BU * GRU_P + 8 * tt),
-                        bn = *(const f32x2*)(pb + 2 * GRU_BU * GRU_P + 8 * tt);
+            const f32x2 br = *(const f32x2*)(pb + 8 * tt), bz = *(const f32x2*)(pb + RNN_BU * GRU_P + 8 * tt),
+                        bn = *(const f32x2*)(pb + 2 * RNN_BU * GRU_P + 8 * tt);
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 acc_r[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[e], br[e], acc_r[0], 0, 0, 0);
@@ -198,10 +160,10 @@ __global__ __launch_bounds__(256) void k_gru_step(const int* __restrict__ wids, 
     }
 
     // epilogue: C layout col = lane & 15 (unit), row = 4 (lane >> 4) + reg
-    const int ul = 16 * wu + li, unit = j * GRU_BU + ul;
+    const int ul = 16 * wu + li, unit = j * RNN_BU + ul;
     if (unit >= dim_q) return;
-    const float* bias = packed + pk.w_floats + (size_t)j * 6 * GRU_BU + ul;
-    const float b_ir = bias[0], b_iz = bias[GRU_BU], b_in = bias[2 * GRU_BU], b_hr = bias[3 * GRU_BU], b_hz = bias[4 * GRU_BU], b_hn = bias[5 * GRU_BU];
+    const float* bias = packed + pk.w_floats + (size_t)j * 6 * RNN_BU + ul;
+    const float b_ir = bias[0], b_iz = bias[RNN_BU], b_in = bias[2 * RNN_BU], b_hr = bias[3 * RNN_BU], b_hz = bias[4 * RNN_BU], b_hn = bias[5 * RNN_BU];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -223,18 +185,11 @@ __global__ __launch_bounds__(256) void k_gru_step(const int* __restrict__ wids, 
 }
 
 namespace ncx {
-bool gru_dims_ok(long long B, long long T, long long dim_emb, long long dim_q) {
-    if (B < 1 || T < 1 || T > GRU_MAX_T || dim_emb < 1 || dim_q < 1) return false;
-    if (B * T >= (1ll << 31) || dim_emb >= (1 << 24) || dim_q >= (1 << 24)) return false;
-    return cdiv(B, GRU_BM) * cdiv(dim_q, GRU_BU) < (1ll << 28);        // the step launch's grid
-}
-
 // ncx_gru_encode's plan and T step launches with the KEEP instantiation: h_t goes to hstash [T][B][dim_q], the gates to `gates`
-int gru_forward_keep(const int32_t* wids, int B, int T, const float* E, int V1, int dim_emb, int dim_q, const float* packed, const GruPlan& p,
+int gru_forward_keep(const int32_t* wids, int B, int T, const float* E, int V1, int dim_emb, int dim_q, const float* packed, const RnnPlan& p,
                      float* hstash, float* gates, float* q_out, int32_t* bad_id_flag, hipStream_t s) {
-    hipLaunchKernelGGL(k_gru_plan, dim3(1), dim3(256), 0, s, wids, B, T, V1, p.perm, p.lens, p.lens_tmp, p.n_t, (int*)bad_id_flag);
-    NCX_HIP_TRY(hipGetLastError());
-    const int tiles_m = (int)cdiv(B, GRU_BM), total = tiles_m * (int)cdiv(dim_q, GRU_BU);
+    NCX_HIP_TRY(rnn_plan(wids, B, T, V1, p, 1, bad_id_flag, s));
+    const int tiles_m = (int)cdiv(B, RNN_BM), total = tiles_m * (int)cdiv(dim_q, RNN_BU);
     const unsigned grid = (unsigned)(8 * cdiv(total, 8));
     const GruKeep<true> keep{gates, B, pad_to(dim_q, GEMM_BK)};
     const size_t hs = (size_t)B * dim_q;
@@ -248,31 +203,30 @@ int gru_forward_keep(const int32_t* wids, int B, int T, const float* E, int V1, 
 }  // namespace ncx
 
 extern "C" {
-struct GruLayout { size_t perm, lens, lens_tmp, n_t, h0, h1, total; };
+struct GruLayout { RnnPlanOff plan; size_t h0, h1, total; };
 
 static GruLayout gru_layout(int B, int dim_q) {
     GruLayout w{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    w.perm = take((size_t)B * 4); w.lens = take((size_t)B * 4); w.lens_tmp = take((size_t)B * 4); w.n_t = take(GRU_MAX_T * 4);
-    w.h0 = take((size_t)B * dim_q * 4); w.h1 = take((size_t)B * dim_q * 4);
-    w.total = off;
+    WsCarver c;
+    w.plan = c.take_plan(B);
+    w.h0 = c.take((size_t)B * dim_q * 4); w.h1 = c.take((size_t)B * dim_q * 4);
+    w.total = c.off;
     return w;
 }
 
 size_t ncx_gru_packed_bytes(int32_t dim_emb, int32_t dim_q) {
-    if (!gru_dims_ok(1, 1, dim_emb, dim_q)) return 0;
+    if (!rnn_dims_ok(1, 1, dim_emb, dim_q)) return 0;
     return gru_packed(dim_emb, dim_q).floats * 4;
 }
 
 size_t ncx_gru_workspace_bytes(int32_t B, int32_t T, int32_t dim_emb, int32_t dim_q) {
-    if (!gru_dims_ok(B, T, dim_emb, dim_q)) return 0;
+    if (!rnn_dims_ok(B, T, dim_emb, dim_q)) return 0;
     return gru_layout(B, dim_q).total;
 }
 
 int ncx_gru_pack(const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, int32_t dim_emb, int32_t dim_q,
                  float* packed, void* stream) {
-    if (!w_ih || !w_hh || !b_ih || !b_hh || !packed || ((uintptr_t)packed & 15) || !gru_dims_ok(1, 1, dim_emb, dim_q)) return -1;
+    if (!rnn_dims_ok(1, 1, dim_emb, dim_q) || !rnn_ptrs_ok({w_ih, w_hh, b_ih, b_hh}, packed)) return -1;
     const size_t n = gru_packed(dim_emb, dim_q).floats;
     hipLaunchKernelGGL(k_gru_pack, dim3((unsigned)cdiv((long long)n, 256)), dim3(256), 0, (hipStream_t)stream, w_ih, w_hh, b_ih, b_hh, dim_emb, dim_q, packed);
     NCX_HIP_TRY(hipGetLastError());
@@ -281,20 +235,18 @@ int ncx_gru_pack(const float* w_ih, const float* w_hh, const float* b_ih, const 
 
 int ncx_gru_encode(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t dim_emb, int32_t dim_q,
                    const float* packed, void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream) {
-    if (!wids || !E || !packed || !workspace || !q_out || !bad_id_flag) return -1;
-    if (!gru_dims_ok(B, T, dim_emb, dim_q) || V1 < 1 || ((uintptr_t)packed & 15)) return -1;
+    if (!rnn_dims_ok(B, T, dim_emb, dim_q) || V1 < 1) return -1;
     const GruLayout w = gru_layout(B, dim_q);
-    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) return -1;
+    if (!rnn_args_ok({wids, E, q_out, bad_id_flag}, packed, workspace, workspace_bytes, w.total)) return -1;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    int* perm = (int*)(ws + w.perm); int* lens = (int*)(ws + w.lens); int* n_t = (int*)(ws + w.n_t);
+    const RnnPlan p = w.plan.at(ws);
     float* h[2] = {(float*)(ws + w.h0), (float*)(ws + w.h1)};
-    hipLaunchKernelGGL(k_gru_plan, dim3(1), dim3(256), 0, s, wids, B, T, V1, perm, lens, (int*)(ws + w.lens_tmp), n_t, (int*)bad_id_flag);
-    NCX_HIP_TRY(hipGetLastError());
-    const int tiles_m = (int)cdiv(B, GRU_BM), total = tiles_m * (int)cdiv(dim_q, GRU_BU);
+    NCX_HIP_TRY(rnn_plan(wids, B, T, V1, p, 1, bad_id_flag, s));
+    const int tiles_m = (int)cdiv(B, RNN_BM), total = tiles_m * (int)cdiv(dim_q, RNN_BU);
     const unsigned grid = (unsigned)(8 * cdiv(total, 8));
     for (int t = 0; t < T; ++t) {              // every step is launched: how many rows it has is known on the device only
-        hipLaunchKernelGGL(k_gru_step<false>, dim3(grid), dim3(256), 0, s, wids, T, t, E, V1, dim_emb, dim_q, packed, perm, lens, n_t,
+        hipLaunchKernelGGL(k_gru_step<false>, dim3(grid), dim3(256), 0, s, wids, T, t, E, V1, dim_emb, dim_q, packed, p.perm, p.lens, p.n_t,
                            h[(t + 1) & 1], h[t & 1], q_out, tiles_m, total, GruKeep<false>{});
         NCX_HIP_TRY(hipGetLastError());
     }

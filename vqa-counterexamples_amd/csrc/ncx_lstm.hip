@@ -8,8 +8,8 @@
 //   layer l:  [i f g o] = W_ih x + b_ih + W_hh h + b_hh;  c' = s(f) c + s(i) tanh(g);  h' = s(o) tanh(c');  h_0 = c_0 = 0;  layer 1's x is layer 0's h'
 //   q[b] = [h^0 | h^1] after step len_b - 1
 // Plan (T + 2 launches, nothing read back, no inter-workgroup wait, no atomics):
-//   k_lstm_plan  one workgroup: k_gru_plan (ncx_gru.hip) with the length rule above.  A kernel of its own so that the GRU encoder's object
-//                code does not change with this file.
+//   k_rnn_plan   (ncx_rnn.hip, shared with the GRU encoder) one workgroup: the length rule above (an all-padding row has length T), the
+//                rows sorted by length (descending) -> perm, n_t = #{b : len_b > t}.
 //   k_lstm_step  launch s in [0, T]: layer 0 at step s (s < T) and layer 1 at step s - 1 (s >= 1) as two ranges of workgroup ids -- a
 //                wavefront: both read only what launch s - 1 wrote.  A layer's step is the GEMM [x_t | h_{t-1}][0:n_t) . [W_ih | W_hh]^T on
 //                v_mfma_f32_16x16x4_f32 (step 0 stops after the x columns: h_0 = 0).  A workgroup owns 64 rows x 32 hidden units with the
@@ -25,18 +25,18 @@ namespace {
 // of a ds_read_b64 fragment read (16 rows, one logical quad, two 8-byte halves) then covers all 64 banks once, as the padded pitch
 // of 36 (ncx_gru.hip) does, and the two buffers take 48 KB instead of 54: three workgroups fit a CU's LDS, not two.
 constexpr int LSTM_P = GEMM_BK;
-constexpr int LSTM_TILE_ROWS = LSTM_BM + 4 * LSTM_BU;
+constexpr int LSTM_TILE_ROWS = RNN_BM + 4 * RNN_BU;
 
 // packed = layer 0 | layer 1;  layer l = W [nj][4 gates][32 units][kp_l] | bias [nj][4][32 units] (b_ih + b_hh)
 struct LstmPacked { int kx[2], kp[2], nj; size_t w_floats[2], off[2], floats; };
 __host__ __device__ inline LstmPacked lstm_packed(int emb, int H) {
     LstmPacked p;
-    p.nj = (H + LSTM_BU - 1) / LSTM_BU;
+    p.nj = (H + RNN_BU - 1) / RNN_BU;
     size_t off = 0;
     for (int l = 0; l < 2; ++l) {
         p.kx[l] = pad_to(l ? H : emb, GEMM_BK); p.kp[l] = p.kx[l] + pad_to(H, GEMM_BK);
-        p.w_floats[l] = (size_t)p.nj * 4 * LSTM_BU * p.kp[l];
-        p.off[l] = off; off += p.w_floats[l] + (size_t)p.nj * 4 * LSTM_BU;
+        p.w_floats[l] = (size_t)p.nj * 4 * RNN_BU * p.kp[l];
+        p.off[l] = off; off += p.w_floats[l] + (size_t)p.nj * 4 * RNN_BU;
     }
     p.floats = off;
     return p;
@@ -67,56 +67,17 @@ __global__ __launch_bounds__(256) void k_lstm_pack(LstmW w0, LstmW w1, int emb, 
     if (o < p.w_floats[l]) {
         const size_t row = o / kp;
         const int c = (int)(o - row * kp);
-        const int u = (int)(row % LSTM_BU), g = (int)(row / LSTM_BU % 4), unit = (int)(row / (4 * LSTM_BU)) * LSTM_BU + u;
+        const int u = (int)(row % RNN_BU), g = (int)(row / RNN_BU % 4), unit = (int)(row / (4 * RNN_BU)) * RNN_BU + u;
         if (unit < H) {
             if (c < kx) { if (c < in) v = w.w_ih[((size_t)g * H + unit) * in + c]; }
             else if (c - kx < H) v = w.w_hh[((size_t)g * H + unit) * H + (c - kx)];
         }
     } else {
         const size_t b = o - p.w_floats[l];
-        const int u = (int)(b % LSTM_BU), g = (int)(b / LSTM_BU % 4), unit = (int)(b / (4 * LSTM_BU)) * LSTM_BU + u;
+        const int u = (int)(b % RNN_BU), g = (int)(b / RNN_BU % 4), unit = (int)(b / (4 * RNN_BU)) * RNN_BU + u;
         if (unit < H) v = w.b_ih[(size_t)g * H + unit] + w.b_hh[(size_t)g * H + unit];
     }
     packed[i] = v;
-}
-
-// One workgroup.  lens_tmp [B] is scratch; perm / lens [B] come out in sorted order (length descending, input order inside a length).
-__global__ __launch_bounds__(256) void k_lstm_plan(const int* __restrict__ wids, int B, int T, int V1, int* __restrict__ perm, int* __restrict__ lens,
-                                                   int* __restrict__ lens_tmp, int* __restrict__ n_t, int* __restrict__ bad) {
-    __shared__ int cnt[LSTM_MAX_T + 2], start[LSTM_MAX_T + 2], sbad;
-    const int tid = threadIdx.x;
-    if (tid == 0) sbad = 0;
-    __syncthreads();
-    bool oob = false;
-    for (int b = tid; b < B; b += 256) {
-        int n = 0;
-        for (int t = 0; t < T; ++t) {
-            const int w = wids[(size_t)b * T + t];
-            oob |= w < 0 || w >= V1;
-            n += w != 0;
-        }
-        lens_tmp[b] = n > 0 ? n : T;           // all padding: select_last indexes step -1, the LAST one
-    }
-    if (oob) sbad = 1;
-    __syncthreads();
-    if (tid == 0 && sbad) *bad = 1;
-    const int L = tid + 1;                     // thread L - 1 owns the rows of length L
-    if (L <= T) {
-        int c = 0;
-        for (int b = 0; b < B; ++b) c += lens_tmp[b] == L;
-        cnt[L] = c;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int run = 0;
-        for (int l = T; l >= 1; --l) { start[l] = run; run += cnt[l]; n_t[l - 1] = run; }   // n_t[t] = #{len >= t + 1}
-    }
-    __syncthreads();
-    if (L <= T) {
-        int pos = start[L];
-        for (int b = 0; b < B; ++b)
-            if (lens_tmp[b] == L) { perm[pos] = b; lens[pos] = L; ++pos; }
-    }
 }
 
 // grid = (layers of this launch) x grid1; workgroups [0, grid1) run layer `layer_base`, [grid1, 2 grid1) layer 1
@@ -134,13 +95,13 @@ __global__ __launch_bounds__(256) void k_lstm_step(LstmStep a, int s, int layer_
     const int w = (bid & 7) * per + (bid >> 3);
     if (w >= a.total) return;
     const int nt = a.n_t[t];
-    const int j = w / a.tiles_m, m0 = (w - j * a.tiles_m) * LSTM_BM;
+    const int j = w / a.tiles_m, m0 = (w - j * a.tiles_m) * RNN_BM;
     if (m0 >= nt) return;                      // (uniform: before any barrier)
 
     const int H = a.H, in = layer ? H : a.emb;
     // (the two layers' entries of lstm_packed by selects: a runtime index into that struct would cost a private copy of it)
     const int kx = pad_to(in, GEMM_BK), kp = kx + pad_to(H, GEMM_BK);
-    const size_t blk = (size_t)((H + LSTM_BU - 1) / LSTM_BU) * 4 * LSTM_BU;                // weight rows of a layer = floats of its bias block
+    const size_t blk = (size_t)((H + RNN_BU - 1) / RNN_BU) * 4 * RNN_BU;                // weight rows of a layer = floats of its bias block
     const size_t w_floats = blk * kp;
     const float* packed = a.packed + (layer ? blk * (pad_to(a.emb, GEMM_BK) + pad_to(H, GEMM_BK)) + blk : 0);
     // (selects, not indexing: a runtime index into the argument struct would cost a private copy of it)
@@ -166,7 +127,7 @@ __global__ __launch_bounds__(256) void k_lstm_step(LstmStep a, int s, int layer_
         const int row = min(m0 + lr + 32 * i, nt - 1);                       // rows beyond n_t: clamped here, never stored
         if (layer == 0) {
             int wid = a.wids[(size_t)a.perm[row] * a.T + t];
-            wid = min(max(wid, 0), a.V1 - 1);                                // an id out of range is never an address (k_lstm_plan flags it)
+            wid = min(max(wid, 0), a.V1 - 1);                                // an id out of range is never an address (k_rnn_plan flags it)
             xptr[i] = a.E + (size_t)wid * a.emb;
         } else {
             if constexpr (KEEP) xptr[i] = keep.h0 + ((size_t)t * keep.B + row) * H;
@@ -175,7 +136,7 @@ __global__ __launch_bounds__(256) void k_lstm_step(LstmStep a, int s, int layer_
         hptr[i] = h_prev + (size_t)row * H;
     }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) bptr[i] = packed + ((size_t)j * 4 * LSTM_BU + lr + 32 * i) * kp + c4;
+    for (int i = 0; i < 4; ++i) bptr[i] = packed + ((size_t)j * 4 * RNN_BU + lr + 32 * i) * kp + c4;
     const int nx = kx / GEMM_BK, ns = nx + (t > 0 ? (kp - kx) / GEMM_BK : 0);
 
     f32x4 va[2], vb[4];
@@ -202,7 +163,7 @@ __global__ __launch_bounds__(256) void k_lstm_step(LstmStep a, int s, int layer_
 #pragma unroll
         for (int i = 0; i < 2; ++i) *(f32x4*)(&lds[buf][(lr + 32 * i) * LSTM_P + sc4]) = va[i];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) *(f32x4*)(&lds[buf][(LSTM_BM + lr + 32 * i) * LSTM_P + sc4]) = vb[i];
+        for (int i = 0; i < 4; ++i) *(f32x4*)(&lds[buf][(RNN_BM + lr + 32 * i) * LSTM_P + sc4]) = vb[i];
     };
 
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -214,13 +175,13 @@ __global__ __launch_bounds__(256) void k_lstm_step(LstmStep a, int s, int layer_
     for (int tt = 0; tt < GEMM_BK / 8; ++tt) co[tt] = 4 * ((2 * tt + (lk >> 1)) ^ ((li >> 1) & 7)) + ((2 * lk) & 3);
     auto compute = [&](int buf) __attribute__((always_inline)) {
         const float* pa = &lds[buf][(32 * wr + li) * LSTM_P];
-        const float* pb = &lds[buf][(LSTM_BM + 16 * wu + li) * LSTM_P];
+        const float* pb = &lds[buf][(RNN_BM + 16 * wu + li) * LSTM_P];
 #pragma unroll
         for (int tt = 0; tt < GEMM_BK / 8; ++tt) {
             const f32x2 a0 = *(const f32x2*)(pa + co[tt]), a1 = *(const f32x2*)(pa + 16 * LSTM_P + co[tt]);
             f32x2 b[4];
 #pragma unroll
-            for (int g = 0; g < 4; ++g) b[g] = *(const f32x2*)(pb + g * LSTM_BU * LSTM_P + co[tt]);
+            for (int g = 0; g < 4; ++g) b[g] = *(const f32x2*)(pb + g * RNN_BU * LSTM_P + co[tt]);
 #pragma unroll
             for (int e = 0; e < 2; ++e)
 #pragma unroll
@@ -245,10 +206,10 @@ __global__ __launch_bounds__(256) void k_lstm_step(LstmStep a, int s, int layer_
     }
 
     // epilogue: C layout col = lane & 15 (unit), row = 4 (lane >> 4) + reg
-    const int ul = 16 * wu + li, unit = j * LSTM_BU + ul;
+    const int ul = 16 * wu + li, unit = j * RNN_BU + ul;
     if (unit >= H) return;
-    const float* bias = packed + w_floats + (size_t)j * 4 * LSTM_BU + ul;
-    const float b_i = bias[0], b_f = bias[LSTM_BU], b_g = bias[2 * LSTM_BU], b_o = bias[3 * LSTM_BU];
+    const float* bias = packed + w_floats + (size_t)j * 4 * RNN_BU + ul;
+    const float b_i = bias[0], b_f = bias[RNN_BU], b_g = bias[2 * RNN_BU], b_o = bias[3 * RNN_BU];
     float* cbuf = layer ? a.c[1] : a.c[0];
     const float* cprev = cbuf;
     if constexpr (KEEP) {
@@ -282,25 +243,24 @@ __global__ __launch_bounds__(256) void k_lstm_step(LstmStep a, int s, int layer_
 
 namespace ncx {
 bool lstm2_dims_ok(long long B, long long T, long long emb, long long H) {
-    // gru_dims_ok bounds B T, the widths and one layer's grid; the launch holds two layers
-    return gru_dims_ok(B, T, emb, H) && 2 * 8 * cdiv(cdiv(B, LSTM_BM) * cdiv(H, LSTM_BU), 8) < (1ll << 30);
+    // rnn_dims_ok bounds B T, the widths and one layer's grid; the launch holds two layers
+    return rnn_dims_ok(B, T, emb, H) && 2 * 8 * cdiv(cdiv(B, RNN_BM) * cdiv(H, RNN_BU), 8) < (1ll << 30);
 }
 
-static LstmStep lstm2_step_args(const int32_t* wids, int B, int T, const float* E, int V1, int emb, int H, const float* packed, const Lstm2Plan& p,
+static LstmStep lstm2_step_args(const int32_t* wids, int B, int T, const float* E, int V1, int emb, int H, const float* packed, const RnnPlan& p,
                                 float* q_out) {
     LstmStep a{};
     a.wids = wids; a.E = E; a.packed = packed; a.perm = p.perm; a.lens = p.lens; a.n_t = p.n_t;
     a.q = q_out; a.T = T; a.V1 = V1; a.emb = emb; a.H = H;
-    a.tiles_m = (int)cdiv(B, LSTM_BM); a.total = a.tiles_m * (int)cdiv(H, LSTM_BU); a.grid1 = (int)(8 * cdiv(a.total, 8));
+    a.tiles_m = (int)cdiv(B, RNN_BM); a.total = a.tiles_m * (int)cdiv(H, RNN_BU); a.grid1 = (int)(8 * cdiv(a.total, 8));
     return a;
 }
 
 // the plan and the T + 1 wavefront launches; KEEP: into the stash
 template <bool KEEP>
-static int lstm2_run(const int32_t* wids, int B, int T, int V1, const Lstm2Plan& p, const LstmStep& a, const LstmKeep<KEEP>& keep, int32_t* bad_id_flag,
+static int lstm2_run(const int32_t* wids, int B, int T, int V1, const RnnPlan& p, const LstmStep& a, const LstmKeep<KEEP>& keep, int32_t* bad_id_flag,
                      hipStream_t st) {
-    hipLaunchKernelGGL(k_lstm_plan, dim3(1), dim3(256), 0, st, wids, B, T, V1, p.perm, p.lens, p.lens_tmp, p.n_t, (int*)bad_id_flag);
-    NCX_HIP_TRY(hipGetLastError());
+    NCX_HIP_TRY(rnn_plan(wids, B, T, V1, p, T, bad_id_flag, st));
     for (int s = 0; s <= T; ++s) {             // every launch is issued: how many rows a step has is known on the device only
         const int layers = (s < T) + (s >= 1);
         hipLaunchKernelGGL(k_lstm_step<KEEP>, dim3((unsigned)(layers * a.grid1)), dim3(256), 0, st, a, s, s < T ? 0 : 1, keep);
@@ -309,24 +269,23 @@ static int lstm2_run(const int32_t* wids, int B, int T, int V1, const Lstm2Plan&
     return NCX_OK;
 }
 
-int lstm2_forward_keep(const int32_t* wids, int B, int T, const float* E, int V1, int emb, int H, const float* packed, const Lstm2Plan& p,
+int lstm2_forward_keep(const int32_t* wids, int B, int T, const float* E, int V1, int emb, int H, const float* packed, const RnnPlan& p,
                        const LstmKeep<true>& keep, float* q_out, int32_t* bad_id_flag, hipStream_t s) {
     return lstm2_run<true>(wids, B, T, V1, p, lstm2_step_args(wids, B, T, E, V1, emb, H, packed, p, q_out), keep, bad_id_flag, s);
 }
 }  // namespace ncx
 
 extern "C" {
-struct Lstm2Layout { size_t perm, lens, lens_tmp, n_t, h[2][2], c[2], total; };
+struct Lstm2Layout { RnnPlanOff plan; size_t h[2][2], c[2], total; };
 
 static Lstm2Layout lstm2_layout(int B, int H) {
     Lstm2Layout w{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    w.perm = take((size_t)B * 4); w.lens = take((size_t)B * 4); w.lens_tmp = take((size_t)B * 4); w.n_t = take(LSTM_MAX_T * 4);
+    WsCarver c;
+    w.plan = c.take_plan(B);
     for (int l = 0; l < 2; ++l) {
-        w.h[l][0] = take((size_t)B * H * 4); w.h[l][1] = take((size_t)B * H * 4); w.c[l] = take((size_t)B * H * 4);
+        w.h[l][0] = c.take((size_t)B * H * 4); w.h[l][1] = c.take((size_t)B * H * 4); w.c[l] = c.take((size_t)B * H * 4);
     }
-    w.total = off;
+    w.total = c.off;
     return w;
 }
 
@@ -342,8 +301,7 @@ size_t ncx_lstm2_workspace_bytes(int32_t B, int32_t T, int32_t emb, int32_t H) {
 
 int ncx_lstm2_pack(const float* w_ih0, const float* w_hh0, const float* b_ih0, const float* b_hh0, const float* w_ih1, const float* w_hh1,
                    const float* b_ih1, const float* b_hh1, int32_t emb, int32_t H, float* packed, void* stream) {
-    if (!w_ih0 || !w_hh0 || !b_ih0 || !b_hh0 || !w_ih1 || !w_hh1 || !b_ih1 || !b_hh1 || !packed || ((uintptr_t)packed & 15)) return -1;
-    if (!lstm2_dims_ok(1, 1, emb, H)) return -1;
+    if (!lstm2_dims_ok(1, 1, emb, H) || !rnn_ptrs_ok({w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1}, packed)) return -1;
     const size_t n = lstm_packed(emb, H).floats;
     if (cdiv((long long)n, 256) >= (1ll << 31)) return -1;
     hipLaunchKernelGGL(k_lstm_pack, dim3((unsigned)cdiv((long long)n, 256)), dim3(256), 0, (hipStream_t)stream, LstmW{w_ih0, w_hh0, b_ih0, b_hh0},
@@ -354,12 +312,11 @@ int ncx_lstm2_pack(const float* w_ih0, const float* w_hh0, const float* b_ih0, c
 
 int ncx_lstm2_encode(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t emb, int32_t H, const float* packed,
                      void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream) {
-    if (!wids || !E || !packed || !workspace || !q_out || !bad_id_flag) return -1;
-    if (!lstm2_dims_ok(B, T, emb, H) || V1 < 1 || ((uintptr_t)packed & 15)) return -1;
+    if (!lstm2_dims_ok(B, T, emb, H) || V1 < 1) return -1;
     const Lstm2Layout w = lstm2_layout(B, H);
-    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) return -1;
+    if (!rnn_args_ok({wids, E, q_out, bad_id_flag}, packed, workspace, workspace_bytes, w.total)) return -1;
     char* ws = (char*)workspace;
-    const Lstm2Plan p{(int*)(ws + w.perm), (int*)(ws + w.lens), (int*)(ws + w.lens_tmp), (int*)(ws + w.n_t)};
+    const RnnPlan p = w.plan.at(ws);
     LstmStep a = lstm2_step_args(wids, B, T, E, V1, emb, H, packed, p, q_out);
     for (int l = 0; l < 2; ++l) { a.h[l][0] = (float*)(ws + w.h[l][0]); a.h[l][1] = (float*)(ws + w.h[l][1]); a.c[l] = (float*)(ws + w.c[l]); }
     return lstm2_run<false>(wids, B, T, V1, p, a, LstmKeep<false>{}, bad_id_flag, (hipStream_t)stream);

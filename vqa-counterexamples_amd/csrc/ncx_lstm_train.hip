@@ -20,18 +20,18 @@
 //                        where len_row - 1 == t, the cell arithmetic from the stash (one tanhf: tanh(c_t) is not kept), dcf and the four
 //                        gate-gradient blocks of step t.
 //   k_lstm_bgemm<true>   dX_t = da^0_t . W_ih^0 for every step in one launch (grid.y = t) after the sweep; skipped when dE is NULL.
-//   k_lstm_dw<GATHER>    the four weight gradients as TN products whose contraction walks (t, row < n_t[t]) with n_t read from memory; one
-//                        workgroup per 128 x 64 output tile, the whole walk in order.  GATHER: x = tanh(E[tok]) on the load side.
-//   k_lstm_dbias         column sums of da^l -> db_ih^l and db_hh^l.
-//   k_lstm_tok, k_lstm_de  the word id of every valid pair (or -1); one workgroup per row of E sums the dX rows of its id in (t, row) order.
+//                        Both share their 64 x 64 tile loop with the GRU's sweep (rnn_nt_tile, ncx_rnn.h).
+//   k_rnn_dw             (ncx_rnn.hip) the four weight gradients as TN products whose contraction walks (t, row < n_t[t]); three over stash
+//                        rows, dW_ih^0 over the gathered rows x = tanh(E[tok]), taken on the load side.
+//   k_lstm_dbias         column sums of da^l (rnn_colsum) -> db_ih^l and db_hh^l.
+//   k_rnn_tok, k_rnn_de  (ncx_rnn.hip) the word id of every valid pair (or -1); one workgroup per row of E sums the dX rows of its id in
+//                        (t, row) order, times 1 - tanh(E)^2.
 #include "ncx_lstm.h"
 
 using namespace ncx;
 
 namespace {
-constexpr int LB_BM = 64, LB_BN = 64, LB_P = GEMM_BK + 4;           // sweep / dX tile; LDS pitch as in k_gru_bgemm
-constexpr int LW_BM = 128, LW_BN = 64;                                // weight-gradient tile: gate rows x feature columns
-constexpr int LW_PA = pitch_rowk(LW_BM), LW_PB = pitch_rowk(LW_BN);   // row-is-k pitches (ncx_gemm.h)
+constexpr int LB_BM = RNN_NT_BM, LB_BN = RNN_NT_BN;                   // sweep / dX tile (rnn_nt_tile, ncx_rnn.h)
 
 // packed_t = P0 [rows_h][8 Hp] | P1 [rows_h][4 Hp] | PX [rows_x][4 Hp]
 struct LstmPackT { int Hp, rows_h, rows_x; size_t off1, offx, floats; };
@@ -82,11 +82,18 @@ struct LbArgs {
     int B, T, H, Hp, emb, tiles_m, grid1;
 };
 
+// rnn_nt_tile's A rows: the k-steps [0, ka) are the first segment, whose rows [n_{t+1}, n_t) count as zeros, the rest the second
+struct LstmBgSrc {
+    const float* pa1[2]; const float* pa2[2]; bool ok1[2]; int ka;
+    __device__ __forceinline__ const float* ptr(int s, int i) const { return s < ka ? pa1[i] + s * GEMM_BK : pa2[i] + (s - ka) * GEMM_BK; }
+    __device__ __forceinline__ bool zero(int s, int i) const { return s < ka && !ok1[i]; }
+};
+
 // DX = false: launch u of the reverse wavefront; workgroups [0, grid1) run layer `layer_base`, [grid1, 2 grid1) layer 0.
 // DX = true: dX_t, t = blockIdx.y.
 template <bool DX>
 __global__ __launch_bounds__(256) void k_lstm_bgemm(const LbArgs a, int u, int layer_base) {
-    __shared__ __attribute__((aligned(16))) float lds[2][(LB_BM + LB_BN) * LB_P];
+    __shared__ __attribute__((aligned(16))) float lds[2][RNN_NT_LDS];
     const int second = !DX && (int)blockIdx.x >= a.grid1;
     const int layer = DX ? 0 : second ? 0 : layer_base, bid = (int)blockIdx.x - second * a.grid1;
     const int t = DX ? (int)blockIdx.y : layer ? u : u + 1;
@@ -112,64 +119,19 @@ __global__ __launch_bounds__(256) void k_lstm_bgemm(const LbArgs a, int u, int l
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     f32x4 acc[2][2] = {{zero, zero}, {zero, zero}};
     if (s0 < s1) {
-        // loader: thread owns column quad c4 of tile rows lr + 32 i (2 of the A tile, 2 of the weight tile); every load is an aligned 16 bytes
-        const float* pa1[2]; const float* pa2[2]; const float* bptr[2];
-        bool ok1[2];
+        LstmBgSrc src;
         const float* seg2 = DX ? a.dg0 : a.dg1;
         const float* wT = DX ? a.wx : layer ? a.w1 : a.w0;
         const int t1 = min(t + 1, a.T - 1);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int r = m0 + lr + 32 * i;
-            ok1[i] = r < nnext;                                                   // rows [n_{t+1}, n_t): zeroed in store()
-            pa1[i] = dgl + ((size_t)t1 * a.B + max(min(r, nnext - 1), 0)) * dg_ld + c4;
-            pa2[i] = seg2 + ((size_t)t * a.B + min(r, nout - 1)) * dg_ld + c4;   // rows beyond n_t: clamped here, never stored
-            bptr[i] = wT + (size_t)(n0 + lr + 32 * i) * wld + c4;               // (weight rows are padded to whole tiles)
+            src.ok1[i] = r < nnext;
+            src.pa1[i] = dgl + ((size_t)t1 * a.B + rnn_clamp_row(r, nnext)) * dg_ld + c4;
+            src.pa2[i] = seg2 + ((size_t)t * a.B + rnn_clamp_row(r, nout)) * dg_ld + c4;
         }
-        f32x4 va[2], vb[2];
-        bool first = false;
-        auto issue = [&](int s) __attribute__((always_inline)) {
-            first = s < ka;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) va[i] = *(const f32x4*)(first ? pa1[i] + s * GEMM_BK : pa2[i] + (s - ka) * GEMM_BK);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) vb[i] = *(const f32x4*)(bptr[i] + s * GEMM_BK);
-        };
-        auto store = [&](int buf) __attribute__((always_inline)) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) *(f32x4*)(&lds[buf][(lr + 32 * i) * LB_P + c4]) = (first && !ok1[i]) ? zero : va[i];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) *(f32x4*)(&lds[buf][(LB_BM + lr + 32 * i) * LB_P + c4]) = vb[i];
-        };
-        // MFMA (tt, e) takes k = 8 tt + 2 lk + e from lane group lk for both operands (ncx_gemm.h)
-        auto compute = [&](int buf) __attribute__((always_inline)) {
-            const float* pa = &lds[buf][(32 * wr + li) * LB_P + 2 * lk];
-            const float* pb = &lds[buf][(LB_BM + 32 * wu + li) * LB_P + 2 * lk];
-#pragma unroll
-            for (int tt = 0; tt < GEMM_BK / 8; ++tt) {
-                const f32x2 a0 = *(const f32x2*)(pa + 8 * tt), a1 = *(const f32x2*)(pa + 16 * LB_P + 8 * tt);
-                const f32x2 b0 = *(const f32x2*)(pb + 8 * tt), b1 = *(const f32x2*)(pb + 16 * LB_P + 8 * tt);
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[e], b0[e], acc[0][0], 0, 0, 0);
-                    acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[e], b0[e], acc[1][0], 0, 0, 0);
-                    acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[e], b1[e], acc[0][1], 0, 0, 0);
-                    acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[e], b1[e], acc[1][1], 0, 0, 0);
-                }
-            }
-        };
-        // register-staged double-buffered LDS, one barrier per k-step: the loads of step s + 1 fly over the MFMAs of step s
-        issue(s0); store(0);
-        __syncthreads();
-        int buf = 0;
-        for (int s = s0; s < s1; ++s) {
-            const bool more = s + 1 < s1;
-            if (more) issue(s + 1);
-            compute(buf);
-            if (more) store(buf ^ 1);
-            __syncthreads();
-            buf ^= 1;
-        }
+        src.ka = ka;
+        rnn_nt_tile(lds, src, wT + (size_t)(n0 + lr) * wld + c4, wld, s0, s1, acc);
     }
 
     // epilogue: C layout col = lane & 15, row = 4 (lane >> 4) + reg
@@ -209,221 +171,36 @@ __global__ __launch_bounds__(256) void k_lstm_bgemm(const LbArgs a, int u, int l
             }
 }
 
-struct LwArgs {
-    const float* dG; const float* X;           // X: a [T][B][cols] stash, row (t - xshift, row); GATHER: E, row tok[t][row]
-    const int* tok; const int* n_t; float* out;
-    int B, T, H, Hp, cols, tiles_m, xshift;     // cols: width of X's rows = columns of out; the walk starts at t = xshift
-};
-
-// out[g H + u][c] = sum over t >= xshift, row < n_t[t] of dG_t[row][g Hp + u] * X(t, row)[c]
-template <bool GATHER>
-__global__ __launch_bounds__(256) void k_lstm_dw(const LwArgs a) {
-    __shared__ __attribute__((aligned(16))) float la[2][GEMM_BK * LW_PA];
-    __shared__ __attribute__((aligned(16))) float lb[2][GEMM_BK * LW_PB];
-    const int tn = (int)blockIdx.x / a.tiles_m, m0 = ((int)blockIdx.x - tn * a.tiles_m) * LW_BM, n0 = tn * LW_BN;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 15, lk = lane >> 4;
-    const int wm0 = (wave >> 1) * (LW_BM / 2), wn0 = (wave & 1) * (LW_BN / 2);
-    const int kr = tid >> 3, cq = 4 * (tid & 7);
-    const int kp = 4 * a.Hp;                   // (a multiple of 128: the gate-row tiles are whole)
-
-    // loader: thread owns k-row kr of the step, column quads cq + 32 i (4 of the gate-gradient tile, 2 of the X tile)
-    int acol[4], bcol[2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acol[i] = min(m0 + cq + 32 * i, kp - 4);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) bcol[i] = n0 + cq + 32 * i;
-    const bool b_full = n0 + LW_BN <= a.cols;
-
-    f32x4 va[4], vb[2];
-    bool a_ok = false;
-    auto issue = [&](int t, int r0, int nr) __attribute__((always_inline)) {
-        const int krow = r0 + kr, rc = min(krow, nr - 1);
-        a_ok = krow < nr;                                                         // rows n_t .. the end of the k-step: zeroed in store()
-        const float* ap = a.dG + ((size_t)t * a.B + rc) * kp;
-        const float* bp = GATHER ? a.X + (size_t)max(a.tok[(size_t)t * a.B + rc], 0) * a.cols  // an id out of range is -1 here: never an address
-                                 : a.X + ((size_t)(t - a.xshift) * a.B + rc) * a.cols;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) va[i] = *(const f32x4*)(ap + acol[i]);
-        if (b_full) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) vb[i] = *(const f32x4u*)(bp + bcol[i]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) vb[i] = load4(bp, bcol[i], a.cols);
-        }
-    };
-    auto store = [&](int buf) __attribute__((always_inline)) {
-        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-        if (GATHER) {                          // x = tanh(E[wid]); tanh(0) = 0 keeps the zero fill
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) vb[i][e] = tanhf(vb[i][e]);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) *(f32x4*)(&la[buf][kr * LW_PA + cq + 32 * i]) = a_ok ? va[i] : zero;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) *(f32x4*)(&lb[buf][kr * LW_PB + cq + 32 * i]) = vb[i];
-    };
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    f32x4 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { acc[i][0] = zero; acc[i][1] = zero; }
-    // interleaved block mapping (ncx_gemm.h): MFMA block i of a wave owns tile rows wm0 + 4 r + i, block j tile columns wn0 + 2 c + j, so one
-    // ds_read_b128 / ds_read_b64 per k-row feeds all of a lane's blocks
-    auto compute = [&](int buf) __attribute__((always_inline)) {
-        const float* pa = &la[buf][wm0 + 4 * li];
-        const float* pb = &lb[buf][wn0 + 2 * li];
-#pragma unroll
-        for (int tt = 0; tt < GEMM_BK / 8; ++tt) {
-            const int kk = 8 * tt + 2 * lk;
-            f32x4 av[2]; f32x2 bv[2];
-#pragma unroll
-            for (int e = 0; e < 2; ++e) { av[e] = *(const f32x4*)(pa + (kk + e) * LW_PA); bv[e] = *(const f32x2*)(pb + (kk + e) * LW_PB); }
-#pragma unroll
-            for (int e = 0; e < 2; ++e)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e][i], bv[e][j], acc[i][j], 0, 0, 0);
-        }
-    };
-
-    // the walk: steps xshift .. while n_t[t] > 0 (n_t never rises), rows in k-steps of 32; same double-buffered pipeline as above
-    int t = a.xshift, r0 = 0, nr = t < a.T ? a.n_t[t] : 0;
-    if (nr > 0) {
-        issue(t, r0, nr); store(0);
-        __syncthreads();
-        int buf = 0;
-        for (;;) {
-            r0 += GEMM_BK;
-            if (r0 >= nr) { ++t; r0 = 0; nr = t < a.T ? a.n_t[t] : 0; }
-            const bool more = nr > 0;
-            if (more) issue(t, r0, nr);
-            compute(buf);
-            if (more) store(buf ^ 1);
-            __syncthreads();
-            buf ^= 1;
-            if (!more) break;
-        }
-    }
-
-    // epilogue: acc[i][j][q] is tile row wm0 + 4 (4 lk + q) + i, tile column wn0 + 2 li + j; with no k-step at all the tile is exactly 0
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int m = m0 + wm0 + 4 * (4 * lk + q) + i, g = m / a.Hp, uu = m - g * a.Hp;
-            if (m >= kp || uu >= a.H) continue;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int c = n0 + wn0 + 2 * li + j;
-                if (c < a.cols) a.out[((size_t)g * a.H + uu) * a.cols + c] = acc[i][j][q];
-            }
-        }
-}
-
-// db_ih^l = db_hh^l = column sums of da^l over every valid pair.  grid = 2 layers x (4 Hp / 32); a workgroup owns 32 columns; thread (g, c)
-// sums rows g, g + 8, ... of every step in ascending order, the 8 partial sums are added in ascending g (k_mt_colsum's scheme).
+// db_ih^l = db_hh^l = column sums of da^l over every valid pair (rnn_colsum, ncx_rnn.h).  grid = 2 layers x (4 Hp / 32); a workgroup owns 32 columns.
 __global__ __launch_bounds__(256) void k_lstm_dbias(const float* __restrict__ dg0, const float* __restrict__ dg1, const int* __restrict__ n_t, int B, int T,
                                                     int H, int Hp, float* __restrict__ db_ih0, float* __restrict__ db_hh0, float* __restrict__ db_ih1,
                                                     float* __restrict__ db_hh1) {
-    __shared__ float part[8][32];
     const int per = 4 * Hp / 32, layer = (int)blockIdx.x >= per;
-    const int c = threadIdx.x & 31, g = threadIdx.x >> 5, col = ((int)blockIdx.x - layer * per) * 32 + c;
-    const float* dG = layer ? dg1 : dg0;
-    const size_t ld = 4 * (size_t)Hp;
-    float sum = 0.f;
-    for (int t = 0; t < T; ++t) {
-        const int nr = n_t[t];
-        if (nr == 0) break;
-        const float* p = dG + (size_t)t * B * ld + col;
-#pragma unroll 4
-        for (int row = g; row < nr; row += 8) sum += p[(size_t)row * ld];
-    }
-    part[g][c] = sum;
-    __syncthreads();
-    if (g != 0) return;
-    float s = part[0][c];
-#pragma unroll
-    for (int k = 1; k < 8; ++k) s += part[k][c];
+    const int col = ((int)blockIdx.x - layer * per) * 32 + (threadIdx.x & 31);
+    float s;
+    if (!rnn_colsum(layer ? dg1 : dg0, 4 * (size_t)Hp, n_t, B, T, col, s)) return;
     const int blk = col / Hp, u = col - blk * Hp;
     if (u >= H) return;
     (layer ? db_ih1 : db_ih0)[blk * H + u] = s;
     (layer ? db_hh1 : db_hh0)[blk * H + u] = s;
 }
 
-// tok[t][row] = the word id of the valid pair (t, row < n_t[t]) when it is inside [0, V1), else -1
-__global__ __launch_bounds__(256) void k_lstm_tok(const int* __restrict__ wids, int B, int T, int V1, const int* __restrict__ perm,
-                                                  const int* __restrict__ n_t, int* __restrict__ tok) {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= B * T) return;
-    const int t = p / B, row = p - t * B;
-    int v = -1;
-    if (row < n_t[t]) {
-        const int w = wids[(size_t)perm[row] * T + t];
-        if (w >= 0 && w < V1) v = w;
-    }
-    tok[p] = v;
-}
-
-// dE[v] = (sum of dX over the valid pairs whose word id is v, in (t, row) order) (1 - tanh(E[v])^2); dE[0] = 0 (padding_idx: torch's
-// embedding backward skips it, whatever read E[0] in the forward).  One workgroup per row of E: it scans tok 256 positions at a time (one
-// ballot per wave) and adds the rows it finds.
-__global__ __launch_bounds__(256) void k_lstm_de(const int* __restrict__ tok, const float* __restrict__ dX, const float* __restrict__ E, int npos, int de,
-                                                 float* __restrict__ dE) {
-    __shared__ unsigned long long found[4];
-    const int v = blockIdx.x, tid = threadIdx.x;
-    for (int c0 = 0; c0 < de; c0 += 1024) {
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        if (v != 0) {
-            for (int p0 = 0; p0 < npos; p0 += 256) {
-                const bool hit = p0 + tid < npos && tok[p0 + tid] == v;
-                const unsigned long long m = __ballot(hit);
-                if ((tid & 63) == 0) found[tid >> 6] = m;
-                __syncthreads();
-                for (int w = 0; w < 4; ++w) {
-                    unsigned long long mm = found[w];
-                    while (mm) {
-                        const int b = __ffsll((long long)mm) - 1;
-                        mm &= mm - 1;
-                        const float* src = dX + (size_t)(p0 + 64 * w + b) * de;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) { const int c = c0 + tid + 256 * k; if (c < de) acc[k] += src[c]; }
-                    }
-                }
-                __syncthreads();
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int c = c0 + tid + 256 * k;
-            if (c >= de) continue;
-            float out = 0.f;
-            if (v != 0) { const float th = tanhf(E[(size_t)v * de + c]); out = acc[k] * (1.f - th * th); }
-            dE[(size_t)v * de + c] = out;
-        }
-    }
-}
-
 extern "C" {
-struct Lstm2TrainLayout { size_t perm, lens, lens_tmp, n_t, tok, h[2], c[2], gates[2], dg[2], dcf[2], dx, total; };
+struct Lstm2TrainLayout { RnnPlanOff plan; size_t tok, h[2], c[2], gates[2], dg[2], dcf[2], dx, total; };
 
 static Lstm2TrainLayout lstm2_train_layout(int B, int T, int emb, int H) {
     Lstm2TrainLayout w{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+    WsCarver c;
     const size_t pairs = (size_t)B * T, Hp = pad_to(H, GEMM_BK);
-    w.perm = take((size_t)B * 4); w.lens = take((size_t)B * 4); w.lens_tmp = take((size_t)B * 4); w.n_t = take(LSTM_MAX_T * 4);
-    w.tok = take(pairs * 4);
+    w.plan = c.take_plan(B);
+    w.tok = c.take(pairs * 4);
     for (int l = 0; l < 2; ++l) {
-        w.h[l] = take(pairs * H * 4); w.c[l] = take(pairs * H * 4);
-        w.gates[l] = take(pairs * 4 * Hp * 4); w.dg[l] = take(pairs * 4 * Hp * 4);
-        w.dcf[l] = take((size_t)B * H * 4);
+        w.h[l] = c.take(pairs * H * 4); w.c[l] = c.take(pairs * H * 4);
+        w.gates[l] = c.take(pairs * 4 * Hp * 4); w.dg[l] = c.take(pairs * 4 * Hp * 4);
+        w.dcf[l] = c.take((size_t)B * H * 4);
     }
-    w.dx = take(pairs * emb * 4);
-    w.total = off;
+    w.dx = c.take(pairs * emb * 4);
+    w.total = c.off;
     return w;
 }
 
@@ -433,7 +210,7 @@ static bool lstm2_train_dims_ok(long long B, long long T, long long emb, long lo
     const long long Hp = pad_to((int)H, GEMM_BK), wide = H > emb ? H : emb;
     if (8 * Hp >= (1ll << 30)) return false;                                                   // k extents and column offsets are ints
     if (2 * cdiv(B, LB_BM) * cdiv(wide, LB_BN) >= (1ll << 28)) return false;                   // sweep (two layers) / dX grids
-    return cdiv(4 * Hp, LW_BM) * cdiv(wide, LW_BN) < (1ll << 28);                              // weight-gradient grids
+    return cdiv(4 * Hp, RNN_DW_BM) * cdiv(wide, RNN_DW_BN) < (1ll << 28);                              // weight-gradient grids
 }
 
 size_t ncx_lstm2_packed_t_bytes(int32_t emb, int32_t H) {
@@ -448,7 +225,7 @@ size_t ncx_lstm2_train_workspace_bytes(int32_t B, int32_t T, int32_t emb, int32_
 
 int ncx_lstm2_pack_t(const float* w_ih0, const float* w_hh0, const float* w_ih1, const float* w_hh1, int32_t emb, int32_t H, float* packed_t,
                      void* stream) {
-    if (!w_ih0 || !w_hh0 || !w_ih1 || !w_hh1 || !packed_t || ((uintptr_t)packed_t & 15) || !lstm2_train_dims_ok(1, 1, emb, H)) return -1;
+    if (!lstm2_train_dims_ok(1, 1, emb, H) || !rnn_ptrs_ok({w_ih0, w_hh0, w_ih1, w_hh1}, packed_t)) return -1;
     const LstmPackT p = lstm_pack_t(emb, H);
     hipLaunchKernelGGL(k_lstm_pack_t, dim3((unsigned)(8 * p.Hp / 32), (unsigned)((2 * p.rows_h + p.rows_x) / 32)), dim3(256), 0, (hipStream_t)stream,
                        w_ih0, w_hh0, w_ih1, w_hh1, emb, H, packed_t);
@@ -458,29 +235,27 @@ int ncx_lstm2_pack_t(const float* w_ih0, const float* w_hh0, const float* w_ih1,
 
 int ncx_lstm2_train_forward(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t emb, int32_t H, const float* packed,
                             void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream) {
-    if (!wids || !E || !packed || !workspace || !q_out || !bad_id_flag) return -1;
-    if (!lstm2_train_dims_ok(B, T, emb, H) || V1 < 1 || ((uintptr_t)packed & 15)) return -1;
+    if (!lstm2_train_dims_ok(B, T, emb, H) || V1 < 1) return -1;
     const Lstm2TrainLayout w = lstm2_train_layout(B, T, emb, H);
-    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) return -1;
+    if (!rnn_args_ok({wids, E, q_out, bad_id_flag}, packed, workspace, workspace_bytes, w.total)) return -1;
     char* ws = (char*)workspace;
-    const Lstm2Plan plan{(int*)(ws + w.perm), (int*)(ws + w.lens), (int*)(ws + w.lens_tmp), (int*)(ws + w.n_t)};
     const LstmKeep<true> keep{(float*)(ws + w.h[0]), (float*)(ws + w.h[1]), (float*)(ws + w.c[0]), (float*)(ws + w.c[1]),
                               (float*)(ws + w.gates[0]), (float*)(ws + w.gates[1]), B, pad_to(H, GEMM_BK)};
-    return lstm2_forward_keep(wids, B, T, E, V1, emb, H, packed, plan, keep, q_out, bad_id_flag, (hipStream_t)stream);
+    return lstm2_forward_keep(wids, B, T, E, V1, emb, H, packed, w.plan.at(ws), keep, q_out, bad_id_flag, (hipStream_t)stream);
 }
 
 int ncx_lstm2_train_backward(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t emb, int32_t H, const float* packed_t,
                              void* workspace, size_t workspace_bytes, const float* dq_out, float* dW_ih0, float* dW_hh0, float* db_ih0,
                              float* db_hh0, float* dW_ih1, float* dW_hh1, float* db_ih1, float* db_hh1, float* dE, void* stream) {
-    if (!wids || !E || !packed_t || !workspace || !dq_out || !dW_ih0 || !dW_hh0 || !db_ih0 || !db_hh0 || !dW_ih1 || !dW_hh1 || !db_ih1 || !db_hh1)
-        return -1;
-    if (!lstm2_train_dims_ok(B, T, emb, H) || V1 < 1 || ((uintptr_t)packed_t & 15)) return -1;
+    if (!lstm2_train_dims_ok(B, T, emb, H) || V1 < 1) return -1;
     const Lstm2TrainLayout w = lstm2_train_layout(B, T, emb, H);
-    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) return -1;
+    if (!rnn_args_ok({wids, E, dq_out, dW_ih0, dW_hh0, db_ih0, db_hh0, dW_ih1, dW_hh1, db_ih1, db_hh1}, packed_t, workspace, workspace_bytes, w.total))
+        return -1;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const LstmPackT pk = lstm_pack_t(emb, H);
-    const int* n_t = (const int*)(ws + w.n_t);
+    const RnnPlan plan = w.plan.at(ws);
+    const int* n_t = plan.n_t;
     int* tok = (int*)(ws + w.tok);
     const float* hst[2] = {(const float*)(ws + w.h[0]), (const float*)(ws + w.h[1])};
 
@@ -489,36 +264,29 @@ int ncx_lstm2_train_backward(const int32_t* wids, int32_t B, int32_t T, const fl
     a.c0 = (const float*)(ws + w.c[0]); a.c1 = (const float*)(ws + w.c[1]);
     a.dg0 = (float*)(ws + w.dg[0]); a.dg1 = (float*)(ws + w.dg[1]); a.dcf0 = (float*)(ws + w.dcf[0]); a.dcf1 = (float*)(ws + w.dcf[1]);
     a.w0 = packed_t; a.w1 = packed_t + pk.off1; a.wx = packed_t + pk.offx;
-    a.perm = (const int*)(ws + w.perm); a.lens = (const int*)(ws + w.lens); a.n_t = n_t; a.dq_out = dq_out; a.dX = (float*)(ws + w.dx);
+    a.perm = plan.perm; a.lens = plan.lens; a.n_t = n_t; a.dq_out = dq_out; a.dX = (float*)(ws + w.dx);
     a.B = B; a.T = T; a.H = H; a.Hp = pk.Hp; a.emb = emb; a.tiles_m = (int)cdiv(B, LB_BM); a.grid1 = a.tiles_m * (int)cdiv(H, LB_BN);
     for (int u = T - 1; u >= -1; --u) {        // every launch is issued: how many rows it has is known on the device only
         const int layers = (u >= 0) + (u + 1 < T);
         hipLaunchKernelGGL(k_lstm_bgemm<false>, dim3((unsigned)(layers * a.grid1)), dim3(256), 0, s, a, u, u >= 0 ? 1 : 0);
         NCX_HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_lstm_tok, dim3((unsigned)cdiv((long long)B * T, 256)), dim3(256), 0, s, wids, B, T, V1, a.perm, n_t, tok);
-    NCX_HIP_TRY(hipGetLastError());
+    NCX_HIP_TRY(rnn_tok(wids, B, T, V1, a.perm, n_t, tok, s));
     if (dE) {
         hipLaunchKernelGGL(k_lstm_bgemm<true>, dim3((unsigned)(a.tiles_m * cdiv(emb, LB_BN)), (unsigned)T), dim3(256), 0, s, a, 0, 0);
         NCX_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_lstm_de, dim3((unsigned)V1), dim3(256), 0, s, tok, a.dX, E, B * T, emb, dE);
-        NCX_HIP_TRY(hipGetLastError());
+        NCX_HIP_TRY(rnn_embed_grad(tok, a.dX, E, B, T, V1, emb, dE, s));
     }
-    LwArgs d{};
-    d.tok = tok; d.n_t = n_t; d.B = B; d.T = T; d.H = H; d.Hp = pk.Hp; d.tiles_m = (int)cdiv(4 * pk.Hp, LW_BM);
-    const unsigned grid_h = (unsigned)(d.tiles_m * cdiv(H, LW_BN));
+    RnnDwArgs d{};
+    d.tok = tok; d.n_t = n_t; d.B = B; d.T = T; d.ld = d.kp = 4 * pk.Hp; d.units = H; d.unitsp = pk.Hp;      // (kp is a multiple of 128: whole gate-row tiles)
     d.dG = a.dg0; d.X = hst[0]; d.out = dW_hh0; d.cols = H; d.xshift = 1;
-    hipLaunchKernelGGL(k_lstm_dw<false>, dim3(grid_h), dim3(256), 0, s, d);
-    NCX_HIP_TRY(hipGetLastError());
+    NCX_HIP_TRY(rnn_dw(d, false, false, s));
     d.dG = a.dg1; d.X = hst[0]; d.out = dW_ih1; d.xshift = 0;
-    hipLaunchKernelGGL(k_lstm_dw<false>, dim3(grid_h), dim3(256), 0, s, d);
-    NCX_HIP_TRY(hipGetLastError());
+    NCX_HIP_TRY(rnn_dw(d, false, false, s));
     d.X = hst[1]; d.out = dW_hh1; d.xshift = 1;
-    hipLaunchKernelGGL(k_lstm_dw<false>, dim3(grid_h), dim3(256), 0, s, d);
-    NCX_HIP_TRY(hipGetLastError());
+    NCX_HIP_TRY(rnn_dw(d, false, false, s));
     d.dG = a.dg0; d.X = E; d.out = dW_ih0; d.cols = emb; d.xshift = 0;
-    hipLaunchKernelGGL(k_lstm_dw<true>, dim3((unsigned)(d.tiles_m * cdiv(emb, LW_BN))), dim3(256), 0, s, d);
-    NCX_HIP_TRY(hipGetLastError());
+    NCX_HIP_TRY(rnn_dw(d, true, true, s));                                     // x = tanh(E[tok])
     hipLaunchKernelGGL(k_lstm_dbias, dim3((unsigned)(2 * 4 * pk.Hp / 32)), dim3(256), 0, s, a.dg0, a.dg1, n_t, B, T, H, pk.Hp, db_ih0, db_hh0,
                        db_ih1, db_hh1);
     NCX_HIP_TRY(hipGetLastError());
