@@ -291,6 +291,41 @@ int ncx_mlb_forward(const ncx_dims* d, const float* feats, const int32_t* img_id
                     const ncx_mlb_params* m, void* workspace, size_t workspace_bytes,
                     float* z_orig, float* z_knns, float* a_knns, float* a_orig, void* stream);
 
+/* ---- the MLB attention model (MLBAtt, vqa/models/att.py:11-192) in eval mode, below the question encoder -------------------
+ * Every dropout is the identity.  V[b] = feats[img_idx[b]] is the image's NCHW map [dv, P] (P = W H positions, p = w H + h), read
+ * in place: never transposed or copied.
+ *   x_q[b]        = act_q_att(q[b] Wq_att^T + bq_att)                                                       [B, dh_att]
+ *   x_att[b,p,h]  = act_mm(act_v_att(sum_c V[b,c,p] Wv_att[h,c] + bv_att[h]) * x_q[b,h])                    (never stored)
+ *   att[b,g,:]    = softmax over p of (sum_h Wa[g,h] x_att[b,p,h] + ba[g])                                  [B, G, P]
+ *   v_att[b,g,c]  = sum_p att[b,g,p] V[b,c,p]
+ *   x_v[b, g dh_f + n] = act_v(v_att[b,g] Wg[g]^T + bg[g])        x_qf = act_q(q Wqf^T + bqf)               [B, G dh_f]
+ *   logits        = act_c(x_v * x_qf) Wc^T + bc                                                             [B, A]
+ * The partial position logits of the dh_att tiles go to a slab and are summed in a fixed order (no float atomics): two calls
+ * on the same inputs are bit-identical. */
+typedef struct ncx_mlb_att_dims {
+    int32_t B, P, dv, dq, dh_att, G, dh_f, A, n_img;   /* B, P, n_img >= 1; 1 <= G <= 8; every width >= 4 */
+} ncx_mlb_att_dims;
+typedef struct ncx_mlb_att_params {
+    const float* wv_att; const float* bv_att;   /* conv_v_att.weight [dh_att, dv(,1,1)], .bias [dh_att]                    */
+    const float* wq_att; const float* bq_att;   /* linear_q_att.weight [dh_att, dq], .bias [dh_att]                        */
+    const float* wa;     const float* ba;       /* conv_att.weight [G, dh_att(,1,1)], .bias [G]                            */
+    const float* wg;     const float* bg;       /* list_linear_v_fusion.{g} stacked: [G, dh_f, dv], [G, dh_f]              */
+    const float* wqf;    const float* bqf;      /* linear_q_fusion.weight [G dh_f, dq], .bias [G dh_f]                     */
+    const float* wc;     const float* bc;       /* linear_classif.weight [A, G dh_f], .bias [A]                            */
+    int32_t act_v_att, act_q_att, act_mm;       /* attention.activation_v / _q / _mm: 0 none, 2 tanh                       */
+    int32_t act_v, act_q, act_c;                /* fusion.activation_v / _q, classif.activation: 0 none, 2 tanh            */
+} ncx_mlb_att_params;
+
+/* 0 for invalid dims or parameters. */
+size_t ncx_mlb_att_workspace_bytes(const ncx_mlb_att_dims* d, const ncx_mlb_att_params* m);
+
+/* feats [n_img, dv, P] (the table of NCHW maps); img_idx [B] int32 (an id outside [0, n_img) is clamped); q_emb [B, dq];
+ * logits [B, A]; att [B, G, P] (always written).  NULL pointers and dims are rejected before any launch; no allocation; the
+ * workspace is 256-byte aligned; every launch is enqueued on `stream`. */
+int ncx_mlb_att_forward(const ncx_mlb_att_dims* d, const float* feats, const int32_t* img_idx, const float* q_emb,
+                        const ncx_mlb_att_params* m, void* workspace, size_t workspace_bytes,
+                        float* logits, float* att, void* stream);
+
 /* ---- brute-force k nearest neighbours of feature rows --------------------------------------
  * Replaces knn.py:41-58 of the reference (sklearn NearestNeighbors(n_neighbors=k).fit(table).kneighbors(queries),
  * brute force, euclidean).  For each of the nq query rows: the k rows of `table` [n, dv] with the smallest

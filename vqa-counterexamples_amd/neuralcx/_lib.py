@@ -19,7 +19,7 @@ NCX_F_BF16 = 16       # BASELINE configs[4]: bf16 operands for the two dominant 
 
 EXPORTS = ("ncx_input_size", "ncx_workspace_bytes", "ncx_forward", "ncx_forward_phase", "ncx_loss_rank", "ncx_backward", "ncx_backward_phase",
            "ncx_adam_step", "ncx_version", "ncx_profile_begin", "ncx_profile_end", "ncx_plan_query",
-           "ncx_vqa_workspace_bytes", "ncx_vqa_forward", "ncx_mlb_workspace_bytes", "ncx_mlb_forward", "ncx_knn_workspace_bytes", "ncx_knn_status_offset", "ncx_knn", "ncx_cosine_gram_workspace_bytes", "ncx_cosine_gram", "ncx_semantic_scores",
+           "ncx_vqa_workspace_bytes", "ncx_vqa_forward", "ncx_mlb_workspace_bytes", "ncx_mlb_forward", "ncx_mlb_att_workspace_bytes", "ncx_mlb_att_forward", "ncx_knn_workspace_bytes", "ncx_knn_status_offset", "ncx_knn", "ncx_cosine_gram_workspace_bytes", "ncx_cosine_gram", "ncx_semantic_scores",
            "ncx_similarity_scores",
            "ncx_gru_packed_bytes", "ncx_gru_pack", "ncx_gru_workspace_bytes", "ncx_gru_encode",
            "ncx_gru_train_workspace_bytes", "ncx_gru_packed_t_bytes", "ncx_gru_pack_t", "ncx_gru_train_forward", "ncx_gru_train_backward",
@@ -76,6 +76,15 @@ class NcxVqaTrainDims(C.Structure):
 class NcxMlbParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("wv", "bv", "wq", "bq", "wc", "bc")] + \
                [(n, C.c_int32) for n in ("dh", "act_v", "act_q", "act_c")]
+
+
+class NcxMlbAttDims(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "P", "dv", "dq", "dh_att", "G", "dh_f", "A", "n_img")]
+
+
+class NcxMlbAttParams(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("wv_att", "bv_att", "wq_att", "bq_att", "wa", "ba", "wg", "bg", "wqf", "bqf", "wc", "bc")] + \
+               [(n, C.c_int32) for n in ("act_v_att", "act_q_att", "act_mm", "act_v", "act_q", "act_c")]
 
 
 class NcxMlbGrads(C.Structure):
@@ -159,6 +168,11 @@ def lib():
     L.ncx_mlb_forward.restype = C.c_int
     L.ncx_mlb_forward.argtypes = [C.POINTER(NcxDims), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NcxMlbParams), C.c_void_p,
                                   C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ncx_mlb_att_workspace_bytes.restype = C.c_size_t
+    L.ncx_mlb_att_workspace_bytes.argtypes = [C.POINTER(NcxMlbAttDims), C.POINTER(NcxMlbAttParams)]
+    L.ncx_mlb_att_forward.restype = C.c_int
+    L.ncx_mlb_att_forward.argtypes = [C.POINTER(NcxMlbAttDims), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NcxMlbAttParams), C.c_void_p,
+                                      C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ncx_knn_workspace_bytes.restype = C.c_size_t
     L.ncx_knn_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
     L.ncx_knn_status_offset.restype = C.c_size_t

@@ -360,6 +360,136 @@ def vqa_forward(feats: torch.Tensor, img_idx: torch.Tensor, q_emb: torch.Tensor,
     return a_o, z_o, a_k, z_k
 
 
+MLB_ATT_FIELDS = ("wv_att", "bv_att", "wq_att", "bq_att", "wa", "ba", "wg", "bg", "wqf", "bqf", "wc", "bc")
+MLB_ATT_ACTS = ("act_v_att", "act_q_att", "act_mm", "act_v", "act_q", "act_c")
+
+
+def mlb_att_acts(opt) -> Optional[Dict[str, int]]:
+    """The six activation codes of ncx_mlb_att_params for a model's options (0 absent, 2 tanh); None when one is neither."""
+    att, fus, cla = opt["attention"], opt["fusion"], opt.get("classif", {})
+    names = (att.get("activation_v"), att.get("activation_q"), att.get("activation_mm"), fus.get("activation_v"), fus.get("activation_q"),
+             cla.get("activation"))
+    code = {None: 0, "tanh": 2}
+    if any(a not in code for a in names):
+        return None
+    return {k: code[a] for k, a in zip(MLB_ATT_ACTS, names)}
+
+
+class MlbAttWeights:
+    """An MLBAtt's frozen parameters as ncx_mlb_att_forward wants them: contiguous fp32, the two 1 x 1 convolutions as matrices,
+    the G glimpse Linears stacked ([G, dh_f, dv], [G, dh_f]).  Built once per weight set; MLBAtt rebuilds it when a parameter changes."""
+
+    def __init__(self, model):
+        acts = mlb_att_acts(model.opt)
+        if acts is None:
+            raise _lib.NcxError("ncx_mlb_att_forward supports activations in {none, tanh}")
+        c = lambda t: t.detach().float().contiguous()
+        lin = list(model.list_linear_v_fusion)
+        self.t = dict(wv_att=c(model.conv_v_att.weight.flatten(1)), bv_att=c(model.conv_v_att.bias),
+                      wq_att=c(model.linear_q_att.weight), bq_att=c(model.linear_q_att.bias),
+                      wa=c(model.conv_att.weight.flatten(1)), ba=c(model.conv_att.bias),
+                      wg=c(torch.stack([l.weight for l in lin])), bg=c(torch.stack([l.bias for l in lin])),
+                      wqf=c(model.linear_q_fusion.weight), bqf=c(model.linear_q_fusion.bias),
+                      wc=c(model.linear_classif.weight), bc=c(model.linear_classif.bias))
+        self.acts = acts
+        self._set_dims()
+
+    @classmethod
+    def from_tensors(cls, t: Dict[str, torch.Tensor], **acts):
+        """The same object around caller-owned tensors in the stacked layout.  Activation codes (0 none, 2 tanh) default to tanh."""
+        self = cls.__new__(cls)
+        self.t = dict(t)
+        self.acts = {k: int(acts.get(k, 2)) for k in MLB_ATT_ACTS}
+        self._set_dims()
+        return self
+
+    def _set_dims(self):
+        t = self.t
+        self.dh_att, self.dv = t["wv_att"].shape
+        self.dq = t["wq_att"].shape[1]
+        self.G, self.dh_f = t["wg"].shape[:2]
+        self.A = t["wc"].shape[0]
+        want = dict(wv_att=(self.dh_att, self.dv), bv_att=(self.dh_att,), wq_att=(self.dh_att, self.dq), bq_att=(self.dh_att,),
+                    wa=(self.G, self.dh_att), ba=(self.G,), wg=(self.G, self.dh_f, self.dv), bg=(self.G, self.dh_f),
+                    wqf=(self.G * self.dh_f, self.dq), bqf=(self.G * self.dh_f,), wc=(self.A, self.G * self.dh_f), bc=(self.A,))
+        for k, shp in want.items():
+            if tuple(t[k].shape) != shp:
+                raise _lib.NcxError("MlbAttWeights: %s has shape %s, expected %s" % (k, tuple(t[k].shape), shp))
+
+    def dims(self, B: int, P: int, n_img: int) -> _lib.NcxMlbAttDims:
+        d = _lib.NcxMlbAttDims()
+        d.B, d.P, d.dv, d.dq, d.dh_att, d.G, d.dh_f, d.A, d.n_img = B, P, self.dv, self.dq, self.dh_att, self.G, self.dh_f, self.A, n_img
+        return d
+
+    def c_struct(self, check_device=True):
+        m = _lib.NcxMlbAttParams()
+        for k in MLB_ATT_FIELDS:
+            setattr(m, k, _ptr(self.t[k], torch.float32, k) if check_device else C.c_void_p(self.t[k].data_ptr()))
+        for k, v in self.acts.items():
+            setattr(m, k, v)
+        return m
+
+
+def mlb_att_weights(module) -> MlbAttWeights:
+    """The weights object of the HIP attention forward for an MLBAtt (vqa/models/att.py)."""
+    return MlbAttWeights(module)
+
+
+def mlb_att_dims_ok(mw: MlbAttWeights, B: int, P: int, n_img: int) -> bool:
+    """The library's own check of the shape (host only: no launch, no device access)."""
+    d = mw.dims(B, P, n_img)
+    return _lib.lib().ncx_mlb_att_workspace_bytes(C.byref(d), C.byref(mw.c_struct(check_device=False))) != 0
+
+
+_MLB_ATT_WS: Dict[torch.device, tuple] = {}          # device -> (shape key, workspace): the last shape's buffer is reused
+
+
+def mlb_att_workspace(mw: MlbAttWeights, B: int, P: int, n_img: int, device) -> torch.Tensor:
+    """The cached workspace of ncx_mlb_att_forward for this shape on `device` (calls on one stream are ordered, so they share it)."""
+    d, m = mw.dims(B, P, n_img), mw.c_struct()
+    need = _lib.lib().ncx_mlb_att_workspace_bytes(C.byref(d), C.byref(m))
+    if need == 0:
+        raise _lib.NcxError("ncx_mlb_att_workspace_bytes: invalid dims")
+    device = torch.device(device)
+    key = tuple(getattr(d, f) for f, _ in d._fields_ if f != "n_img")
+    hit = _MLB_ATT_WS.get(device)
+    if hit is None or hit[0] != key or hit[1].numel() < need + 256:
+        hit = _MLB_ATT_WS[device] = (key, torch.empty(need + 256, dtype=torch.uint8, device=device))
+    return hit[1]
+
+
+def mlb_att_forward(feats: torch.Tensor, img_idx: Optional[torch.Tensor], q_emb: torch.Tensor, mw: MlbAttWeights, ws=None):
+    """MLBAtt.forward below the question encoder, in eval mode (ncx_mlb_att_forward; reference vqa/models/att.py:39-163), on the
+    current stream.  feats: the table of NCHW maps [n_img, dv, W, H] (or [n_img, dv, P]), read in place; img_idx [B] int32 picks
+    each question's image, None = the dense input (question b reads feats[b]).  q_emb [B, dq].
+    -> (logits [B, A], att [B, G, P]); att[:, g] is the module's list_att[g], position p = w H + h."""
+    if feats.dim() not in (3, 4):
+        raise ValueError("feats must be [n_img, dv, W, H] or [n_img, dv, P], got %s" % (tuple(feats.shape),))
+    n_img, dv = feats.shape[:2]
+    P = feats[0, 0].numel()
+    dev = feats.device
+    B = q_emb.shape[0]
+    if img_idx is None:
+        if n_img != B:
+            raise ValueError("dense input: %d maps for %d questions" % (n_img, B))
+        img_idx = torch.arange(B, dtype=torch.int32, device=dev)
+    if img_idx.shape != (B,):
+        raise ValueError("img_idx must be [B] = [%d], got %s" % (B, tuple(img_idx.shape)))
+    if dv != mw.dv or q_emb.shape[1] != mw.dq:
+        raise ValueError("feats / q_emb widths (%d, %d) do not match the weights (%d, %d)" % (dv, q_emb.shape[1], mw.dv, mw.dq))
+    d, m = mw.dims(B, P, n_img), mw.c_struct()
+    if ws is None:
+        ws = mlb_att_workspace(mw, B, P, n_img, dev)
+    logits = torch.empty(B, mw.A, dtype=torch.float32, device=dev)
+    att = torch.empty(B, mw.G, P, dtype=torch.float32, device=dev)
+    p, n = _ws_ptr(ws)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().ncx_mlb_att_forward(C.byref(d), _ptr(feats, torch.float32, "feats"), _ptr(img_idx, torch.int32, "img_idx"),
+                                                  _ptr(q_emb, torch.float32, "q_emb"), C.byref(m), p, n, C.c_void_p(logits.data_ptr()),
+                                                  C.c_void_p(att.data_ptr()), _stream()), "ncx_mlb_att_forward")
+    return logits, att
+
+
 def cosine_gram(emb: torch.Tensor) -> torch.Tensor:
     """sklearn cosine_similarity(emb) on the device (ncx_cosine_gram; reference cx.py:174-175): [A, da] fp32 -> [A, A] fp32.
     A zero row stays zero (its similarities are 0, the diagonal included), as sklearn's normalisation leaves it."""

@@ -1,5 +1,6 @@
 """Trains a no-attention VQA model (model.arch: MutanNoAtt, the default YAML, or MLBNoAtt): the producer of
-<logs.dir_logs>/best_model.pth.tar, the checkpoint counterexamples.py and contrastive.py load with pretrained_vqa.
+<logs.dir_logs>/best_model.pth.tar, the checkpoint counterexamples.py and contrastive.py load with pretrained_vqa.  Also trains the
+MLBAtt attention model (options/vqa2/mlb_att_train.yaml, --synthetic only) on the module route: see below.
 
 Keeps the reference's flags where they apply (train.py:20-67), its loop (vqa/lib/engine.py:6-100: CrossEntropyLoss, Adam over the
 parameters that require grad, acc1 / acc5) and its checkpoint files (train.py:290-367: <dir_logs>/{ckpt,best}_{info,model,optim}
@@ -14,6 +15,9 @@ Three routes:
                             forward and backward through time run in HIP too (GRUEncoder.use_hip_train, neuralcx.vqa_train.GruTrainFunction);
                             --hip_2lstm_train is the same for the 2-lstm encoder (TwoLSTM.use_hip_bptt, neuralcx.vqa_train.LstmTrainFunction).
   --no_hip                  the same loop on the plain PyTorch modules (also runs on a CPU).
+model.arch MLBAtt: training is the module under torch autograd (there is no HIP backward or engine for the attention model, with or
+without --freeze_seq2vec); evaluate() / --evaluate run the module in eval mode under no_grad, i.e. its HIP forward
+(ncx_mlb_att_forward), unless --no_hip.  The images are a seeded synthetic attention table [syn_images, dim_v, syn_grid, syn_grid].
 """
 import argparse
 import json
@@ -34,6 +38,7 @@ from vqa import models                                       # noqa: E402
 from vqa.lib import utils                                    # noqa: E402
 
 CKPT_PARTS = ("info", "model", "optim")
+ATT_ARCHS = ("MLBAtt",)                                      # models whose image input is the NCHW map [B, dim_v, W, H]
 
 
 def build_parser():
@@ -55,6 +60,7 @@ def build_parser():
     p.add_argument("--syn_examples", type=int, default=8192)
     p.add_argument("--syn_images", type=int, default=1024)
     p.add_argument("--syn_vocab", type=int, default=1000)
+    p.add_argument("--syn_grid", type=int, default=14, help="attention archs only: the synthetic maps are [dim_v, syn_grid, syn_grid]")
     p.add_argument("--path_trainset", type=str, default=None, help="overrides vqa.path_trainset of the YAML")
     p.add_argument("--path_features", type=str, default=None, help="overrides coco.path_features of the YAML")
     p.add_argument("--freeze_seq2vec", action="store_true", help="freeze the question encoder: q_emb once per split, the whole step in HIP")
@@ -88,13 +94,22 @@ class _Split:
 
 def load_data(args, opt, dev):
     """-> (train split, val split, vocab_words, vocab_answers)"""
+    att = opt["model"].get("arch") in ATT_ARCHS
+    if att and not args.synthetic:
+        raise SystemExit("train.py: model.arch %s reads attention tables (hdf5 'att', [n_img, dim_v, 14, 14]); real-data attention tables "
+                         "are not supported, use --synthetic" % opt["model"]["arch"])
     if args.synthetic:
         from neuralcx.synth import SyntheticVQA
-        s = SyntheticVQA(n_examples=args.syn_examples, n_img=args.syn_images, dv=opt["model"]["fusion"]["dim_v"], vocab=args.syn_vocab,
+        dv = opt["model"]["dim_v"] if att else opt["model"]["fusion"]["dim_v"]
+        s = SyntheticVQA(n_examples=args.syn_examples, n_img=args.syn_images, dv=dv, vocab=args.syn_vocab,
                          T=opt["vqa"].get("maxlength", 26), A=opt["vqa"]["nans"], seed=1234, device=dev)
+        feats = s.feats
+        if att:             # the attention table: every image row spread over a syn_grid x syn_grid map by seeded factors in [0, 2)
+            g = torch.Generator(device=dev).manual_seed(1234 + 1)
+            feats = s.feats[:, :, None, None] * (2.0 * torch.rand(args.syn_images, dv, args.syn_grid, args.syn_grid, generator=g, device=dev))
         n = s.n_train
-        return (_Split(s.feats, s.img_idx[:n], s.question_wids[:n], s.answer_aids[:n]),
-                _Split(s.feats, s.img_idx[n:], s.question_wids[n:], s.answer_aids[n:]), s.vocab_words, s.vocab_answers)
+        return (_Split(feats, s.img_idx[:n], s.question_wids[:n], s.answer_aids[:n]),
+                _Split(feats, s.img_idx[n:], s.question_wids[n:], s.answer_aids[n:]), s.vocab_words, s.vocab_answers)
     from neuralcx import formats
     vqa_dir = args.path_trainset or opt["vqa"].get("path_trainset")
     feat_dir = args.path_features or opt["coco"].get("path_features")
@@ -134,8 +149,15 @@ class Trainer:
         self.freeze = args.freeze_seq2vec
         from neuralcx import vqa_train
         mlb = opt["model"].get("arch") == "MLBNoAtt"
+        self.att = opt["model"].get("arch") in ATT_ARCHS
         route_for, engine_cls = (vqa_train.mlb_route_for, vqa_train.MlbTrainEngine) if mlb else (vqa_train.route_for, vqa_train.VqaTrainEngine)
-        self.route = "torch path: --no_hip" if args.no_hip else route_for(opt["model"])
+        if self.att:            # no HIP training step for the attention model: the module trains under autograd, its eval forward is HIP
+            self.route = "torch path: --no_hip" if args.no_hip else \
+                "module under torch autograd; eval-mode forward in HIP (ncx_mlb_att_forward)%s" % (
+                    "; --freeze_seq2vec: the encoder is frozen, there is no HIP engine for this model" if self.freeze else "")
+            self.model.use_hip = not args.no_hip
+        else:
+            self.route = "torch path: --no_hip" if args.no_hip else route_for(opt["model"])
         self.hip = self.route == "hip"
         self.engine = None
         if self.freeze or opt["model"]["seq2vec"].get("fixed_emb"):
@@ -146,7 +168,8 @@ class Trainer:
             self.engine = engine_cls.from_options(opt["model"], len(va), lr=self.lr, device=self.dev, seed=args.seed)
             self.engine.load_state_dict(self.model.state_dict())          # nn.Linear's init under --seed; seq2vec.* carried through
         else:
-            self.model.use_hip_train = self.hip
+            if not self.att:
+                self.model.use_hip_train = self.hip
             self.hip_seq2vec = bool(args.hip_seq2vec_train and self.hip and hasattr(type(self.model.seq2vec), "use_hip_train"))
             if args.hip_seq2vec_train and not self.hip_seq2vec:
                 raise SystemExit("train.py: --hip_seq2vec_train needs the HIP route and the GRU encoder (%s); the 2-lstm encoder trains in HIP "
@@ -185,7 +208,9 @@ class Trainer:
         v = split.feats.index_select(0, idx.long())
         wids = split.wids.index_select(0, sel)
         with torch.set_grad_enabled(train):
-            if self.freeze:                                       # (torch path only: the HIP route with a frozen encoder is the engine)
+            if self.freeze and self.att:
+                logits = self.model.forward_from_q(v, self.q_emb_of(split).index_select(0, sel))
+            elif self.freeze:                                     # (torch path only: the HIP route with a frozen encoder is the engine)
                 logits = self.model._classif(self.model._fusion(v, self.q_emb_of(split).index_select(0, sel)))
             else:
                 logits = self.model(v, wids)

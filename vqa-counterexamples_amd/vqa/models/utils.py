@@ -3,9 +3,10 @@ reference's nn.DataParallel wrapper (immediately unwrapped by counterexamples.py
 data_parallel=True is accepted and ignored."""
 import copy
 
+from .att import MLBAtt
 from .noatt import MLBNoAtt, MutanNoAtt
 
-_REGISTRY = {"MutanNoAtt": MutanNoAtt, "MLBNoAtt": MLBNoAtt}
+_REGISTRY = {"MutanNoAtt": MutanNoAtt, "MLBNoAtt": MLBNoAtt, "MLBAtt": MLBAtt}
 model_names = sorted(_REGISTRY)
 
 
