@@ -208,6 +208,10 @@ int ncx_backward_phase(const ncx_dims* d, const ncx_inputs* in, const ncx_params
 #define NCX_WS_DGT 1
 #define NCX_WS_H1 2     /* diagnostics / tests: post-dropout activations of linear_1, [B*K, H] (valid after ncx_forward) */
 #define NCX_WS_DPRE1 3  /* diagnostics / tests: gradient of linear_1's pre-activations, [B*K, H] (valid after ncx_backward) */
+/* diagnostics / tests: int32 [A + 1], valid after ncx_backward (and phase 1) on the fp32 path: the answer ids that occur in the batch's
+ * answer_aids ascending, then the others ascending, and in [A] how many occur -- the row order of the answer_embedding gradient's product,
+ * whose row tiles without an answer of the batch skip the dGgt^T operand (all zeros there).  Size 0 where the product keeps the full form. */
+#define NCX_WS_DE_PERM 4
 int ncx_ws_region(const ncx_dims* d, int32_t which, size_t* offset, size_t* bytes);
 
 /* NCX_F_FUSED_TAIL: replaces, in one pass over h_L, the tail of ncx_forward (`out`, cx.py:327), ncx_loss_rank

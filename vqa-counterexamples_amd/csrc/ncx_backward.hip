@@ -351,19 +351,60 @@ struct EmbPrepArgs {
     const float* dsh; const int* aid; float* dggtT;        // scatter
     const float* src[3]; float* dst[3]; long long lds_[3]; int cols[3], ldd[3], dcols[3], tile0[4];   // transposes: src [H][cols] -> dst [cols][ldd], dst cols < dcols written
     int B, H, A, Hp4;
+    int* perm;                                             // presence permutation (nullable): block 0 builds it, every other role moves up one block
 };
+// perm (ea.perm != NULL): perm[0 .. A) = the answer ids that occur in aid[0 .. B) ascending, then the others ascending; perm[A] = how many occur.
+// ONE block: a bitmap of the ids in LDS (atomicOr: the order of its updates cannot change it), a scan of the per-thread population counts,
+// then every thread places the ids of its bitmap words.  Rebuilt on every call, read by the dE launch that follows on the stream.
 // `fix` (valid: blocks beyond a.B + a.tile0[3]): the deferred split fix-up of the dW1[:, a_other] GEMM (64 x 64 tiles) rides along
 __global__ __launch_bounds__(256) void k_emb_prep(const EmbPrepArgs a, const FixupArgs fix, const Tn8ReduceArgs red) {
     __shared__ unsigned bits[NCX_SCATTER_MAX_B / 32 > 32 * 33 ? NCX_SCATTER_MAX_B / 32 : 32 * 33];     // scatter: id bitmap; transposes: a [32][33] tile
-    if ((int)blockIdx.x >= a.B + a.tile0[3]) {
-        const int id = blockIdx.x - (a.B + a.tile0[3]);
+    const int bx = (int)blockIdx.x - (a.perm ? 1 : 0);
+    if (bx < 0) {
+        __shared__ int scan[256];
+        static_assert(NCX_PERM_MAX_A / 32 <= (int)(sizeof(bits) / sizeof(bits[0])), "one bit per answer");
+        const int A = a.A, nw = (A + 31) / 32, per = (nw + 255) / 256, tid = threadIdx.x;
+        for (int w = tid; w < nw; w += 256) bits[w] = 0u;
+        __syncthreads();
+        for (int j = tid; j < a.B; j += 256) {
+            const int id = a.aid[j];
+            if ((unsigned)id < (unsigned)A) atomicOr(&bits[id >> 5], 1u << (id & 31));
+        }
+        __syncthreads();
+        const int w0 = min(tid * per, nw), w1 = min(w0 + per, nw);      // this thread's bitmap words
+        int cnt = 0;
+        for (int w = w0; w < w1; ++w) cnt += __popc(bits[w]);
+        scan[tid] = cnt;
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) {                        // inclusive scan over the 256 threads
+            const int v = tid >= off ? scan[tid - off] : 0;
+            __syncthreads();
+            scan[tid] += v;
+            __syncthreads();
+        }
+        const int n_present = scan[255];
+        int pos = scan[tid] - cnt;                                       // present ids below 32 w0
+        for (int w = w0; w < w1; ++w) {
+            const unsigned m = bits[w];
+            for (int bit = 0; bit < 32; ++bit) {
+                const int id = 32 * w + bit;
+                if (id >= A) break;
+                if ((m >> bit) & 1u) a.perm[pos++] = id;
+                else a.perm[n_present + (id - pos)] = id;                // id - pos: absent ids below id
+            }
+        }
+        if (tid == 0) a.perm[A] = n_present;
+        return;
+    }
+    if (bx >= a.B + a.tile0[3]) {
+        const int id = bx - (a.B + a.tile0[3]);
         const int nfix = fix.valid ? fix.grid_x * 4 : 0;
         if (id < nfix) split_fixup_body<64, 64>(fix, id / 4, id % 4);
         else tn8_reduce_body(red, id - nfix);            // the partial tiles of the dW1[:, a_other] launch (ncx_dwtn.hip)
         return;
     }
-    if ((int)blockIdx.x < a.B) {
-        const int b = blockIdx.x, B = a.B;
+    if (bx < a.B) {
+        const int b = bx, B = a.B;
         const int id = a.aid[b];
         int earlier = 0;
         for (int j = threadIdx.x; j < b; j += 256) earlier |= a.aid[j] == id;
@@ -385,7 +426,7 @@ __global__ __launch_bounds__(256) void k_emb_prep(const EmbPrepArgs a, const Fix
         return;
     }
     float* tile = (float*)bits;                                        // [32][33]
-    int t = blockIdx.x - a.B, e = 0;
+    int t = bx - a.B, e = 0;
     while (e < 2 && t >= a.tile0[e + 1]) ++e;
     t -= a.tile0[e];
     const int tiles_h = (a.dcols[e] + 31) / 32;                        // tiles along the source-row (h) direction
@@ -514,6 +555,11 @@ static int backward_impl(const ncx_dims* dp, const ncx_inputs* in, const ncx_par
     const bool only_de = phase == 4;                    // phase 4: just the dE GEMM
     const bool skip_de = phase == 3 || phase == 5;
     const bool do1 = phase != 2 && !only_de, do2 = phase != 1 && phase != 5 && !only_de;
+    // The dE product skips the dGgt^T segment of the row tiles without an answer of THIS batch where the call that scatters dSh also runs the
+    // product (the one-call backward and phase 1).  Phases 3 | 4 and 5 | 2 | 4 keep the full form: between them a data-parallel job sums
+    // the dGt^T | dGgt^T block over ranks, so it carries other batches' answers.
+    const bool de_skip = r.de_skip && (phase == 0 || phase == 1);
+    int* const de_perm = (int*)(ws + w.de_perm);
     if (!do1) {                                       // phase 2: dpre_1 lives where phase 1 left it
         dpre = (float*)(ws + w.dpre[(d.L - 1) & 1]);
     } else if (d.flags & NCX_F_FUSED_TAIL) {
@@ -713,8 +759,9 @@ static int backward_impl(const ncx_dims* dp, const ncx_inputs* in, const ncx_par
                 ea.tile0[e] = tiles; tiles += ((ldds[e] + 31) / 32) * ((colss[e] + 31) / 32);
             }
             ea.tile0[3] = tiles;
+            ea.perm = de_skip ? de_perm : (int*)nullptr;
             // (the dW1[:, a_other] GEMM above left its split fix-up to this launch)
-            hipLaunchKernelGGL(k_emb_prep, dim3(d.B + tiles + (fix_ak.valid ? fix_ak.grid_x * 4 : 0) + red_ak.n_tiles_total * 8), dim3(256), 0, se, ea, fix_ak, red_ak);
+            hipLaunchKernelGGL(k_emb_prep, dim3((de_skip ? 1 : 0) + d.B + tiles + (fix_ak.valid ? fix_ak.grid_x * 4 : 0) + red_ak.n_tiles_total * 8), dim3(256), 0, se, ea, fix_ak, red_ak);
             fix_ak.valid = 0; red_ak.n_tiles_total = 0;
             NCX_HIP_TRY(hipGetLastError());
         } else if (do1) {   // dGgt = one-hot(aid)^T dSh   (dGgt was cleared by k_bwd_prelude)
@@ -730,7 +777,11 @@ static int backward_impl(const ncx_dims* dp, const ncx_inputs* in, const ncx_par
             a.seg[1].kind = MK_PLAIN; a.seg[1].a = dagtT; a.seg[1].lda = Hp4; a.seg[1].klen = Hp4; a.seg[1].b = w1agtT; a.seg[1].ldb = Hp32;
             a.out = g->answer_embedding; a.ldo = d.da;
             a.split = 1;
-            rc = profiled(U_DE, se, [&] { return main_forward(a, se); }); if (rc) return rc;
+            if (de_skip) {      // rows in the order of de_perm: dGgt^T has a non-zero row only for an answer of the batch, and those come first
+                a.seg[0].kind = MK_GATHER; a.seg[0].idx = de_perm;
+                a.seg[1].kind = MK_GATHER; a.seg[1].idx = de_perm;
+            }
+            rc = profiled(U_DE, se, [&] { return de_skip ? main_forward_rowmap(a, se) : main_forward(a, se); }); if (rc) return rc;
         } else if ((do1 && !skip_de) || only_de) {   // dE[a][j] = sum_n dGt[n][a] W1ak[n][j] + sum_n dGgt[n][a] W1agt[n][j]
             GemmArgs a{}; a.mode = MODE_CHAIN; a.nseg = 2; a.M = d.A;
             a.a[0] = x_plain(dgt, d.A, H, d.A);  a.b[0] = x_plain(p->w1 + o.a_other, din, H, d.da); a.klen[0] = H;
@@ -760,9 +811,13 @@ int ncx_backward_phase(const ncx_dims* dp, const ncx_inputs* in, const ncx_param
 int ncx_ws_region(const ncx_dims* dp, int32_t which, size_t* offset, size_t* bytes) {
     if (check_dims(dp) != NCX_OK) return NCX_E_DIMS;
     if (!offset || !bytes) return NCX_E_NULL;
-    if (which != NCX_WS_DGT && which != NCX_WS_H1 && which != NCX_WS_DPRE1) return NCX_E_FLAGS;
+    if (which != NCX_WS_DGT && which != NCX_WS_H1 && which != NCX_WS_DPRE1 && which != NCX_WS_DE_PERM) return NCX_E_FLAGS;
     const StepRoutes r = routes(*dp);
     const WsLayout w = ws_layout(*dp, r);
+    if (which == NCX_WS_DE_PERM) {      // (size 0: the shape or the variant keeps the full form of the product)
+        *offset = w.de_perm; *bytes = r.de_skip ? ((size_t)dp->A + 1) * 4 : 0;
+        return NCX_OK;
+    }
     if (which == NCX_WS_H1 || which == NCX_WS_DPRE1) {
         *offset = which == NCX_WS_H1 ? w.h[0] : w.dpre[(dp->L - 1) & 1];
         *bytes = (size_t)dp->B * dp->K * dp->H * 4;

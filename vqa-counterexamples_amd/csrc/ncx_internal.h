@@ -66,6 +66,7 @@ struct WsLayout {
     size_t dagt;                        // dGgt [H][A]  (bf16 variant only; the fp32 path keeps it transposed, below)
     size_t dgtT;                        // fp32 path: dGt^T [A][Hp4] then dGgt^T [A][Hp4] (contiguous: the all-reduce bucket under DP); Hp4 = H up to a multiple of 4
     size_t dgtT2;                       // private copy of dGt^T with zero rows up to a multiple of 32 (A operand of the dW1[:, a_other] launch, ncx_dwtn.hip)
+    size_t de_perm;                     // fp32 path: int32 [A + 1]: the batch's present answer ids ascending, then the absent ones ascending; [A] = how many are present (k_emb_prep)
     size_t w1aT;                        // fp32 path: W1[:, a_other]^T then W1[:, a_gt]^T, [da][Hp32] each (zero padded)
     size_t partial;                     // column-sum partials [NCX_COLSUM_CHUNKS][H] x 2 + scalars
     size_t slab;                        // split-K slabs (max over all uses)
@@ -114,6 +115,9 @@ struct MainArgs {
     float* t_out; float* t_out0;     // main_forward_mlb only (nullable): t = tanh(z) of the rows that go to out / epi.out0, leading dimension N
 };
 int main_forward(MainArgs& a, hipStream_t s);
+// The chain over permuted rows (EPI_ROWMAP of ncx_main.h): two MK_GATHER segments sharing one table idx[0 .. M]; tile row r reads operand rows
+// idx[r] and writes output row idx[r]; row tiles from idx[M] on stop after the first segment.  Same tile form per shape as main_forward.
+int main_forward_rowmap(MainArgs& a, hipStream_t s);
 // The MLB producer's x_v product (ncx_mlb.hip): one MK_GATHER segment with the EPI_MLB epilogue of ncx_main.h
 int main_forward_mlb(MainArgs& a, hipStream_t s);
 // k-split of a problem for the fused forward kernel (48 x 128 tiles): 1 when its tiles already give every CU a workgroup,

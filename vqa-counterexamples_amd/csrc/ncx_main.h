@@ -63,8 +63,15 @@ struct MainCfg {
 // (epi.rowsplit_g = K + 1: image 0 of a question -> epi.out0, images 1 .. K -> out) and, when args.t_out is set, t = tanh(z) is stored
 // beside it in the same pass (t_out0 / t_out, leading dimension N): the classifier's plain operand.  A compile-time choice: the
 // other instantiations keep their code.
-enum { EPI_STD = 0, EPI_MLB = 1 };
+//
+// EPI_ROWMAP (the answer-embedding gradient over permuted rows, ncx_backward.hip): the sequence is two MK_GATHER segments that share ONE
+// index table idx[0 .. M] -- idx[0 .. M) is a permutation of the rows, idx[M] the number of leading tile rows whose second-segment operand
+// rows can be non-zero.  Tile row r reads operand rows idx[r] and its result goes to OUTPUT row idx[r]; a row tile that starts at or beyond
+// idx[M] stops after the first segment (its second-segment rows are exact zeros: the products it leaves out add +0 to accumulators that
+// are never -0, so every element keeps its bits).  Long tiles have the low row-tile numbers, hence the low workgroup ids: dispatched first.
+enum { EPI_STD = 0, EPI_MLB = 1, EPI_ROWMAP = 2 };
 template <class CFG> struct WithMlbEpi : CFG { static constexpr int EPI = EPI_MLB; };
+template <class CFG> struct WithRowMap : CFG { static constexpr int EPI = EPI_ROWMAP; };
 
 typedef const __attribute__((address_space(1))) float* gfptr;      // global address space: global_load, never flat_load
 typedef const __attribute__((address_space(1))) int* giptr;
@@ -205,7 +212,13 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
     int nsteps[MAIN_MAX_SEG], total_steps = 0;
 #pragma unroll
     for (int i = 0; i < MAIN_MAX_SEG; ++i) { nsteps[i] = i < NSEG ? (args.seg[i].klen + BK - 1) / BK : 0; total_steps += nsteps[i]; }
-    const int g0 = (int)((long long)total_steps * z / S), g1 = (int)((long long)total_steps * (z + 1) / S);
+    constexpr bool ROWMAP = CFG::EPI == EPI_ROWMAP;
+    static_assert(!ROWMAP || (K0 == MK_GATHER && K1 == MK_GATHER && NSEG == 2 && !DIST && !X6), "row map: two gathered segments");
+    const int g0 = (int)((long long)total_steps * z / S), g1_all = (int)((long long)total_steps * (z + 1) / S);
+    const int g1 = [&]() __attribute__((always_inline)) {
+        if constexpr (ROWMAP) return m0 >= ((giptr)args.seg[0].idx)[M] ? min(g1_all, nsteps[0]) : g1_all;      // (uniform per workgroup: a scalar load and a scalar compare)
+        else return g1_all;
+    }();
 
     // Global-load register sets and operand pointers of the segment being loaded (shared by all segments).
     f32x4 va[DEPTH][NA], vm[DEPTH][NA], vb[DEPTH][NB];
@@ -1070,12 +1083,19 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
     f32x4 add0 = {0.f, 0.f, 0.f, 0.f}, add1 = add0, add2 = add0;
     if (use_add) { add0 = fetch_add(min(tid, LAST_F)); add1 = fetch_add(min(tid + MT, LAST_F)); add2 = fetch_add(min(tid + 2 * MT, LAST_F)); }
     // (the three requests above are in flight while the accumulators go through LDS)
+    int orow_v = 0;                                      // ROWMAP: output row of tile row `tid` (in flight with them)
+    if constexpr (ROWMAP) orow_v = ((giptr)args.seg[0].idx)[min(m0 + min(tid, BM - 1), M - 1)];
 #pragma unroll
     for (int i = 0; i < WM; ++i)
 #pragma unroll
         for (int j = 0; j < WN; ++j)
 #pragma unroll
             for (int q = 0; q < 4; ++q) stage[(wm0 + 16 * i + 4 * lk + q) * SP + wn0 + 16 * j + li] = acc[i][j][q];
+    int* const orow = (int*)(stage + BM * SP);           // ROWMAP: output row of every tile row, behind the staged tile
+    if constexpr (ROWMAP) {
+        static_assert(!ROWMAP || (BM <= MT && (BM * SP + BM) * 4 <= CFG::LDS), "row map: one thread per tile row, table behind the staged tile");
+        if (tid < BM) orow[tid] = orow_v;
+    }
     __syncthreads();
 #pragma unroll 1
     for (int f = tid; f < BM * QR; f += MT) {
@@ -1125,6 +1145,7 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
             continue;
         }
         float* o = dst + (long long)r * ldd + n;
+        if constexpr (ROWMAP) o = dst + (long long)orow[f / QR] * ldd + n;
         if (n + 3 < N) *(f32x4u*)o = v;
         else { o[0] = v[0]; if (n + 1 < N) o[1] = v[1]; if (n + 2 < N) o[2] = v[2]; }
     }
@@ -1187,6 +1208,13 @@ static inline int launch_main_fwd(MainArgs& a, hipStream_t s) {
     auto is = [&](std::initializer_list<int> ks) { if ((int)ks.size() != a.nseg) return false; int i = 0; for (int k : ks) if (a.seg[i++].kind != k) return false; return true; };
     constexpr int G = MK_GATHER, X = MK_GATHER_MUL, P = MK_PLAIN, S = MK_SOFTMAX;
     constexpr int V = MK_VFOLD;
+    if constexpr (CFG::EPI == EPI_ROWMAP) {  // permuted rows: two gathered segments over one table of M + 1 entries, unsplit, plain stores
+        const EpiArgs& e = a.epi;
+        if (!is({G, G}) || a.split > 1 || a.dist_out || !a.out || !a.seg[0].idx || a.seg[0].idx != a.seg[1].idx ||
+            e.rowadd || e.bias || e.relu || e.dropout || e.gate)
+            return NCX_E_FLAGS;
+        return launch_main_fwd_seq<CFG, false, G, G>(a, s);
+    } else
     if constexpr (CFG::EPI == EPI_MLB) {     // the MLB producer's x_v: one gathered segment, unsplit, every epilogue operand present
         if (!is({G}) || a.split > 1 || a.dist_out || a.N < 4 || !a.epi.bias || !a.epi.fold_mul || a.epi.rowsplit_g < 2 || !a.epi.out0 ||
             !a.out || (a.t_out && !a.t_out0))

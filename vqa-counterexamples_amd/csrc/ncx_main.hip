@@ -13,6 +13,36 @@ typedef MainCfg<96, 64, 2, 2, 2, 2> MainCfgFold4;   // MK_VFOLD sequences: 96 x 
 typedef MainCfg<192, 64, 4, 2, 2, 2, 512, true> MainCfgFold8X6;   // ... with the segments after the fold on the bf16 matrix path, three-plane operands (NCX_F_X6)
 typedef MainCfg<192, 64, 4, 2, 2, 2, 512> MainCfgFold8;   // MK_VFOLD on 192 x 64 tiles: ONE 8-wave workgroup per CU, eight triplets share the W_k | W_m tiles (experiment: NCX_FOLD8)
 
+// The tile form of a chain without the per-triplet fold.  W: the epilogue the kernels are compiled with (AsIs: the standard one; WithRowMap:
+// permuted rows -- the same choice of tile for a shape, so the two forms of the answer-embedding gradient add every element's products in one order)
+template <class C> using AsIs = C;
+template <template <class> class W>
+static int main_forward_chain(MainArgs& a, hipStream_t s) {
+    long long T = 0;
+    for (int i = 0; i < a.nseg; ++i) T += (a.seg[i].klen + MF_BK - 1) / MF_BK;
+    if (a.split <= 1 && T <= 32 && (long long)((a.M + 63) / 64) * ((a.N + 63) / 64) >= 2 * num_cus() && !hook_env("NCX_MAIN_CFG"))
+        return launch_main_fwd<W<MainCfg3>>(a, s);          // a workgroup that short spends as long starting and storing as multiplying: more of them per CU
+    const long long tiles96 = (long long)((a.M + 95) / 96) * ((a.N + 127) / 128);
+    constexpr bool wide_ok = W<MainCfgW>::EPI != EPI_ROWMAP;      // (the 160-row tile leaves no LDS behind its staged tile for the row table)
+    if constexpr (wide_ok)
+    if (a.split <= 1 && a.nseg == 1 && a.seg[0].kind == MK_GATHER && !hook_env("NCX_MAIN_CFG")) {
+        // x_v of the MUTAN producer at configs[2]: 12 800 x 360 outputs = 402 tiles of 96 x 128 = 1.57 rounds of the one-per-CU slots (the second
+        // round 57 % full); 160-row tiles: 240 workgroups, ONE round
+        const long long cus = num_cus(), tiles160 = (long long)((a.M + 159) / 160) * ((a.N + 127) / 128);
+        const double e96 = (double)tiles96 / (double)(((tiles96 + cus - 1) / cus) * cus), e160 = (double)tiles160 / (double)(((tiles160 + cus - 1) / cus) * cus);
+        if (tiles160 * 10 >= cus * 7 && e160 > e96 + 0.1) return launch_main_fwd<W<MainCfgW>>(a, s);
+    }
+    int cfg = (a.split <= 1 && tiles96 * 10 >= (long long)num_cus() * 9) ? 2 : 0;
+    if (const char* e = hook_env("NCX_MAIN_CFG")) cfg = atoi(e);       // experiment hook (NCX_EXPERIMENT=1)
+    if (cfg == 3) {
+        if constexpr (wide_ok) return launch_main_fwd<W<MainCfgW>>(a, s);
+        else return NCX_E_FLAGS;
+    }
+    if (cfg == 1) return launch_main_fwd<W<MainCfg1>>(a, s);
+    if (cfg == 2) return launch_main_fwd<W<MainCfg2>>(a, s);
+    return launch_main_fwd<W<MainCfg0>>(a, s);
+}
+
 // Measured inside the training step at configs[1] (B = 512: 256 tiles of 96 x 128): 338 us with one 96 x 128 workgroup per CU,
 // 346 / 348 us with two 48 x 128 / 96 x 64 workgroups per CU (on back-to-back launches of the kernel alone the order is the
 // other way round: the step leaves the caches in another state).  The big tile needs enough tiles to fill the chip; smaller
@@ -27,24 +57,12 @@ int main_forward(MainArgs& a, hipStream_t s) {
         if (rows == 192 && a.x6 && a.epi.rowdiv == 24) return launch_main_fwd<MainCfgFold8X6>(a, s);      // (K = 24: a triplet per wave)
         return rows == 192 ? launch_main_fwd<MainCfgFold8>(a, s) : rows == 96 ? launch_main_fwd<MainCfgFold4>(a, s) : launch_main_fwd<MainCfgFold>(a, s);
     }
-    long long T = 0;
-    for (int i = 0; i < a.nseg; ++i) T += (a.seg[i].klen + MF_BK - 1) / MF_BK;
-    if (a.split <= 1 && T <= 32 && (long long)((a.M + 63) / 64) * ((a.N + 63) / 64) >= 2 * num_cus() && !hook_env("NCX_MAIN_CFG"))
-        return launch_main_fwd<MainCfg3>(a, s);          // a workgroup that short spends as long starting and storing as multiplying: more of them per CU
-    const long long tiles96 = (long long)((a.M + 95) / 96) * ((a.N + 127) / 128);
-    if (a.split <= 1 && a.nseg == 1 && a.seg[0].kind == MK_GATHER && !hook_env("NCX_MAIN_CFG")) {
-        // x_v of the MUTAN producer at configs[2]: 12 800 x 360 outputs = 402 tiles of 96 x 128 = 1.57 rounds of the one-per-CU slots (the second
-        // round 57 % full); 160-row tiles: 240 workgroups, ONE round
-        const long long cus = num_cus(), tiles160 = (long long)((a.M + 159) / 160) * ((a.N + 127) / 128);
-        const double e96 = (double)tiles96 / (double)(((tiles96 + cus - 1) / cus) * cus), e160 = (double)tiles160 / (double)(((tiles160 + cus - 1) / cus) * cus);
-        if (tiles160 * 10 >= cus * 7 && e160 > e96 + 0.1) return launch_main_fwd<MainCfgW>(a, s);
-    }
-    int cfg = (a.split <= 1 && tiles96 * 10 >= (long long)num_cus() * 9) ? 2 : 0;
-    if (const char* e = hook_env("NCX_MAIN_CFG")) cfg = atoi(e);       // experiment hook (NCX_EXPERIMENT=1)
-    if (cfg == 3) return launch_main_fwd<MainCfgW>(a, s);
-    if (cfg == 1) return launch_main_fwd<MainCfg1>(a, s);
-    if (cfg == 2) return launch_main_fwd<MainCfg2>(a, s);
-    return launch_main_fwd<MainCfg0>(a, s);
+    return main_forward_chain<AsIs>(a, s);
+}
+
+int main_forward_rowmap(MainArgs& a, hipStream_t s) {
+    if (a.nseg != 2 || a.seg[0].kind != MK_GATHER) return NCX_E_FLAGS;
+    return main_forward_chain<WithRowMap>(a, s);
 }
 
 // x_v of the MLB producer: 96 x 128 tiles, one workgroup per CU, once they fill the chip (12 800 x 1200 at B = 512: 1340 tiles), else 48 x 128

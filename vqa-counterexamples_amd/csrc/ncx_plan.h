@@ -5,6 +5,7 @@
 #pragma GCC visibility push(hidden)
 namespace ncx {
 constexpr int NCX_SCATTER_MAX_B = 32768;     // k_scatter_dsh_by_answer / k_emb_prep keep one bit per triplet in LDS
+constexpr int NCX_PERM_MAX_A = 32768;        // k_emb_prep keeps one bit per answer in LDS while it builds the presence permutation
 int check_dims(const ncx_dims* d);
 
 // The route decisions of a step that more than one site needs, taken ONCE from the predicates of the kernels that own them
@@ -17,6 +18,7 @@ struct StepRoutes {
     bool tn8_shared;        // the per-triplet shared segments take that kernel (bf16 variant: on a launch of their own)
     bool tn8_x6;            // ... on the bf16 matrix path with three-plane operands (NCX_F_X6)
     bool emb_nt;            // the answer-embedding gradient runs in NT form (operands dGt^T | dGgt^T, ncx_main.h)
+    bool de_skip;           // ... over permuted rows, the row tiles without an answer of the batch stopping after the dGt^T segment (one-call backward and phase 1)
     long long cand_ksteps;  // k-steps of linear_1's candidate chain: v_other (| v_mult) | dist, rank | z_other | softmax(a) or a_other
     // dW1[:, a_other] = dGt . E on the balanced TN kernel (not with the side stream: the kernel's slab is the main stream's)
     bool dw1ak_on_tn8(bool side) const { return tn8 && emb_nt && !side; }

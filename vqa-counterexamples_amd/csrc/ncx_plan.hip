@@ -111,6 +111,8 @@ StepRoutes routes(const ncx_dims& d) {
     // NT form of the answer-embedding gradient: the fp32 path with the a_emb segment on (ncx_train_tail and backward_impl fill
     // the dGt^T | dGgt^T block in that form, ncx_ws_region names it)
     r.emb_nt = aemb && !bf16 && !hook_env("NCX_NO_EMB_NT");
+    // ... over rows permuted so that the answers of the batch come first: the row tiles behind them skip the dGgt^T segment (all zeros there)
+    r.de_skip = r.emb_nt && d.A <= NCX_PERM_MAX_A && !hook_env("NCX_NO_DE_SKIP");
     r.cand_ksteps = ksteps(d.dv) * ((d.flags & NCX_F_V_MULT) ? 2 : 1) + ksteps(d.K + 1) + ksteps(d.dz) + ksteps(aemb ? d.A : d.da);
     return r;
 }
@@ -243,6 +245,7 @@ WsLayout ws_layout(const ncx_dims& d, const StepRoutes& r) {
     w.dgtT = take((size_t)2 * d.A * pad_to(d.H, 4) * 4);
     w.w1aT = take((size_t)2 * d.da * pad_to(d.H, 32) * 4);
     w.dgtT2 = take(r.tn8 ? (size_t)pad_to(d.A, 32) * pad_to(d.H, 4) * 4 : 0);
+    w.de_perm = take(r.emb_nt ? ((size_t)d.A + 1) * 4 : 0);
     w.partial = take((size_t)NCX_PRELUDE_WAVES * H * 4 * 2 + (size_t)NCX_PRELUDE_WAVES * 4 + 256);     // (>= NCX_COLSUM_CHUNKS rows)
     GemmUse u[U_COUNT];
     list_uses(d, r, u);

@@ -219,6 +219,15 @@ def ws_dgt_view(d: NcxDims, ws: torch.Tensor) -> torch.Tensor:
     return ws[base + off.value: base + off.value + nbytes.value].view(torch.float32)
 
 
+def ws_de_perm_view(d: NcxDims, ws: torch.Tensor) -> torch.Tensor:
+    """int32 view [A + 1] of the presence permutation the last backward (phase 0 or 1) built for the answer_embedding gradient: the
+    answer ids of the batch ascending, then the others ascending, and in [A] how many occur.  Empty where the product keeps the full form."""
+    off, nbytes = C.c_size_t(0), C.c_size_t(0)
+    _lib.check(_lib.lib().ncx_ws_region(C.byref(d), 4, C.byref(off), C.byref(nbytes)), "ncx_ws_region")
+    base = (ws.data_ptr() + 255) // 256 * 256 - ws.data_ptr()
+    return ws[base + off.value: base + off.value + nbytes.value].view(torch.int32)
+
+
 def ranking_loss(scores: torch.Tensor, gt: torch.Tensor, scale: float = 0.0, want_grad: bool = True):
     """Listwise softmax-CE / B + rank of the ground truth + Recall@1/@5 hit counts in one pass."""
     B, K = scores.shape
