@@ -686,6 +686,49 @@ int ncx_mlb_train_backward(const ncx_vqa_train_dims* d, const ncx_mlb_params* m,
 /* which: NCX_VT_WS_VD, NCX_VT_WS_QD, NCX_VT_WS_ZC (here tc = drop_c(act_c(z)) [B, dh]); valid after ncx_mlb_train_forward. */
 int ncx_mlb_train_ws_region(const ncx_vqa_train_dims* d, const ncx_mlb_params* m, int32_t which, size_t* offset, size_t* bytes);
 
+/* ---- training the MLBAtt attention model: the step below the question encoder -----------------------------------------
+ * MLBAtt in TRAINING mode (reference vqa/models/att.py:39-163) on ncx_mlb_att_dims / ncx_mlb_att_params: forward with the six dropouts
+ * active, backward through the classifier, the glimpse fusion, the pooling, the softmax over positions and the attention head.  No
+ * gradient goes to the feature table.  Dropout layers (generator layer id; element index = linear index in the tensor named):
+ *   1 the map fed to conv_v_att [B, dv, P] (the pooled map is NOT dropped)   2 q_emb fed to linear_q_att [B, dq]
+ *   3 x_att after activation_mm [B, P, dh_att]                               4 v_att fed to the glimpse Linears [B, G, dv]
+ *   5 q_emb fed to linear_q_fusion [B, dq]                                   6 act_c(x_v * x_qf) [B, G dh_f]
+ * dropout_mode as in ncx_vqa_train_dims: 0 off, 1 the counter-based generator under `seed` (keep <=> u >= p, scale 1 / (1 - p)),
+ * 2 explicit keep masks (0 / 1 floats), the six tensors concatenated in that order.  0 <= p < 1.  Status codes as the rest of the ABI,
+ * all checked before any launch (NULL pointers, dims, modes, p's); no allocation; every launch on `stream`; no host read-back; no
+ * float atomics, every reduction in a fixed order: two calls on the same inputs are bit-identical.  The loss is ncx_ce_loss. */
+typedef struct ncx_mlb_att_train {
+    float    p_att_v, p_att_q, p_att_mm, p_v, p_q, p_c;   /* layers 1 .. 6 */
+    int32_t  dropout_mode;
+    int32_t  want_dq;          /* backward also writes d loss / d q_emb */
+    uint64_t seed;
+} ncx_mlb_att_train;
+typedef struct ncx_mlb_att_grads {        /* shapes of ncx_mlb_att_params' tensors; OVERWRITTEN by ncx_mlb_att_train_backward */
+    float* wv_att; float* bv_att; float* wq_att; float* bq_att; float* wa; float* ba;
+    float* wg;     float* bg;     float* wqf;    float* bqf;    float* wc; float* bc;
+} ncx_mlb_att_grads;
+/* Workspace of the forward / backward pair (256-byte aligned); 0 for invalid dims, modes, p's or activations (m's pointers are not read). */
+size_t ncx_mlb_att_train_workspace_bytes(const ncx_mlb_att_dims* d, const ncx_mlb_att_train* t, const ncx_mlb_att_params* m);
+/* feats, img_idx, q_emb as ncx_mlb_att_forward; logits [B, A]; att [B, G, P].  masks: dropout_mode 2 only, else nullable.  Xv, x_q,
+ * v_att, x_v, x_qf, t and the dropped tensors stay in the workspace for the backward. */
+int ncx_mlb_att_train_forward(const ncx_mlb_att_dims* d, const ncx_mlb_att_train* t, const float* feats, const int32_t* img_idx,
+                              const float* q_emb, const ncx_mlb_att_params* m, const float* masks, void* workspace,
+                              size_t workspace_bytes, float* logits, float* att, void* stream);
+/* After ncx_mlb_att_train_forward on the same workspace, inputs and `att`.  Every field of `g` is overwritten; dq_emb [B, dq] when
+ * t->want_dq (else nullable).  The Xv stash is overwritten with dXv: one backward per forward. */
+int ncx_mlb_att_train_backward(const ncx_mlb_att_dims* d, const ncx_mlb_att_train* t, const float* feats, const int32_t* img_idx,
+                               const float* q_emb, const ncx_mlb_att_params* m, const float* masks, void* workspace,
+                               size_t workspace_bytes, const float* att, const float* dlogits, const ncx_mlb_att_grads* g,
+                               float* dq_emb, void* stream);
+/* Diagnostics / tests: byte offset and size of a workspace region. */
+#define NCX_AT_WS_XV     1   /* Xv = act_v_att(conv_v_att(drop(V))) [B, P, dh_att]; dXv after the backward               */
+#define NCX_AT_WS_VATT   2   /* v_att [B, G, dv], before layer 4's dropout                                                 */
+#define NCX_AT_WS_T      3   /* t = act_c(x_v * x_qf) [B, G dh_f], before layer 6's dropout                                */
+#define NCX_AT_WS_VD     4   /* drop(V) [B, dv, P]; 0 bytes when layer 1 is off (the table is read in place)               */
+#define NCX_AT_WS_DWV    5   /* partial sums of d conv_v_att.weight [S][dh_att][dv], one per group of ceil(B / S) images   */
+int ncx_mlb_att_train_ws_region(const ncx_mlb_att_dims* d, const ncx_mlb_att_train* t, const ncx_mlb_att_params* m, int32_t which,
+                                size_t* offset, size_t* bytes);
+
 /* ---- diagnostics (bench.py / tests only; the only process-global state, off by default) --------------
  * GEMM ids: 0 Gt = W1[:,a_other].E^T, 1 Sh (shared segments), 2 MAIN (candidate segments, the dominant
  * forward kernel), 3 hidden layer l>=2 forward, 4 dW1 candidate columns (+dGt; the dominant backward

@@ -1,0 +1,125 @@
+"""One training step of the MLB attention model below the question encoder at full widths (dv 2048, dq 2400, attention dim_h 1200,
+fusion dim_h 1200, 2000 answers, 14 x 14 maps): forward + cross-entropy + backward through neuralcx.vqa_train.MlbAttTrainFunction
+(the module with use_hip_train = True) against the same module's torch path under autograd, in the same process.  q_emb is given and
+requires grad (d loss / d q_emb is computed on both sides); dropout runs at the YAML's p = 0.5 on both sides.  Runs: B = 128 and 512
+with G = 4, B = 128 with G = 2.  HIP events around --steps steps after --warmup warm-up steps, best of 3 windows, the two paths
+alternating.  Prints one JSON line; --out writes it.
+--steps-only N: N steps of the HIP path at --batch / --glimpses and nothing else (the run a kernel trace is taken from)."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "vqa-counterexamples_amd")]
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+import vqa.models as M  # noqa: E402
+
+PEAK_FP32_MFMA = 157.3e12      # MI355X matrix fp32, FLOP/s
+DV, DQ, DH_ATT, DH_F, A, GRID = 2048, 2400, 1200, 1200, 2000, 14
+
+
+def build(G):
+    opt = dict(arch="MLBAtt", dim_v=DV, dim_q=DQ, seq2vec=dict(arch="gru", emb_size=8, dropout=0.0),
+               attention=dict(nb_glimpses=G, dim_h=DH_ATT, dropout_v=0.5, dropout_q=0.5, dropout_mm=0.5, activation_v="tanh",
+                              activation_q="tanh", activation_mm="tanh"),
+               fusion=dict(dim_h=DH_F, dropout_v=0.5, dropout_q=0.5, activation_v="tanh", activation_q="tanh"),
+               classif=dict(activation="tanh", dropout=0.5))
+    return M.factory(opt, ["w%d" % i for i in range(10)], ["a%d" % i for i in range(A)], cuda=True, data_parallel=False).train()
+
+
+def flops(B, G):
+    """Algorithmic FLOP of the step: the forward's products, and two products of the same size for each in the backward, except
+    conv_v_att, whose input gradient is not taken (no gradient goes to the map)."""
+    P = GRID * GRID
+    fwd = dict(conv_v_att=2.0 * B * P * DV * DH_ATT, linear_q_att=2.0 * B * DQ * DH_ATT, conv_att=2.0 * B * P * DH_ATT * G,
+               pooling=2.0 * B * P * DV * G, glimpse_linears=2.0 * B * G * DV * DH_F, linear_q_fusion=2.0 * B * DQ * G * DH_F,
+               classifier=2.0 * B * G * DH_F * A)
+    total = sum(fwd.values()) + fwd["conv_v_att"] + 2.0 * (sum(fwd.values()) - fwd["conv_v_att"]) - fwd["pooling"]
+    return total, fwd
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=128)
+    ap.add_argument("--glimpses", type=int, default=4)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--steps-only", type=int, default=0)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_mlb_att_train.py needs the MI355X"
+    torch.manual_seed(1)
+
+    def paths(B, G):
+        model = build(G)
+        v = torch.randn(B, DV, GRID, GRID, device="cuda").abs() * 0.45
+        q = (torch.randn(B, DQ, device="cuda") * 0.3).requires_grad_(True)
+        target = torch.randint(0, A, (B,), device="cuda")
+        head = [p for n, p in model.named_parameters() if not n.startswith("seq2vec.")]
+
+        def step(flag):
+            model.use_hip_train = flag
+            for p in head:
+                p.grad = None
+            q.grad = None
+            loss = F.cross_entropy(model.forward_from_q(v, q), target)
+            loss.backward()
+            return loss
+
+        return (lambda: step(True)), (lambda: step(False))
+
+    if a.steps_only:
+        hip_step, _ = paths(a.batch, a.glimpses)
+        for _ in range(a.steps_only):
+            hip_step()
+        torch.cuda.synchronize()
+        return
+
+    def window(fn):
+        for _ in range(a.warmup):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.steps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / a.steps
+
+    cases = []
+    for B, G in ((128, 4), (512, 4), (128, 2)):
+        hip_step, torch_step = paths(B, G)
+        t_hip, t_torch = [], []
+        for _ in range(3):
+            t_hip.append(window(hip_step))
+            t_torch.append(window(torch_step))
+        torch.cuda.reset_peak_memory_stats()
+        l_h = float(hip_step())
+        mem_h = torch.cuda.max_memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        l_t = float(torch_step())
+        mem_t = torch.cuda.max_memory_allocated()
+        total, fwd = flops(B, G)
+        best, best_t = min(t_hip), min(t_torch)
+        cases.append(dict(B=B, G=G, hip_ms=best, hip_ms_windows=t_hip, hip_spread=(max(t_hip) - best) / best,
+                          torch_ms=best_t, torch_ms_windows=t_torch, torch_spread=(max(t_torch) - best_t) / best_t,
+                          speedup_vs_torch=best_t / best, algorithmic_gflop=total / 1e9, dwv_att_gflop=fwd["conv_v_att"] / 1e9,
+                          floor_ms_at_peak=total / PEAK_FP32_MFMA * 1e3, fraction_of_fp32_mfma_peak=total / (best * 1e-3) / PEAK_FP32_MFMA,
+                          loss_hip=l_h, loss_torch=l_t, peak_memory_mb=dict(hip=mem_h / 2 ** 20, torch=mem_t / 2 ** 20)))
+        del hip_step, torch_step
+        torch.cuda.empty_cache()
+    res = dict(metric="mlb_att_train_step_ms", shape=dict(dv=DV, dq=DQ, dh_att=DH_ATT, dh_f=DH_F, A=A, grid=[GRID, GRID]), steps=a.steps,
+               warmup=a.warmup, dropout_p=0.5, cases=cases, device=torch.cuda.get_device_name(0))
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -32,7 +32,8 @@ EXPORTS = ("ncx_input_size", "ncx_workspace_bytes", "ncx_forward", "ncx_forward_
            "ncx_contrastive_workspace_bytes", "ncx_contrastive_forward", "ncx_contrastive_distances", "ncx_contrastive_loss",
            "ncx_contrastive_backward",
            "ncx_vqa_train_workspace_bytes", "ncx_vqa_train_forward", "ncx_ce_loss", "ncx_vqa_train_backward", "ncx_vqa_train_ws_region",
-           "ncx_mlb_train_workspace_bytes", "ncx_mlb_train_forward", "ncx_mlb_train_backward", "ncx_mlb_train_ws_region")
+           "ncx_mlb_train_workspace_bytes", "ncx_mlb_train_forward", "ncx_mlb_train_backward", "ncx_mlb_train_ws_region",
+           "ncx_mlb_att_train_workspace_bytes", "ncx_mlb_att_train_forward", "ncx_mlb_att_train_backward", "ncx_mlb_att_train_ws_region")
 
 
 class NcxDims(C.Structure):
@@ -85,6 +86,15 @@ class NcxMlbAttDims(C.Structure):
 class NcxMlbAttParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("wv_att", "bv_att", "wq_att", "bq_att", "wa", "ba", "wg", "bg", "wqf", "bqf", "wc", "bc")] + \
                [(n, C.c_int32) for n in ("act_v_att", "act_q_att", "act_mm", "act_v", "act_q", "act_c")]
+
+
+class NcxMlbAttTrain(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("p_att_v", "p_att_q", "p_att_mm", "p_v", "p_q", "p_c")] + \
+               [("dropout_mode", C.c_int32), ("want_dq", C.c_int32), ("seed", C.c_uint64)]
+
+
+class NcxMlbAttGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("wv_att", "bv_att", "wq_att", "bq_att", "wa", "ba", "wg", "bg", "wqf", "bqf", "wc", "bc")]
 
 
 class NcxMlbGrads(C.Structure):
@@ -297,6 +307,17 @@ def lib():
                                          C.c_void_p]
     L.ncx_mlb_train_ws_region.restype = C.c_int
     L.ncx_mlb_train_ws_region.argtypes = [P_VT, P_LP, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    P_AD, P_AT, P_AP = C.POINTER(NcxMlbAttDims), C.POINTER(NcxMlbAttTrain), C.POINTER(NcxMlbAttParams)
+    L.ncx_mlb_att_train_workspace_bytes.restype = C.c_size_t
+    L.ncx_mlb_att_train_workspace_bytes.argtypes = [P_AD, P_AT, P_AP]
+    L.ncx_mlb_att_train_forward.restype = C.c_int
+    L.ncx_mlb_att_train_forward.argtypes = [P_AD, P_AT, C.c_void_p, C.c_void_p, C.c_void_p, P_AP, C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ncx_mlb_att_train_backward.restype = C.c_int
+    L.ncx_mlb_att_train_backward.argtypes = [P_AD, P_AT, C.c_void_p, C.c_void_p, C.c_void_p, P_AP, C.c_void_p, C.c_void_p, C.c_size_t,
+                                             C.c_void_p, C.c_void_p, C.POINTER(NcxMlbAttGrads), C.c_void_p, C.c_void_p]
+    L.ncx_mlb_att_train_ws_region.restype = C.c_int
+    L.ncx_mlb_att_train_ws_region.argtypes = [P_AD, P_AT, P_AP, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     _lib = L
     return L
 

@@ -1402,6 +1402,86 @@ def mlb_train_ws_region(d, mw, ws, which) -> torch.Tensor:
     return _train_ws_view("ncx_mlb_train_ws_region", d, mw, ws, which)
 
 
+# ---- training the MLBAtt attention model (include/neuralcx.h: ncx_mlb_att_train_*) ---------------------------------------------
+AT_WS_XV, AT_WS_VATT, AT_WS_T, AT_WS_VD, AT_WS_DWV = 1, 2, 3, 4, 5
+AT_LAYERS = dict(att_v=1, att_q=2, att_mm=3, v=4, q=5, c=6)      # layer ids of the counter-based dropout generator
+
+
+def mlb_att_dropouts(opt):
+    """The six dropout p's of an MLBAtt's options in layer order (attention.dropout_v/_q/_mm, fusion.dropout_v/_q, classif.dropout)."""
+    att, fus, cla = opt["attention"], opt["fusion"], opt.get("classif", {})
+    return tuple(float(x or 0.0) for x in (att.get("dropout_v"), att.get("dropout_q"), att.get("dropout_mm"), fus.get("dropout_v"),
+                                           fus.get("dropout_q"), cla.get("dropout")))
+
+
+def mlb_att_mask_sizes(B, P, dv, dq, dh_att, G, dh_f):
+    """Element counts of the six keep masks of dropout_mode 2, in the order they are concatenated."""
+    return (B * dv * P, B * dq, B * P * dh_att, B * G * dv, B * dq, B * G * dh_f)
+
+
+def mlb_att_train_dims(mw: MlbAttWeights, B, P, n_img, p=(0.0,) * 6, dropout_mode=0, seed=0, want_dq=False):
+    """-> (ncx_mlb_att_dims, ncx_mlb_att_train) of one training step."""
+    t = _lib.NcxMlbAttTrain()
+    t.p_att_v, t.p_att_q, t.p_att_mm, t.p_v, t.p_q, t.p_c = (float(x) for x in p)
+    t.dropout_mode, t.want_dq, t.seed = int(dropout_mode), int(bool(want_dq)), int(seed) & 0xFFFFFFFFFFFFFFFF
+    return mw.dims(int(B), int(P), int(n_img)), t
+
+
+def mlb_att_train_dims_ok(mw: MlbAttWeights, dt) -> bool:
+    """The library's own check of the shape and the dropout settings (host only)."""
+    return _lib.lib().ncx_mlb_att_train_workspace_bytes(C.byref(dt[0]), C.byref(dt[1]), C.byref(mw.c_struct(check_device=False))) != 0
+
+
+def mlb_att_train_workspace(dt, mw: MlbAttWeights, device) -> torch.Tensor:
+    need = _lib.lib().ncx_mlb_att_train_workspace_bytes(C.byref(dt[0]), C.byref(dt[1]), C.byref(mw.c_struct()))
+    if need == 0:
+        raise _lib.NcxError("ncx_mlb_att_train_workspace_bytes: unsupported dims, dropout settings or activation")
+    return torch.empty(need + 256, dtype=torch.uint8, device=device)
+
+
+def mlb_att_train_forward(dt, feats, img_idx, q_emb, mw: MlbAttWeights, ws, masks=None):
+    """Training-mode MLBAtt below the question encoder (ncx_mlb_att_train_forward) -> (logits [B, A], att [B, G, P]); the stashes
+    stay in ws.  feats [n_img, dv, W, H] or [n_img, dv, P], read in place; img_idx [B] int32."""
+    d, t = dt
+    logits = torch.empty(d.B, d.A, dtype=torch.float32, device=feats.device)
+    att = torch.empty(d.B, d.G, d.P, dtype=torch.float32, device=feats.device)
+    p, n = _ws_ptr(ws)
+    with torch.cuda.device(feats.device):
+        _lib.check(_lib.lib().ncx_mlb_att_train_forward(C.byref(d), C.byref(t), _ptr(feats, torch.float32, "feats"),
+                                                        _ptr(img_idx, torch.int32, "img_idx"), _ptr(q_emb, torch.float32, "q_emb"),
+                                                        C.byref(mw.c_struct()), _ptr(masks, torch.float32, "masks"), p, n,
+                                                        C.c_void_p(logits.data_ptr()), C.c_void_p(att.data_ptr()), _stream()),
+                   "ncx_mlb_att_train_forward")
+    return logits, att
+
+
+def mlb_att_train_backward(dt, feats, img_idx, q_emb, mw: MlbAttWeights, ws, att, dlogits, grads: Dict[str, torch.Tensor], masks=None):
+    """Every gradient of MLB_ATT_FIELDS into `grads` (overwritten) after mlb_att_train_forward on the same workspace and inputs;
+    -> d loss / d q_emb [B, dq] when want_dq, else None."""
+    d, t = dt
+    g = _lib.NcxMlbAttGrads()
+    for k in MLB_ATT_FIELDS:
+        setattr(g, k, _ptr(grads[k], torch.float32, "grad " + k))
+    dq = torch.empty(d.B, d.dq, dtype=torch.float32, device=dlogits.device) if t.want_dq else None
+    p, n = _ws_ptr(ws)
+    with torch.cuda.device(dlogits.device):
+        _lib.check(_lib.lib().ncx_mlb_att_train_backward(C.byref(d), C.byref(t), _ptr(feats, torch.float32, "feats"),
+                                                         _ptr(img_idx, torch.int32, "img_idx"), _ptr(q_emb, torch.float32, "q_emb"),
+                                                         C.byref(mw.c_struct()), _ptr(masks, torch.float32, "masks"), p, n,
+                                                         _ptr(att, torch.float32, "att"), _ptr(dlogits, torch.float32, "dlogits"), C.byref(g),
+                                                         _ptr(dq, torch.float32, "dq_emb"), _stream()), "ncx_mlb_att_train_backward")
+    return dq
+
+
+def mlb_att_train_ws_region(dt, mw: MlbAttWeights, ws, which) -> torch.Tensor:
+    """A region of the workspace (AT_WS_XV / _VATT / _T / _VD / _DWV) as a flat fp32 view (tests, diagnostics)."""
+    off, nb = C.c_size_t(), C.c_size_t()
+    _lib.check(_lib.lib().ncx_mlb_att_train_ws_region(C.byref(dt[0]), C.byref(dt[1]), C.byref(mw.c_struct()), which, C.byref(off), C.byref(nb)),
+               "ncx_mlb_att_train_ws_region")
+    pad = (-ws.data_ptr()) % 256
+    return ws[pad + off.value: pad + off.value + nb.value].view(torch.float32)
+
+
 _VQA_FLAGS: Dict[torch.device, torch.Tensor] = {}
 
 

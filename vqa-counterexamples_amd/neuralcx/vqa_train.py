@@ -206,6 +206,52 @@ def mlb_module_forward(model, input_v: torch.Tensor, q_emb: torch.Tensor) -> tor
                                   model.linear_classif.weight, model.linear_classif.bias, cfg)
 
 
+class MlbAttTrainFunction(torch.autograd.Function):
+    """(logits, att) = MLBAtt below the question encoder in training mode (ncx_mlb_att_train_forward / _backward) with the twelve
+    parameter tensors in ops.MLB_ATT_FIELDS order (the two 1 x 1 convolutions as matrices, the glimpse Linears stacked).  feats is the
+    table of NCHW maps, read in place; no gradient goes to it.  Gradients: the parameters, and q_emb when it requires grad; att
+    [B, G, P] is not differentiable.  cfg = (acts, p, seed, training): acts the dict of ops.mlb_att_acts, p the six dropout p's in
+    layer order; dropout runs on the counter-based generator under `seed` when training."""
+
+    @staticmethod
+    def forward(ctx, feats, img_idx, q_emb, wv_att, bv_att, wq_att, bq_att, wa, ba, wg, bg, wqf, bqf, wc, bc, cfg):
+        acts, p, seed, training = cfg
+        t = {k: x.detach().float().contiguous() for k, x in zip(ops.MLB_ATT_FIELDS, (wv_att, bv_att, wq_att, bq_att, wa, ba, wg, bg, wqf, bqf, wc, bc))}
+        mw = ops.MlbAttWeights.from_tensors(t, **acts)
+        mode = 1 if training and any(x > 0 for x in p) else 0
+        feats = feats.detach().float().contiguous()
+        q = q_emb.detach().float().contiguous()
+        dt = ops.mlb_att_train_dims(mw, img_idx.shape[0], feats[0, 0].numel(), feats.shape[0], p=p if mode else (0.0,) * 6, dropout_mode=mode,
+                                    seed=seed, want_dq=ctx.needs_input_grad[2])
+        ws = ops.mlb_att_train_workspace(dt, mw, feats.device)
+        logits, att = ops.mlb_att_train_forward(dt, feats, img_idx, q, mw, ws)
+        ctx.hip = (dt, mw, ws, feats, img_idx, q, att)
+        ctx.mark_non_differentiable(att)
+        return logits, att
+
+    @staticmethod
+    def backward(ctx, dlogits, _datt=None):
+        dt, mw, ws, feats, img_idx, q, att = ctx.hip
+        grads = {k: torch.empty_like(v) for k, v in mw.t.items()}
+        dq = ops.mlb_att_train_backward(dt, feats, img_idx, q, mw, ws, att, dlogits.float().contiguous(), grads)
+        ctx.hip = None                                            # the stash is the step's largest buffer: let go of it here
+        return (None, None, dq) + tuple(grads[k] for k in ops.MLB_ATT_FIELDS) + (None,)
+
+
+def mlb_att_module_forward(model, input_v: torch.Tensor, q_emb: torch.Tensor):
+    """The HIP training route of MLBAtt.forward below seq2vec -> (logits, att [B, G, P]): input_v [B, dv, W, H] is the table of maps,
+    the index the identity."""
+    idx = torch.arange(input_v.shape[0], dtype=torch.int32, device=input_v.device)
+    seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if model.training else 0      # torch's CPU generator: torch.manual_seed reproduces it
+    cfg = (ops.mlb_att_acts(model.opt), ops.mlb_att_dropouts(model.opt), seed, bool(model.training))
+    lin = list(model.list_linear_v_fusion)
+    return MlbAttTrainFunction.apply(input_v, idx, q_emb, model.conv_v_att.weight.flatten(1), model.conv_v_att.bias,
+                                     model.linear_q_att.weight, model.linear_q_att.bias, model.conv_att.weight.flatten(1), model.conv_att.bias,
+                                     torch.stack([l.weight for l in lin]), torch.stack([l.bias for l in lin]),
+                                     model.linear_q_fusion.weight, model.linear_q_fusion.bias,
+                                     model.linear_classif.weight, model.linear_classif.bias, cfg)
+
+
 class _TrainEngine:
     """What the two engines share: one flat parameter buffer, one flat gradient buffer (both in the layout of the model's weights
     object) and two Adam state buffers; the reference's state_dict keys over views of the flat buffer, seq2vec.* entries carried

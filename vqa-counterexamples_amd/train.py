@@ -15,8 +15,10 @@ Three routes:
                             forward and backward through time run in HIP too (GRUEncoder.use_hip_train, neuralcx.vqa_train.GruTrainFunction);
                             --hip_2lstm_train is the same for the 2-lstm encoder (TwoLSTM.use_hip_bptt, neuralcx.vqa_train.LstmTrainFunction).
   --no_hip                  the same loop on the plain PyTorch modules (also runs on a CPU).
-model.arch MLBAtt: training is the module under torch autograd (there is no HIP backward or engine for the attention model, with or
-without --freeze_seq2vec); evaluate() / --evaluate run the module in eval mode under no_grad, i.e. its HIP forward
+model.arch MLBAtt: training is the module under torch autograd by default (there is no flat-parameter engine for the attention model,
+with or without --freeze_seq2vec); --hip_att_train sets the model's use_hip_train: the step below the question encoder (attention head,
+glimpse fusion, classifier; forward with dropout and backward) then runs in HIP inside torch autograd
+(neuralcx.vqa_train.MlbAttTrainFunction), the encoder trains under autograd unless --freeze_seq2vec, torch.optim.Adam steps.  evaluate() / --evaluate run the module in eval mode under no_grad, i.e. its HIP forward
 (ncx_mlb_att_forward), unless --no_hip.  The images are a seeded synthetic attention table [syn_images, dim_v, syn_grid, syn_grid].
 """
 import argparse
@@ -66,6 +68,8 @@ def build_parser():
     p.add_argument("--freeze_seq2vec", action="store_true", help="freeze the question encoder: q_emb once per split, the whole step in HIP")
     p.add_argument("--hip_seq2vec_train", action="store_true", help="default route only: train the question encoder in HIP as well (backward through time)")
     p.add_argument("--hip_2lstm_train", action="store_true", help="default route only: train the 2-lstm question encoder (TwoLSTM) in HIP as well (backward through time)")
+    p.add_argument("--hip_att_train", action="store_true", help="attention archs only: the training step below the question encoder in HIP as well "
+                   "(MLBAtt.use_hip_train: attention head, glimpse fusion, classifier; torch.optim.Adam steps)")
     p.add_argument("--no_hip", action="store_true", help="the plain PyTorch modules (no HIP library; runs on a CPU too)")
     p.add_argument("--seed", type=int, default=1337)
     return p
@@ -135,6 +139,10 @@ class Trainer:
             raise SystemExit("train.py: --hip_2lstm_train trains the encoder in HIP; it cannot be combined with --no_hip")
         if args.hip_2lstm_train and args.freeze_seq2vec:
             raise SystemExit("train.py: --hip_2lstm_train has nothing to train under --freeze_seq2vec")
+        if args.hip_att_train and args.no_hip:
+            raise SystemExit("train.py: --hip_att_train trains the attention model in HIP; it cannot be combined with --no_hip")
+        if args.hip_att_train and opt["model"].get("arch") not in ATT_ARCHS:
+            raise SystemExit("train.py: --hip_att_train needs an attention arch (%s); this YAML builds %r" % (", ".join(ATT_ARCHS), opt["model"].get("arch")))
         s2v = opt["model"]["seq2vec"]
         if args.hip_2lstm_train and not (s2v.get("arch") == "2-lstm" and "hidden_size" in s2v):       # seq2vec.factory's TwoLSTM branch
             raise SystemExit("train.py: --hip_2lstm_train needs the 2-lstm encoder (seq2vec: {arch: 2-lstm, hidden_size: ...}); this YAML builds %r"
@@ -156,6 +164,14 @@ class Trainer:
                 "module under torch autograd; eval-mode forward in HIP (ncx_mlb_att_forward)%s" % (
                     "; --freeze_seq2vec: the encoder is frozen, there is no HIP engine for this model" if self.freeze else "")
             self.model.use_hip = not args.no_hip
+            if args.hip_att_train:
+                from neuralcx import ops
+                if ops.mlb_att_acts(opt["model"]) is None:
+                    raise SystemExit("train.py: --hip_att_train needs the HIP route: an activation of this YAML is neither absent nor tanh")
+                self.model.use_hip_train = True
+                self.route = "attention head, glimpse fusion and classifier train in HIP (ncx_mlb_att_train_forward / _backward, --hip_att_train); " \
+                    "torch.optim.Adam steps; eval-mode forward in HIP (ncx_mlb_att_forward)%s" % (
+                        "; --freeze_seq2vec: the encoder is frozen, no d loss / d q_emb is taken" if self.freeze else "")
         else:
             self.route = "torch path: --no_hip" if args.no_hip else route_for(opt["model"])
         self.hip = self.route == "hip"

@@ -80,8 +80,11 @@ class MLBAtt(AbstractAtt):
     On a CUDA device in eval mode, when no gradient can be wanted, everything below the question encoder runs in the HIP library
     (ops.mlb_att_forward: the convolution reads the NCHW map in place, the attention head lives in its epilogue); `use_hip = False`
     keeps it in PyTorch, and so do training mode, grad mode with a parameter that requires grad, an activation other than tanh,
-    non-fp32 tensors and shapes the library refuses.  It trains under torch autograd."""
+    non-fp32 tensors and shapes the library refuses.  It trains under torch autograd, unless `use_hip_train` is set: then the
+    training step below the encoder runs in HIP too (neuralcx.vqa_train.MlbAttTrainFunction: forward with the six dropouts on the
+    counter-based generator, backward through the attention), the encoder training from the d loss / d q_emb it returns."""
     use_hip = True
+    use_hip_train = False
 
     def __init__(self, opt=None, vocab_words=(), vocab_answers=()):
         opt = opt or {}
@@ -131,8 +134,36 @@ class MLBAtt(AbstractAtt):
             raise ValueError("input_v must be [B, dim_v, W, H] and input_q [B, T]")
         return self.forward_from_q(input_v, self.seq2vec(input_q))
 
+    def _hip_train_ok(self, input_v, q_vec):
+        """The opt-in HIP training route (`use_hip_train`): training mode, or grad mode with a parameter that requires grad; CUDA, fp32,
+        activations in {none, tanh}, a shape the library accepts.  Anything else keeps the torch path."""
+        if not (self.use_hip_train and input_v.is_cuda and q_vec.is_cuda):
+            return False
+        params = self._head_params()
+        if not (self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in params))):
+            return False
+        if input_v.dtype != torch.float32 or q_vec.dtype != torch.float32 or q_vec.device != input_v.device:
+            return False
+        if not all(p.dtype == torch.float32 and p.device == input_v.device for p in params):
+            return False
+        from neuralcx import ops
+        if ops.mlb_att_acts(self.opt) is None:
+            return False
+        mw = self._hip_weights()
+        p = ops.mlb_att_dropouts(self.opt) if self.training else (0.0,) * 6
+        if not all(0.0 <= x < 1.0 for x in p):
+            return False
+        mode = 1 if any(x > 0 for x in p) else 0
+        B = input_v.shape[0]
+        return ops.mlb_att_train_dims_ok(mw, ops.mlb_att_train_dims(mw, B, input_v.shape[2] * input_v.shape[3], B, p=p, dropout_mode=mode))
+
     def forward_from_q(self, input_v, q_vec):
         """forward below the question encoder: q_vec [B, dim_q] is the encoder's output (a caller with a frozen encoder keeps it)."""
+        if self._hip_train_ok(input_v, q_vec):
+            from neuralcx import vqa_train
+            logits, att = vqa_train.mlb_att_module_forward(self, input_v, q_vec)
+            self.list_att = list(att.detach().unbind(1))
+            return logits
         if self._hip_ok(input_v, q_vec):
             from neuralcx import ops
             logits, att = ops.mlb_att_forward(input_v.contiguous(), None, q_vec.contiguous(), self._hip_weights())
