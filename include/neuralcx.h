@@ -73,7 +73,8 @@ extern "C" {
  * 2^-16 error fails the suite's ReLU-kink conditioning: DESIGN 5d).  Covered:
  *   - linear_1 forward on the 192-row form at K = 24 (per-triplet fold: the effective weight is formed in fp32, b = fma(v_o, W_m, W_k), then cut),
  *   - d linear_1.weight[:, v_other | v_orig*v_other] (the per-triplet fold pass, H % 256 == 0 and dv % 64 == 0),
- *   - dGt and every other column block of d linear_1.weight (the balanced TN launch, B <= 2048).
+ *   - dGt and every other column block of d linear_1.weight (the balanced TN launch, B <= 2048),
+ *   - the conv_v_att product of the MLB attention model (ncx_mlb_att_forward_flags, ncx_mlb_att_train_forward_flags: P >= 4, any dv, dh_att, G).
  * Shapes outside fall back to the fp32 kernels silently (same results to rounding).  Results agree with the fp32 kernels to fp32 rounding, not
  * bitwise (another summation order); every parity test of the suite passes at its unchanged tolerance with the bit set (NCX_X6=1 in the
  * environment of the Python binding sets it for a whole process). */
@@ -329,6 +330,17 @@ size_t ncx_mlb_att_workspace_bytes(const ncx_mlb_att_dims* d, const ncx_mlb_att_
 int ncx_mlb_att_forward(const ncx_mlb_att_dims* d, const float* feats, const int32_t* img_idx, const float* q_emb,
                         const ncx_mlb_att_params* m, void* workspace, size_t workspace_bytes,
                         float* logits, float* att, void* stream);
+/* ncx_mlb_att_forward (att.py:39-192) with `flags`: 0 (the same call) or NCX_F_X6, which puts the conv_v_att product (att.py:46-57) on
+ * the bf16 matrix path with three-plane operands; P < 4 stays fp32.  Any other value is NCX_E_DIMS before any launch.  Same workspace,
+ * same slab layout, same fixed summation order over the dh_att tiles; two calls are bit-identical.  Non-finite map or weight values are
+ * outside the X6 contract. */
+int ncx_mlb_att_forward_flags(const ncx_mlb_att_dims* d, const float* feats, const int32_t* img_idx, const float* q_emb,
+                              const ncx_mlb_att_params* m, uint32_t flags, void* workspace, size_t workspace_bytes,
+                              float* logits, float* att, void* stream);
+/* Host only (no launch, no device access): the kernel the conv_v_att / conv_att stage (att.py:46-57,71-90) takes for these dims under
+ * `flags` (0 or NCX_F_X6).  0 k_att_logits_small (P < 4), 1 fp32 64-row tiles, 2 fp32 208-row tiles, 3 X6 64-row, 4 X6 208-row;
+ * negative: a status code for dims or flags the forward refuses. */
+int ncx_mlb_att_logits_form(const ncx_mlb_att_dims* d, uint32_t flags);
 
 /* ---- brute-force k nearest neighbours of feature rows --------------------------------------
  * Replaces knn.py:41-58 of the reference (sklearn NearestNeighbors(n_neighbors=k).fit(table).kneighbors(queries),
@@ -714,7 +726,13 @@ size_t ncx_mlb_att_train_workspace_bytes(const ncx_mlb_att_dims* d, const ncx_ml
 int ncx_mlb_att_train_forward(const ncx_mlb_att_dims* d, const ncx_mlb_att_train* t, const float* feats, const int32_t* img_idx,
                               const float* q_emb, const ncx_mlb_att_params* m, const float* masks, void* workspace,
                               size_t workspace_bytes, float* logits, float* att, void* stream);
-/* After ncx_mlb_att_train_forward on the same workspace, inputs and `att`.  Every field of `g` is overwritten; dq_emb [B, dq] when
+/* ncx_mlb_att_train_forward (att.py:39-163) with `flags`: 0 (the same call) or NCX_F_X6 (the Xv stash, the position logits and the maps
+ * come from the X6 form of the conv_v_att product); any other value is NCX_E_DIMS before any launch.  ncx_mlb_att_train_backward runs
+ * unchanged after either. */
+int ncx_mlb_att_train_forward_flags(const ncx_mlb_att_dims* d, const ncx_mlb_att_train* t, const float* feats, const int32_t* img_idx,
+                                    const float* q_emb, const ncx_mlb_att_params* m, const float* masks, uint32_t flags, void* workspace,
+                                    size_t workspace_bytes, float* logits, float* att, void* stream);
+/* After ncx_mlb_att_train_forward[_flags] on the same workspace, inputs and `att`.  Every field of `g` is overwritten; dq_emb [B, dq] when
  * t->want_dq (else nullable).  The Xv stash is overwritten with dXv: one backward per forward. */
 int ncx_mlb_att_train_backward(const ncx_mlb_att_dims* d, const ncx_mlb_att_train* t, const float* feats, const int32_t* img_idx,
                                const float* q_emb, const ncx_mlb_att_params* m, const float* masks, void* workspace,

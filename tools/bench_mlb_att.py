@@ -2,7 +2,10 @@
 answers, 14 x 14 maps): ops.mlb_att_forward against the same module's torch path (use_hip = False) in the same process, at
 B in {128, 512} and G in {4, 2}.  HIP events around --steps steps after --warmup warm-up steps, best of 3 windows, the two paths
 alternating.  Prints one JSON line; --out writes it.
---steps-only N: N steps of the HIP path at --batch / --glimpses and nothing else (the run a kernel trace is taken from)."""
+--x6: three paths instead of two, alternating window by window under the same protocol: the fp32 HIP forward (x6=False), the X6 HIP
+forward (x6=True: NCX_F_X6 on the attention kernel) and the torch path; metric mlb_att_x6_forward_ms.
+--steps-only N: N steps of the HIP path (the X6 form with --x6) at --batch / --glimpses and nothing else (the run a kernel trace is
+taken from)."""
 import argparse
 import json
 import os
@@ -43,6 +46,7 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--steps-only", type=int, default=0)
+    ap.add_argument("--x6", action="store_true", help="also time the X6 form of the attention kernel (three paths)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_mlb_att.py needs the MI355X"
@@ -56,18 +60,21 @@ def main():
         q = torch.randn(B, DQ, device="cuda") * 0.3
 
         def hip_step():
-            return ops.mlb_att_forward(v, None, q, mw)
+            return ops.mlb_att_forward(v, None, q, mw, x6=False) if a.x6 else ops.mlb_att_forward(v, None, q, mw)
+
+        def x6_step():
+            return ops.mlb_att_forward(v, None, q, mw, x6=True)
 
         @torch.no_grad()
         def torch_step():
             return model.forward_from_q(v, q), torch.stack(model.list_att, 1)
 
-        return hip_step, torch_step
+        return hip_step, torch_step, x6_step, mw
 
     if a.steps_only:
-        hip_step, _ = paths(a.batch, a.glimpses)
+        hip_step, _, x6_step, _ = paths(a.batch, a.glimpses)
         for _ in range(a.steps_only):
-            hip_step()
+            x6_step() if a.x6 else hip_step()
         torch.cuda.synchronize()
         return
 
@@ -85,10 +92,12 @@ def main():
     cases = []
     for G in (4, 2):
         for B in (128, 512):
-            hip_step, torch_step = paths(B, G)
-            t_hip, t_torch = [], []
+            hip_step, torch_step, x6_step, mw = paths(B, G)
+            t_hip, t_torch, t_x6 = [], [], []
             for _ in range(3):
                 t_hip.append(window(hip_step))
+                if a.x6:
+                    t_x6.append(window(x6_step))
                 t_torch.append(window(torch_step))
             (l_h, a_h), (l_t, a_t) = hip_step(), torch_step()
             total, parts = flops(B, G)
@@ -99,9 +108,17 @@ def main():
                               floor_ms_at_peak=total / PEAK_FP32_MFMA * 1e3, hip_tflops=total / best / 1e9,
                               fraction_of_fp32_mfma_peak=total / (best * 1e-3) / PEAK_FP32_MFMA,
                               max_abs_diff_vs_torch=dict(logits=float((l_h - l_t).abs().max()), att=float((a_h - a_t).abs().max()))))
-            del hip_step, torch_step
+            if a.x6:
+                l_6, a_6 = x6_step()
+                best6 = min(t_x6)
+                win = best - best6 > max(max(t_hip) - best, max(t_x6) - best6)       # beats the fp32 form by more than the larger spread
+                cases[-1].update(x6_ms=best6, x6_ms_windows=t_x6, x6_spread=(max(t_x6) - best6) / best6, x6_speedup_vs_fp32_hip=best / best6,
+                                 x6_speedup_vs_torch=best_t / best6, x6_faster_than_fp32_hip_beyond_spreads=bool(win),
+                                 x6_max_abs_diff_vs_fp32_hip=dict(logits=float((l_6 - l_h).abs().max()), att=float((a_6 - a_h).abs().max())),
+                                 x6_logits_form=ops.mlb_att_logits_form(mw, B, GRID * GRID, B, x6=True))
+            del hip_step, torch_step, x6_step, mw
             torch.cuda.empty_cache()
-    res = dict(metric="mlb_att_forward_ms", shape=dict(dv=DV, dq=DQ, dh_att=DH_ATT, dh_f=DH_F, A=A, grid=[GRID, GRID]), steps=a.steps,
+    res = dict(metric="mlb_att_x6_forward_ms" if a.x6 else "mlb_att_forward_ms", shape=dict(dv=DV, dq=DQ, dh_att=DH_ATT, dh_f=DH_F, A=A, grid=[GRID, GRID]), steps=a.steps,
                warmup=a.warmup, cases=cases, device=torch.cuda.get_device_name(0))
     line = json.dumps(res)
     print(line)

@@ -4,7 +4,10 @@ fusion dim_h 1200, 2000 answers, 14 x 14 maps): forward + cross-entropy + backwa
 requires grad (d loss / d q_emb is computed on both sides); dropout runs at the YAML's p = 0.5 on both sides.  Runs: B = 128 and 512
 with G = 4, B = 128 with G = 2.  HIP events around --steps steps after --warmup warm-up steps, best of 3 windows, the two paths
 alternating.  Prints one JSON line; --out writes it.
---steps-only N: N steps of the HIP path at --batch / --glimpses and nothing else (the run a kernel trace is taken from)."""
+--x6: three paths instead of two, alternating window by window: the HIP step with the fp32 forward (hip_x6 = False), the HIP step
+with the X6 forward (hip_x6 = True: NCX_F_X6 on the attention kernel; the backward is the same) and the torch path.
+--steps-only N: N steps of the HIP path (the X6 forward with --x6) at --batch / --glimpses and nothing else (the run a kernel trace
+is taken from)."""
 import argparse
 import json
 import os
@@ -48,6 +51,7 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--steps-only", type=int, default=0)
+    ap.add_argument("--x6", action="store_true", help="also time the step with the X6 form of the attention kernel (three paths)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_mlb_att_train.py needs the MI355X"
@@ -60,8 +64,9 @@ def main():
         target = torch.randint(0, A, (B,), device="cuda")
         head = [p for n, p in model.named_parameters() if not n.startswith("seq2vec.")]
 
-        def step(flag):
+        def step(flag, x6=None):
             model.use_hip_train = flag
+            model.hip_x6 = x6
             for p in head:
                 p.grad = None
             q.grad = None
@@ -69,12 +74,12 @@ def main():
             loss.backward()
             return loss
 
-        return (lambda: step(True)), (lambda: step(False))
+        return (lambda: step(True, False if a.x6 else None)), (lambda: step(False)), (lambda: step(True, True))
 
     if a.steps_only:
-        hip_step, _ = paths(a.batch, a.glimpses)
+        hip_step, _, x6_step = paths(a.batch, a.glimpses)
         for _ in range(a.steps_only):
-            hip_step()
+            x6_step() if a.x6 else hip_step()
         torch.cuda.synchronize()
         return
 
@@ -91,10 +96,12 @@ def main():
 
     cases = []
     for B, G in ((128, 4), (512, 4), (128, 2)):
-        hip_step, torch_step = paths(B, G)
-        t_hip, t_torch = [], []
+        hip_step, torch_step, x6_step = paths(B, G)
+        t_hip, t_torch, t_x6 = [], [], []
         for _ in range(3):
             t_hip.append(window(hip_step))
+            if a.x6:
+                t_x6.append(window(x6_step))
             t_torch.append(window(torch_step))
         torch.cuda.reset_peak_memory_stats()
         l_h = float(hip_step())
@@ -109,9 +116,14 @@ def main():
                           speedup_vs_torch=best_t / best, algorithmic_gflop=total / 1e9, dwv_att_gflop=fwd["conv_v_att"] / 1e9,
                           floor_ms_at_peak=total / PEAK_FP32_MFMA * 1e3, fraction_of_fp32_mfma_peak=total / (best * 1e-3) / PEAK_FP32_MFMA,
                           loss_hip=l_h, loss_torch=l_t, peak_memory_mb=dict(hip=mem_h / 2 ** 20, torch=mem_t / 2 ** 20)))
-        del hip_step, torch_step
+        if a.x6:
+            best6 = min(t_x6)
+            win = best - best6 > max(max(t_hip) - best, max(t_x6) - best6)           # beats the fp32 forward by more than the larger spread
+            cases[-1].update(x6_ms=best6, x6_ms_windows=t_x6, x6_spread=(max(t_x6) - best6) / best6, x6_speedup_vs_fp32_hip=best / best6,
+                             x6_speedup_vs_torch=best_t / best6, x6_faster_than_fp32_hip_beyond_spreads=bool(win), loss_x6=float(x6_step()))
+        del hip_step, torch_step, x6_step
         torch.cuda.empty_cache()
-    res = dict(metric="mlb_att_train_step_ms", shape=dict(dv=DV, dq=DQ, dh_att=DH_ATT, dh_f=DH_F, A=A, grid=[GRID, GRID]), steps=a.steps,
+    res = dict(metric="mlb_att_x6_train_step_ms" if a.x6 else "mlb_att_train_step_ms", shape=dict(dv=DV, dq=DQ, dh_att=DH_ATT, dh_f=DH_F, A=A, grid=[GRID, GRID]), steps=a.steps,
                warmup=a.warmup, dropout_p=0.5, cases=cases, device=torch.cuda.get_device_name(0))
     line = json.dumps(res)
     print(line)

@@ -1,5 +1,6 @@
 // ncx_mlb_att.hip -- the MLB attention model (MLBAtt in eval mode) below the question encoder: ncx_mlb_att_workspace_bytes,
-// ncx_mlb_att_forward.
+// ncx_mlb_att_forward, ncx_mlb_att_forward_flags (flags = NCX_F_X6: step b on k_att_logits_x6, ncx_mlb_att.h; same slab, same
+// workspace), ncx_mlb_att_logits_form.
 //
 // Reference: AbstractAtt._attention / _fusion_glimpses / _classif and MLBAtt (vqa/models/att.py:39-192); every dropout the identity.
 //   a. x_q = act(q . Wq_att^T + b)                                       generic engine
@@ -66,9 +67,23 @@ size_t ncx_mlb_att_workspace_bytes(const ncx_mlb_att_dims* d, const ncx_mlb_att_
     return att_layout(*d).total;
 }
 
+int ncx_mlb_att_logits_form(const ncx_mlb_att_dims* d, uint32_t flags) {
+    if (!att_flags_ok(flags)) return NCX_E_DIMS;
+    const int rc = check_att_dims(d);
+    if (rc != NCX_OK) return rc;
+    return att_logits_form(d->P, flags);
+}
+
 int ncx_mlb_att_forward(const ncx_mlb_att_dims* dp, const float* feats, const int32_t* img_idx, const float* q_emb,
                         const ncx_mlb_att_params* mp, void* workspace, size_t workspace_bytes,
                         float* logits, float* att, void* stream_) {
+    return ncx_mlb_att_forward_flags(dp, feats, img_idx, q_emb, mp, 0, workspace, workspace_bytes, logits, att, stream_);
+}
+
+int ncx_mlb_att_forward_flags(const ncx_mlb_att_dims* dp, const float* feats, const int32_t* img_idx, const float* q_emb,
+                              const ncx_mlb_att_params* mp, uint32_t flags, void* workspace, size_t workspace_bytes,
+                              float* logits, float* att, void* stream_) {
+    if (!att_flags_ok(flags)) return NCX_E_DIMS;
     int rc = check_att(dp, mp);
     if (rc != NCX_OK) return rc;
     if (!feats || !img_idx || !q_emb || !workspace || !logits || !att) return NCX_E_NULL;
@@ -90,12 +105,7 @@ int ncx_mlb_att_forward(const ncx_mlb_att_dims* dp, const float* feats, const in
         a.P = d.P; a.dv = d.dv; a.dh = d.dh_att; a.G = d.G; a.n_img = d.n_img; a.HT = w.HT; a.PT = w.PT;
         a.act_v = m.act_v_att; a.act_mm = m.act_mm;
         const AttTrain tr{};
-        if (w.TM == 208) rc = launch_att_logits<208, false>(a, tr, d.B, s);
-        else if (w.TM == 64) rc = launch_att_logits<64, false>(a, tr, d.B, s);
-        else {
-            hipLaunchKernelGGL(k_att_logits_small<false>, dim3((unsigned)((long long)d.B * d.P)), dim3(256), 0, s, a, tr);
-            rc = (int)hipGetLastError();
-        }
+        rc = run_att_logits<false>(a, tr, d.B, flags, s);
         if (rc) return rc;
     }
     {   // c. softmax over the positions, attention-weighted pooling                    att.py:91-116

@@ -549,6 +549,13 @@ int ncx_mlb_att_train_ws_region(const ncx_mlb_att_dims* d, const ncx_mlb_att_tra
 int ncx_mlb_att_train_forward(const ncx_mlb_att_dims* dp, const ncx_mlb_att_train* tp, const float* feats, const int32_t* img_idx,
                               const float* q_emb, const ncx_mlb_att_params* mp, const float* masks, void* workspace,
                               size_t workspace_bytes, float* logits, float* att, void* stream_) {
+    return ncx_mlb_att_train_forward_flags(dp, tp, feats, img_idx, q_emb, mp, masks, 0, workspace, workspace_bytes, logits, att, stream_);
+}
+
+int ncx_mlb_att_train_forward_flags(const ncx_mlb_att_dims* dp, const ncx_mlb_att_train* tp, const float* feats, const int32_t* img_idx,
+                                    const float* q_emb, const ncx_mlb_att_params* mp, const float* masks, uint32_t flags, void* workspace,
+                                    size_t workspace_bytes, float* logits, float* att, void* stream_) {
+    if (!att_flags_ok(flags)) return NCX_E_DIMS;
     int rc = at_check(dp, tp, mp, true);
     if (rc != NCX_OK) return rc;
     if (!feats || !img_idx || !q_emb || !workspace || !logits || !att) return NCX_E_NULL;
@@ -590,12 +597,7 @@ int ncx_mlb_att_train_forward(const ncx_mlb_att_dims* dp, const ncx_mlb_att_trai
         a.act_v = m.act_v_att; a.act_mm = m.act_mm;
         AttTrain tr{};
         tr.xv_stash = F(w.stash); tr.mask3 = at_off(mk, w.m_off[2]); tr.drop = k; tr.identity = at_on(t, 1) ? 1 : 0;
-        if (w.TM == 208) rc = launch_att_logits<208, true>(a, tr, d.B, s);
-        else if (w.TM == 64) rc = launch_att_logits<64, true>(a, tr, d.B, s);
-        else {
-            hipLaunchKernelGGL(k_att_logits_small<true>, dim3((unsigned)((long long)d.B * d.P)), dim3(256), 0, s, a, tr);
-            rc = (int)hipGetLastError();
-        }
+        rc = run_att_logits<true>(a, tr, d.B, flags, s);
         if (rc) return rc;
     }
     {

@@ -19,7 +19,7 @@ NCX_F_BF16 = 16       # BASELINE configs[4]: bf16 operands for the two dominant 
 
 EXPORTS = ("ncx_input_size", "ncx_workspace_bytes", "ncx_forward", "ncx_forward_phase", "ncx_loss_rank", "ncx_backward", "ncx_backward_phase",
            "ncx_adam_step", "ncx_version", "ncx_profile_begin", "ncx_profile_end", "ncx_plan_query",
-           "ncx_vqa_workspace_bytes", "ncx_vqa_forward", "ncx_mlb_workspace_bytes", "ncx_mlb_forward", "ncx_mlb_att_workspace_bytes", "ncx_mlb_att_forward", "ncx_knn_workspace_bytes", "ncx_knn_status_offset", "ncx_knn", "ncx_cosine_gram_workspace_bytes", "ncx_cosine_gram", "ncx_semantic_scores",
+           "ncx_vqa_workspace_bytes", "ncx_vqa_forward", "ncx_mlb_workspace_bytes", "ncx_mlb_forward", "ncx_mlb_att_workspace_bytes", "ncx_mlb_att_forward", "ncx_mlb_att_forward_flags", "ncx_mlb_att_logits_form", "ncx_knn_workspace_bytes", "ncx_knn_status_offset", "ncx_knn", "ncx_cosine_gram_workspace_bytes", "ncx_cosine_gram", "ncx_semantic_scores",
            "ncx_similarity_scores",
            "ncx_gru_packed_bytes", "ncx_gru_pack", "ncx_gru_workspace_bytes", "ncx_gru_encode",
            "ncx_gru_train_workspace_bytes", "ncx_gru_packed_t_bytes", "ncx_gru_pack_t", "ncx_gru_train_forward", "ncx_gru_train_backward",
@@ -33,7 +33,7 @@ EXPORTS = ("ncx_input_size", "ncx_workspace_bytes", "ncx_forward", "ncx_forward_
            "ncx_contrastive_backward",
            "ncx_vqa_train_workspace_bytes", "ncx_vqa_train_forward", "ncx_ce_loss", "ncx_vqa_train_backward", "ncx_vqa_train_ws_region",
            "ncx_mlb_train_workspace_bytes", "ncx_mlb_train_forward", "ncx_mlb_train_backward", "ncx_mlb_train_ws_region",
-           "ncx_mlb_att_train_workspace_bytes", "ncx_mlb_att_train_forward", "ncx_mlb_att_train_backward", "ncx_mlb_att_train_ws_region")
+           "ncx_mlb_att_train_workspace_bytes", "ncx_mlb_att_train_forward", "ncx_mlb_att_train_forward_flags", "ncx_mlb_att_train_backward", "ncx_mlb_att_train_ws_region")
 
 
 class NcxDims(C.Structure):
@@ -183,6 +183,11 @@ def lib():
     L.ncx_mlb_att_forward.restype = C.c_int
     L.ncx_mlb_att_forward.argtypes = [C.POINTER(NcxMlbAttDims), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NcxMlbAttParams), C.c_void_p,
                                       C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ncx_mlb_att_forward_flags.restype = C.c_int
+    L.ncx_mlb_att_forward_flags.argtypes = [C.POINTER(NcxMlbAttDims), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NcxMlbAttParams), C.c_uint32,
+                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ncx_mlb_att_logits_form.restype = C.c_int
+    L.ncx_mlb_att_logits_form.argtypes = [C.POINTER(NcxMlbAttDims), C.c_uint32]
     L.ncx_knn_workspace_bytes.restype = C.c_size_t
     L.ncx_knn_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
     L.ncx_knn_status_offset.restype = C.c_size_t
@@ -313,6 +318,9 @@ def lib():
     L.ncx_mlb_att_train_forward.restype = C.c_int
     L.ncx_mlb_att_train_forward.argtypes = [P_AD, P_AT, C.c_void_p, C.c_void_p, C.c_void_p, P_AP, C.c_void_p, C.c_void_p, C.c_size_t,
                                             C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ncx_mlb_att_train_forward_flags.restype = C.c_int
+    L.ncx_mlb_att_train_forward_flags.argtypes = [P_AD, P_AT, C.c_void_p, C.c_void_p, C.c_void_p, P_AP, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                  C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ncx_mlb_att_train_backward.restype = C.c_int
     L.ncx_mlb_att_train_backward.argtypes = [P_AD, P_AT, C.c_void_p, C.c_void_p, C.c_void_p, P_AP, C.c_void_p, C.c_void_p, C.c_size_t,
                                              C.c_void_p, C.c_void_p, C.POINTER(NcxMlbAttGrads), C.c_void_p, C.c_void_p]

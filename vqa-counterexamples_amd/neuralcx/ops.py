@@ -98,6 +98,7 @@ class Batch:
 
 # Flag bits OR-ed into every ncx_dims built here.  NCX_X6=1 in the environment puts the whole process on the split-bf16 ("bf16 x 6") variant
 # of the balanced TN weight-gradient launch (include/neuralcx.h: NCX_F_X6; not the default) -- how the unchanged GPU suite is run against it.
+# The attention model's forwards read the bit at call time (mlb_att_flags).
 EXTRA_FLAGS = _lib.NCX_F_X6 if os.environ.get("NCX_X6", "0") not in ("", "0") else 0
 
 
@@ -467,10 +468,28 @@ def mlb_att_workspace(mw: MlbAttWeights, B: int, P: int, n_img: int, device) -> 
     return hit[1]
 
 
-def mlb_att_forward(feats: torch.Tensor, img_idx: Optional[torch.Tensor], q_emb: torch.Tensor, mw: MlbAttWeights, ws=None):
-    """MLBAtt.forward below the question encoder, in eval mode (ncx_mlb_att_forward; reference vqa/models/att.py:39-163), on the
+def mlb_att_flags(x6=None) -> int:
+    """The flags of the attention model's ..._flags entry points: x6 None = the process-wide choice (EXTRA_FLAGS, read now: NCX_X6=1
+    in the environment), True / False force the form."""
+    return _lib.NCX_F_X6 if (bool(EXTRA_FLAGS & _lib.NCX_F_X6) if x6 is None else bool(x6)) else 0
+
+
+MLB_ATT_LOGITS_FORMS = ("small", "fp32_64", "fp32_208", "x6_64", "x6_208")
+
+
+def mlb_att_logits_form(mw: MlbAttWeights, B: int, P: int, n_img: int, x6=None) -> str:
+    """Which kernel the conv_v_att stage takes for this shape (ncx_mlb_att_logits_form; host only: no launch, no device access)."""
+    d = mw.dims(B, P, n_img)
+    rc = _lib.lib().ncx_mlb_att_logits_form(C.byref(d), mlb_att_flags(x6))
+    if rc < 0:
+        _lib.check(rc, "ncx_mlb_att_logits_form")
+    return MLB_ATT_LOGITS_FORMS[rc]
+
+
+def mlb_att_forward(feats: torch.Tensor, img_idx: Optional[torch.Tensor], q_emb: torch.Tensor, mw: MlbAttWeights, ws=None, x6=None):
+    """MLBAtt.forward below the question encoder, in eval mode (ncx_mlb_att_forward_flags; reference vqa/models/att.py:39-163), on the
     current stream.  feats: the table of NCHW maps [n_img, dv, W, H] (or [n_img, dv, P]), read in place; img_idx [B] int32 picks
-    each question's image, None = the dense input (question b reads feats[b]).  q_emb [B, dq].
+    each question's image, None = the dense input (question b reads feats[b]).  q_emb [B, dq].  x6: mlb_att_flags.
     -> (logits [B, A], att [B, G, P]); att[:, g] is the module's list_att[g], position p = w H + h."""
     if feats.dim() not in (3, 4):
         raise ValueError("feats must be [n_img, dv, W, H] or [n_img, dv, P], got %s" % (tuple(feats.shape),))
@@ -493,9 +512,10 @@ def mlb_att_forward(feats: torch.Tensor, img_idx: Optional[torch.Tensor], q_emb:
     att = torch.empty(B, mw.G, P, dtype=torch.float32, device=dev)
     p, n = _ws_ptr(ws)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().ncx_mlb_att_forward(C.byref(d), _ptr(feats, torch.float32, "feats"), _ptr(img_idx, torch.int32, "img_idx"),
-                                                  _ptr(q_emb, torch.float32, "q_emb"), C.byref(m), p, n, C.c_void_p(logits.data_ptr()),
-                                                  C.c_void_p(att.data_ptr()), _stream()), "ncx_mlb_att_forward")
+        _lib.check(_lib.lib().ncx_mlb_att_forward_flags(C.byref(d), _ptr(feats, torch.float32, "feats"), _ptr(img_idx, torch.int32, "img_idx"),
+                                                        _ptr(q_emb, torch.float32, "q_emb"), C.byref(m), mlb_att_flags(x6), p, n,
+                                                        C.c_void_p(logits.data_ptr()), C.c_void_p(att.data_ptr()), _stream()),
+                   "ncx_mlb_att_forward_flags")
     return logits, att
 
 
@@ -1439,19 +1459,19 @@ def mlb_att_train_workspace(dt, mw: MlbAttWeights, device) -> torch.Tensor:
     return torch.empty(need + 256, dtype=torch.uint8, device=device)
 
 
-def mlb_att_train_forward(dt, feats, img_idx, q_emb, mw: MlbAttWeights, ws, masks=None):
-    """Training-mode MLBAtt below the question encoder (ncx_mlb_att_train_forward) -> (logits [B, A], att [B, G, P]); the stashes
-    stay in ws.  feats [n_img, dv, W, H] or [n_img, dv, P], read in place; img_idx [B] int32."""
+def mlb_att_train_forward(dt, feats, img_idx, q_emb, mw: MlbAttWeights, ws, masks=None, x6=None):
+    """Training-mode MLBAtt below the question encoder (ncx_mlb_att_train_forward_flags) -> (logits [B, A], att [B, G, P]); the stashes
+    stay in ws.  feats [n_img, dv, W, H] or [n_img, dv, P], read in place; img_idx [B] int32.  x6: mlb_att_flags."""
     d, t = dt
     logits = torch.empty(d.B, d.A, dtype=torch.float32, device=feats.device)
     att = torch.empty(d.B, d.G, d.P, dtype=torch.float32, device=feats.device)
     p, n = _ws_ptr(ws)
     with torch.cuda.device(feats.device):
-        _lib.check(_lib.lib().ncx_mlb_att_train_forward(C.byref(d), C.byref(t), _ptr(feats, torch.float32, "feats"),
-                                                        _ptr(img_idx, torch.int32, "img_idx"), _ptr(q_emb, torch.float32, "q_emb"),
-                                                        C.byref(mw.c_struct()), _ptr(masks, torch.float32, "masks"), p, n,
-                                                        C.c_void_p(logits.data_ptr()), C.c_void_p(att.data_ptr()), _stream()),
-                   "ncx_mlb_att_train_forward")
+        _lib.check(_lib.lib().ncx_mlb_att_train_forward_flags(C.byref(d), C.byref(t), _ptr(feats, torch.float32, "feats"),
+                                                              _ptr(img_idx, torch.int32, "img_idx"), _ptr(q_emb, torch.float32, "q_emb"),
+                                                              C.byref(mw.c_struct()), _ptr(masks, torch.float32, "masks"), mlb_att_flags(x6),
+                                                              p, n, C.c_void_p(logits.data_ptr()), C.c_void_p(att.data_ptr()), _stream()),
+                   "ncx_mlb_att_train_forward_flags")
     return logits, att
 
 

@@ -211,11 +211,13 @@ class MlbAttTrainFunction(torch.autograd.Function):
     parameter tensors in ops.MLB_ATT_FIELDS order (the two 1 x 1 convolutions as matrices, the glimpse Linears stacked).  feats is the
     table of NCHW maps, read in place; no gradient goes to it.  Gradients: the parameters, and q_emb when it requires grad; att
     [B, G, P] is not differentiable.  cfg = (acts, p, seed, training): acts the dict of ops.mlb_att_acts, p the six dropout p's in
-    layer order; dropout runs on the counter-based generator under `seed` when training."""
+    layer order; dropout runs on the counter-based generator under `seed` when training.  An optional fifth entry is the x6 choice of
+    ops.mlb_att_flags for the forward (absent or None: the process-wide one)."""
 
     @staticmethod
     def forward(ctx, feats, img_idx, q_emb, wv_att, bv_att, wq_att, bq_att, wa, ba, wg, bg, wqf, bqf, wc, bc, cfg):
-        acts, p, seed, training = cfg
+        acts, p, seed, training = cfg[:4]
+        x6 = cfg[4] if len(cfg) > 4 else None
         t = {k: x.detach().float().contiguous() for k, x in zip(ops.MLB_ATT_FIELDS, (wv_att, bv_att, wq_att, bq_att, wa, ba, wg, bg, wqf, bqf, wc, bc))}
         mw = ops.MlbAttWeights.from_tensors(t, **acts)
         mode = 1 if training and any(x > 0 for x in p) else 0
@@ -224,7 +226,7 @@ class MlbAttTrainFunction(torch.autograd.Function):
         dt = ops.mlb_att_train_dims(mw, img_idx.shape[0], feats[0, 0].numel(), feats.shape[0], p=p if mode else (0.0,) * 6, dropout_mode=mode,
                                     seed=seed, want_dq=ctx.needs_input_grad[2])
         ws = ops.mlb_att_train_workspace(dt, mw, feats.device)
-        logits, att = ops.mlb_att_train_forward(dt, feats, img_idx, q, mw, ws)
+        logits, att = ops.mlb_att_train_forward(dt, feats, img_idx, q, mw, ws, x6=x6)
         ctx.hip = (dt, mw, ws, feats, img_idx, q, att)
         ctx.mark_non_differentiable(att)
         return logits, att
@@ -240,10 +242,10 @@ class MlbAttTrainFunction(torch.autograd.Function):
 
 def mlb_att_module_forward(model, input_v: torch.Tensor, q_emb: torch.Tensor):
     """The HIP training route of MLBAtt.forward below seq2vec -> (logits, att [B, G, P]): input_v [B, dv, W, H] is the table of maps,
-    the index the identity."""
+    the index the identity.  The module's hip_x6 picks the form of the attention kernel (ops.mlb_att_flags)."""
     idx = torch.arange(input_v.shape[0], dtype=torch.int32, device=input_v.device)
     seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if model.training else 0      # torch's CPU generator: torch.manual_seed reproduces it
-    cfg = (ops.mlb_att_acts(model.opt), ops.mlb_att_dropouts(model.opt), seed, bool(model.training))
+    cfg = (ops.mlb_att_acts(model.opt), ops.mlb_att_dropouts(model.opt), seed, bool(model.training), getattr(model, "hip_x6", None))
     lin = list(model.list_linear_v_fusion)
     return MlbAttTrainFunction.apply(input_v, idx, q_emb, model.conv_v_att.weight.flatten(1), model.conv_v_att.bias,
                                      model.linear_q_att.weight, model.linear_q_att.bias, model.conv_att.weight.flatten(1), model.conv_att.bias,

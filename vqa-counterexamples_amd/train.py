@@ -19,7 +19,8 @@ model.arch MLBAtt: training is the module under torch autograd by default (there
 with or without --freeze_seq2vec); --hip_att_train sets the model's use_hip_train: the step below the question encoder (attention head,
 glimpse fusion, classifier; forward with dropout and backward) then runs in HIP inside torch autograd
 (neuralcx.vqa_train.MlbAttTrainFunction), the encoder trains under autograd unless --freeze_seq2vec, torch.optim.Adam steps.  evaluate() / --evaluate run the module in eval mode under no_grad, i.e. its HIP forward
-(ncx_mlb_att_forward), unless --no_hip.  The images are a seeded synthetic attention table [syn_images, dim_v, syn_grid, syn_grid].
+(ncx_mlb_att_forward), unless --no_hip.  --x6 sets the model's hip_x6: both HIP routes of the attention model then run the conv_v_att
+product on the bf16 matrix path with three-plane operands (NCX_F_X6: same results to fp32 rounding; not the default).  The images are a seeded synthetic attention table [syn_images, dim_v, syn_grid, syn_grid].
 """
 import argparse
 import json
@@ -70,6 +71,7 @@ def build_parser():
     p.add_argument("--hip_2lstm_train", action="store_true", help="default route only: train the 2-lstm question encoder (TwoLSTM) in HIP as well (backward through time)")
     p.add_argument("--hip_att_train", action="store_true", help="attention archs only: the training step below the question encoder in HIP as well "
                    "(MLBAtt.use_hip_train: attention head, glimpse fusion, classifier; torch.optim.Adam steps)")
+    p.add_argument("--x6", action="store_true", help="attention archs only: NCX_F_X6 on the attention kernel, same results to fp32 rounding; not the default")
     p.add_argument("--no_hip", action="store_true", help="the plain PyTorch modules (no HIP library; runs on a CPU too)")
     p.add_argument("--seed", type=int, default=1337)
     return p
@@ -143,6 +145,10 @@ class Trainer:
             raise SystemExit("train.py: --hip_att_train trains the attention model in HIP; it cannot be combined with --no_hip")
         if args.hip_att_train and opt["model"].get("arch") not in ATT_ARCHS:
             raise SystemExit("train.py: --hip_att_train needs an attention arch (%s); this YAML builds %r" % (", ".join(ATT_ARCHS), opt["model"].get("arch")))
+        if args.x6 and args.no_hip:
+            raise SystemExit("train.py: --x6 picks a form of the HIP attention kernel; it cannot be combined with --no_hip")
+        if args.x6 and opt["model"].get("arch") not in ATT_ARCHS:
+            raise SystemExit("train.py: --x6 needs an attention arch (%s); this YAML builds %r" % (", ".join(ATT_ARCHS), opt["model"].get("arch")))
         s2v = opt["model"]["seq2vec"]
         if args.hip_2lstm_train and not (s2v.get("arch") == "2-lstm" and "hidden_size" in s2v):       # seq2vec.factory's TwoLSTM branch
             raise SystemExit("train.py: --hip_2lstm_train needs the 2-lstm encoder (seq2vec: {arch: 2-lstm, hidden_size: ...}); this YAML builds %r"
@@ -172,6 +178,9 @@ class Trainer:
                 self.route = "attention head, glimpse fusion and classifier train in HIP (ncx_mlb_att_train_forward / _backward, --hip_att_train); " \
                     "torch.optim.Adam steps; eval-mode forward in HIP (ncx_mlb_att_forward)%s" % (
                         "; --freeze_seq2vec: the encoder is frozen, no d loss / d q_emb is taken" if self.freeze else "")
+            if args.x6:
+                self.model.hip_x6 = True
+                self.route += " (bf16 x 6 attention kernel)"
         else:
             self.route = "torch path: --no_hip" if args.no_hip else route_for(opt["model"])
         self.hip = self.route == "hip"

@@ -82,9 +82,12 @@ class MLBAtt(AbstractAtt):
     keeps it in PyTorch, and so do training mode, grad mode with a parameter that requires grad, an activation other than tanh,
     non-fp32 tensors and shapes the library refuses.  It trains under torch autograd, unless `use_hip_train` is set: then the
     training step below the encoder runs in HIP too (neuralcx.vqa_train.MlbAttTrainFunction: forward with the six dropouts on the
-    counter-based generator, backward through the attention), the encoder training from the d loss / d q_emb it returns."""
+    counter-based generator, backward through the attention), the encoder training from the d loss / d q_emb it returns.
+    `hip_x6` picks the form of the attention kernel on both HIP routes: None the process-wide choice (ops.EXTRA_FLAGS, NCX_X6=1 in
+    the environment), True / False force NCX_F_X6 on / off.  It changes no routing decision."""
     use_hip = True
     use_hip_train = False
+    hip_x6 = None
 
     def __init__(self, opt=None, vocab_words=(), vocab_answers=()):
         opt = opt or {}
@@ -166,7 +169,7 @@ class MLBAtt(AbstractAtt):
             return logits
         if self._hip_ok(input_v, q_vec):
             from neuralcx import ops
-            logits, att = ops.mlb_att_forward(input_v.contiguous(), None, q_vec.contiguous(), self._hip_weights())
+            logits, att = ops.mlb_att_forward(input_v.contiguous(), None, q_vec.contiguous(), self._hip_weights(), x6=self.hip_x6)
             self.list_att = list(att.unbind(1))
             return logits
         return self._torch_forward(input_v, q_vec)
