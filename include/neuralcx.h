@@ -75,6 +75,7 @@ extern "C" {
  *   - d linear_1.weight[:, v_other | v_orig*v_other] (the per-triplet fold pass, H % 256 == 0 and dv % 64 == 0),
  *   - dGt and every other column block of d linear_1.weight (the balanced TN launch, B <= 2048),
  *   - the conv_v_att product of the MLB attention model (ncx_mlb_att_forward_flags, ncx_mlb_att_train_forward_flags: P >= 4, any dv, dh_att, G).
+ *   - d conv_v_att.weight of the MLB attention model's training step (ncx_mlb_att_train_backward_flags: P >= 4, any dv, dh_att, G, B).
  * Shapes outside fall back to the fp32 kernels silently (same results to rounding).  Results agree with the fp32 kernels to fp32 rounding, not
  * bitwise (another summation order); every parity test of the suite passes at its unchanged tolerance with the bit set (NCX_X6=1 in the
  * environment of the Python binding sets it for a whole process). */
@@ -727,8 +728,8 @@ int ncx_mlb_att_train_forward(const ncx_mlb_att_dims* d, const ncx_mlb_att_train
                               const float* q_emb, const ncx_mlb_att_params* m, const float* masks, void* workspace,
                               size_t workspace_bytes, float* logits, float* att, void* stream);
 /* ncx_mlb_att_train_forward (att.py:39-163) with `flags`: 0 (the same call) or NCX_F_X6 (the Xv stash, the position logits and the maps
- * come from the X6 form of the conv_v_att product); any other value is NCX_E_DIMS before any launch.  ncx_mlb_att_train_backward runs
- * unchanged after either. */
+ * come from the X6 form of the conv_v_att product); any other value is NCX_E_DIMS before any launch.  ncx_mlb_att_train_backward[_flags]
+ * runs after either, whatever its own flags. */
 int ncx_mlb_att_train_forward_flags(const ncx_mlb_att_dims* d, const ncx_mlb_att_train* t, const float* feats, const int32_t* img_idx,
                                     const float* q_emb, const ncx_mlb_att_params* m, const float* masks, uint32_t flags, void* workspace,
                                     size_t workspace_bytes, float* logits, float* att, void* stream);
@@ -738,6 +739,19 @@ int ncx_mlb_att_train_backward(const ncx_mlb_att_dims* d, const ncx_mlb_att_trai
                                const float* q_emb, const ncx_mlb_att_params* m, const float* masks, void* workspace,
                                size_t workspace_bytes, const float* att, const float* dlogits, const ncx_mlb_att_grads* g,
                                float* dq_emb, void* stream);
+/* ncx_mlb_att_train_backward with `flags`: 0 (the same call) or NCX_F_X6, which puts d conv_v_att.weight[h, c] = sum over b, p of
+ * dXv[b, p, h] V[b, c, p] (the twin of the forward's conv_v_att product; V is the dropped map when layer 1 is on, else the table read
+ * through img_idx) on the bf16 matrix path with three-plane operands; P < 4 stays fp32; every other gradient and dq_emb are the bits
+ * of the fp32 call.  Any other value is NCX_E_DIMS before any launch.  Same workspace and the same partial-sum slab (NCX_AT_WS_DWV),
+ * written without atomics and summed in the same order: two calls are bit-identical.  d conv_v_att.weight agrees with the fp32 form
+ * to fp32 rounding, not bitwise.  A non-finite map or dXv value is outside the X6 contract (the cut computes Inf - Inf). */
+int ncx_mlb_att_train_backward_flags(const ncx_mlb_att_dims* d, const ncx_mlb_att_train* t, const float* feats, const int32_t* img_idx,
+                                     const float* q_emb, const ncx_mlb_att_params* m, const float* masks, uint32_t flags, void* workspace,
+                                     size_t workspace_bytes, const float* att, const float* dlogits, const ncx_mlb_att_grads* g,
+                                     float* dq_emb, void* stream);
+/* Host only, no launch: which kernel ncx_mlb_att_train_backward_flags takes for d conv_v_att.weight under `flags` (0 or NCX_F_X6).
+ * 0 k_att_dwv_small (P < 4), 1 fp32 k_att_dwv, 2 k_att_dwv_x6; negative: the status the backward returns for these dims or flags. */
+int ncx_mlb_att_dwv_form(const ncx_mlb_att_dims* d, uint32_t flags);
 /* Diagnostics / tests: byte offset and size of a workspace region. */
 #define NCX_AT_WS_XV     1   /* Xv = act_v_att(conv_v_att(drop(V))) [B, P, dh_att]; dXv after the backward               */
 #define NCX_AT_WS_VATT   2   /* v_att [B, G, dv], before layer 4's dropout                                                 */

@@ -1,5 +1,5 @@
 // ncx_mlb_att_train.hip -- the trainable MLB attention model (MLBAtt in training mode) below the question encoder:
-// ncx_mlb_att_train_workspace_bytes, _forward, _backward, _ws_region.  Reference: vqa/models/att.py:39-163 with F.dropout active;
+// ncx_mlb_att_train_workspace_bytes, _forward[_flags], _backward[_flags], _ws_region, ncx_mlb_att_dwv_form.  Reference: vqa/models/att.py:39-163 with F.dropout active;
 // the kernels of the eval-mode forward are shared through ncx_mlb_att.h.  DESIGN 5r.
 //
 // Dropout layers (generator layer id, element index = linear index in the tensor): 1 the map fed to conv_v_att [B, dv, P] (the pooled
@@ -28,6 +28,8 @@
 //                       the stash with dXv = du x_q (1 - Xv^2)
 //   k_att_dwv           dWv_att[h, c] = sum_{b, p} dXv[b, p, h] Vd[b, c, p]: fp32 MFMA, A = the stash (row-is-k), B = the map (col-is-k),
 //                       the two loaders of k_att_logits swapped; the reduction is split over S groups of images into a slab
+//                       (NCX_F_X6 on the backward: k_att_dwv_x6, the same product and slab on the bf16 matrix path with three-plane
+//                       operands; a non-finite map or dXv value is outside that contract)
 //   k_at_sumrows        fixed-order sums over b / S: dWv_att, dWa, dbv_att, dba, and the bias gradients of the tail
 //   k_at_dact, TN       dpq = dxq (1 - x_q^2);  dWq_att = dpq^T q2
 //   NN + drop2, NN + drop5, k_at_add      dq_emb, on request
@@ -331,6 +333,204 @@ __global__ __launch_bounds__(256, 2) void k_att_dwv(const DwvArgs a) {
                 if (h < a.dh && c < a.dv) out[(long long)h * a.dv + c] = acc[i][j][q];
             }
 }
+// ---- the same product on the bf16 matrix path with fp32-grade operands (NCX_F_X6; not the default) ----------------------------------
+// The cut, the six products and their order are those of k_att_logits_x6 (ncx_mlb_att.h), and so is the LDS image, with the roles
+// renamed: the operand whose k runs along rows is dXv [P positions][dh_att] (there the map [dv channels][P]) and goes to LDS in the
+// global layout, three planes of [32 positions][DWV6_TH hidden] at a pitch of DWV6_TH * 2 + 32 bytes (8 consecutive position rows on
+// 8 distinct 32-byte bank groups), read through ds_read_b64_tr_b16; the operand whose k is contiguous is the map [dv][P] (there the
+// weight [dh_att][dv]), three planes of [128 channels][32 positions] at 80 bytes per row, read with plain 16-byte loads.  A transposed
+// read hands lane group lk the positions 4 lk .. 4 lk + 3 and 16 + 4 lk .. 16 + 4 lk + 3, so a map row is stored in that order:
+// position quad q < 4 at byte 16 q, quad q >= 4 at byte 16 (q - 4) + 8.  Neither fragment is permuted in registers.
+// One workgroup: 8 waves in a 2 x 4 grid, DWV6_TH = 160 hidden x 128 channels (5 block rows x 2 column blocks of 16 x 16 per wave),
+// all images of group z as ONE pipeline of 32-deep steps like k_att_dwv: tile t lives in register set t & 1 and LDS buffer t & 1;
+// step t issues the loads of tile t + 2 (re-pointed at the next image when tile t + 1 was an image's last), multiplies tile t, and
+// cuts and stores tile t + 1 part by part under the MFMAs of the later block rows.  One barrier per step.  The ragged last step of
+// an image is a full 32-deep step whose rows beyond P are stored as exact zeros (clamped loads, zeroed by select at store time):
+// 7 x 32 = 224 against P = 196 is 12.5 % more MFMA work, accepted because the kernel is bound by its loader path, not by the matrix
+// cores, and a 16-deep MFMA needs a second fragment layout.  160 hidden units: at dh_att = 1200, dv = 2048 the slab's S = 4 groups
+// give 8 x 16 x 4 = 512 workgroups, two whole rounds at one workgroup per CU, and 1280 / 1200 is the smallest padding of any tile
+// that fits LDS.  The slab, S, ipg and the order k_at_sumrows adds the groups in are those of k_att_dwv.
+constexpr int DWV6_TH = 160, DWV6_TC = 128, DWV6_T = 512, DWV6_PB = 80;
+struct DwvCfg6 {
+    static constexpr int PA = DWV6_TH * 2 + 32;                                // bytes per position row of one dXv plane
+    static constexpr int A_PL = GEMM_BK * PA, PL = A_PL + DWV6_TC * DWV6_PB, BUF = 3 * PL;     // one plane (dXv rows | map rows), one buffer
+    static constexpr int QR = DWV6_TH / 4, QA = QR * GEMM_BK;                  // 16-byte items per position row, per dXv tile
+    static constexpr int NA = (QA + DWV6_T - 1) / DWV6_T, NB = DWV6_TC * 8 / DWV6_T;      // items per thread: 3 (the last one half used); 2
+    static constexpr int LDS_BYTES = 2 * BUF;
+    static constexpr int WM = DWV6_TH / 32, WN = 2;                            // 16 x 16 blocks per wave
+    static_assert(PA % 64 == 32, "dXv pitch: an odd number of 32-byte bank groups");
+    static_assert(DWV6_TH % 32 == 0 && GEMM_BK == 32, "wave grid");
+    static_assert(LDS_BYTES <= 160 * 1024, "LDS");
+};
+
+__global__ __launch_bounds__(DWV6_T, 1) void k_att_dwv_x6(const DwvArgs a) {
+    typedef DwvCfg6 Cfg;
+    constexpr int T = DWV6_T, PA = Cfg::PA, PB = DWV6_PB, PL = Cfg::PL, A_PL = Cfg::A_PL, BUF = Cfg::BUF, WM = Cfg::WM, WN = Cfg::WN;
+    constexpr int NA = Cfg::NA, NB = Cfg::NB, QR = Cfg::QR, QA = Cfg::QA, BK = GEMM_BK;
+    extern __shared__ __attribute__((aligned(16))) float dwv6_smem[];
+    unsigned char* const lds = (unsigned char*)dwv6_smem;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lk = lane >> 4;
+    const int wm0 = (wave >> 2) * (WM * 16), wn0 = (wave & 3) * (WN * 16);
+    int id = blockIdx.x;
+    const int ct = id % a.CT; id /= a.CT;
+    const int ht = id % a.HT;
+    const int z = id / a.HT;
+    const int h0 = ht * DWV6_TH, c0 = ct * DWV6_TC, P = a.P, dh = a.dh, dv = a.dv;
+    const int b0 = z * a.ipg, b1 = min(a.B, b0 + a.ipg);
+    const int nsteps = (b1 - b0) * ((P + BK - 1) / BK);
+
+    // ---- loader: dXv item e = tid + T i -> position row e / QR, hidden units h0 + 4 (e % QR) ..; map item i -> channel row
+    // (tid >> 3) + 64 i, position quad tid & 7.  16-byte windows slid left to stay inside the row and repaired at store time.
+    int arow[NA], acol[NA], adst[NA];
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+        const int e = min(tid + T * i, QA - 1);            // (items beyond the tile re-load its last one; never stored)
+        arow[i] = e / QR; acol[i] = h0 + 4 * (e % QR);
+        adst[i] = arow[i] * PA + (e % QR) * 8;
+    }
+    const int bq = tid & 7;
+    int boff[NB], bdst[NB];
+    bool bok[NB];
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+        const int r = (tid >> 3) + 64 * i, c = c0 + r;
+        bok[i] = c < dv;
+        boff[i] = min(c, dv - 1) * P;                      // 32-bit offsets inside one image
+        bdst[i] = A_PL + r * PB + (bq < 4 ? 16 * bq : 16 * (bq - 4) + 8);
+    }
+    f32x4 va[2][NA], vb[2][NB];                            // two register sets: the loads run a whole step ahead of their store
+    auto issue = [&](auto set_c, int b, int k) __attribute__((always_inline)) {
+        constexpr int S = decltype(set_c)::value;
+        const int img = a.identity ? b : clamp_img(a.img_idx[b], a.n_img);
+        const float* const xb = a.dxv + (long long)b * P * dh;               // 64-bit bases; 32-bit offsets inside a row-block
+        const float* const mb = a.map + (long long)img * dv * P;
+        if (k + BK <= P) {                                 // whole 32-position steps: straight-line
+#pragma unroll
+            for (int i = 0; i < NA; ++i) va[S][i] = load_window(xb + (k + arow[i]) * dh, acol[i], dh);
+#pragma unroll
+            for (int i = 0; i < NB; ++i) vb[S][i] = *(const f32x4u*)(mb + boff[i] + k + 4 * bq);
+        } else {                                           // the ragged last step of an image: position rows clamped, position windows slid
+#pragma unroll
+            for (int i = 0; i < NA; ++i) va[S][i] = load_window(xb + min(k + arow[i], P - 1) * dh, acol[i], dh);
+#pragma unroll
+            for (int i = 0; i < NB; ++i) vb[S][i] = load_window(mb + boff[i], k + 4 * bq, P);
+        }
+    };
+    // x -> three bf16 planes (four values: one 8-byte store per plane)
+    auto split_store = [&](f32x4 v, unsigned char* base) __attribute__((always_inline)) {
+        unsigned p1[4], p2[4], p3[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float xj = v[j];               // (a scalar copy first: __builtin_bit_cast applied to the vector element itself reads element 0 -- hipcc 7.2)
+            p1[j] = __builtin_bit_cast(unsigned, xj) & 0xFFFF0000u;
+            const float r1 = xj - __builtin_bit_cast(float, p1[j]);
+            p2[j] = __builtin_bit_cast(unsigned, r1) & 0xFFFF0000u;
+            const float r2 = r1 - __builtin_bit_cast(float, p2[j]);
+            p3[j] = __builtin_bit_cast(unsigned, r2);            // (at most 8 significant bits are left: the high half holds them all)
+        }
+        const att_u32x2 w1 = {__builtin_amdgcn_perm(p1[1], p1[0], 0x07060302u), __builtin_amdgcn_perm(p1[3], p1[2], 0x07060302u)};
+        const att_u32x2 w2 = {__builtin_amdgcn_perm(p2[1], p2[0], 0x07060302u), __builtin_amdgcn_perm(p2[3], p2[2], 0x07060302u)};
+        const att_u32x2 w3 = {__builtin_amdgcn_perm(p3[1], p3[0], 0x07060302u), __builtin_amdgcn_perm(p3[3], p3[2], 0x07060302u)};
+        *(att_u32x2*)(base) = w1; *(att_u32x2*)(base + PL) = w2; *(att_u32x2*)(base + 2 * PL) = w3;
+    };
+    // part s < NA: dXv item s; part NA + i: map item i.  Positions beyond P, hidden units beyond dh_att and channels beyond dv are zero.
+    auto store = [&](auto set_c, int k, int buf, int s0, int s1) __attribute__((always_inline)) {
+        constexpr int S = decltype(set_c)::value;
+        unsigned char* const base = lds + buf * BUF;
+        const bool ragged = k + BK > P;
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            if (i < s0 || i >= s1) continue;
+            if (NA * T != QA && tid + T * i >= QA) continue;
+            f32x4 v = fix_window(va[S][i], acol[i], dh);
+            if (ragged && k + arow[i] >= P) v = zero;
+            split_store(v, base + adst[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            if (NA + i < s0 || NA + i >= s1) continue;
+            f32x4 v = vb[S][i];
+            if (ragged) v = fix_window(v, k + 4 * bq, P);
+            if (!bok[i]) v = zero;
+            split_store(v, base + bdst[i]);
+        }
+    };
+
+    f32x4 acc[WM][WN];
+#pragma unroll
+    for (int i = 0; i < WM; ++i)
+#pragma unroll
+        for (int j = 0; j < WN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    typedef __attribute__((address_space(3))) att_s16x4* lds_s16x4;
+    const int tq = li >> 2, tp = li & 3;
+    const int fragA = (4 * lk + tq) * PA + (wm0 + 4 * tp) * 2, fragB = A_PL + (wn0 + li) * PB + 16 * lk;
+    constexpr int NP = NA + NB;                        // parts of the next tile's store, spread over the block rows of this step
+    typedef std::integral_constant<int, 0> S0; typedef std::integral_constant<int, 1> S1;
+    int k1 = 0;                                        // first position of tile t + 1
+    int b2 = b0, k2 = 0;                               // image and first position of tile t + 2
+    auto advance = [&](int& b, int& k) __attribute__((always_inline)) { k += BK; if (k >= P) { k = 0; ++b; } };
+    auto step = [&](auto par_c, int t) __attribute__((always_inline)) {
+        constexpr int PAR = decltype(par_c)::value;
+        typedef std::integral_constant<int, PAR ^ 1> SN;
+        const bool has_next = t + 1 < nsteps;
+        if (t + 2 < nsteps) { issue(par_c, b2, k2); advance(b2, k2); }
+        const unsigned char* const base = lds + PAR * BUF;
+        att_bf16x8 bf[WN][3];
+#pragma unroll
+        for (int j = 0; j < WN; ++j)
+#pragma unroll
+            for (int p = 0; p < 3; ++p) bf[j][p] = *(const att_bf16x8*)(base + p * PL + fragB + j * 16 * PB);
+#pragma unroll
+        for (int i = 0; i < WM; ++i) {
+            att_bf16x8 af[3];
+#pragma unroll
+            for (int p = 0; p < 3; ++p) {
+                const unsigned char* ta = base + p * PL + fragA + i * 32;
+                const att_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(ta));
+                const att_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(ta + 16 * PA));
+                af[p] = __builtin_bit_cast(att_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+            }
+            // the 12 MFMAs of block row i: the two column blocks alternate (a dependent MFMA is two issues away); small terms first
+#pragma unroll
+            for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bf[j][2], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bf[j][1], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[2], bf[j][0], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bf[j][1], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bf[j][0], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bf[j][0], acc[i][j], 0, 0, 0);
+            if (has_next) store(SN{}, k1, PAR ^ 1, i * NP / WM, (i + 1) * NP / WM);
+        }
+        __syncthreads();
+        k1 += BK; if (k1 >= P) k1 = 0;
+    };
+    issue(S0{}, b2, k2); advance(b2, k2);
+    if (nsteps > 1) { issue(S1{}, b2, k2); advance(b2, k2); }
+    store(S0{}, 0, 0, 0, NP);
+    __syncthreads();
+    k1 = BK < P ? BK : 0;
+    for (int t = 0; t < nsteps; t += 2) {
+        step(S0{}, t);
+        if (t + 1 < nsteps) step(S1{}, t + 1);
+    }
+    float* const out = a.slab + (long long)z * dh * dv;
+#pragma unroll
+    for (int i = 0; i < WM; ++i)
+#pragma unroll
+        for (int j = 0; j < WN; ++j)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int h = h0 + wm0 + i * 16 + lk * 4 + q, c = c0 + wn0 + j * 16 + li;
+                if (h < dh && c < dv) out[(long long)h * dv + c] = acc[i][j][q];
+            }
+}
 // P < 4 (no 16-byte window fits a row of the map): one thread per (h, c), b then p ascending
 __global__ __launch_bounds__(256) void k_att_dwv_small(const DwvArgs a, float* __restrict__ out) {
     const long long i = blockIdx.x * 256ll + threadIdx.x;
@@ -375,6 +575,17 @@ AttDrop at_drop(const ncx_mlb_att_train& t) {
     return k;
 }
 
+// the limits the training step adds to check_att_dims (d has passed it)
+int at_check_dims(const ncx_mlb_att_dims* d) {
+    const long long lim = 1ll << 31, B = d->B;
+    if ((long long)d->P * d->dh_att * 4 >= lim) return NCX_E_DIMS;                    // 32-bit offsets inside one question's stash block
+    if ((long long)d->dh_att * d->dv >= lim / 4 || (long long)d->G * d->dh_att >= lim) return NCX_E_DIMS;
+    if (B * d->dv * (long long)d->P / 256 >= lim - 1 || B * d->P * (long long)d->dh_att / 256 >= lim - 1) return NCX_E_DIMS;     // grids
+    if (B * d->dq >= lim || (long long)d->G * d->dh_f * (long long)(d->dq > d->dv ? d->dq : d->dv) >= lim || (long long)d->A * d->G * d->dh_f >= lim ||
+        (long long)d->dh_att * d->dq >= lim) return NCX_E_DIMS;
+    if (cdiv(d->dh_att, DWV_TH) * cdiv(d->dv, DWV_TC) * DWV_MAX_S >= lim || d->B > 65535 || cdiv(d->dv, DATT_ROWS) > 65535) return NCX_E_DIMS;
+    return NCX_OK;
+}
 int at_check(const ncx_mlb_att_dims* d, const ncx_mlb_att_train* t, const ncx_mlb_att_params* m, bool need_ptrs) {
     if (!d || !t || !m) return NCX_E_NULL;
     if (need_ptrs) { const int rc = check_att(d, m); if (rc != NCX_OK) return rc; }
@@ -388,14 +599,7 @@ int at_check(const ncx_mlb_att_dims* d, const ncx_mlb_att_train* t, const ncx_ml
     if (t->dropout_mode < 0 || t->dropout_mode > 2) return NCX_E_DIMS;
     const float ps[6] = {t->p_att_v, t->p_att_q, t->p_att_mm, t->p_v, t->p_q, t->p_c};
     for (int i = 0; i < 6; ++i) if (!(ps[i] >= 0.f && ps[i] < 1.f)) return NCX_E_DIMS;
-    const long long lim = 1ll << 31, B = d->B;
-    if ((long long)d->P * d->dh_att * 4 >= lim) return NCX_E_DIMS;                    // 32-bit offsets inside one question's stash block
-    if ((long long)d->dh_att * d->dv >= lim / 4 || (long long)d->G * d->dh_att >= lim) return NCX_E_DIMS;
-    if (B * d->dv * (long long)d->P / 256 >= lim - 1 || B * d->P * (long long)d->dh_att / 256 >= lim - 1) return NCX_E_DIMS;     // grids
-    if (B * d->dq >= lim || (long long)d->G * d->dh_f * (long long)(d->dq > d->dv ? d->dq : d->dv) >= lim || (long long)d->A * d->G * d->dh_f >= lim ||
-        (long long)d->dh_att * d->dq >= lim) return NCX_E_DIMS;
-    if (cdiv(d->dh_att, DWV_TH) * cdiv(d->dv, DWV_TC) * DWV_MAX_S >= lim || d->B > 65535 || cdiv(d->dv, DATT_ROWS) > 65535) return NCX_E_DIMS;
-    return NCX_OK;
+    return at_check_dims(d);
 }
 
 // The products of the step on the generic engine (pointers may be NULL when only sizing the slab).  AT_DVATT: problem `gi` of G.
@@ -519,6 +723,9 @@ int at_run(const ncx_mlb_att_dims& d, const ncx_mlb_att_train& t, const ncx_mlb_
     return run_gemm_planned(a, form, pl, (float*)(ws + w.slab), w.slab_bytes, bias, s);
 }
 
+// which kernel d conv_v_att.weight takes (ncx_mlb_att_dwv_form): 0 k_att_dwv_small, 1 fp32 k_att_dwv, 2 k_att_dwv_x6
+inline int at_dwv_form(int P, uint32_t flags) { return P < 4 ? 0 : (flags & NCX_F_X6) ? 2 : 1; }
+
 bool at_grads_null(const ncx_mlb_att_grads* g) {
     return !g->wv_att || !g->bv_att || !g->wq_att || !g->bq_att || !g->wa || !g->ba || !g->wg || !g->bg || !g->wqf || !g->bqf || !g->wc || !g->bc;
 }
@@ -630,6 +837,22 @@ int ncx_mlb_att_train_backward(const ncx_mlb_att_dims* dp, const ncx_mlb_att_tra
                                const float* q_emb, const ncx_mlb_att_params* mp, const float* masks, void* workspace,
                                size_t workspace_bytes, const float* att, const float* dlogits, const ncx_mlb_att_grads* g,
                                float* dq_emb, void* stream_) {
+    return ncx_mlb_att_train_backward_flags(dp, tp, feats, img_idx, q_emb, mp, masks, 0, workspace, workspace_bytes, att, dlogits, g, dq_emb,
+                                            stream_);
+}
+
+int ncx_mlb_att_dwv_form(const ncx_mlb_att_dims* d, uint32_t flags) {
+    if (!att_flags_ok(flags)) return NCX_E_DIMS;
+    int rc = check_att_dims(d);
+    if (rc == NCX_OK) rc = at_check_dims(d);
+    return rc != NCX_OK ? rc : at_dwv_form(d->P, flags);
+}
+
+int ncx_mlb_att_train_backward_flags(const ncx_mlb_att_dims* dp, const ncx_mlb_att_train* tp, const float* feats, const int32_t* img_idx,
+                                     const float* q_emb, const ncx_mlb_att_params* mp, const float* masks, uint32_t flags, void* workspace,
+                                     size_t workspace_bytes, const float* att, const float* dlogits, const ncx_mlb_att_grads* g,
+                                     float* dq_emb, void* stream_) {
+    if (!att_flags_ok(flags)) return NCX_E_DIMS;
     int rc = at_check(dp, tp, mp, true);
     if (rc != NCX_OK) return rc;
     if (!feats || !img_idx || !q_emb || !workspace || !att || !dlogits || !g || at_grads_null(g)) return NCX_E_NULL;
@@ -696,7 +919,14 @@ int ncx_mlb_att_train_backward(const ncx_mlb_att_dims* dp, const ncx_mlb_att_tra
         a.dxv = F(w.stash); a.map = at_on(t, 1) ? F(w.vd) : feats; a.img_idx = img_idx; a.slab = F(w.dwv);
         a.P = d.P; a.dv = d.dv; a.dh = d.dh_att; a.B = B; a.n_img = d.n_img; a.ipg = w.ipg;
         a.HT = (int)cdiv(d.dh_att, DWV_TH); a.CT = (int)cdiv(d.dv, DWV_TC); a.identity = at_on(t, 1) ? 1 : 0;
-        if (d.P >= 4) {
+        if (at_dwv_form(d.P, flags) == 2) {             // the same slab, groups and sum; fewer, larger tiles
+            static DevMask attr_set{0};
+            a.HT = (int)cdiv(d.dh_att, DWV6_TH); a.CT = (int)cdiv(d.dv, DWV6_TC);
+            NCX_HIP_TRY(set_max_lds_once(attr_set, (const void*)k_att_dwv_x6, DwvCfg6::LDS_BYTES));
+            hipLaunchKernelGGL(k_att_dwv_x6, dim3((unsigned)((long long)w.S * a.HT * a.CT)), dim3(DWV6_T), DwvCfg6::LDS_BYTES, s, a);
+            NCX_HIP_TRY(hipGetLastError());
+            rc = sumrows(F(w.dwv), (long long)d.dh_att * d.dv, w.S, g->wv_att); if (rc) return rc;
+        } else if (d.P >= 4) {
             hipLaunchKernelGGL(k_att_dwv, dim3((unsigned)((long long)w.S * a.HT * a.CT)), dim3(256), 0, s, a);
             NCX_HIP_TRY(hipGetLastError());
             rc = sumrows(F(w.dwv), (long long)d.dh_att * d.dv, w.S, g->wv_att); if (rc) return rc;

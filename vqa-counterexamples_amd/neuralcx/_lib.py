@@ -33,7 +33,8 @@ EXPORTS = ("ncx_input_size", "ncx_workspace_bytes", "ncx_forward", "ncx_forward_
            "ncx_contrastive_backward",
            "ncx_vqa_train_workspace_bytes", "ncx_vqa_train_forward", "ncx_ce_loss", "ncx_vqa_train_backward", "ncx_vqa_train_ws_region",
            "ncx_mlb_train_workspace_bytes", "ncx_mlb_train_forward", "ncx_mlb_train_backward", "ncx_mlb_train_ws_region",
-           "ncx_mlb_att_train_workspace_bytes", "ncx_mlb_att_train_forward", "ncx_mlb_att_train_forward_flags", "ncx_mlb_att_train_backward", "ncx_mlb_att_train_ws_region")
+           "ncx_mlb_att_train_workspace_bytes", "ncx_mlb_att_train_forward", "ncx_mlb_att_train_forward_flags", "ncx_mlb_att_train_backward", "ncx_mlb_att_train_ws_region",
+           "ncx_mlb_att_train_backward_flags", "ncx_mlb_att_dwv_form")
 
 
 class NcxDims(C.Structure):
@@ -324,6 +325,11 @@ def lib():
     L.ncx_mlb_att_train_backward.restype = C.c_int
     L.ncx_mlb_att_train_backward.argtypes = [P_AD, P_AT, C.c_void_p, C.c_void_p, C.c_void_p, P_AP, C.c_void_p, C.c_void_p, C.c_size_t,
                                              C.c_void_p, C.c_void_p, C.POINTER(NcxMlbAttGrads), C.c_void_p, C.c_void_p]
+    L.ncx_mlb_att_train_backward_flags.restype = C.c_int
+    L.ncx_mlb_att_train_backward_flags.argtypes = [P_AD, P_AT, C.c_void_p, C.c_void_p, C.c_void_p, P_AP, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                   C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(NcxMlbAttGrads), C.c_void_p, C.c_void_p]
+    L.ncx_mlb_att_dwv_form.restype = C.c_int
+    L.ncx_mlb_att_dwv_form.argtypes = [P_AD, C.c_uint32]
     L.ncx_mlb_att_train_ws_region.restype = C.c_int
     L.ncx_mlb_att_train_ws_region.argtypes = [P_AD, P_AT, P_AP, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     _lib = L

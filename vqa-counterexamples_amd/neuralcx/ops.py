@@ -1475,9 +1475,22 @@ def mlb_att_train_forward(dt, feats, img_idx, q_emb, mw: MlbAttWeights, ws, mask
     return logits, att
 
 
-def mlb_att_train_backward(dt, feats, img_idx, q_emb, mw: MlbAttWeights, ws, att, dlogits, grads: Dict[str, torch.Tensor], masks=None):
-    """Every gradient of MLB_ATT_FIELDS into `grads` (overwritten) after mlb_att_train_forward on the same workspace and inputs;
-    -> d loss / d q_emb [B, dq] when want_dq, else None."""
+MLB_ATT_DWV_FORMS = ("small", "fp32", "x6")
+
+
+def mlb_att_dwv_form(mw: MlbAttWeights, B: int, P: int, n_img: int, x6=None) -> str:
+    """Which kernel d conv_v_att.weight takes for this shape (ncx_mlb_att_dwv_form; host only: no launch, no device access)."""
+    d = mw.dims(B, P, n_img)
+    rc = _lib.lib().ncx_mlb_att_dwv_form(C.byref(d), mlb_att_flags(x6))
+    if rc < 0:
+        _lib.check(rc, "ncx_mlb_att_dwv_form")
+    return MLB_ATT_DWV_FORMS[rc]
+
+
+def mlb_att_train_backward(dt, feats, img_idx, q_emb, mw: MlbAttWeights, ws, att, dlogits, grads: Dict[str, torch.Tensor], masks=None, x6=None):
+    """Every gradient of MLB_ATT_FIELDS into `grads` (overwritten) after mlb_att_train_forward on the same workspace and inputs
+    (ncx_mlb_att_train_backward_flags; x6: mlb_att_flags, independent of the forward's); -> d loss / d q_emb [B, dq] when want_dq,
+    else None."""
     d, t = dt
     g = _lib.NcxMlbAttGrads()
     for k in MLB_ATT_FIELDS:
@@ -1485,11 +1498,12 @@ def mlb_att_train_backward(dt, feats, img_idx, q_emb, mw: MlbAttWeights, ws, att
     dq = torch.empty(d.B, d.dq, dtype=torch.float32, device=dlogits.device) if t.want_dq else None
     p, n = _ws_ptr(ws)
     with torch.cuda.device(dlogits.device):
-        _lib.check(_lib.lib().ncx_mlb_att_train_backward(C.byref(d), C.byref(t), _ptr(feats, torch.float32, "feats"),
-                                                         _ptr(img_idx, torch.int32, "img_idx"), _ptr(q_emb, torch.float32, "q_emb"),
-                                                         C.byref(mw.c_struct()), _ptr(masks, torch.float32, "masks"), p, n,
-                                                         _ptr(att, torch.float32, "att"), _ptr(dlogits, torch.float32, "dlogits"), C.byref(g),
-                                                         _ptr(dq, torch.float32, "dq_emb"), _stream()), "ncx_mlb_att_train_backward")
+        _lib.check(_lib.lib().ncx_mlb_att_train_backward_flags(C.byref(d), C.byref(t), _ptr(feats, torch.float32, "feats"),
+                                                               _ptr(img_idx, torch.int32, "img_idx"), _ptr(q_emb, torch.float32, "q_emb"),
+                                                               C.byref(mw.c_struct()), _ptr(masks, torch.float32, "masks"), mlb_att_flags(x6),
+                                                               p, n, _ptr(att, torch.float32, "att"), _ptr(dlogits, torch.float32, "dlogits"),
+                                                               C.byref(g), _ptr(dq, torch.float32, "dq_emb"), _stream()),
+                   "ncx_mlb_att_train_backward_flags")
     return dq
 
 

@@ -212,7 +212,7 @@ class MlbAttTrainFunction(torch.autograd.Function):
     table of NCHW maps, read in place; no gradient goes to it.  Gradients: the parameters, and q_emb when it requires grad; att
     [B, G, P] is not differentiable.  cfg = (acts, p, seed, training): acts the dict of ops.mlb_att_acts, p the six dropout p's in
     layer order; dropout runs on the counter-based generator under `seed` when training.  An optional fifth entry is the x6 choice of
-    ops.mlb_att_flags for the forward (absent or None: the process-wide one)."""
+    ops.mlb_att_flags for the forward and the backward (absent or None: the process-wide one)."""
 
     @staticmethod
     def forward(ctx, feats, img_idx, q_emb, wv_att, bv_att, wq_att, bq_att, wa, ba, wg, bg, wqf, bqf, wc, bc, cfg):
@@ -227,22 +227,22 @@ class MlbAttTrainFunction(torch.autograd.Function):
                                     seed=seed, want_dq=ctx.needs_input_grad[2])
         ws = ops.mlb_att_train_workspace(dt, mw, feats.device)
         logits, att = ops.mlb_att_train_forward(dt, feats, img_idx, q, mw, ws, x6=x6)
-        ctx.hip = (dt, mw, ws, feats, img_idx, q, att)
+        ctx.hip = (dt, mw, ws, feats, img_idx, q, att, x6)
         ctx.mark_non_differentiable(att)
         return logits, att
 
     @staticmethod
     def backward(ctx, dlogits, _datt=None):
-        dt, mw, ws, feats, img_idx, q, att = ctx.hip
+        dt, mw, ws, feats, img_idx, q, att, x6 = ctx.hip
         grads = {k: torch.empty_like(v) for k, v in mw.t.items()}
-        dq = ops.mlb_att_train_backward(dt, feats, img_idx, q, mw, ws, att, dlogits.float().contiguous(), grads)
+        dq = ops.mlb_att_train_backward(dt, feats, img_idx, q, mw, ws, att, dlogits.float().contiguous(), grads, x6=x6)
         ctx.hip = None                                            # the stash is the step's largest buffer: let go of it here
         return (None, None, dq) + tuple(grads[k] for k in ops.MLB_ATT_FIELDS) + (None,)
 
 
 def mlb_att_module_forward(model, input_v: torch.Tensor, q_emb: torch.Tensor):
     """The HIP training route of MLBAtt.forward below seq2vec -> (logits, att [B, G, P]): input_v [B, dv, W, H] is the table of maps,
-    the index the identity.  The module's hip_x6 picks the form of the attention kernel (ops.mlb_att_flags)."""
+    the index the identity.  The module's hip_x6 picks the form of the attention kernel and of its weight-gradient twin (ops.mlb_att_flags)."""
     idx = torch.arange(input_v.shape[0], dtype=torch.int32, device=input_v.device)
     seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if model.training else 0      # torch's CPU generator: torch.manual_seed reproduces it
     cfg = (ops.mlb_att_acts(model.opt), ops.mlb_att_dropouts(model.opt), seed, bool(model.training), getattr(model, "hip_x6", None))

@@ -20,7 +20,8 @@ with or without --freeze_seq2vec); --hip_att_train sets the model's use_hip_trai
 glimpse fusion, classifier; forward with dropout and backward) then runs in HIP inside torch autograd
 (neuralcx.vqa_train.MlbAttTrainFunction), the encoder trains under autograd unless --freeze_seq2vec, torch.optim.Adam steps.  evaluate() / --evaluate run the module in eval mode under no_grad, i.e. its HIP forward
 (ncx_mlb_att_forward), unless --no_hip.  --x6 sets the model's hip_x6: both HIP routes of the attention model then run the conv_v_att
-product on the bf16 matrix path with three-plane operands (NCX_F_X6: same results to fp32 rounding; not the default).  The images are a seeded synthetic attention table [syn_images, dim_v, syn_grid, syn_grid].
+product on the bf16 matrix path with three-plane operands (NCX_F_X6: same results to fp32 rounding; not the default), and with
+--hip_att_train the backward runs its twin, d conv_v_att.weight, there as well.  The images are a seeded synthetic attention table [syn_images, dim_v, syn_grid, syn_grid].
 """
 import argparse
 import json
@@ -181,6 +182,8 @@ class Trainer:
             if args.x6:
                 self.model.hip_x6 = True
                 self.route += " (bf16 x 6 attention kernel)"
+                if args.hip_att_train:
+                    self.route += " (and its weight-gradient twin in the backward)"
         else:
             self.route = "torch path: --no_hip" if args.no_hip else route_for(opt["model"])
         self.hip = self.route == "hip"

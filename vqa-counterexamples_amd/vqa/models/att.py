@@ -83,7 +83,7 @@ class MLBAtt(AbstractAtt):
     non-fp32 tensors and shapes the library refuses.  It trains under torch autograd, unless `use_hip_train` is set: then the
     training step below the encoder runs in HIP too (neuralcx.vqa_train.MlbAttTrainFunction: forward with the six dropouts on the
     counter-based generator, backward through the attention), the encoder training from the d loss / d q_emb it returns.
-    `hip_x6` picks the form of the attention kernel on both HIP routes: None the process-wide choice (ops.EXTRA_FLAGS, NCX_X6=1 in
+    `hip_x6` picks the form of the attention kernel on both HIP routes, and of its weight-gradient twin in the training route's backward: None the process-wide choice (ops.EXTRA_FLAGS, NCX_X6=1 in
     the environment), True / False force NCX_F_X6 on / off.  It changes no routing decision."""
     use_hip = True
     use_hip_train = False
