@@ -76,6 +76,8 @@ extern "C" {
  *   - dGt and every other column block of d linear_1.weight (the balanced TN launch, B <= 2048),
  *   - the conv_v_att product of the MLB attention model (ncx_mlb_att_forward_flags, ncx_mlb_att_train_forward_flags: P >= 4, any dv, dh_att, G).
  *   - d conv_v_att.weight of the MLB attention model's training step (ncx_mlb_att_train_backward_flags: P >= 4, any dv, dh_att, G, B).
+ *   - the GRU question encoder's step product [x_t | h_{t-1}] . [W_ih | W_hh]^T (ncx_gru_encode_flags, ncx_gru_train_forward_flags: every legal
+ *     shape, no fall-back; these two take the bit from their own `flags` argument only).
  * Shapes outside fall back to the fp32 kernels silently (same results to rounding).  Results agree with the fp32 kernels to fp32 rounding, not
  * bitwise (another summation order); every parity test of the suite passes at its unchanged tolerance with the bit set (NCX_X6=1 in the
  * environment of the Python binding sets it for a whole process). */
@@ -430,6 +432,17 @@ size_t ncx_gru_workspace_bytes(int32_t B, int32_t T, int32_t dim_emb, int32_t di
  * address (it is clamped; that row's output is meaningless) and *bad_id_flag is set to 1 (never cleared here; the caller zeroes it). */
 int ncx_gru_encode(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t dim_emb, int32_t dim_q,
                    const float* packed, void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream);
+/* ncx_gru_encode (seq2vec.py:11-25) with `flags`: 0 (the same call, the same bits) or NCX_F_X6, which runs every step's product
+ * [x_t | h_{t-1}] . [W_ih | W_hh]^T on the bf16 matrix path with three-plane operands (k_gru_step_x6, csrc/ncx_gru_x6.hip): the same packed
+ * weights, the same workspace, the same T + 1 launches, the same epilogue; every legal shape, no fall-back to the fp32 kernel.  Results
+ * agree with flags 0 to fp32 rounding, not bitwise; bit-identical from run to run.  Any other `flags` returns -1 before any launch or
+ * pointer use. */
+int ncx_gru_encode_flags(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t dim_emb, int32_t dim_q,
+                         const float* packed, uint32_t flags, void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag,
+                         void* stream);
+/* Host only, no launch: which step kernel ncx_gru_encode_flags / ncx_gru_train_forward_flags take for these dims under `flags`:
+ * 0 = the fp32 step kernel, 1 = the X6 step kernel, -1 = dims or flags refused. */
+int ncx_gru_step_form(int32_t B, int32_t T, int32_t dim_emb, int32_t dim_q, uint32_t flags);
 
 /* ---- training the question encoder: backward through time (csrc/ncx_gru_train.hip) -------------------------------------------------
  * Takes the role of torch autograd through GRUEncoder.forward -- nn.Embedding, nn.GRU and the last-step selection (the stand-in for the
@@ -461,6 +474,12 @@ int ncx_gru_pack_t(const float* w_ih, const float* w_hh, int32_t dim_emb, int32_
  * hn of every valid (row, t) pair to the stash.  q_out is bit-identical to ncx_gru_encode's for the same inputs. */
 int ncx_gru_train_forward(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t dim_emb, int32_t dim_q,
                           const float* packed, void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream);
+/* ncx_gru_train_forward with `flags`: 0 (the same call) or NCX_F_X6 (the KEEP instantiation of the X6 step kernel: the same stash layout,
+ * so ncx_gru_train_backward consumes whichever stash the forward left).  q_out is bit-identical to ncx_gru_encode_flags's under the same
+ * `flags`.  Any other `flags` returns -1 before any launch or pointer use. */
+int ncx_gru_train_forward_flags(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t dim_emb, int32_t dim_q,
+                                const float* packed, uint32_t flags, void* workspace, size_t workspace_bytes, float* q_out,
+                                int32_t* bad_id_flag, void* stream);
 /* Takes the role of loss.backward() below q = seq2vec(wids) (torch's GRU, embedding and index backward).  `workspace` as the forward of
  * the same wids left it; dq_out [B, dim_q] in the input row order.  Outputs in torch's layouts: dW_ih [3 dim_q, dim_emb], dW_hh [3 dim_q,
  * dim_q], db_ih, db_hh [3 dim_q], dE [V1, dim_emb] (every row written).  dE == NULL: a fixed embedding (--st_fixed_emb), the dX product

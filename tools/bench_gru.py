@@ -6,7 +6,9 @@ Three length distributions:
   (c) vqa      VQA-like: len = 3 + Poisson(3) clipped to 3..26 -- mean ~ 6, the mass on 4..8, a thin tail (VQA v1 questions average
                a little over 6 words)
 HIP events around --steps calls after --warmup calls; --repeats windows per path, the two paths alternating; reported: the median
-window and the spread (max - min) / median of each path.  Prints one JSON line; --out writes it."""
+window and the spread (max - min) / median of each path.  Prints one JSON line; --out writes it.
+--x6: three paths alternate window by window, the fp32 step kernel (x6=False: the yardstick), the bf16 x 6 step kernel (x6=True,
+NCX_F_X6: the x6_* fields) and torch."""
 import argparse
 import json
 import os
@@ -37,7 +39,9 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--steps-only", type=int, default=0, help="N calls of the HIP path on (b) and nothing else (for a kernel trace)")
+    ap.add_argument("--steps-only", type=int, default=0, help="N calls of the HIP path on (b) and nothing else (for a kernel trace); "
+                    "with --x6: N calls of each form on (a), where every step has n_t = B rows")
+    ap.add_argument("--x6", action="store_true", help="time the bf16 x 6 step kernel beside the fp32 one")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_gru.py needs the MI355X"
@@ -56,9 +60,10 @@ def main():
         return torch.from_numpy(w).cuda(), lens
 
     if a.steps_only:
-        w, _ = make("uniform")
-        for _ in range(a.steps_only):
-            ops.gru_encode(w, gw)
+        w, _ = make("all26" if a.x6 else "uniform")
+        for x6 in ((False, True) if a.x6 else (None,)):
+            for _ in range(a.steps_only):
+                ops.gru_encode(w, gw, x6=x6)
         torch.cuda.synchronize()
         return
 
@@ -79,7 +84,10 @@ def main():
         w, lens = make(kind)
 
         def hip_step():
-            return ops.gru_encode(w, gw)
+            return ops.gru_encode(w, gw, x6=False if a.x6 else None)
+
+        def x6_step():
+            return ops.gru_encode(w, gw, x6=True)
 
         @torch.no_grad()
         def torch_step():       # the path GRUEncoder.forward takes with use_hip off
@@ -87,9 +95,11 @@ def main():
             last = (w > 0).sum(1).clamp(min=1) - 1
             return out[torch.arange(B, device=w.device), last]
 
-        t_hip, t_torch = [], []
+        t_hip, t_x6, t_torch = [], [], []
         for _ in range(a.repeats):
             t_hip.append(window(hip_step))
+            if a.x6:
+                t_x6.append(window(x6_step))
             t_torch.append(window(torch_step))
         err = float((hip_step() - torch_step()).abs().max())
         ops.check_gru_ids(device=w.device)
@@ -101,6 +111,10 @@ def main():
                                   torch_spread=(max(t_torch) - min(t_torch)) / mt, speedup_vs_torch=mt / mh, valid_gflop=flops / 1e9,
                                   hip_tflops_valid=flops / mh / 1e9, fraction_of_fp32_mfma_peak=flops / (mh * 1e-3) / PEAK_FP32_MFMA,
                                   torch_tflops_padded=B * T * flop_token / mt / 1e9, max_abs_diff_vs_torch=err)
+        if a.x6:
+            m6 = float(np.median(t_x6))
+            res["cases"][kind].update(x6_ms=m6, x6_ms_windows=t_x6, x6_spread=(max(t_x6) - min(t_x6)) / m6, x6_speedup_vs_fp32=mh / m6,
+                                      x6_tflops_valid=flops / m6 / 1e9, max_abs_diff_x6_vs_fp32=float((x6_step() - hip_step()).abs().max()))
     line = json.dumps(res)
     print(line)
     if a.out:

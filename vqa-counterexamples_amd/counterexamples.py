@@ -79,6 +79,7 @@ def build_parser():
     p.add_argument("--max_steps", type=int, default=-1, help="stop an epoch early (smoke runs)")
     p.add_argument("--no_vqa_cache", action="store_true", help="produce q / z / answer logits per batch instead of once per split")
     p.add_argument("--no_hip_seq2vec", action="store_true", help="run the question encoder in PyTorch instead of the HIP library (GRUEncoder.use_hip = False)")
+    p.add_argument("--x6_seq2vec", action="store_true", help="NCX_F_X6 on the step kernel of the HIP question encoder (GRUEncoder.hip_x6 = True; same results to fp32 rounding; not the default)")
     p.add_argument("--bf16", action="store_true", help="bf16 operands on the two dominant GEMMs (fp32 accumulate / master weights)")
     p.add_argument("--x6", action="store_true", help="NCX_F_X6: the three big fp32 products on the bf16 matrix cores with three-plane fp32-grade operands (same results to fp32 rounding; not the default)")
     p.add_argument("--path_trainset", type=str, default=None, help="overrides vqa.path_trainset of the YAML")
@@ -176,6 +177,9 @@ class Runner:
         self.vqa.eval()                                                                      # cx.py:73-80 (frozen)
         if a.no_hip_seq2vec and hasattr(self.vqa.seq2vec, "use_hip"):
             self.vqa.seq2vec.use_hip = False
+        if getattr(a, "x6_seq2vec", False) and hasattr(self.vqa.seq2vec, "hip_x6"):
+            self.vqa.seq2vec.hip_x6 = True
+            self.log("=> question encoder: HIP forward (bf16 x 6 step kernel)")
         for p_ in self.vqa.parameters():
             p_.requires_grad_(False)
         # the HIP producer's weights object: MutanWeights or (MLBNoAtt) MlbWeights; ops.vqa_forward dispatches on it
@@ -360,6 +364,8 @@ def main(argv=None):
                          "it)".format(args.cx_model, " / ".join(SCORERS)))
     if args.cx_model in ("LinearContext", "PairwiseLinearModel") and (args.bf16 or getattr(args, "x6", False)):
         raise SystemExit("--bf16 / --x6 are variants of NeuralModel's kernels; -cx {} runs in fp32 only".format(args.cx_model))
+    if getattr(args, "x6_seq2vec", False) and args.no_hip_seq2vec:
+        raise SystemExit("--x6_seq2vec picks a form of the HIP question encoder's step kernel; it cannot be combined with --no_hip_seq2vec")
     if args.cx_model == "SemanticBaseline":
         if args.sb_lambda is None:                                         # counterexamples.py:240-242
             raise ValueError("If semantic baseline is selected then --sb_lambda must also be provided.")

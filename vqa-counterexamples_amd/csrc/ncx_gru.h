@@ -1,4 +1,5 @@
-// ncx_gru.h -- what the question encoder's forward (ncx_gru.hip) shares with its training entries (ncx_gru_train.hip).
+// ncx_gru.h -- what the question encoder's forward (ncx_gru.hip) shares with its bf16 x 6 step kernel (ncx_gru_x6.hip) and its training
+// entries (ncx_gru_train.hip).
 #pragma once
 #include "ncx_rnn.h"
 
@@ -9,8 +10,53 @@ namespace ncx {
 template <bool KEEP> struct GruKeep {};
 template <> struct GruKeep<true> { float* gates; int B, dqp; };
 
+// The packed layout of ncx_gru_pack: kx / kp the k extents of the x segment / of a whole weight row, nj the 32-unit blocks
+struct GruPacked { int kx, kp, nj; size_t w_floats, floats; };
+__host__ __device__ inline GruPacked gru_packed(int dim_emb, int dim_q) {
+    GruPacked p;
+    p.kx = pad_to(dim_emb, GEMM_BK); p.kp = p.kx + pad_to(dim_q, GEMM_BK); p.nj = (dim_q + RNN_BU - 1) / RNN_BU;
+    p.w_floats = (size_t)p.nj * 3 * RNN_BU * p.kp;
+    p.floats = p.w_floats + (size_t)p.nj * 6 * RNN_BU;
+    return p;
+}
+
+#if defined(__HIPCC__)
+// One (row, unit) element of a step's epilogue, shared by both forms of the step kernel: the gate arithmetic from the four accumulators
+// (a_nx = W_in x and a_nh = W_hn h apart), h_t, q[perm[row]] at the row's last step and, with KEEP, the gate stash.
+struct GruBias { float ir, iz, in, hr, hz, hn; };
+__device__ __forceinline__ GruBias gru_bias(const float* __restrict__ packed, const GruPacked& pk, int j, int ul) {
+    const float* bias = packed + pk.w_floats + (size_t)j * 6 * RNN_BU + ul;
+    return {bias[0], bias[RNN_BU], bias[2 * RNN_BU], bias[3 * RNN_BU], bias[4 * RNN_BU], bias[5 * RNN_BU]};
+}
+template <bool KEEP>
+__device__ __forceinline__ void gru_gate_store(float a_r, float a_z, float a_nx, float a_nh, const GruBias& b, int t, int row, int unit, int dim_q,
+                                               const float* __restrict__ h_prev, float* __restrict__ h_next, float* __restrict__ q,
+                                               const int* __restrict__ perm, const int* __restrict__ lens, const GruKeep<KEEP>& keep) {
+    const float r = 1.f / (1.f + expf(-(a_r + b.ir + b.hr)));
+    const float z = 1.f / (1.f + expf(-(a_z + b.iz + b.hz)));
+    const float n = tanhf(a_nx + b.in + r * (a_nh + b.hn));
+    const float hp = t > 0 ? h_prev[(size_t)row * dim_q + unit] : 0.f;
+    const float hn = (1.f - z) * n + z * hp;
+    h_next[(size_t)row * dim_q + unit] = hn;
+    if (t == lens[row] - 1) q[(size_t)perm[row] * dim_q + unit] = hn;
+    if constexpr (KEEP) {
+        float* g = keep.gates + ((size_t)t * keep.B + row) * (4 * (size_t)keep.dqp) + unit;
+        g[0] = r; g[keep.dqp] = z; g[2 * keep.dqp] = n; g[3 * keep.dqp] = a_nh + b.hn;
+    }
+}
+#endif
+
+// the flags of the ..._flags entry points: 0 or NCX_F_X6
+inline bool gru_flags_ok(uint32_t flags) { return flags == 0 || flags == NCX_F_X6; }
+
+// The T step launches of the bf16 x 6 form (ncx_gru_x6.hip) after rnn_plan.  gates == NULL: ncx_gru_encode's, step t writes h_t to ha (t even) or hb
+// (t odd) and reads the other; otherwise the training forward's, ha is the h stash [T][B][dim_q] (hb unused) and `gates` the gate stash.
+__attribute__((visibility("hidden"))) int gru_steps_x6(const int32_t* wids, int B, int T, const float* E, int V1, int dim_emb, int dim_q,
+                                                       const float* packed, const RnnPlan& p, float* ha, float* hb, float* gates, float* q_out,
+                                                       hipStream_t s);
+
 __attribute__((visibility("hidden"))) int gru_forward_keep(const int32_t* wids, int B, int T, const float* E, int V1, int dim_emb, int dim_q,
                                                            const float* packed, const RnnPlan& p, float* hstash, float* gates, float* q_out,
-                                                           int32_t* bad_id_flag, hipStream_t s);
+                                                           int32_t* bad_id_flag, uint32_t flags, hipStream_t s);
 
 }  // namespace ncx

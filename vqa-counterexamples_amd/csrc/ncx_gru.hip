@@ -1,5 +1,6 @@
 // ncx_gru.hip -- the frozen question encoder (GRUEncoder in eval mode: embedding -> one-layer GRU -> last valid step):
-// ncx_gru_packed_bytes, ncx_gru_pack, ncx_gru_workspace_bytes, ncx_gru_encode.  Forward only.
+// ncx_gru_packed_bytes, ncx_gru_pack, ncx_gru_workspace_bytes, ncx_gru_encode[_flags], ncx_gru_step_form.  Forward only.  The step kernel here is
+// the fp32 one; under NCX_F_X6 the entries launch its bf16 x 6 form instead (ncx_gru_x6.hip).
 //
 // Reference: vqa/models/seq2vec.py -- process_lengths + select_last (11-25: the length of a right-padded question and the hidden
 // state of its last word) and factory (79-97: the GRU 620 -> 2400 encoder the VQA model is built with).  Semantics, gate order r, z, n
@@ -25,15 +26,6 @@ using namespace ncx;
 namespace {
 constexpr int GRU_P = GEMM_BK + 4;   // LDS pitch of a 32-deep k-step (conflict-free ds_read_b64 fragments, ncx_gemm.h)
 constexpr int GRU_TILE_ROWS = RNN_BM + 3 * RNN_BU;
-
-struct GruPacked { int kx, kp, nj; size_t w_floats, floats; };
-__host__ __device__ inline GruPacked gru_packed(int dim_emb, int dim_q) {
-    GruPacked p;
-    p.kx = pad_to(dim_emb, GEMM_BK); p.kp = p.kx + pad_to(dim_q, GEMM_BK); p.nj = (dim_q + RNN_BU - 1) / RNN_BU;
-    p.w_floats = (size_t)p.nj * 3 * RNN_BU * p.kp;
-    p.floats = p.w_floats + (size_t)p.nj * 6 * RNN_BU;
-    return p;
-}
 }  // namespace
 
 // packed = W [nj][3 gates][32 units][kp] | bias [nj][6: ir iz in hr hz hn][32 units]; row (j, g, u) = W_i{g}[32 j + u, :] zero-padded to
@@ -162,33 +154,23 @@ __global__ __launch_bounds__(256) void k_gru_step(const int* __restrict__ wids, 
     // epilogue: C layout col = lane & 15 (unit), row = 4 (lane >> 4) + reg
     const int ul = 16 * wu + li, unit = j * RNN_BU + ul;
     if (unit >= dim_q) return;
-    const float* bias = packed + pk.w_floats + (size_t)j * 6 * RNN_BU + ul;
-    const float b_ir = bias[0], b_iz = bias[RNN_BU], b_in = bias[2 * RNN_BU], b_hr = bias[3 * RNN_BU], b_hz = bias[4 * RNN_BU], b_hn = bias[5 * RNN_BU];
+    const GruBias bias = gru_bias(packed, pk, j, ul);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int row = m0 + 32 * wr + 16 * i + 4 * lk + e;
             if (row >= nt) continue;
-            const float r = 1.f / (1.f + expf(-(acc_r[i][e] + b_ir + b_hr)));
-            const float z = 1.f / (1.f + expf(-(acc_z[i][e] + b_iz + b_hz)));
-            const float n = tanhf(acc_nx[i][e] + b_in + r * (acc_nh[i][e] + b_hn));
-            const float hp = t > 0 ? h_prev[(size_t)row * dim_q + unit] : 0.f;
-            const float hn = (1.f - z) * n + z * hp;
-            h_next[(size_t)row * dim_q + unit] = hn;
-            if (t == lens[row] - 1) q[(size_t)perm[row] * dim_q + unit] = hn;
-            if constexpr (KEEP) {
-                float* g = keep.gates + ((size_t)t * keep.B + row) * (4 * (size_t)keep.dqp) + unit;
-                g[0] = r; g[keep.dqp] = z; g[2 * keep.dqp] = n; g[3 * keep.dqp] = acc_nh[i][e] + b_hn;
-            }
+            gru_gate_store<KEEP>(acc_r[i][e], acc_z[i][e], acc_nx[i][e], acc_nh[i][e], bias, t, row, unit, dim_q, h_prev, h_next, q, perm, lens, keep);
         }
 }
 
 namespace ncx {
-// ncx_gru_encode's plan and T step launches with the KEEP instantiation: h_t goes to hstash [T][B][dim_q], the gates to `gates`
+// ncx_gru_encode_flags's plan and T step launches with the KEEP instantiation: h_t goes to hstash [T][B][dim_q], the gates to `gates`
 int gru_forward_keep(const int32_t* wids, int B, int T, const float* E, int V1, int dim_emb, int dim_q, const float* packed, const RnnPlan& p,
-                     float* hstash, float* gates, float* q_out, int32_t* bad_id_flag, hipStream_t s) {
+                     float* hstash, float* gates, float* q_out, int32_t* bad_id_flag, uint32_t flags, hipStream_t s) {
     NCX_HIP_TRY(rnn_plan(wids, B, T, V1, p, 1, bad_id_flag, s));
+    if (flags & NCX_F_X6) return gru_steps_x6(wids, B, T, E, V1, dim_emb, dim_q, packed, p, hstash, nullptr, gates, q_out, s);
     const int tiles_m = (int)cdiv(B, RNN_BM), total = tiles_m * (int)cdiv(dim_q, RNN_BU);
     const unsigned grid = (unsigned)(8 * cdiv(total, 8));
     const GruKeep<true> keep{gates, B, pad_to(dim_q, GEMM_BK)};
@@ -233,9 +215,20 @@ int ncx_gru_pack(const float* w_ih, const float* w_hh, const float* b_ih, const 
     return NCX_OK;
 }
 
+int ncx_gru_step_form(int32_t B, int32_t T, int32_t dim_emb, int32_t dim_q, uint32_t flags) {
+    if (!gru_flags_ok(flags) || !rnn_dims_ok(B, T, dim_emb, dim_q)) return -1;
+    return (flags & NCX_F_X6) ? 1 : 0;
+}
+
 int ncx_gru_encode(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t dim_emb, int32_t dim_q,
                    const float* packed, void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream) {
-    if (!rnn_dims_ok(B, T, dim_emb, dim_q) || V1 < 1) return -1;
+    return ncx_gru_encode_flags(wids, B, T, E, V1, dim_emb, dim_q, packed, 0, workspace, workspace_bytes, q_out, bad_id_flag, stream);
+}
+
+int ncx_gru_encode_flags(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t dim_emb, int32_t dim_q,
+                         const float* packed, uint32_t flags, void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag,
+                         void* stream) {
+    if (!gru_flags_ok(flags) || !rnn_dims_ok(B, T, dim_emb, dim_q) || V1 < 1) return -1;
     const GruLayout w = gru_layout(B, dim_q);
     if (!rnn_args_ok({wids, E, q_out, bad_id_flag}, packed, workspace, workspace_bytes, w.total)) return -1;
     hipStream_t s = (hipStream_t)stream;
@@ -243,6 +236,7 @@ int ncx_gru_encode(const int32_t* wids, int32_t B, int32_t T, const float* E, in
     const RnnPlan p = w.plan.at(ws);
     float* h[2] = {(float*)(ws + w.h0), (float*)(ws + w.h1)};
     NCX_HIP_TRY(rnn_plan(wids, B, T, V1, p, 1, bad_id_flag, s));
+    if (flags & NCX_F_X6) return gru_steps_x6(wids, B, T, E, V1, dim_emb, dim_q, packed, p, h[0], h[1], nullptr, q_out, s);
     const int tiles_m = (int)cdiv(B, RNN_BM), total = tiles_m * (int)cdiv(dim_q, RNN_BU);
     const unsigned grid = (unsigned)(8 * cdiv(total, 8));
     for (int t = 0; t < T; ++t) {              // every step is launched: how many rows it has is known on the device only

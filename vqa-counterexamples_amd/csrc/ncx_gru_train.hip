@@ -194,12 +194,18 @@ int ncx_gru_pack_t(const float* w_ih, const float* w_hh, int32_t dim_emb, int32_
 
 int ncx_gru_train_forward(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t dim_emb, int32_t dim_q,
                           const float* packed, void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream) {
-    if (!gru_train_dims_ok(B, T, dim_emb, dim_q) || V1 < 1) return -1;
+    return ncx_gru_train_forward_flags(wids, B, T, E, V1, dim_emb, dim_q, packed, 0, workspace, workspace_bytes, q_out, bad_id_flag, stream);
+}
+
+int ncx_gru_train_forward_flags(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t dim_emb, int32_t dim_q,
+                                const float* packed, uint32_t flags, void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag,
+                                void* stream) {
+    if (!gru_flags_ok(flags) || !gru_train_dims_ok(B, T, dim_emb, dim_q) || V1 < 1) return -1;
     const GruTrainLayout w = gru_train_layout(B, T, dim_emb, dim_q);
     if (!rnn_args_ok({wids, E, q_out, bad_id_flag}, packed, workspace, workspace_bytes, w.total)) return -1;
     char* ws = (char*)workspace;
     return gru_forward_keep(wids, B, T, E, V1, dim_emb, dim_q, packed, w.plan.at(ws), (float*)(ws + w.h), (float*)(ws + w.gates), q_out, bad_id_flag,
-                            (hipStream_t)stream);
+                            flags, (hipStream_t)stream);
 }
 
 int ncx_gru_train_backward(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t dim_emb, int32_t dim_q,

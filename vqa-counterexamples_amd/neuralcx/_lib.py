@@ -21,8 +21,8 @@ EXPORTS = ("ncx_input_size", "ncx_workspace_bytes", "ncx_forward", "ncx_forward_
            "ncx_adam_step", "ncx_version", "ncx_profile_begin", "ncx_profile_end", "ncx_plan_query",
            "ncx_vqa_workspace_bytes", "ncx_vqa_forward", "ncx_mlb_workspace_bytes", "ncx_mlb_forward", "ncx_mlb_att_workspace_bytes", "ncx_mlb_att_forward", "ncx_mlb_att_forward_flags", "ncx_mlb_att_logits_form", "ncx_knn_workspace_bytes", "ncx_knn_status_offset", "ncx_knn", "ncx_cosine_gram_workspace_bytes", "ncx_cosine_gram", "ncx_semantic_scores",
            "ncx_similarity_scores",
-           "ncx_gru_packed_bytes", "ncx_gru_pack", "ncx_gru_workspace_bytes", "ncx_gru_encode",
-           "ncx_gru_train_workspace_bytes", "ncx_gru_packed_t_bytes", "ncx_gru_pack_t", "ncx_gru_train_forward", "ncx_gru_train_backward",
+           "ncx_gru_packed_bytes", "ncx_gru_pack", "ncx_gru_workspace_bytes", "ncx_gru_encode", "ncx_gru_encode_flags", "ncx_gru_step_form",
+           "ncx_gru_train_workspace_bytes", "ncx_gru_packed_t_bytes", "ncx_gru_pack_t", "ncx_gru_train_forward", "ncx_gru_train_forward_flags", "ncx_gru_train_backward",
            "ncx_lstm2_packed_bytes", "ncx_lstm2_pack", "ncx_lstm2_workspace_bytes", "ncx_lstm2_encode",
            "ncx_lstm2_train_workspace_bytes", "ncx_lstm2_packed_t_bytes", "ncx_lstm2_pack_t", "ncx_lstm2_train_forward", "ncx_lstm2_train_backward",
            "ncx_ws_region", "ncx_wgmap_check",
@@ -215,6 +215,10 @@ def lib():
     L.ncx_gru_encode.restype = C.c_int
     L.ncx_gru_encode.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                  C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ncx_gru_encode_flags.restype = C.c_int
+    L.ncx_gru_encode_flags.argtypes = L.ncx_gru_encode.argtypes[:8] + [C.c_uint32] + L.ncx_gru_encode.argtypes[8:]
+    L.ncx_gru_step_form.restype = C.c_int
+    L.ncx_gru_step_form.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32]
     L.ncx_gru_train_workspace_bytes.restype = C.c_size_t
     L.ncx_gru_train_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.ncx_gru_packed_t_bytes.restype = C.c_size_t
@@ -223,6 +227,8 @@ def lib():
     L.ncx_gru_pack_t.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.ncx_gru_train_forward.restype = C.c_int
     L.ncx_gru_train_forward.argtypes = L.ncx_gru_encode.argtypes
+    L.ncx_gru_train_forward_flags.restype = C.c_int
+    L.ncx_gru_train_forward_flags.argtypes = L.ncx_gru_encode_flags.argtypes
     L.ncx_gru_train_backward.restype = C.c_int
     L.ncx_gru_train_backward.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                          C.c_size_t] + [C.c_void_p] * 7

@@ -724,9 +724,22 @@ def gru_bad_flag(device) -> torch.Tensor:
     return f
 
 
-def gru_encode(wids: torch.Tensor, gw: GruWeights, bad_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The question encoder (ncx_gru_encode; GRUEncoder.forward in eval mode) on the current stream, no host sync: wids [B, T] word
+GRU_STEP_FORMS = ("fp32", "x6")
+
+
+def gru_step_form(dim_emb: int, dim_q: int, B: int, T: int, x6=None) -> str:
+    """Which step kernel gru_encode / gru_train_forward take for this shape (ncx_gru_step_form; host only: no launch, no device
+    access).  x6: as mlb_att_flags -- None = the process-wide choice (EXTRA_FLAGS, read now: NCX_X6=1), True / False force the form."""
+    rc = _lib.lib().ncx_gru_step_form(B, T, dim_emb, dim_q, mlb_att_flags(x6))
+    if rc < 0:
+        raise _lib.NcxError("ncx_gru_step_form: dims out of range (B %d, T %d, dim_emb %d, dim_q %d)" % (B, T, dim_emb, dim_q))
+    return GRU_STEP_FORMS[rc]
+
+
+def gru_encode(wids: torch.Tensor, gw: GruWeights, bad_flag: Optional[torch.Tensor] = None, x6=None) -> torch.Tensor:
+    """The question encoder (ncx_gru_encode_flags; GRUEncoder.forward in eval mode) on the current stream, no host sync: wids [B, T] word
     ids right-padded with 0 -> q [B, dim_q], the hidden state after each question's last word.  Padded steps are not computed.
+    x6 (gru_step_form): the bf16 x 6 form of the step kernel -- fp32-grade, not bit-equal to the fp32 form.
     A word id outside [0, V + 1) is never used as an address; it sets `bad_flag` (default: gru_bad_flag(device)) and
     check_gru_ids raises the IndexError -- deferred, as for semantic_scores."""
     if wids.dim() != 2:
@@ -748,9 +761,9 @@ def gru_encode(wids: torch.Tensor, gw: GruWeights, bad_flag: Optional[torch.Tens
     ws = torch.empty(n + 256, dtype=torch.uint8, device=dev)
     p, n = _ws_ptr(ws)
     q = torch.empty(B, gw.dim_q, dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().ncx_gru_encode(_ptr(wids, torch.int32, "wids"), B, T, _ptr(gw.E, torch.float32, "E"), gw.V1, gw.dim_emb, gw.dim_q,
-                                         _ptr(gw.packed, torch.float32, "packed"), p, n, C.c_void_p(q.data_ptr()),
-                                         _ptr(bad_flag, torch.int32, "bad_flag"), _stream()), "ncx_gru_encode")
+    _lib.check(_lib.lib().ncx_gru_encode_flags(_ptr(wids, torch.int32, "wids"), B, T, _ptr(gw.E, torch.float32, "E"), gw.V1, gw.dim_emb,
+                                               gw.dim_q, _ptr(gw.packed, torch.float32, "packed"), mlb_att_flags(x6), p, n,
+                                               C.c_void_p(q.data_ptr()), _ptr(bad_flag, torch.int32, "bad_flag"), _stream()), "ncx_gru_encode")
     return q
 
 
@@ -960,16 +973,18 @@ def gru_train_workspace(B: int, T: int, gw: GruTrainWeights, device) -> torch.Te
     return torch.empty(n + 256, dtype=torch.uint8, device=device)
 
 
-def gru_train_forward(wids: torch.Tensor, gw: GruTrainWeights, ws: torch.Tensor, bad_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """ncx_gru_train_forward: gru_encode's q (bit for bit), with the stash of the valid (row, t) pairs left in `ws`."""
+def gru_train_forward(wids: torch.Tensor, gw: GruTrainWeights, ws: torch.Tensor, bad_flag: Optional[torch.Tensor] = None, x6=None) -> torch.Tensor:
+    """ncx_gru_train_forward_flags: gru_encode's q under the same x6 (bit for bit), with the stash of the valid (row, t) pairs left in
+    `ws`.  x6: gru_step_form; the backward takes whichever stash the forward left."""
     B, T, wids = _gru_train_args(wids, gw, "gru_train_forward")
     if bad_flag is None:
         bad_flag = gru_bad_flag(wids.device)
     p, n = _ws_ptr(ws)
     q = torch.empty(B, gw.dim_q, dtype=torch.float32, device=wids.device)
-    _lib.check(_lib.lib().ncx_gru_train_forward(_ptr(wids, torch.int32, "wids"), B, T, _ptr(gw.E, torch.float32, "E"), gw.V1, gw.dim_emb,
-                                                gw.dim_q, _ptr(gw.packed, torch.float32, "packed"), p, n, C.c_void_p(q.data_ptr()),
-                                                _ptr(bad_flag, torch.int32, "bad_flag"), _stream()), "ncx_gru_train_forward")
+    _lib.check(_lib.lib().ncx_gru_train_forward_flags(_ptr(wids, torch.int32, "wids"), B, T, _ptr(gw.E, torch.float32, "E"), gw.V1, gw.dim_emb,
+                                                      gw.dim_q, _ptr(gw.packed, torch.float32, "packed"), mlb_att_flags(x6), p, n,
+                                                      C.c_void_p(q.data_ptr()), _ptr(bad_flag, torch.int32, "bad_flag"), _stream()),
+               "ncx_gru_train_forward")
     return q
 
 

@@ -77,7 +77,7 @@ class GruTrainFunction(torch.autograd.Function):
     """q = the hidden state after each question's last word (GRUEncoder below its dropout) through ncx_gru_train_forward / _backward.
     Inputs: wids, E, w_ih, w_hh, b_ih, b_hh and the encoder module, on which the packs are cached (keyed on data_ptr / _version of the
     five tensors, like GRUEncoder._hip_weights: rebuilt after an optimizer step).  Gradients: the five tensors; None for E when it does
-    not require grad (a fixed embedding: the dX product is skipped)."""
+    not require grad (a fixed embedding: the dX product is skipped).  The forward's step kernel follows module.hip_x6 (ops.gru_step_form)."""
 
     @staticmethod
     def weights(module, tensors):
@@ -93,7 +93,7 @@ class GruTrainFunction(torch.autograd.Function):
     def forward(ctx, wids, E, w_ih, w_hh, b_ih, b_hh, module=None):
         gw = GruTrainFunction.weights(module, (E, w_ih, w_hh, b_ih, b_hh))
         ws = ops.gru_train_workspace(wids.shape[0], wids.shape[1], gw, wids.device)
-        q = ops.gru_train_forward(wids, gw, ws)
+        q = ops.gru_train_forward(wids, gw, ws, x6=getattr(module, "hip_x6", None))
         ctx.hip = (wids, gw, ws)
         return q
 

@@ -21,7 +21,9 @@ glimpse fusion, classifier; forward with dropout and backward) then runs in HIP 
 (neuralcx.vqa_train.MlbAttTrainFunction), the encoder trains under autograd unless --freeze_seq2vec, torch.optim.Adam steps.  evaluate() / --evaluate run the module in eval mode under no_grad, i.e. its HIP forward
 (ncx_mlb_att_forward), unless --no_hip.  --x6 sets the model's hip_x6: both HIP routes of the attention model then run the conv_v_att
 product on the bf16 matrix path with three-plane operands (NCX_F_X6: same results to fp32 rounding; not the default), and with
---hip_att_train the backward runs its twin, d conv_v_att.weight, there as well.  The images are a seeded synthetic attention table [syn_images, dim_v, syn_grid, syn_grid].
+--hip_att_train the backward runs its twin, d conv_v_att.weight, there as well.  --x6_seq2vec is the same choice for the GRU question
+encoder (any arch): it sets GRUEncoder.hip_x6, and the encoder's HIP forward (eval mode and --hip_seq2vec_train) runs the bf16 x 6 form of
+its step kernel.  The images are a seeded synthetic attention table [syn_images, dim_v, syn_grid, syn_grid].
 """
 import argparse
 import json
@@ -73,6 +75,7 @@ def build_parser():
     p.add_argument("--hip_att_train", action="store_true", help="attention archs only: the training step below the question encoder in HIP as well "
                    "(MLBAtt.use_hip_train: attention head, glimpse fusion, classifier; torch.optim.Adam steps)")
     p.add_argument("--x6", action="store_true", help="attention archs only: NCX_F_X6 on the attention kernel, same results to fp32 rounding; not the default")
+    p.add_argument("--x6_seq2vec", action="store_true", help="GRU question encoder only: NCX_F_X6 on its HIP step kernel, same results to fp32 rounding; not the default")
     p.add_argument("--no_hip", action="store_true", help="the plain PyTorch modules (no HIP library; runs on a CPU too)")
     p.add_argument("--seed", type=int, default=1337)
     return p
@@ -151,6 +154,10 @@ class Trainer:
         if args.x6 and opt["model"].get("arch") not in ATT_ARCHS:
             raise SystemExit("train.py: --x6 needs an attention arch (%s); this YAML builds %r" % (", ".join(ATT_ARCHS), opt["model"].get("arch")))
         s2v = opt["model"]["seq2vec"]
+        if getattr(args, "x6_seq2vec", False) and args.no_hip:
+            raise SystemExit("train.py: --x6_seq2vec picks a form of the HIP step kernel of the GRU encoder; it cannot be combined with --no_hip")
+        if getattr(args, "x6_seq2vec", False) and s2v.get("arch") == "2-lstm" and "hidden_size" in s2v:                   # seq2vec.factory's TwoLSTM branch
+            raise SystemExit("train.py: --x6_seq2vec needs the GRU encoder; this YAML builds the 2-lstm encoder, whose step kernel has no bf16 x 6 form")
         if args.hip_2lstm_train and not (s2v.get("arch") == "2-lstm" and "hidden_size" in s2v):       # seq2vec.factory's TwoLSTM branch
             raise SystemExit("train.py: --hip_2lstm_train needs the 2-lstm encoder (seq2vec: {arch: 2-lstm, hidden_size: ...}); this YAML builds %r"
                              % s2v.get("arch", "skipthoughts"))
@@ -186,6 +193,10 @@ class Trainer:
                     self.route += " (and its weight-gradient twin in the backward)"
         else:
             self.route = "torch path: --no_hip" if args.no_hip else route_for(opt["model"])
+        if getattr(args, "x6_seq2vec", False):
+            if not isinstance(self.model.seq2vec, models.seq2vec.GRUEncoder):
+                raise SystemExit("train.py: --x6_seq2vec needs the GRU encoder; this YAML builds %s" % type(self.model.seq2vec).__name__)
+            self.model.seq2vec.hip_x6 = True
         self.hip = self.route == "hip"
         self.engine = None
         if self.freeze or opt["model"]["seq2vec"].get("fixed_emb"):
@@ -212,10 +223,10 @@ class Trainer:
             self.optim = torch.optim.Adam([p_ for p_ in self.model.parameters() if p_.requires_grad], self.lr)     # train.py:143-144
             self.criterion = nn.CrossEntropyLoss()
         self.best_acc1, self.history = 0.0, []
-        print("=> route: %s%s%s" % ("hip" if self.hip else self.route, " (engine: whole step in HIP)" if self.engine else "",
+        print("=> route: %s%s%s%s" % ("hip" if self.hip else self.route, " (engine: whole step in HIP)" if self.engine else "",
                                     " (question encoder: HIP forward + backward through time)" if getattr(self, "hip_seq2vec", False) else
                                     " (2-lstm question encoder: HIP forward + backward through time, --hip_2lstm_train)" if getattr(self, "hip_2lstm", False)
-                                    else ""), flush=True)
+                                    else "", " (question encoder: bf16 x 6 step kernel)" if getattr(args, "x6_seq2vec", False) else ""), flush=True)
 
     # ---- data ------------------------------------------------------------------------------------------------
     def q_emb_of(self, split):

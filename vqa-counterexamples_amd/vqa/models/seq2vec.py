@@ -11,9 +11,12 @@ class GRUEncoder(nn.Module):
     """nn.Embedding -> nn.GRU -> the hidden state after the last word.  On a CUDA device, when no gradient can be wanted and dropout
     is inert, forward runs in the HIP library (ops.gru_encode: padded steps are skipped); `use_hip = False` keeps it in PyTorch.
     `use_hip_train = True` (off by default) also trains it there: a CUDA fp32 module called with grad mode on and a parameter that
-    requires grad runs neuralcx.vqa_train.GruTrainFunction (forward with a stash, backward through time); its dropout stays in torch."""
+    requires grad runs neuralcx.vqa_train.GruTrainFunction (forward with a stash, backward through time); its dropout stays in torch.
+    `hip_x6` is handed to both HIP routes and changes no routing decision: None = the process-wide choice (ops.EXTRA_FLAGS, NCX_X6=1),
+    True / False = the bf16 x 6 / the fp32 form of the step kernel (ops.gru_step_form; train.py --x6_seq2vec sets True)."""
     use_hip = True
     use_hip_train = False
+    hip_x6 = None
 
     def __init__(self, vocab_words, dim_q=2400, dim_emb=620, dropout=0.25):
         super().__init__()
@@ -56,7 +59,7 @@ class GRUEncoder(nn.Module):
     def forward(self, wids):
         if self._hip_ok(wids):
             from neuralcx import ops
-            return ops.gru_encode(wids, self._hip_weights())
+            return ops.gru_encode(wids, self._hip_weights(), x6=self.hip_x6)
         if self._hip_train_ok(wids):
             from neuralcx.vqa_train import GruTrainFunction
             g = self.gru
