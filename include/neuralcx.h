@@ -173,7 +173,8 @@ int ncx_forward_phase(const ncx_dims* d, const ncx_inputs* in, const ncx_params*
  *   dscores[B,K]  (softmax - onehot) * scale      (nullable)   == d loss / d scores
  *   rank[B]       #{k: s_k > s_gt} + #{k < gt: s_k == s_gt}    (nullable)
  *   hits[2]       OVERWRITTEN with #{rank < 1}, #{rank < 5}    (nullable)
- * scale = 1/B when scale <= 0.   K <= 64. */
+ * scale = 1/B when scale <= 0.   K <= 64.
+ * Precondition: every gt[b] lies in [0, K); the kernel does not check it (unlike ncx_ce_loss's targets). */
 int ncx_loss_rank(const float* scores, const int32_t* gt, int32_t B, int32_t K, float scale,
                   float* loss_rows, float* loss, float* dscores, int32_t* rank, int32_t* hits,
                   void* stream);
@@ -223,7 +224,7 @@ int ncx_ws_region(const ncx_dims* d, int32_t which, size_t* offset, size_t* byte
  * pre-activations; for L == 1 also d linear_1.bias).  Call order: ncx_forward, ncx_train_tail, ncx_backward[_phase], all with the
  * same dims (flag set) and workspace.  Outputs as ncx_loss_rank (scale = dims.loss_scale, 1/B when <= 0) plus `scores`
  * [B, K]; dscores is optional.  Bit-identical to the three separate calls except d out.bias (zero in maths; its partial sums
- * are taken in another order). */
+ * are taken in another order).  Precondition, as for ncx_loss_rank: every gt[b] lies in [0, K); it is not checked. */
 int ncx_train_tail(const ncx_dims* d, const ncx_params* p, void* workspace, size_t workspace_bytes, const int32_t* gt,
                    float* scores, float* loss_rows, float* loss, float* dscores, int32_t* rank, int32_t* hits,
                    const ncx_grads* g, void* stream);

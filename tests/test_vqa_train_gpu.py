@@ -11,6 +11,7 @@ import torch
 import vqa_train_ref as R
 from conftest import GOLDEN, PKG
 from helpers import grad_tol
+from loss_adam_ref import ce_ref as _ce_ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -237,17 +238,6 @@ def test_ce_loss_alone(A):
         with pytest.raises(IndexError):
             ops.check_vqa_targets(device=DEV)
         ops.check_vqa_targets(device=DEV)                        # cleared
-
-
-def _ce_ref(x, t, scale=None):
-    x = x.astype(np.float64); B, A = x.shape
-    scale = 1.0 / B if scale is None else scale
-    mx = x.max(1, keepdims=True)
-    lse = np.log(np.exp(x - mx).sum(1)) + mx[:, 0]
-    xt = x[np.arange(B), t]
-    dl = np.exp(x - lse[:, None]); dl[np.arange(B), t] -= 1.0
-    rank = (x > xt[:, None]).sum(1) + ((x == xt[:, None]) & (np.arange(A)[None, :] < t[:, None])).sum(1)
-    return dict(loss=float(((lse - xt) * scale).sum()), dl=dl * scale, rank=rank)
 
 
 def _ce_into(x, t, guard, B, A):

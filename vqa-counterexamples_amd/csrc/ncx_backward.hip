@@ -273,7 +273,7 @@ __global__ __launch_bounds__(64) void k_train_tail(const float* __restrict__ h, 
         if (dscores && lane < K) dscores[r0 + lane] = dsc;
         const bool ahead = lane < K && (s > sg || (s == sg && lane < g));
         const unsigned long long bal = __ballot(ahead);
-        if (lane == 0) { loss_rows[b] = (logf(sum) + m - sg) * loss_scale; rank[b] = __popcll(bal); }
+        if (lane == 0) { loss_rows[b] = (logf(sum) - (sg - m)) * loss_scale; rank[b] = __popcll(bal); }
         sb += dsc;
         // backward of out + dropout + relu (k_bwd_prelude)
         f32x4 ds = {0.f, 0.f, 0.f, 0.f};

@@ -21,7 +21,7 @@ __global__ __launch_bounds__(256) void k_loss_rank(const float* __restrict__ sco
     const bool ahead = lane < K && (s > sg || (s == sg && lane < g));
     const unsigned long long bal = __ballot(ahead);
     if (lane == 0) {
-        if (loss_rows) loss_rows[b] = (logf(sum) + m - sg) * scale;
+        if (loss_rows) loss_rows[b] = (logf(sum) - (sg - m)) * scale;      // (sg - m first: log(sum) + m would round at the magnitude of the scores, not of the loss)
         if (rank) rank[b] = __popcll(bal);
     }
 }

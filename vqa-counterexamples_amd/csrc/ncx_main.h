@@ -1066,7 +1066,10 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
         const f32x4 w = *(const f32x4u*)(p + nl);
         f32x4 o;
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj) o[jj] = jj + sh < 4 ? (sh == 0 ? w[jj] : sh == 1 ? w[(jj + 1) & 3] : sh == 2 ? w[(jj + 2) & 3] : w[(jj + 3) & 3]) : 0.f;
+        // (selected by the source element jj + sh.  The same selection keyed on sh alone -- sh == 0 ? w[jj] : sh == 1 ? w[(jj + 1) & 3] : ... --
+        //  ran wrong on the MI355X for sh == 3 though it reads right: it took w[1], so the last column of every unsplit output with
+        //  N % 4 == 1 got the row-add operand of column N - 3; tests/test_loss_adam_gpu.py, the H = 5 and H = 253 tail cases)
+        for (int jj = 0; jj < 4; ++jj) { const int sj = jj + sh; o[jj] = sj == 0 ? w[0] : sj == 1 ? w[1] : sj == 2 ? w[2] : sj == 3 ? w[3] : 0.f; }
         return o;
     };
     const bool use_add = !plain && e.rowadd;

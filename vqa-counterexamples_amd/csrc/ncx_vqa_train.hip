@@ -253,7 +253,7 @@ __global__ __launch_bounds__(256) void k_ce_rows(const float* __restrict__ logit
         for (int c = t; c < A; c += 256) dlogits[(long long)b * A + c] = (__expf(x[c] - mx) * inv - (c == tg ? 1.f : 0.f)) * scale;
     }
     if (t == 0) {
-        rows[b] = (logf(se) + mx - xt) * scale;
+        rows[b] = (logf(se) - (xt - mx)) * scale;              // (xt - mx first: the row's offset never meets the small log term)
         ((int*)rows)[B + b] = (rank < 1 ? 1 : 0) | (rank < 5 ? 2 : 0);
     }
 }
