@@ -251,6 +251,27 @@ int ncx_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
                   float lr, float beta1, float beta2, float eps, int32_t step, float grad_scale,
                   void* stream);
 
+/* ncx_backward followed by ncx_adam_step over the model's flat parameter buffer, as one call (single-GPU training: nothing sums
+ * gradients between the two).  `opt` describes the flat buffers: param / grad / exp_avg / exp_avg_sq of n floats each, 16-byte
+ * aligned, answer_embedding first (n_emb = its A * da elements plus any padding behind it; the other tensors of ncx_params /
+ * ncx_grads lie in [n_emb, n) of param / grad), the 1-based step and Adam's constants as in ncx_adam_step.
+ * Where the answer_embedding gradient is the fp32 NT product on 64 x 64 tiles (the full model at training shapes), the launch that
+ * produces it also applies Adam -- each tile updates the elements it has just produced, further workgroups of the same launch update
+ * the rest of the buffer -- and no separate pass over the buffer runs.  Everywhere else (bf16 variant, a_emb lesion, small shapes,
+ * padding behind the embedding, the internal side stream) the call runs ncx_backward then the ncx_adam_step kernel.  Gradients,
+ * parameters and moments are bit-identical to the two separate calls either way.
+ * NCX_E_NULL: a NULL argument or buffer.  NCX_E_DIMS: step < 1, n == 0, n_emb > n or < A * da, params->answer_embedding != param,
+ * grads->answer_embedding != grad, or a tensor outside its flat buffer.  NCX_E_WORKSPACE: a misaligned buffer.  Nothing is enqueued then. */
+typedef struct ncx_adam_state {
+    float* param; const float* grad; float* exp_avg; float* exp_avg_sq;
+    size_t n, n_emb;
+    int32_t step;
+    float lr, beta1, beta2, eps, grad_scale;
+} ncx_adam_state;
+int ncx_backward_adam(const ncx_dims* d, const ncx_inputs* in, const ncx_params* p,
+                      void* workspace, size_t workspace_bytes, const float* dscores,
+                      const ncx_grads* g, const ncx_adam_state* opt, void* stream);
+
 /* ---- the frozen VQA producer upstream of NeuralCX -----------------------------------------
  * Replaces CXModelBase.vqa_forward (vqa/models/cx.py:64-104) for the MutanNoAtt model in eval mode:
  * MutanFusion.forward (vqa/models/fusion.py:78-121: linear_v/linear_q + activation, R x {linear_hv_i, linear_hq_i,
@@ -807,6 +828,9 @@ int ncx_mlb_att_train_ws_region(const ncx_mlb_att_dims* d, const ncx_mlb_att_tra
  *         kernel's shape rules exclude it); dW1[:, a_other] on the TN kernel (1) or the chain GEMM (0); the piece limit (out6[2] above
  *         it: grouped)} */
 #define NCX_QUERY_DW1_ROUTE 32
+/* Not a GEMM id either: out6 = {1 when ncx_backward_adam applies Adam inside the answer_embedding gradient's launch for these dims (given an
+ * unpadded embedding slice), else 0; the passenger workgroups of that launch; 0, 0, 0, 0} */
+#define NCX_QUERY_FUSED_ADAM 33
 int ncx_profile_begin(uint32_t gemm_mask /* bit i = gemm id i */, int32_t max_launches);
 int ncx_profile_end(float* ms, int32_t* ids, int32_t cap);
 /* In-kernel clock diagnostics of the MAIN launch (the fused forward kernel of linear_1): while `stamps` is non-NULL

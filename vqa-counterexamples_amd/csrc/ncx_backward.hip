@@ -453,6 +453,16 @@ __global__ __launch_bounds__(256) void k_zero_cols(float* __restrict__ p, int ro
 }
 }  // namespace ncx
 
+namespace ncx {
+// ncx_backward_adam's dE launch applies Adam itself: the fp32 NT product (X6 leaves it fp32 too) on its 64 x 64 form, on the caller's stream.
+// Experiment hook NCX_NO_FUSED_ADAM: the separate k_adam pass instead.
+bool fused_adam_route(const ncx_dims& d, const StepRoutes& r) {
+    if (!(d.flags & NCX_F_A_EMB) || (d.flags & NCX_F_BF16) || !r.emb_nt) return false;
+    if (km_defers_to_side_stream(d, r) || hook_env("NCX_NO_FUSED_ADAM")) return false;
+    return main_short_form(d.A, d.da, 2 * cdiv(pad_to(d.H, 4), GEMM_BK), 1);
+}
+}  // namespace ncx
+
 using namespace ncx;
 extern "C" {
 int ncx_train_tail(const ncx_dims* dp, const ncx_params* p, void* workspace, size_t workspace_bytes, const int32_t* gt,
@@ -510,8 +520,11 @@ int ncx_train_tail(const ncx_dims* dp, const ncx_params* p, void* workspace, siz
 // region can be on the wire while phase 2 (the bulk of the backward) runs.
 // phase 4: answer_embedding gradient from dGt | dGgt.  3 then 4 == 0 bit for bit; under data parallelism the
 // 2 x [H, A] block is summed over ranks between the two, so the [A, da] embedding gradient never crosses the wire.
+// adam (phase 0 only, nullable): the optimiser's buffers for the dE launch that applies Adam itself (fused_adam_route); *adam_done tells the
+// caller whether that launch ran -- it does not when the dE product takes another route after all.
 static int backward_impl(const ncx_dims* dp, const ncx_inputs* in, const ncx_params* p, void* workspace,
-                         size_t workspace_bytes, const float* dscores, const ncx_grads* g, void* stream_, int phase) {
+                         size_t workspace_bytes, const float* dscores, const ncx_grads* g, void* stream_, int phase,
+                         const AdamFuse* adam = nullptr, bool* adam_done = nullptr) {
     int rc = check_dims(dp);
     if (rc != NCX_OK) return rc;
     if (!in || !p || !workspace || !g || (!dscores && !(dp->flags & NCX_F_FUSED_TAIL))) return NCX_E_NULL;
@@ -781,7 +794,16 @@ static int backward_impl(const ncx_dims* dp, const ncx_inputs* in, const ncx_par
                 a.seg[0].kind = MK_GATHER; a.seg[0].idx = de_perm;
                 a.seg[1].kind = MK_GATHER; a.seg[1].idx = de_perm;
             }
+            // Nothing below reads a weight, and with no side stream every other gradient is final on this stream: g->w1 (the fold kernel, the TN
+            // launch and their reduction; the a_other block's reduction or fix-up in k_emb_prep's launch or just above), the biases, the hidden
+            // and out layers.  The product reads the workspace copies k_emb_prep made (W1ak^T, W1agt^T), never p->w1 or p->answer_embedding.
+            if (adam && phase == 0 && !ss) {
+                a.adam = *adam;
+                rc = profiled(U_DE, se, [&] { return main_forward_adam(a, de_skip, se); }); if (rc) return rc;
+                if (adam_done) *adam_done = true;
+            } else {
             rc = profiled(U_DE, se, [&] { return de_skip ? main_forward_rowmap(a, se) : main_forward(a, se); }); if (rc) return rc;
+            }
         } else if ((do1 && !skip_de) || only_de) {   // dE[a][j] = sum_n dGt[n][a] W1ak[n][j] + sum_n dGgt[n][a] W1agt[n][j]
             GemmArgs a{}; a.mode = MODE_CHAIN; a.nseg = 2; a.M = d.A;
             a.a[0] = x_plain(dgt, d.A, H, d.A);  a.b[0] = x_plain(p->w1 + o.a_other, din, H, d.da); a.klen[0] = H;
@@ -800,6 +822,44 @@ static int backward_impl(const ncx_dims* dp, const ncx_inputs* in, const ncx_par
 int ncx_backward(const ncx_dims* dp, const ncx_inputs* in, const ncx_params* p, void* workspace,
                  size_t workspace_bytes, const float* dscores, const ncx_grads* g, void* stream_) {
     return backward_impl(dp, in, p, workspace, workspace_bytes, dscores, g, stream_, 0);
+}
+
+int ncx_backward_adam(const ncx_dims* dp, const ncx_inputs* in, const ncx_params* p, void* workspace, size_t workspace_bytes,
+                      const float* dscores, const ncx_grads* g, const ncx_adam_state* opt, void* stream_) {
+    int rc = check_dims(dp);
+    if (rc != NCX_OK) return rc;
+    if (!in || !p || !g || !opt || !opt->param || !opt->grad || !opt->exp_avg || !opt->exp_avg_sq) return NCX_E_NULL;
+    if (!p->answer_embedding || !g->answer_embedding) return NCX_E_NULL;
+    const ncx_dims& d = *dp;
+    const size_t n = opt->n, n_emb = opt->n_emb, emb = (size_t)d.A * d.da;
+    if (opt->step < 1 || n == 0 || n_emb > n || n_emb < emb) return NCX_E_DIMS;
+    if (((uintptr_t)opt->param | (uintptr_t)opt->grad | (uintptr_t)opt->exp_avg | (uintptr_t)opt->exp_avg_sq) & 15) return NCX_E_WORKSPACE;
+    // answer_embedding leads both flat buffers; every other tensor of the model lies behind it, inside them
+    if (p->answer_embedding != opt->param || g->answer_embedding != opt->grad) return NCX_E_DIMS;
+    const SegOffsets o = seg_offsets(d);
+    const size_t H = (size_t)d.H;
+    auto inside = [&](const float* x, const float* base, size_t count) { return !x || (x >= base + n_emb && x + count <= base + n); };
+    const float* const pf[8] = {p->w1, p->b1, p->w2, p->b2, p->w3, p->b3, p->w_out, p->b_out};
+    const float* const gf[8] = {g->w1, g->b1, g->w2, g->b2, g->w3, g->b3, g->w_out, g->b_out};
+    const size_t cnt[8] = {H * (size_t)o.din, H, H * H, H, H * H, H, H, 1};
+    for (int i = 0; i < 8; ++i) {
+        const bool used = i < 2 || i >= 6 || (d.L >= 2 && i < 4) || d.L >= 3;
+        if (!used) continue;
+        if (!inside(pf[i], opt->param, cnt[i]) || !inside(gf[i], opt->grad, cnt[i])) return NCX_E_DIMS;
+    }
+    const AdamScalars sc = adam_scalars(opt->lr, opt->beta1, opt->beta2, opt->eps, opt->step, opt->grad_scale);
+    AdamFuse af{};
+    // (the tile epilogue covers exactly the A x da elements, the passengers the rest: the embedding slice has no padding behind it)
+    const bool want = fused_adam_route(d, routes(d)) && n_emb == emb && emb % 4 == 0;
+    if (want) {
+        af.p = opt->param; af.m = opt->exp_avg; af.v = opt->exp_avg_sq;
+        af.tp = opt->param + n_emb; af.tg = opt->grad + n_emb; af.tm = opt->exp_avg + n_emb; af.tv = opt->exp_avg_sq + n_emb;
+        af.tn = n - n_emb; af.s = sc;
+    }
+    bool done = false;
+    rc = backward_impl(dp, in, p, workspace, workspace_bytes, dscores, g, stream_, 0, want ? &af : nullptr, &done);
+    if (rc != NCX_OK || done) return rc;
+    return adam_launch(opt->param, opt->grad, opt->exp_avg, opt->exp_avg_sq, n, sc, (hipStream_t)stream_);
 }
 
 int ncx_backward_phase(const ncx_dims* dp, const ncx_inputs* in, const ncx_params* p, void* workspace,

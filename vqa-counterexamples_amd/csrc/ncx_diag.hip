@@ -79,6 +79,13 @@ int ncx_plan_query(const ncx_dims* d, int32_t gemm_id, int32_t* out6) {
         out6[5] = TN8_MAX_SEG;
         return NCX_OK;
     }
+    if (gemm_id == NCX_QUERY_FUSED_ADAM) {
+        const bool on = fused_adam_route(*d, routes(*d)) && ((size_t)d->A * d->da) % 4 == 0;
+        for (int i = 0; i < 6; ++i) out6[i] = 0;
+        out6[0] = on ? 1 : 0;
+        out6[1] = on ? main_adam_passengers() : 0;
+        return NCX_OK;
+    }
     if (gemm_id < 0 || gemm_id >= U_COUNT) return NCX_E_DIMS;
     GemmUse u[U_COUNT];
     list_uses(*d, routes(*d), u);

@@ -10,6 +10,7 @@ SideStream* side_stream();                                   // null unless NCX_
 int side_fork(SideStream* ss, hipStream_t main);
 int side_join(SideStream* ss, hipStream_t main);
 bool km_defers_to_side_stream(const ncx_dims& d, const StepRoutes& r);
+bool fused_adam_route(const ncx_dims& d, const StepRoutes& r);   // ncx_backward.hip: ncx_backward_adam applies Adam inside the dE launch
 
 struct ProfState { bool on; unsigned mask; int n, cap; hipEvent_t* ev; int* ids; };
 extern ProfState g_prof;

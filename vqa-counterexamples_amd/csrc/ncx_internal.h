@@ -2,6 +2,7 @@
 #pragma once
 #include "ncx_common.h"
 #include "ncx_gemm.h"
+#include "ncx_adam.h"
 
 namespace ncx {
 
@@ -113,11 +114,18 @@ struct MainArgs {
     unsigned long long* stamps;      // diagnostics (tools/mb/mb_main.hip): 16 words per workgroup of s_memtime / s_memrealtime stamps; NULL in the library
     int x6;                          // NCX_F_X6: the plain / softmax segments of the 192 x 64 fold form on the bf16 matrix path with three-plane operands
     float* t_out; float* t_out0;     // main_forward_mlb only (nullable): t = tanh(z) of the rows that go to out / epi.out0, leading dimension N
+    AdamFuse adam;                   // main_forward_adam only: the optimiser's buffers (last: the other forms' arguments keep their offsets)
 };
 int main_forward(MainArgs& a, hipStream_t s);
 // The chain over permuted rows (EPI_ROWMAP of ncx_main.h): two MK_GATHER segments sharing one table idx[0 .. M]; tile row r reads operand rows
 // idx[r] and writes output row idx[r]; row tiles from idx[M] on stop after the first segment.  Same tile form per shape as main_forward.
 int main_forward_rowmap(MainArgs& a, hipStream_t s);
+// a chain of T k-steps over an M x N output takes the 64 x 64 form with three workgroups per CU
+bool main_short_form(long long M, long long N, long long T, int split);
+// The answer-embedding gradient (two segments, plain or -- rowmap -- over permuted rows) on that form with Adam applied by the same launch
+// (a.adam; WithAdam of ncx_main.h).  NCX_E_FLAGS when the shape does not take the 64 x 64 form: callers ask main_short_form first.
+int main_forward_adam(MainArgs& a, bool rowmap, hipStream_t s);
+int main_adam_passengers();          // passenger workgroups of that launch
 // The MLB producer's x_v product (ncx_mlb.hip): one MK_GATHER segment with the EPI_MLB epilogue of ncx_main.h
 int main_forward_mlb(MainArgs& a, hipStream_t s);
 // k-split of a problem for the fused forward kernel (48 x 128 tiles): 1 when its tiles already give every CU a workgroup,

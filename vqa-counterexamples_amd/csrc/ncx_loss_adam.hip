@@ -1,6 +1,7 @@
 // ncx_loss_adam.hip -- the two entry points every scorer shares: the listwise loss / rank (ncx_loss_rank) and the Adam update
 // (ncx_adam_step).
 #include "ncx_wave.h"
+#include "ncx_adam.h"
 
 namespace ncx {
 // Listwise softmax cross-entropy over the K candidates of a triplet + rank of the ground truth.
@@ -47,35 +48,24 @@ __global__ __launch_bounds__(256) void k_loss_finish(const float* __restrict__ l
     }
 }
 
-// torch.optim.Adam (counterexamples.py:275-276): m = lerp(m, g, 1-b1); v = b2 v + (1-b2) g^2;
-// p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps).
+// torch.optim.Adam on a flat buffer: the update itself is adam_update (ncx_adam.h), shared with the launch that applies it where the
+// answer-embedding gradient is produced.
 __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                              float* __restrict__ v, size_t n, float step_size, float b1, float b2,
-                                              float eps, float inv_bc2_sqrt, float gscale) {
+                                              float* __restrict__ v, size_t n, const AdamScalars s) {
     size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
     const size_t stride = (size_t)gridDim.x * 256 * 4;
     for (; i < n; i += stride) {
-        if (i + 3 < n) {
-            f32x4 pv = *(f32x4*)(p + i), gv = *(const f32x4*)(g + i), mv = *(f32x4*)(m + i), vv = *(f32x4*)(v + i);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float gj = gv[j] * gscale;
-                mv[j] = mv[j] + (gj - mv[j]) * (1.f - b1);
-                vv[j] = vv[j] * b2 + (1.f - b2) * gj * gj;
-                const float den = sqrtf(vv[j]) * inv_bc2_sqrt + eps;
-                pv[j] = pv[j] - step_size * (mv[j] / den);
-            }
-            *(f32x4*)(p + i) = pv; *(f32x4*)(m + i) = mv; *(f32x4*)(v + i) = vv;
-        } else {
-            for (size_t j = i; j < n; ++j) {
-                const float gj = g[j] * gscale;
-                const float mj = m[j] + (gj - m[j]) * (1.f - b1);
-                const float vj = v[j] * b2 + (1.f - b2) * gj * gj;
-                m[j] = mj; v[j] = vj;
-                p[j] = p[j] - step_size * (mj / (sqrtf(vj) * inv_bc2_sqrt + eps));
-            }
-        }
+        if (i + 3 < n) adam_quad(p, g, m, v, i, s);
+        else adam_tail(p, g, m, v, i, n, s);
     }
+}
+
+int adam_launch(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, const AdamScalars& s, hipStream_t stream) {
+    size_t blocks = (n + 1023) / 1024;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_adam, dim3((unsigned)blocks), dim3(256), 0, stream, param, grad, exp_avg, exp_avg_sq, n, s);
+    NCX_HIP_TRY(hipGetLastError());
+    return NCX_OK;
 }
 }  // namespace ncx
 
@@ -102,15 +92,6 @@ int ncx_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
     if (!param || !grad || !exp_avg || !exp_avg_sq) return NCX_E_NULL;
     if (step < 1 || n == 0) return NCX_E_DIMS;
     if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return NCX_E_WORKSPACE;
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    const float step_size = (float)((double)lr / bc1);
-    const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-    size_t blocks = (n + 1023) / 1024;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_adam, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, param, grad, exp_avg, exp_avg_sq, n,
-                       step_size, beta1, beta2, eps, inv_bc2_sqrt, grad_scale);
-    NCX_HIP_TRY(hipGetLastError());
-    return NCX_OK;
+    return adam_launch(param, grad, exp_avg, exp_avg_sq, n, adam_scalars(lr, beta1, beta2, eps, step, grad_scale), (hipStream_t)stream_);
 }
 }  // extern "C"

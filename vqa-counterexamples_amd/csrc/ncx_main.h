@@ -29,6 +29,7 @@
 //     hand-over is compiled for its two kinds and the register allocator sees exactly what is live where.
 #pragma once
 #include "ncx_internal.h"
+#include "ncx_adam.h"
 #include <type_traits>
 
 namespace ncx {
@@ -48,6 +49,7 @@ struct MainCfg {
     static constexpr int BM = BM_, BN = BN_, WGM = WGM_, WGN = WGN_, DEPTH = DEPTH_, OCC = OCC_, T = T_;
     static constexpr bool X6 = X6_;
     static constexpr int EPI = 0;                                   // which epilogue the kernel is compiled with (EPI_MLB: WithMlbEpi below)
+    static constexpr bool ADAM = false;                             // the launch also applies Adam (WithAdam below)
     static constexpr int RP = T / 8;                                // tile rows per loader pass (8 threads x 16 bytes per 32-float row)
     static constexpr int BM_LDS = (BM + RP - 1) / RP * RP;        // A rows held in LDS (a multiple of the loader pass)
     static constexpr int LDS6 = 2 * 3 * (BM_LDS + BN) * MF6_P;      // X6: [2 buffers][3 planes][A rows | W rows][MF6_P]
@@ -72,6 +74,12 @@ struct MainCfg {
 enum { EPI_STD = 0, EPI_MLB = 1, EPI_ROWMAP = 2 };
 template <class CFG> struct WithMlbEpi : CFG { static constexpr int EPI = EPI_MLB; };
 template <class CFG> struct WithRowMap : CFG { static constexpr int EPI = EPI_ROWMAP; };
+// ADAM (the answer-embedding gradient, ncx_backward_adam): nothing after this product reads a weight and every other gradient is final when it is
+// launched, so the launch is also the optimiser step (args.adam, ncx_adam.h).  A tile's epilogue stores its piece of the gradient as always, then
+// updates the parameter and the two moments of the same elements (each is produced exactly once: split == 1); the workgroups
+// [adam.pass_at, adam.pass_at + adam.n_pass) of the grid carry no tile: they update a slice of the rest of the flat buffer, HBM traffic beside
+// short latency-bound tiles.  The workgroup ids on either side of the passengers are the tile ids of the plain form, in order.
+template <class CFG> struct WithAdam : CFG { static constexpr bool ADAM = true; };
 
 typedef const __attribute__((address_space(1))) float* gfptr;      // global address space: global_load, never flat_load
 typedef const __attribute__((address_space(1))) int* giptr;
@@ -108,8 +116,14 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
     // accumulators to slab[z][M][N]; k_main_fixup sums the S slabs in fixed order and applies the epilogue.
     const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
     const int S = args.split > 1 ? args.split : 1;
+    int bid = blockIdx.x;
+    if constexpr (CFG::ADAM) {                           // passengers leave here (uniform per workgroup), before any barrier and before the tile map
+        const int pa = args.adam.pass_at, np = args.adam.n_pass;
+        if (bid >= pa && bid < pa + np) { adam_passenger(args.adam, bid - pa, tid, MT); return; }
+        if (bid >= pa + np) bid -= np;
+    }
     // (row tile, k-chunk) units are dealt over the XCDs; the column tiles of a unit are consecutive ids on one XCD
-    const int id = blockIdx.x, xcd = id & 7, local = id >> 3;
+    const int id = bid, xcd = id & 7, local = id >> 3;
     const int tn = local % tiles_n, unit = (local / tiles_n) * 8 + xcd;
     if (unit >= tiles_m * S) return;
     const int tm = unit / S, z = unit - tm * S;
@@ -1151,6 +1165,29 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
         if constexpr (ROWMAP) o = dst + (long long)orow[f / QR] * ldd + n;
         if (n + 3 < N) *(f32x4u*)o = v;
         else { o[0] = v[0]; if (n + 1 < N) o[1] = v[1]; if (n + 2 < N) o[2] = v[2]; }
+        if constexpr (CFG::ADAM) {                       // (split == 1, no epilogue operand: host-checked) v is the finished gradient of elements o[0 .. 3]
+            const AdamFuse& ad = args.adam;
+            const long long off = o - dst;
+            float* const pp = ad.p + off; float* const pm = ad.m + off; float* const pv = ad.v + off;
+            if (n + 3 < N) {
+                f32x4 p4 = *(const f32x4u*)pp, m4 = *(const f32x4u*)pm, v4 = *(const f32x4u*)pv;
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) {
+                    float pj = p4[jj], mj = m4[jj], vj = v4[jj];
+                    adam_update(pj, v[jj], mj, vj, ad.s.step_size, ad.s.b1, ad.s.b2, ad.s.eps, ad.s.inv_bc2_sqrt, ad.s.gscale);
+                    p4[jj] = pj; m4[jj] = mj; v4[jj] = vj;
+                }
+                *(f32x4u*)pp = p4; *(f32x4u*)pm = m4; *(f32x4u*)pv = v4;
+            } else {
+#pragma unroll
+                for (int jj = 0; jj < 3; ++jj) {
+                    if (n + jj >= N) break;
+                    float pj = pp[jj], mj = pm[jj], vj = pv[jj];
+                    adam_update(pj, v[jj], mj, vj, ad.s.step_size, ad.s.b1, ad.s.b2, ad.s.eps, ad.s.inv_bc2_sqrt, ad.s.gscale);
+                    pp[jj] = pj; pm[jj] = mj; pv[jj] = vj;
+                }
+            }
+        }
     }
     stamp(8);
     if (stamps && tid == 0) stamps[15] = __builtin_amdgcn_s_memrealtime();
@@ -1185,6 +1222,7 @@ template <int K0, int... REST> struct FirstKind { static constexpr int value = K
 
 template <class CFG, bool DIST, int... KINDS>
 static inline int launch_main_fwd_seq(MainArgs& a, hipStream_t s) {
+    static_assert(!CFG::ADAM, "launch_main_fwd_adam sizes the grid of the forms with passengers");
     constexpr int lds = FirstKind<KINDS...>::value == MK_VFOLD ? (CFG::LDS_FOLD > CFG::LDS ? CFG::LDS_FOLD : CFG::LDS) : CFG::LDS;
     static DevMask attr{0};
     NCX_HIP_TRY(set_max_lds_once(attr, (const void*)k_main_fwd<CFG, DIST, KINDS...>, lds));
@@ -1270,6 +1308,35 @@ static inline int launch_main_fwd(MainArgs& a, hipStream_t s) {
     return NCX_E_FLAGS;
     }
     }
+}
+
+
+// The forms with Adam (WithAdam): the answer-embedding gradient's two-segment chain, plain rows or permuted rows (WithRowMap), unsplit, no
+// epilogue operand.  a.adam carries the optimiser's buffers; n_pass and pass_at are set here: n_pass workgroups for the tail (none when it is
+// empty), placed after the first `pass_at_hint` tile workgroups (< 0 or beyond the grid: after all of them).
+template <class CFG>
+static inline int launch_main_fwd_adam(MainArgs& a, int n_pass, int pass_at_hint, hipStream_t s) {
+    static_assert(CFG::ADAM && CFG::EPI != EPI_MLB && !CFG::X6, "the answer-embedding gradient's forms");
+    if (a.nseg != 2 || a.M < 1 || a.N < 1 || a.split > 1 || a.dist_out || !a.out) return NCX_E_FLAGS;
+    for (int i = 0; i < 2; ++i) if (!main_fwd_operand_ok(a.seg[i].klen)) return NCX_E_DIMS;
+    const EpiArgs& e = a.epi;
+    if (e.rowadd || e.bias || e.relu || e.dropout || e.gate) return NCX_E_FLAGS;
+    AdamFuse& ad = a.adam;
+    if (!ad.p || !ad.m || !ad.v || (ad.tn && (!ad.tp || !ad.tg || !ad.tm || !ad.tv))) return NCX_E_NULL;
+    constexpr bool RM = CFG::EPI == EPI_ROWMAP;
+    constexpr int KIND = RM ? MK_GATHER : MK_PLAIN;
+    if (a.seg[0].kind != KIND || a.seg[1].kind != KIND) return NCX_E_FLAGS;
+    if (RM && (!a.seg[0].idx || a.seg[0].idx != a.seg[1].idx)) return NCX_E_FLAGS;
+    constexpr int lds = CFG::LDS;
+    static DevMask attr{0};
+    NCX_HIP_TRY(set_max_lds_once(attr, (const void*)k_main_fwd<CFG, false, KIND, KIND>, lds));
+    const int tiles_m = (a.M + CFG::BM - 1) / CFG::BM, tiles_n = (a.N + CFG::BN - 1) / CFG::BN;
+    const int grid = ((tiles_m + 7) / 8) * 8 * tiles_n;
+    ad.n_pass = ad.tn ? (n_pass > 0 ? n_pass : 1) : 0;
+    ad.pass_at = pass_at_hint >= 0 && pass_at_hint < grid ? pass_at_hint : grid;
+    hipLaunchKernelGGL((k_main_fwd<CFG, false, KIND, KIND>), dim3(grid + ad.n_pass), dim3(CFG::T), lds, s, a);
+    NCX_HIP_TRY(hipGetLastError());
+    return NCX_OK;
 }
 
 }  // namespace ncx

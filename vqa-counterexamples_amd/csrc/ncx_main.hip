@@ -13,6 +13,10 @@ typedef MainCfg<96, 64, 2, 2, 2, 2> MainCfgFold4;   // MK_VFOLD sequences: 96 x 
 typedef MainCfg<192, 64, 4, 2, 2, 2, 512, true> MainCfgFold8X6;   // ... with the segments after the fold on the bf16 matrix path, three-plane operands (NCX_F_X6)
 typedef MainCfg<192, 64, 4, 2, 2, 2, 512> MainCfgFold8;   // MK_VFOLD on 192 x 64 tiles: ONE 8-wave workgroup per CU, eight triplets share the W_k | W_m tiles (experiment: NCX_FOLD8)
 
+bool main_short_form(long long M, long long N, long long T, int split) {
+    return split <= 1 && T <= 32 && ((M + 63) / 64) * ((N + 63) / 64) >= 2 * num_cus() && !hook_env("NCX_MAIN_CFG");
+}
+
 // The tile form of a chain without the per-triplet fold.  W: the epilogue the kernels are compiled with (AsIs: the standard one; WithRowMap:
 // permuted rows -- the same choice of tile for a shape, so the two forms of the answer-embedding gradient add every element's products in one order)
 template <class C> using AsIs = C;
@@ -20,7 +24,7 @@ template <template <class> class W>
 static int main_forward_chain(MainArgs& a, hipStream_t s) {
     long long T = 0;
     for (int i = 0; i < a.nseg; ++i) T += (a.seg[i].klen + MF_BK - 1) / MF_BK;
-    if (a.split <= 1 && T <= 32 && (long long)((a.M + 63) / 64) * ((a.N + 63) / 64) >= 2 * num_cus() && !hook_env("NCX_MAIN_CFG"))
+    if (main_short_form(a.M, a.N, T, a.split))
         return launch_main_fwd<W<MainCfg3>>(a, s);          // a workgroup that short spends as long starting and storing as multiplying: more of them per CU
     const long long tiles96 = (long long)((a.M + 95) / 96) * ((a.N + 127) / 128);
     constexpr bool wide_ok = W<MainCfgW>::EPI != EPI_ROWMAP;      // (the 160-row tile leaves no LDS behind its staged tile for the row table)
@@ -63,6 +67,25 @@ int main_forward(MainArgs& a, hipStream_t s) {
 int main_forward_rowmap(MainArgs& a, hipStream_t s) {
     if (a.nseg != 2 || a.seg[0].kind != MK_GATHER) return NCX_E_FLAGS;
     return main_forward_chain<WithRowMap>(a, s);
+}
+
+// One passenger per CU: the tiles keep their three-per-CU slots and every CU's share of the tail streams beside them.
+// Experiment hooks: NCX_ADAM_PASS (their number), NCX_ADAM_PASS_AT (the tile workgroups dispatched before them; negative: all).
+int main_adam_passengers() {
+    if (const char* e = hook_env("NCX_ADAM_PASS")) { const int n = atoi(e); if (n > 0) return n; }
+    return num_cus();
+}
+
+int main_forward_adam(MainArgs& a, bool rowmap, hipStream_t s) {
+    long long T = 0;
+    for (int i = 0; i < a.nseg; ++i) T += (a.seg[i].klen + MF_BK - 1) / MF_BK;
+    if (!main_short_form(a.M, a.N, T, a.split)) return NCX_E_FLAGS;
+    // behind the first round of tiles (three per CU): they start as the first tiles retire and stream under the rest -- 67.6 us against 71.9
+    // behind all tiles at configs[1]; a grid of one round or less has them last
+    int at = 3 * num_cus();
+    if (const char* e = hook_env("NCX_ADAM_PASS_AT")) at = atoi(e);
+    const int np = main_adam_passengers();
+    return rowmap ? launch_main_fwd_adam<WithAdam<WithRowMap<MainCfg3>>>(a, np, at, s) : launch_main_fwd_adam<WithAdam<MainCfg3>>(a, np, at, s);
 }
 
 // x_v of the MLB producer: 96 x 128 tiles, one workgroup per CU, once they fill the chip (12 800 x 1200 at B = 512: 1340 tiles), else 48 x 128

@@ -18,7 +18,7 @@ NCX_F_X6 = 128         # NOT the default: the balanced TN weight-gradient launch
 NCX_F_BF16 = 16       # BASELINE configs[4]: bf16 operands for the two dominant GEMMs (include/neuralcx.h)
 
 EXPORTS = ("ncx_input_size", "ncx_workspace_bytes", "ncx_forward", "ncx_forward_phase", "ncx_loss_rank", "ncx_backward", "ncx_backward_phase",
-           "ncx_adam_step", "ncx_version", "ncx_profile_begin", "ncx_profile_end", "ncx_plan_query",
+           "ncx_adam_step", "ncx_backward_adam", "ncx_version", "ncx_profile_begin", "ncx_profile_end", "ncx_plan_query",
            "ncx_vqa_workspace_bytes", "ncx_vqa_forward", "ncx_mlb_workspace_bytes", "ncx_mlb_forward", "ncx_mlb_att_workspace_bytes", "ncx_mlb_att_forward", "ncx_mlb_att_forward_flags", "ncx_mlb_att_logits_form", "ncx_knn_workspace_bytes", "ncx_knn_status_offset", "ncx_knn", "ncx_cosine_gram_workspace_bytes", "ncx_cosine_gram", "ncx_semantic_scores",
            "ncx_similarity_scores",
            "ncx_gru_packed_bytes", "ncx_gru_pack", "ncx_gru_workspace_bytes", "ncx_gru_encode", "ncx_gru_encode_flags", "ncx_gru_step_form",
@@ -59,6 +59,12 @@ class NcxParams(C.Structure):
 
 class NcxGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in _PNAMES]
+
+
+class NcxAdamState(C.Structure):             # ncx_adam_state (include/neuralcx.h): the flat buffers of ncx_backward_adam
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("n", C.c_size_t), ("n_emb", C.c_size_t), ("step", C.c_int32),
+                ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("grad_scale", C.c_float)]
 
 
 class NcxMutanParams(C.Structure):
@@ -169,6 +175,9 @@ def lib():
     L.ncx_adam_step.restype = C.c_int
     L.ncx_adam_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float,
                                 C.c_float, C.c_float, C.c_float, C.c_int32, C.c_float, C.c_void_p]
+    L.ncx_backward_adam.restype = C.c_int
+    L.ncx_backward_adam.argtypes = [C.POINTER(NcxDims), C.POINTER(NcxInputs), C.POINTER(NcxParams), C.c_void_p,
+                                    C.c_size_t, C.c_void_p, C.POINTER(NcxGrads), C.POINTER(NcxAdamState), C.c_void_p]
     L.ncx_vqa_workspace_bytes.restype = C.c_size_t
     L.ncx_vqa_workspace_bytes.argtypes = [C.POINTER(NcxDims), C.POINTER(NcxMutanParams)]
     L.ncx_vqa_forward.restype = C.c_int
@@ -391,8 +400,14 @@ DW1_FOLD_FORMS = ("none", "k_dw_km8", "k_dw_km_x6", "k_dw_km", "grouped")
 DW1_TN_FORMS = ("grouped", "k_dw_tn8", "k_dw_tn8_x6")
 
 
+NCX_QUERY_FUSED_ADAM = 33       # include/neuralcx.h
+
+
 def plan_query(d, name):
     out = (C.c_int32 * 6)()
+    if name == "FUSED_ADAM":
+        check(lib().ncx_plan_query(C.byref(d), NCX_QUERY_FUSED_ADAM, out), "ncx_plan_query")
+        return dict(fused=bool(out[0]), passengers=out[1])
     if name == "DW1_ROUTE":
         check(lib().ncx_plan_query(C.byref(d), NCX_QUERY_DW1_ROUTE, out), "ncx_plan_query")
         return dict(fold=DW1_FOLD_FORMS[out[0]], tn=DW1_TN_FORMS[out[1]], tn_pieces=out[2], tn_grid=out[3],

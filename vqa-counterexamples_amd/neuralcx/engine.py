@@ -235,7 +235,13 @@ class NeuralCXEngine:
                 ops.backward(d, batch, f, self._ws, r["dscores"], self.grads.fields())
                 torch.distributed.all_reduce(self.grads.flat[n_emb:], group=self.pg)
         else:
-            ops.backward(d, batch, self.params.fields(), self._ws, r["dscores"], self.grads.fields())
+            # one GPU: nothing sums gradients between the backward and the optimiser, so they are one call (the launch of the
+            # answer_embedding gradient applies Adam where the route allows, ncx_backward_adam)
+            ops.backward_adam(d, batch, self.params.fields(), self._ws, r["dscores"], self.grads.fields(), self.params.flat,
+                              self.grads.flat, self.exp_avg, self.exp_avg_sq, self.params.offsets["linear_1.weight"], self.step_count,
+                              lr=self.lr)
+            r["scores"] = scores
+            return r
         ops.adam_step(self.params.flat, self.grads.flat, self.exp_avg, self.exp_avg_sq, self.step_count, lr=self.lr)
         r["scores"] = scores
         return r

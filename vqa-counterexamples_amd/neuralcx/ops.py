@@ -254,6 +254,23 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr=1e-4, betas=(0.9, 0.999
                "ncx_adam_step")
 
 
+def backward_adam(d: NcxDims, batch: Batch, params: Dict[str, torch.Tensor], ws: torch.Tensor, dscores: torch.Tensor,
+                  grads: Dict[str, torch.Tensor], param, grad, exp_avg, exp_avg_sq, n_emb, step, lr=1e-4, betas=(0.9, 0.999),
+                  eps=1e-8, grad_scale=1.0) -> None:
+    """backward (phase 0) + adam_step over the flat buffers as one call (ncx_backward_adam): `params` / `grads` are views into the flat
+    `param` / `grad`, answer_embedding first, n_emb = where the next tensor starts.  Where the route allows, the launch of the
+    answer_embedding gradient applies Adam itself; everywhere else the call runs the two steps.  Same bits either way."""
+    n = param.numel()
+    assert grad.numel() == n and exp_avg.numel() == n and exp_avg_sq.numel() == n
+    p, nb = _ws_ptr(ws)
+    ins, ps, gs = batch.c_struct(), _params_struct(params, NcxParams), _params_struct(grads, NcxGrads)
+    st = _lib.NcxAdamState(_ptr(param, torch.float32, "param"), _ptr(grad, torch.float32, "grad"),
+                           _ptr(exp_avg, torch.float32, "exp_avg"), _ptr(exp_avg_sq, torch.float32, "exp_avg_sq"),
+                           n, int(n_emb), int(step), lr, betas[0], betas[1], eps, float(grad_scale))
+    _lib.check(_lib.lib().ncx_backward_adam(C.byref(d), C.byref(ins), C.byref(ps), p, nb, _ptr(dscores, torch.float32, "dscores"),
+                                            C.byref(gs), C.byref(st), _stream()), "ncx_backward_adam")
+
+
 class MutanWeights:
     """Frozen MutanNoAtt parameters in the layout ncx_vqa_forward wants: the R rank-1 projections stacked
     (fusion.list_linear_hv.{i} -> [R*dim_mm, dim_hv]).  Built once per model; re-stack after loading a checkpoint."""
