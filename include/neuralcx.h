@@ -78,6 +78,8 @@ extern "C" {
  *   - d conv_v_att.weight of the MLB attention model's training step (ncx_mlb_att_train_backward_flags: P >= 4, any dv, dh_att, G, B).
  *   - the GRU question encoder's step product [x_t | h_{t-1}] . [W_ih | W_hh]^T (ncx_gru_encode_flags, ncx_gru_train_forward_flags: every legal
  *     shape, no fall-back; these two take the bit from their own `flags` argument only).
+ *   - the 2-lstm question encoder's step product [x_t | h_{t-1}] . [W_ih | W_hh]^T of both layers (ncx_lstm2_encode_flags,
+ *     ncx_lstm2_train_forward_flags: every legal shape, no fall-back; the bit comes from their own `flags` argument only).
  * Shapes outside fall back to the fp32 kernels silently (same results to rounding).  Results agree with the fp32 kernels to fp32 rounding, not
  * bitwise (another summation order); every parity test of the suite passes at its unchanged tolerance with the bit set (NCX_X6=1 in the
  * environment of the Python binding sets it for a whole process). */
@@ -540,6 +542,16 @@ size_t ncx_lstm2_workspace_bytes(int32_t B, int32_t T, int32_t emb, int32_t H);
  * used as an address (clamped; that row's output is meaningless) and *bad_id_flag is set to 1, as by ncx_gru_encode. */
 int ncx_lstm2_encode(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t emb, int32_t H, const float* packed,
                      void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream);
+/* ncx_lstm2_encode (seq2vec.py:11-25, 61-76) with `flags`: 0 (the same call, the same bits) or NCX_F_X6, which runs every step's product
+ * [x_t | h_{t-1}] . [W_ih | W_hh]^T of both layers on the bf16 matrix path with three-plane operands (k_lstm_step_x6, csrc/ncx_lstm_x6.hip):
+ * the same packed weights, the same workspace, the same T + 2 launches, the same epilogue; every legal shape, no fall-back to the fp32
+ * kernel.  Results agree with flags 0 to fp32 rounding, not bitwise; bit-identical from run to run.  Any other `flags` returns -1 before
+ * any launch or pointer use. */
+int ncx_lstm2_encode_flags(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t emb, int32_t H, const float* packed,
+                           uint32_t flags, void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream);
+/* Host only, no launch: which step kernel ncx_lstm2_encode_flags / ncx_lstm2_train_forward_flags take for these dims under `flags`:
+ * 0 = the fp32 step kernel, 1 = the X6 step kernel, -1 = dims or flags refused. */
+int ncx_lstm2_step_form(int32_t B, int32_t T, int32_t emb, int32_t H, uint32_t flags);
 
 /* ---- training the two-layer LSTM question encoder: backward through time (csrc/ncx_lstm_train.hip) ----------------------------------
  * Take the role of torch autograd through TwoLSTM.forward below its dropout (seq2vec.py:48-76: tanh(embedding), rnn_0, rnn_1, and the
@@ -572,6 +584,12 @@ int ncx_lstm2_pack_t(const float* w_ih0, const float* w_hh0, const float* w_ih1,
  * and the four activated gates of every valid (row, t) pair of both layers to the stash.  q_out is bit-identical to ncx_lstm2_encode's. */
 int ncx_lstm2_train_forward(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t emb, int32_t H, const float* packed,
                             void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream);
+/* ncx_lstm2_train_forward with `flags`: 0 (the same call) or NCX_F_X6 (the KEEP instantiation of the X6 step kernel: the same stash layout,
+ * pad columns zero, so ncx_lstm2_train_backward consumes whichever stash the forward left).  q_out is bit-identical to
+ * ncx_lstm2_encode_flags's under the same `flags`.  Any other `flags` returns -1 before any launch or pointer use. */
+int ncx_lstm2_train_forward_flags(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t emb, int32_t H,
+                                  const float* packed, uint32_t flags, void* workspace, size_t workspace_bytes, float* q_out,
+                                  int32_t* bad_id_flag, void* stream);
 /* Takes the role of loss.backward() below q = seq2vec(wids) (torch's LSTM, tanh, embedding and index backward; seq2vec.py:61-76).
  * `workspace` as the forward of the same wids left it; dq_out [B, 2 H] in the input row order.  Outputs in torch's layouts: dW_ih0 [4 H,
  * emb], dW_hh0, dW_ih1, dW_hh1 [4 H, H], the four db [4 H], dE [V1, emb]; every element of every output is written.  dE == NULL: a fixed

@@ -6,7 +6,9 @@ steps + last-step selection, no_grad, eval mode) in the same process.  Three len
   (c) vqa      VQA-like: len = 3 + Poisson(3) clipped to 3..26 -- mean ~ 6, the mass on 4..8, a thin tail
 HIP events around --steps calls after --warmup calls; --repeats windows per path, the two paths alternating; reported: the median
 window and the spread (max - min) / median of each path.  Also max |q - fp64| of both paths at the `real` test shape (B 40, lengths
-3..26, weights x 3; the fp64 restatement is tests/lstm_ref.py).  Prints one JSON line; --out writes it."""
+3..26, weights x 3; the fp64 restatement is tests/lstm_ref.py).  Prints one JSON line; --out writes it.
+--x6: three paths alternate window by window, the fp32 step kernel (x6=False: the yardstick), the bf16 x 6 step kernel (x6=True,
+NCX_F_X6: the x6_* fields) and torch."""
 import argparse
 import json
 import os
@@ -40,8 +42,8 @@ def make_wids(lens, T, V, rng):
     return w
 
 
-def errors_vs_fp64(emb, H, T, V):
-    """max |q - fp64| of the HIP path and of torch's fp32 path on the device, B 40, lengths 3..26, nn.LSTM's init x 3"""
+def errors_vs_fp64(emb, H, T, V, x6=False):
+    """max |q - fp64| of the HIP path (x6: of both its forms) and of torch's fp32 path on the device, B 40, lengths 3..26, nn.LSTM's init x 3"""
     torch.manual_seed(2)
     rng = np.random.default_rng(2)
     enc = TwoLSTM(["w"] * V, emb, H).eval()
@@ -57,10 +59,16 @@ def errors_vs_fp64(emb, H, T, V):
     enc = enc.cuda()
     w = torch.from_numpy(wids).cuda()
     with torch.no_grad():
+        enc.hip_x6 = False if x6 else None
         hip = enc(w).cpu().numpy()
+        enc.hip_x6 = True
+        hip6 = enc(w).cpu().numpy() if x6 else None
         enc.use_hip = False
         tor = enc(w).cpu().numpy()
-    return dict(B=40, hip_max_abs_err_vs_fp64=float(np.abs(hip - ref).max()), torch_fp32_max_abs_err_vs_fp64=float(np.abs(tor - ref).max()))
+    out = dict(B=40, hip_max_abs_err_vs_fp64=float(np.abs(hip - ref).max()), torch_fp32_max_abs_err_vs_fp64=float(np.abs(tor - ref).max()))
+    if x6:
+        out.update(x6_max_abs_err_vs_fp64=float(np.abs(hip6 - ref).max()))
+    return out
 
 
 def main():
@@ -69,7 +77,9 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--steps-only", type=int, default=0, help="N calls of the HIP path on (b) and nothing else (for a kernel trace)")
+    ap.add_argument("--steps-only", type=int, default=0, help="N calls of the HIP path on (b) and nothing else (for a kernel trace); "
+                    "with --x6: N calls of each form on (a), where every step has n_t = B rows")
+    ap.add_argument("--x6", action="store_true", help="time the bf16 x 6 step kernel beside the fp32 one")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_lstm.py needs the MI355X"
@@ -84,9 +94,10 @@ def main():
     flop_token = 2.0 * 4 * H * (emb + H) + 2.0 * 4 * H * (H + H)    # 17.5 + 23.0 MFLOP
 
     if a.steps_only:
-        w = torch.from_numpy(make_wids(lengths("uniform", B, T, rng), T, V, rng)).cuda()
-        for _ in range(a.steps_only):
-            ops.lstm_encode(w, lw)
+        w = torch.from_numpy(make_wids(lengths("all26" if a.x6 else "uniform", B, T, rng), T, V, rng)).cuda()
+        for x6 in ((False, True) if a.x6 else (None,)):
+            for _ in range(a.steps_only):
+                ops.lstm_encode(w, lw, x6=x6)
         torch.cuda.synchronize()
         return
 
@@ -108,15 +119,20 @@ def main():
         w = torch.from_numpy(make_wids(lens, T, V, rng)).cuda()
 
         def hip_step():
-            return ops.lstm_encode(w, lw)
+            return ops.lstm_encode(w, lw, x6=False if a.x6 else None)
+
+        def x6_step():
+            return ops.lstm_encode(w, lw, x6=True)
 
         @torch.no_grad()
         def torch_step():
             return ref_enc(w)
 
-        t_hip, t_torch = [], []
+        t_hip, t_x6, t_torch = [], [], []
         for _ in range(a.repeats):
             t_hip.append(window(hip_step))
+            if a.x6:
+                t_x6.append(window(x6_step))
             t_torch.append(window(torch_step))
         err = float((hip_step() - torch_step()).abs().max())
         ops.check_gru_ids(device=w.device)
@@ -129,7 +145,14 @@ def main():
                                   faster_by_more_than_the_spreads=bool((mt - mh) / mt > sh + st), valid_gflop=flops / 1e9,
                                   hip_tflops_valid=flops / mh / 1e9, fraction_of_fp32_mfma_peak=flops / (mh * 1e-3) / PEAK_FP32_MFMA,
                                   torch_tflops_padded=B * T * flop_token / mt / 1e9, max_abs_diff_vs_torch=err)
-    res["real_shape_errors"] = errors_vs_fp64(emb, H, T, 50)
+        if a.x6:
+            m6 = float(np.median(t_x6))
+            s6 = (max(t_x6) - min(t_x6)) / m6
+            res["cases"][kind].update(x6_ms=m6, x6_ms_windows=t_x6, x6_spread=s6, x6_speedup_vs_fp32=mh / m6, x6_speedup_vs_torch=mt / m6,
+                                      x6_faster_than_fp32_by_more_than_the_spreads=bool((mh - m6) / mh > sh + s6),
+                                      x6_faster_than_torch_by_more_than_the_spreads=bool((mt - m6) / mt > st + s6),
+                                      x6_tflops_valid=flops / m6 / 1e9, max_abs_diff_x6_vs_fp32=float((x6_step() - hip_step()).abs().max()))
+    res["real_shape_errors"] = errors_vs_fp64(emb, H, T, 50, x6=a.x6)
     line = json.dumps(res)
     print(line)
     if a.out:

@@ -8,7 +8,9 @@ protocol and the three length distributions of tools/bench_gru_train.py:
   (c) vqa      VQA-like: len = 3 + Poisson(3) clipped to 3..26 -- mean ~ 6
 HIP events around --steps calls after --warmup calls; --repeats windows per path, the two paths alternating; reported: the median
 window and the spread (max - min) / median of each path.  The packs are built once (they belong to a weight set, not to a step); the
-workspace is allocated once.  Prints one JSON line; --out writes it."""
+workspace is allocated once.  Prints one JSON line; --out writes it.
+--x6: three paths alternate window by window, the forward on the fp32 step kernel (x6=False: the yardstick), on the bf16 x 6 step
+kernel (x6=True, NCX_F_X6: the x6_* fields; the backward is the same code on either stash) and torch."""
 import argparse
 import json
 import os
@@ -33,6 +35,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--x6", action="store_true", help="time the forward on the bf16 x 6 step kernel beside the fp32 one")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_lstm_train.py needs the MI355X"
@@ -73,15 +76,21 @@ def main():
         w, lens = make(kind)
 
         def hip_step():
-            ops.lstm_train_forward(w, lw, ws)
+            ops.lstm_train_forward(w, lw, ws, x6=False if a.x6 else None)
+            return ops.lstm_train_backward(w, lw, ws, dq_out)
+
+        def x6_step():
+            ops.lstm_train_forward(w, lw, ws, x6=True)
             return ops.lstm_train_backward(w, lw, ws, dq_out)
 
         def torch_step():       # the path TwoLSTM.forward takes with use_hip_bptt off, and its backward
             return torch.autograd.grad(enc(w), params, dq_out)
 
-        t_hip, t_torch = [], []
+        t_hip, t_x6, t_torch = [], [], []
         for _ in range(a.repeats):
             t_hip.append(window(hip_step))
+            if a.x6:
+                t_x6.append(window(x6_step))
             t_torch.append(window(torch_step))
         g, ref = hip_step(), torch_step()
         ops.check_gru_ids(device=w.device)
@@ -95,6 +104,11 @@ def main():
                                   faster_by_more_than_the_spreads=bool(mt - mh > (max(t_hip) - min(t_hip)) + (max(t_torch) - min(t_torch))),
                                   valid_gflop=flops / 1e9, hip_tflops_valid=flops / mh / 1e9,
                                   fraction_of_fp32_mfma_peak=flops / (mh * 1e-3) / PEAK_FP32_MFMA, max_rel_diff_vs_torch=err)
+        if a.x6:
+            m6, g6 = float(np.median(t_x6)), x6_step()
+            err6 = {k: float((g6[k] - r).abs().max() / r.abs().max()) for k, r in zip(("E",) + ops.LSTM_GRADS, ref)}
+            res["cases"][kind].update(x6_ms=m6, x6_ms_windows=t_x6, x6_spread=(max(t_x6) - min(t_x6)) / m6, x6_speedup_vs_fp32=mh / m6,
+                                      x6_speedup_vs_torch=mt / m6, x6_tflops_valid=flops / m6 / 1e9, x6_max_rel_diff_vs_torch=err6)
     line = json.dumps(res)
     print(line)
     if a.out:

@@ -79,7 +79,7 @@ def build_parser():
     p.add_argument("--max_steps", type=int, default=-1, help="stop an epoch early (smoke runs)")
     p.add_argument("--no_vqa_cache", action="store_true", help="produce q / z / answer logits per batch instead of once per split")
     p.add_argument("--no_hip_seq2vec", action="store_true", help="run the question encoder in PyTorch instead of the HIP library (GRUEncoder.use_hip = False)")
-    p.add_argument("--x6_seq2vec", action="store_true", help="NCX_F_X6 on the step kernel of the HIP question encoder (GRUEncoder.hip_x6 = True; same results to fp32 rounding; not the default)")
+    p.add_argument("--x6_seq2vec", action="store_true", help="NCX_F_X6 on the step kernel of the HIP question encoder (GRUEncoder.hip_x6 / TwoLSTM.hip_x6 = True; same results to fp32 rounding; not the default)")
     p.add_argument("--bf16", action="store_true", help="bf16 operands on the two dominant GEMMs (fp32 accumulate / master weights)")
     p.add_argument("--x6", action="store_true", help="NCX_F_X6: the three big fp32 products on the bf16 matrix cores with three-plane fp32-grade operands (same results to fp32 rounding; not the default)")
     p.add_argument("--path_trainset", type=str, default=None, help="overrides vqa.path_trainset of the YAML")

@@ -40,27 +40,7 @@ static_assert(GEMM_BK == 32, "one k-step is one MFMA depth");
 static_assert(G6_LDS <= 160 * 1024, "LDS");
 static_assert(G6_BM == 2 * G6_LR, "the loader takes the A tile in two passes");
 
-typedef __bf16 g6_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int g6_u32x2 __attribute__((ext_vector_type(2)));
-
-// x -> three bf16 planes (four values: one 8-byte store per plane), as split_store of k_att_logits_x6
-__device__ __forceinline__ void g6_split_store(f32x4 v, unsigned char* base) {
-    unsigned p1[4], p2[4], p3[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float xj = v[j];               // (a scalar copy first: __builtin_bit_cast applied to the vector element itself reads element 0 -- hipcc 7.2)
-        p1[j] = __builtin_bit_cast(unsigned, xj) & 0xFFFF0000u;
-        const float r1 = xj - __builtin_bit_cast(float, p1[j]);
-        p2[j] = __builtin_bit_cast(unsigned, r1) & 0xFFFF0000u;
-        const float r2 = r1 - __builtin_bit_cast(float, p2[j]);
-        p3[j] = __builtin_bit_cast(unsigned, r2);            // (at most 8 significant bits are left: the high half holds them all)
-    }
-    // v_perm_b32: the high halves of two dwords -> one dword (the even element in the low half)
-    const g6_u32x2 w1 = {__builtin_amdgcn_perm(p1[1], p1[0], 0x07060302u), __builtin_amdgcn_perm(p1[3], p1[2], 0x07060302u)};
-    const g6_u32x2 w2 = {__builtin_amdgcn_perm(p2[1], p2[0], 0x07060302u), __builtin_amdgcn_perm(p2[3], p2[2], 0x07060302u)};
-    const g6_u32x2 w3 = {__builtin_amdgcn_perm(p3[1], p3[0], 0x07060302u), __builtin_amdgcn_perm(p3[3], p3[2], 0x07060302u)};
-    *(g6_u32x2*)(base) = w1; *(g6_u32x2*)(base + G6_PL) = w2; *(g6_u32x2*)(base + 2 * G6_PL) = w3;
-}
+typedef rnn_bf16x8 g6_bf16x8;
 }  // namespace
 
 template <bool KEEP>
@@ -121,10 +101,10 @@ __global__ __launch_bounds__(G6_T, 1) void k_gru_step_x6(const int* __restrict__
     auto store = [&](int buf) __attribute__((always_inline)) {
         unsigned char* const base = lds6 + buf * G6_BUF + 2 * c4;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) g6_split_store(va[i], base + (lr + G6_LR * i) * G6_PB);
+        for (int i = 0; i < 2; ++i) rnn_split_store(va[i], base + (lr + G6_LR * i) * G6_PB, G6_PL);
 #pragma unroll
         for (int i = 0; i < G6_NB; ++i)
-            if (bok[i]) g6_split_store(vb[i], base + (G6_BM + lr + G6_LR * i) * G6_PB);
+            if (bok[i]) rnn_split_store(vb[i], base + (G6_BM + lr + G6_LR * i) * G6_PB, G6_PL);
     };
 
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};

@@ -1,6 +1,7 @@
 // ncx_lstm.hip -- the two-layer LSTM question encoder (TwoLSTM in eval mode: tanh(embedding) -> LSTM -> LSTM -> both layers' hidden
-// state at the last valid step, side by side): ncx_lstm2_packed_bytes, ncx_lstm2_pack, ncx_lstm2_workspace_bytes, ncx_lstm2_encode.
-// The training forward (ncx_lstm_train.hip) is the same step kernel with KEEP = true.
+// state at the last valid step, side by side): ncx_lstm2_packed_bytes, ncx_lstm2_pack, ncx_lstm2_workspace_bytes, ncx_lstm2_encode[_flags],
+// ncx_lstm2_step_form.  The training forward (ncx_lstm_train.hip) is the same step kernel with KEEP = true.  The step kernel here is the
+// fp32 one; under NCX_F_X6 the entries launch its bf16 x 6 form instead (ncx_lstm_x6.hip).
 //
 // Reference: vqa/models/seq2vec.py -- process_lengths + select_last (11-25), TwoLSTM (48-76), factory's `2-lstm` branch (86-89).
 // Semantics, gate order i, f, g, o as torch.nn.LSTM, the recurrence over TIME (batch_first; DESIGN 5n on why not as written):
@@ -43,14 +44,6 @@ __host__ __device__ inline LstmPacked lstm_packed(int emb, int H) {
 }
 
 struct LstmW { const float* w_ih; const float* w_hh; const float* b_ih; const float* b_hh; };
-
-struct LstmStep {
-    const int* wids; const float* E; const float* packed; const int* perm; const int* lens; const int* n_t;
-    float* h[2][2];      // [layer][t & 1]: h_t of the rows [0, n_t), sorted row order, [B][H]
-    float* c[2];         // [layer]: the cell state, [B][H], updated in place
-    float* q;            // [B][2 H], input row order
-    int T, V1, emb, H, tiles_m, total, grid1;
-};
 }  // namespace
 
 // row (j, g, u) of layer l = W_ih^l[g H + 32 j + u, :] zero-padded to whole k-steps, then W_hh^l[g H + 32 j + u, :] likewise; units beyond H
@@ -208,8 +201,7 @@ __global__ __launch_bounds__(256) void k_lstm_step(LstmStep a, int s, int layer_
     // epilogue: C layout col = lane & 15 (unit), row = 4 (lane >> 4) + reg
     const int ul = 16 * wu + li, unit = j * RNN_BU + ul;
     if (unit >= H) return;
-    const float* bias = packed + w_floats + (size_t)j * 4 * RNN_BU + ul;
-    const float b_i = bias[0], b_f = bias[RNN_BU], b_g = bias[2 * RNN_BU], b_o = bias[3 * RNN_BU];
+    const LstmBias bias = lstm_bias(packed + w_floats + (size_t)j * 4 * RNN_BU + ul);
     float* cbuf = layer ? a.c[1] : a.c[0];
     const float* cprev = cbuf;
     if constexpr (KEEP) {
@@ -223,21 +215,8 @@ __global__ __launch_bounds__(256) void k_lstm_step(LstmStep a, int s, int layer_
         for (int e = 0; e < 4; ++e) {
             const int row = m0 + 32 * wr + 16 * i + 4 * lk + e;
             if (row >= nt) continue;
-            const size_t at = (size_t)row * H + unit;
-            const float gi = 1.f / (1.f + expf(-(acc[0][i][e] + b_i)));
-            const float gf = 1.f / (1.f + expf(-(acc[1][i][e] + b_f)));
-            const float gg = tanhf(acc[2][i][e] + b_g);
-            const float go = 1.f / (1.f + expf(-(acc[3][i][e] + b_o)));
-            const float cp = t > 0 ? cprev[at] : 0.f;                        // step 0 never reads the workspace
-            const float cn = gf * cp + gi * gg;
-            const float hn = go * tanhf(cn);
-            cbuf[at] = cn;
-            h_next[at] = hn;
-            if (t == a.lens[row] - 1) a.q[(size_t)a.perm[row] * (2 * (size_t)H) + (size_t)layer * H + unit] = hn;
-            if constexpr (KEEP) {
-                float* g = (layer ? keep.g1 : keep.g0) + ((size_t)t * keep.B + row) * (4 * (size_t)keep.Hp) + unit;
-                g[0] = gi; g[keep.Hp] = gf; g[2 * keep.Hp] = gg; g[3 * keep.Hp] = go;
-            }
+            lstm_cell_store<KEEP>(acc[0][i][e], acc[1][i][e], acc[2][i][e], acc[3][i][e], bias, t, layer, row, unit, H, cprev, cbuf, h_next, a.q, a.perm,
+                                  a.lens, keep);
         }
 }
 
@@ -259,8 +238,12 @@ static LstmStep lstm2_step_args(const int32_t* wids, int B, int T, const float* 
 // the plan and the T + 1 wavefront launches; KEEP: into the stash
 template <bool KEEP>
 static int lstm2_run(const int32_t* wids, int B, int T, int V1, const RnnPlan& p, const LstmStep& a, const LstmKeep<KEEP>& keep, int32_t* bad_id_flag,
-                     hipStream_t st) {
+                     uint32_t flags, hipStream_t st) {
     NCX_HIP_TRY(rnn_plan(wids, B, T, V1, p, T, bad_id_flag, st));
+    if (flags & NCX_F_X6) {
+        if constexpr (KEEP) return lstm2_steps_x6(B, T, a, &keep, st);
+        else return lstm2_steps_x6(B, T, a, nullptr, st);
+    }
     for (int s = 0; s <= T; ++s) {             // every launch is issued: how many rows a step has is known on the device only
         const int layers = (s < T) + (s >= 1);
         hipLaunchKernelGGL(k_lstm_step<KEEP>, dim3((unsigned)(layers * a.grid1)), dim3(256), 0, st, a, s, s < T ? 0 : 1, keep);
@@ -270,8 +253,8 @@ static int lstm2_run(const int32_t* wids, int B, int T, int V1, const RnnPlan& p
 }
 
 int lstm2_forward_keep(const int32_t* wids, int B, int T, const float* E, int V1, int emb, int H, const float* packed, const RnnPlan& p,
-                       const LstmKeep<true>& keep, float* q_out, int32_t* bad_id_flag, hipStream_t s) {
-    return lstm2_run<true>(wids, B, T, V1, p, lstm2_step_args(wids, B, T, E, V1, emb, H, packed, p, q_out), keep, bad_id_flag, s);
+                       const LstmKeep<true>& keep, float* q_out, int32_t* bad_id_flag, uint32_t flags, hipStream_t s) {
+    return lstm2_run<true>(wids, B, T, V1, p, lstm2_step_args(wids, B, T, E, V1, emb, H, packed, p, q_out), keep, bad_id_flag, flags, s);
 }
 }  // namespace ncx
 
@@ -310,15 +293,25 @@ int ncx_lstm2_pack(const float* w_ih0, const float* w_hh0, const float* b_ih0, c
     return NCX_OK;
 }
 
+int ncx_lstm2_step_form(int32_t B, int32_t T, int32_t emb, int32_t H, uint32_t flags) {
+    if (!lstm2_flags_ok(flags) || !lstm2_dims_ok(B, T, emb, H)) return -1;
+    return (flags & NCX_F_X6) ? 1 : 0;
+}
+
 int ncx_lstm2_encode(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t emb, int32_t H, const float* packed,
                      void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream) {
-    if (!lstm2_dims_ok(B, T, emb, H) || V1 < 1) return -1;
+    return ncx_lstm2_encode_flags(wids, B, T, E, V1, emb, H, packed, 0, workspace, workspace_bytes, q_out, bad_id_flag, stream);
+}
+
+int ncx_lstm2_encode_flags(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t emb, int32_t H, const float* packed,
+                           uint32_t flags, void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream) {
+    if (!lstm2_flags_ok(flags) || !lstm2_dims_ok(B, T, emb, H) || V1 < 1) return -1;
     const Lstm2Layout w = lstm2_layout(B, H);
     if (!rnn_args_ok({wids, E, q_out, bad_id_flag}, packed, workspace, workspace_bytes, w.total)) return -1;
     char* ws = (char*)workspace;
     const RnnPlan p = w.plan.at(ws);
     LstmStep a = lstm2_step_args(wids, B, T, E, V1, emb, H, packed, p, q_out);
     for (int l = 0; l < 2; ++l) { a.h[l][0] = (float*)(ws + w.h[l][0]); a.h[l][1] = (float*)(ws + w.h[l][1]); a.c[l] = (float*)(ws + w.c[l]); }
-    return lstm2_run<false>(wids, B, T, V1, p, a, LstmKeep<false>{}, bad_id_flag, (hipStream_t)stream);
+    return lstm2_run<false>(wids, B, T, V1, p, a, LstmKeep<false>{}, bad_id_flag, flags, (hipStream_t)stream);
 }
 }  // extern "C"

@@ -235,13 +235,18 @@ int ncx_lstm2_pack_t(const float* w_ih0, const float* w_hh0, const float* w_ih1,
 
 int ncx_lstm2_train_forward(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t emb, int32_t H, const float* packed,
                             void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream) {
-    if (!lstm2_train_dims_ok(B, T, emb, H) || V1 < 1) return -1;
+    return ncx_lstm2_train_forward_flags(wids, B, T, E, V1, emb, H, packed, 0, workspace, workspace_bytes, q_out, bad_id_flag, stream);
+}
+
+int ncx_lstm2_train_forward_flags(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t emb, int32_t H, const float* packed,
+                                  uint32_t flags, void* workspace, size_t workspace_bytes, float* q_out, int32_t* bad_id_flag, void* stream) {
+    if (!lstm2_flags_ok(flags) || !lstm2_train_dims_ok(B, T, emb, H) || V1 < 1) return -1;
     const Lstm2TrainLayout w = lstm2_train_layout(B, T, emb, H);
     if (!rnn_args_ok({wids, E, q_out, bad_id_flag}, packed, workspace, workspace_bytes, w.total)) return -1;
     char* ws = (char*)workspace;
     const LstmKeep<true> keep{(float*)(ws + w.h[0]), (float*)(ws + w.h[1]), (float*)(ws + w.c[0]), (float*)(ws + w.c[1]),
                               (float*)(ws + w.gates[0]), (float*)(ws + w.gates[1]), B, pad_to(H, GEMM_BK)};
-    return lstm2_forward_keep(wids, B, T, E, V1, emb, H, packed, w.plan.at(ws), keep, q_out, bad_id_flag, (hipStream_t)stream);
+    return lstm2_forward_keep(wids, B, T, E, V1, emb, H, packed, w.plan.at(ws), keep, q_out, bad_id_flag, flags, (hipStream_t)stream);
 }
 
 int ncx_lstm2_train_backward(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t emb, int32_t H, const float* packed_t,

@@ -73,6 +73,29 @@ __attribute__((visibility("hidden"))) hipError_t rnn_dw(const RnnDwArgs& a, bool
 // A row index at or beyond n is read from row n - 1 (row 0 when n is 0): such rows are never stored, or are zeroed on the way to LDS
 __device__ __forceinline__ int rnn_clamp_row(int r, int n) { return max(min(r, n - 1), 0); }
 
+// The cut of the bf16 x 6 step kernels (ncx_gru_x6.hip, ncx_lstm_x6.hip): x -> three bf16 values by truncation, x = x1 + x2 + x3 exactly
+// (x1 = x & 0xFFFF0000, x2 = (x - x1) & 0xFFFF0000, x3 = x - x1 - x2), as split_store of k_att_logits_x6.  Four values: one 8-byte store
+// per plane, the planes `plane` bytes apart.
+typedef __bf16 rnn_bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned int rnn_u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void rnn_split_store(f32x4 v, unsigned char* base, int plane) {
+    unsigned p1[4], p2[4], p3[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float xj = v[j];               // (a scalar copy first: __builtin_bit_cast applied to the vector element itself reads element 0 -- hipcc 7.2)
+        p1[j] = __builtin_bit_cast(unsigned, xj) & 0xFFFF0000u;
+        const float r1 = xj - __builtin_bit_cast(float, p1[j]);
+        p2[j] = __builtin_bit_cast(unsigned, r1) & 0xFFFF0000u;
+        const float r2 = r1 - __builtin_bit_cast(float, p2[j]);
+        p3[j] = __builtin_bit_cast(unsigned, r2);            // (at most 8 significant bits are left: the high half holds them all)
+    }
+    // v_perm_b32: the high halves of two dwords -> one dword (the even element in the low half)
+    const rnn_u32x2 w1 = {__builtin_amdgcn_perm(p1[1], p1[0], 0x07060302u), __builtin_amdgcn_perm(p1[3], p1[2], 0x07060302u)};
+    const rnn_u32x2 w2 = {__builtin_amdgcn_perm(p2[1], p2[0], 0x07060302u), __builtin_amdgcn_perm(p2[3], p2[2], 0x07060302u)};
+    const rnn_u32x2 w3 = {__builtin_amdgcn_perm(p3[1], p3[0], 0x07060302u), __builtin_amdgcn_perm(p3[3], p3[2], 0x07060302u)};
+    *(rnn_u32x2*)(base) = w1; *(rnn_u32x2*)(base + plane) = w2; *(rnn_u32x2*)(base + 2 * plane) = w3;
+}
+
 // The 64 x 64 NT tile of the backward sweeps and the dX products: acc += A[m0 .. + 64][k-steps s0 .. s1) . W[n0 .. + 64]^T on
 // v_mfma_f32_16x16x4_f32, both operands col-is-k at LDS pitch RNN_NT_P (conflict-free ds_read_b64 fragments, ncx_gemm.h).
 //   src.ptr(s, i)   where the loader's quad of A row lr + 32 i sits at k-step s (an aligned, readable 16 bytes)

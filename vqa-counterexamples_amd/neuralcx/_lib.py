@@ -23,8 +23,8 @@ EXPORTS = ("ncx_input_size", "ncx_workspace_bytes", "ncx_forward", "ncx_forward_
            "ncx_similarity_scores",
            "ncx_gru_packed_bytes", "ncx_gru_pack", "ncx_gru_workspace_bytes", "ncx_gru_encode", "ncx_gru_encode_flags", "ncx_gru_step_form",
            "ncx_gru_train_workspace_bytes", "ncx_gru_packed_t_bytes", "ncx_gru_pack_t", "ncx_gru_train_forward", "ncx_gru_train_forward_flags", "ncx_gru_train_backward",
-           "ncx_lstm2_packed_bytes", "ncx_lstm2_pack", "ncx_lstm2_workspace_bytes", "ncx_lstm2_encode",
-           "ncx_lstm2_train_workspace_bytes", "ncx_lstm2_packed_t_bytes", "ncx_lstm2_pack_t", "ncx_lstm2_train_forward", "ncx_lstm2_train_backward",
+           "ncx_lstm2_packed_bytes", "ncx_lstm2_pack", "ncx_lstm2_workspace_bytes", "ncx_lstm2_encode", "ncx_lstm2_encode_flags", "ncx_lstm2_step_form",
+           "ncx_lstm2_train_workspace_bytes", "ncx_lstm2_packed_t_bytes", "ncx_lstm2_pack_t", "ncx_lstm2_train_forward", "ncx_lstm2_train_forward_flags", "ncx_lstm2_train_backward",
            "ncx_ws_region", "ncx_wgmap_check",
            "ncx_comm_unique_id", "ncx_comm_create", "ncx_comm_destroy", "ncx_allreduce", "ncx_train_tail", "ncx_profile_stamps",
            "ncx_pairlin_workspace_bytes", "ncx_pairlin_forward", "ncx_pairlin_backward",
@@ -249,6 +249,10 @@ def lib():
     L.ncx_lstm2_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.ncx_lstm2_encode.restype = C.c_int
     L.ncx_lstm2_encode.argtypes = L.ncx_gru_encode.argtypes
+    L.ncx_lstm2_encode_flags.restype = C.c_int
+    L.ncx_lstm2_encode_flags.argtypes = L.ncx_gru_encode_flags.argtypes
+    L.ncx_lstm2_step_form.restype = C.c_int
+    L.ncx_lstm2_step_form.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32]
     L.ncx_lstm2_train_workspace_bytes.restype = C.c_size_t
     L.ncx_lstm2_train_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.ncx_lstm2_packed_t_bytes.restype = C.c_size_t
@@ -257,6 +261,8 @@ def lib():
     L.ncx_lstm2_pack_t.argtypes = [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.ncx_lstm2_train_forward.restype = C.c_int
     L.ncx_lstm2_train_forward.argtypes = L.ncx_gru_encode.argtypes
+    L.ncx_lstm2_train_forward_flags.restype = C.c_int
+    L.ncx_lstm2_train_forward_flags.argtypes = L.ncx_gru_encode_flags.argtypes
     L.ncx_lstm2_train_backward.restype = C.c_int
     L.ncx_lstm2_train_backward.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                            C.c_size_t] + [C.c_void_p] * 11

@@ -875,10 +875,20 @@ def lstm_weights(encoder) -> LstmWeights:
     return LstmWeights(encoder)
 
 
-def lstm_encode(wids: torch.Tensor, lw: LstmWeights, bad_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The two-layer LSTM question encoder (ncx_lstm2_encode; TwoLSTM.forward in eval mode) on the current stream, no host sync: wids
+def lstm_step_form(emb: int, H: int, B: int, T: int, x6=None) -> str:
+    """Which step kernel lstm_encode / lstm_train_forward take for this shape (ncx_lstm2_step_form; host only: no launch, no device
+    access).  x6: as gru_step_form -- None = the process-wide choice (EXTRA_FLAGS, read now: NCX_X6=1), True / False force the form."""
+    rc = _lib.lib().ncx_lstm2_step_form(B, T, emb, H, mlb_att_flags(x6))
+    if rc < 0:
+        raise _lib.NcxError("ncx_lstm2_step_form: dims out of range (B %d, T %d, emb %d, H %d)" % (B, T, emb, H))
+    return GRU_STEP_FORMS[rc]
+
+
+def lstm_encode(wids: torch.Tensor, lw: LstmWeights, bad_flag: Optional[torch.Tensor] = None, x6=None) -> torch.Tensor:
+    """The two-layer LSTM question encoder (ncx_lstm2_encode_flags; TwoLSTM.forward in eval mode) on the current stream, no host sync: wids
     [B, T] -> q [B, 2 H], layer 0's and layer 1's hidden state after each question's last word.  len = the number of nonzero ids, T for
-    an all-padding row; padded steps are not computed.  A word id outside [0, V + 1) is never used as an address; it sets `bad_flag`
+    an all-padding row; padded steps are not computed.  x6 (lstm_step_form): the bf16 x 6 form of the step kernel -- fp32-grade, not
+    bit-equal to the fp32 form.  A word id outside [0, V + 1) is never used as an address; it sets `bad_flag`
     (default: gru_bad_flag(device), the flag check_gru_ids reads)."""
     if wids.dim() != 2:
         raise ValueError("wids must be [B, T], got %s" % (tuple(wids.shape),))
@@ -899,9 +909,9 @@ def lstm_encode(wids: torch.Tensor, lw: LstmWeights, bad_flag: Optional[torch.Te
     ws = torch.empty(n + 256, dtype=torch.uint8, device=dev)
     p, n = _ws_ptr(ws)
     q = torch.empty(B, 2 * lw.H, dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().ncx_lstm2_encode(_ptr(wids, torch.int32, "wids"), B, T, _ptr(lw.E, torch.float32, "E"), lw.V1, lw.emb, lw.H,
-                                           _ptr(lw.packed, torch.float32, "packed"), p, n, C.c_void_p(q.data_ptr()),
-                                           _ptr(bad_flag, torch.int32, "bad_flag"), _stream()), "ncx_lstm2_encode")
+    _lib.check(_lib.lib().ncx_lstm2_encode_flags(_ptr(wids, torch.int32, "wids"), B, T, _ptr(lw.E, torch.float32, "E"), lw.V1, lw.emb, lw.H,
+                                                 _ptr(lw.packed, torch.float32, "packed"), mlb_att_flags(x6), p, n, C.c_void_p(q.data_ptr()),
+                                                 _ptr(bad_flag, torch.int32, "bad_flag"), _stream()), "ncx_lstm2_encode")
     return q
 
 
@@ -1121,16 +1131,18 @@ def lstm_train_workspace(B: int, T: int, lw: LstmTrainWeights, device) -> torch.
     return torch.empty(n + 256, dtype=torch.uint8, device=device)
 
 
-def lstm_train_forward(wids: torch.Tensor, lw: LstmTrainWeights, ws: torch.Tensor, bad_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """ncx_lstm2_train_forward: lstm_encode's q [B, 2 H] (bit for bit), with the stash of the valid (row, t) pairs left in `ws`."""
+def lstm_train_forward(wids: torch.Tensor, lw: LstmTrainWeights, ws: torch.Tensor, bad_flag: Optional[torch.Tensor] = None, x6=None) -> torch.Tensor:
+    """ncx_lstm2_train_forward_flags: lstm_encode's q [B, 2 H] under the same x6 (bit for bit), with the stash of the valid (row, t) pairs
+    left in `ws`.  x6: lstm_step_form; the backward takes whichever stash the forward left."""
     B, T, wids = _lstm_train_args(wids, lw, "lstm_train_forward")
     if bad_flag is None:
         bad_flag = gru_bad_flag(wids.device)
     p, n = _ws_ptr(ws)
     q = torch.empty(B, 2 * lw.H, dtype=torch.float32, device=wids.device)
-    _lib.check(_lib.lib().ncx_lstm2_train_forward(_ptr(wids, torch.int32, "wids"), B, T, _ptr(lw.E, torch.float32, "E"), lw.V1, lw.emb, lw.H,
-                                                  _ptr(lw.packed, torch.float32, "packed"), p, n, C.c_void_p(q.data_ptr()),
-                                                  _ptr(bad_flag, torch.int32, "bad_flag"), _stream()), "ncx_lstm2_train_forward")
+    _lib.check(_lib.lib().ncx_lstm2_train_forward_flags(_ptr(wids, torch.int32, "wids"), B, T, _ptr(lw.E, torch.float32, "E"), lw.V1, lw.emb,
+                                                        lw.H, _ptr(lw.packed, torch.float32, "packed"), mlb_att_flags(x6), p, n,
+                                                        C.c_void_p(q.data_ptr()), _ptr(bad_flag, torch.int32, "bad_flag"), _stream()),
+               "ncx_lstm2_train_forward")
     return q
 
 

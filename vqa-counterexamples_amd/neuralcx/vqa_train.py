@@ -109,7 +109,8 @@ class LstmTrainFunction(torch.autograd.Function):
     """q = [h^0 | h^1] after each question's last word (TwoLSTM below its dropout) through ncx_lstm2_train_forward / _backward.
     Inputs: wids, E, rnn_0's w_ih, w_hh, b_ih, b_hh, rnn_1's four and the encoder module, on which the packs are cached (keyed on
     data_ptr / _version of the nine tensors, like GruTrainFunction: rebuilt after an optimizer step).  Gradients: the nine tensors;
-    None for E when it does not require grad (a fixed embedding: the dX product is skipped)."""
+    None for E when it does not require grad (a fixed embedding: the dX product is skipped).  The forward's step kernel follows
+    module.hip_x6 (ops.lstm_step_form)."""
 
     @staticmethod
     def weights(module, tensors):
@@ -125,7 +126,7 @@ class LstmTrainFunction(torch.autograd.Function):
     def forward(ctx, wids, E, w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1, module=None):
         lw = LstmTrainFunction.weights(module, (E, w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1))
         ws = ops.lstm_train_workspace(wids.shape[0], wids.shape[1], lw, wids.device)
-        q = ops.lstm_train_forward(wids, lw, ws)
+        q = ops.lstm_train_forward(wids, lw, ws, x6=getattr(module, "hip_x6", None))
         ctx.hip = (wids, lw, ws)
         return q
 

@@ -23,7 +23,8 @@ glimpse fusion, classifier; forward with dropout and backward) then runs in HIP 
 product on the bf16 matrix path with three-plane operands (NCX_F_X6: same results to fp32 rounding; not the default), and with
 --hip_att_train the backward runs its twin, d conv_v_att.weight, there as well.  --x6_seq2vec is the same choice for the GRU question
 encoder (any arch): it sets GRUEncoder.hip_x6, and the encoder's HIP forward (eval mode and --hip_seq2vec_train) runs the bf16 x 6 form of
-its step kernel.  The images are a seeded synthetic attention table [syn_images, dim_v, syn_grid, syn_grid].
+its step kernel; --x6_2lstm is that choice for the 2-lstm encoder (TwoLSTM.hip_x6: its eval-mode forward and --hip_2lstm_train run
+k_lstm_step_x6).  The images are a seeded synthetic attention table [syn_images, dim_v, syn_grid, syn_grid].
 """
 import argparse
 import json
@@ -76,6 +77,7 @@ def build_parser():
                    "(MLBAtt.use_hip_train: attention head, glimpse fusion, classifier; torch.optim.Adam steps)")
     p.add_argument("--x6", action="store_true", help="attention archs only: NCX_F_X6 on the attention kernel, same results to fp32 rounding; not the default")
     p.add_argument("--x6_seq2vec", action="store_true", help="GRU question encoder only: NCX_F_X6 on its HIP step kernel, same results to fp32 rounding; not the default")
+    p.add_argument("--x6_2lstm", action="store_true", help="2-lstm question encoder only: NCX_F_X6 on its HIP step kernel, same results to fp32 rounding; not the default")
     p.add_argument("--no_hip", action="store_true", help="the plain PyTorch modules (no HIP library; runs on a CPU too)")
     p.add_argument("--seed", type=int, default=1337)
     return p
@@ -157,7 +159,12 @@ class Trainer:
         if getattr(args, "x6_seq2vec", False) and args.no_hip:
             raise SystemExit("train.py: --x6_seq2vec picks a form of the HIP step kernel of the GRU encoder; it cannot be combined with --no_hip")
         if getattr(args, "x6_seq2vec", False) and s2v.get("arch") == "2-lstm" and "hidden_size" in s2v:                   # seq2vec.factory's TwoLSTM branch
-            raise SystemExit("train.py: --x6_seq2vec needs the GRU encoder; this YAML builds the 2-lstm encoder, whose step kernel has no bf16 x 6 form")
+            raise SystemExit("train.py: --x6_seq2vec needs the GRU encoder; this YAML builds the 2-lstm encoder, whose bf16 x 6 step kernel is picked with --x6_2lstm")
+        if getattr(args, "x6_2lstm", False) and args.no_hip:
+            raise SystemExit("train.py: --x6_2lstm picks a form of the HIP step kernel of the 2-lstm encoder; it cannot be combined with --no_hip")
+        if getattr(args, "x6_2lstm", False) and not (s2v.get("arch") == "2-lstm" and "hidden_size" in s2v):     # seq2vec.factory's TwoLSTM branch
+            raise SystemExit("train.py: --x6_2lstm needs the 2-lstm encoder (seq2vec: {arch: 2-lstm, hidden_size: ...}); this YAML builds %r"
+                             % s2v.get("arch", "skipthoughts"))
         if args.hip_2lstm_train and not (s2v.get("arch") == "2-lstm" and "hidden_size" in s2v):       # seq2vec.factory's TwoLSTM branch
             raise SystemExit("train.py: --hip_2lstm_train needs the 2-lstm encoder (seq2vec: {arch: 2-lstm, hidden_size: ...}); this YAML builds %r"
                              % s2v.get("arch", "skipthoughts"))
@@ -197,6 +204,10 @@ class Trainer:
             if not isinstance(self.model.seq2vec, models.seq2vec.GRUEncoder):
                 raise SystemExit("train.py: --x6_seq2vec needs the GRU encoder; this YAML builds %s" % type(self.model.seq2vec).__name__)
             self.model.seq2vec.hip_x6 = True
+        if getattr(args, "x6_2lstm", False):
+            if not isinstance(self.model.seq2vec, models.seq2vec.TwoLSTM):
+                raise SystemExit("train.py: --x6_2lstm needs the TwoLSTM encoder; this YAML builds %s" % type(self.model.seq2vec).__name__)
+            self.model.seq2vec.hip_x6 = True
         self.hip = self.route == "hip"
         self.engine = None
         if self.freeze or opt["model"]["seq2vec"].get("fixed_emb"):
@@ -223,10 +234,11 @@ class Trainer:
             self.optim = torch.optim.Adam([p_ for p_ in self.model.parameters() if p_.requires_grad], self.lr)     # train.py:143-144
             self.criterion = nn.CrossEntropyLoss()
         self.best_acc1, self.history = 0.0, []
-        print("=> route: %s%s%s%s" % ("hip" if self.hip else self.route, " (engine: whole step in HIP)" if self.engine else "",
+        print("=> route: %s%s%s%s%s" % ("hip" if self.hip else self.route, " (engine: whole step in HIP)" if self.engine else "",
                                     " (question encoder: HIP forward + backward through time)" if getattr(self, "hip_seq2vec", False) else
                                     " (2-lstm question encoder: HIP forward + backward through time, --hip_2lstm_train)" if getattr(self, "hip_2lstm", False)
-                                    else "", " (question encoder: bf16 x 6 step kernel)" if getattr(args, "x6_seq2vec", False) else ""), flush=True)
+                                    else "", " (question encoder: bf16 x 6 step kernel)" if getattr(args, "x6_seq2vec", False) else "",
+                                      " (2-lstm question encoder: bf16 x 6 step kernel)" if getattr(args, "x6_2lstm", False) else ""), flush=True)
 
     # ---- data ------------------------------------------------------------------------------------------------
     def q_emb_of(self, split):

@@ -86,9 +86,12 @@ class TwoLSTM(nn.Module):
     skipped, the two layers run as a wavefront); `use_hip = False` keeps it in PyTorch.  It trains under torch autograd, unless
     `use_hip_bptt = True` (off by default; train.py --hip_2lstm_train): then a CUDA fp32 module called with grad mode on and a parameter
     that requires grad runs neuralcx.vqa_train.LstmTrainFunction (forward with a stash, backward through time); its dropout stays in
-    torch, on the two halves in the torch path's order."""
+    torch, on the two halves in the torch path's order.
+    `hip_x6` is handed to both HIP routes and changes no routing decision: None = the process-wide choice (ops.EXTRA_FLAGS, NCX_X6=1),
+    True / False = the bf16 x 6 / the fp32 form of the step kernel (ops.lstm_step_form; train.py --x6_2lstm sets True)."""
     use_hip = True
     use_hip_bptt = False
+    hip_x6 = None
     p_drop = 0.3
 
     def __init__(self, vocab_words, emb_size, hidden_size):
@@ -132,7 +135,7 @@ class TwoLSTM(nn.Module):
     def forward(self, wids):
         if self._hip_ok(wids):
             from neuralcx import ops
-            return ops.lstm_encode(wids, self._hip_weights())
+            return ops.lstm_encode(wids, self._hip_weights(), x6=self.hip_x6)
         if self._hip_bptt_ok(wids):
             from neuralcx.vqa_train import LstmTrainFunction
             r0, r1, H = self.rnn_0, self.rnn_1, self.hidden_size
