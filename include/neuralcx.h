@@ -219,6 +219,8 @@ int ncx_backward_phase(const ncx_dims* d, const ncx_inputs* in, const ncx_params
  * answer_aids ascending, then the others ascending, and in [A] how many occur -- the row order of the answer_embedding gradient's product,
  * whose row tiles without an answer of the batch skip the dGgt^T operand (all zeros there).  Size 0 where the product keeps the full form. */
 #define NCX_WS_DE_PERM 4
+#define NCX_WS_H2 5     /* diagnostics / tests: post-dropout activations of linear_2, [B*K, H] (valid after ncx_forward; size 0 when L < 2) */
+#define NCX_WS_H3 6     /* ... of linear_3 (size 0 when L < 3) */
 int ncx_ws_region(const ncx_dims* d, int32_t which, size_t* offset, size_t* bytes);
 
 /* NCX_F_FUSED_TAIL: replaces, in one pass over h_L, the tail of ncx_forward (`out`, cx.py:327), ncx_loss_rank
@@ -849,6 +851,17 @@ int ncx_mlb_att_train_ws_region(const ncx_mlb_att_dims* d, const ncx_mlb_att_tra
 /* Not a GEMM id either: out6 = {1 when ncx_backward_adam applies Adam inside the answer_embedding gradient's launch for these dims (given an
  * unpadded embedding slice), else 0; the passenger workgroups of that launch; 0, 0, 0, 0} */
 #define NCX_QUERY_FUSED_ADAM 33
+/* Not a GEMM id either: the route ncx_forward takes through its Linear layers for these dims, as launched (experiment hooks applied; read
+ * from the functions the launchers themselves call).
+ * out6 = {linear_1's engine: 0 the generic segmented GEMM, 1 the fused forward kernel on a chain of segments, 2 the fused forward kernel with
+ *         the per-triplet fold of the two v segments, 3 the bf16 variant's product;
+ *         its tile form -- chain: 0 48x128, 1 96x64, 2 96x128, 3 160x128, 4 64x64 (short chains); fold: the tile rows 48 / 96 / 192; generic
+ *         engine: the tile cfg code of ncx_plan_query(NCX_GEMM_MAIN); bf16: 0;
+ *         k-chunks per output tile (1 = no split; bf16: 0);
+ *         1 when the pairwise distance is computed inside the fused forward kernel, else 0 (k_prep computes it);
+ *         the hidden layers' engine: 0 generic, 1 the fused forward kernel, -1 when L == 1;
+ *         their k-chunks per output tile (0 when L == 1)} */
+#define NCX_QUERY_FWD_ROUTE 34
 int ncx_profile_begin(uint32_t gemm_mask /* bit i = gemm id i */, int32_t max_launches);
 int ncx_profile_end(float* ms, int32_t* ids, int32_t cap);
 /* In-kernel clock diagnostics of the MAIN launch (the fused forward kernel of linear_1): while `stamps` is non-NULL

@@ -31,11 +31,15 @@ def test_golden_forward_loss_recall_backward(name):
 
 @pytest.mark.parametrize("B,K,H,L", [(1, 24, 16, 1), (7, 24, 20, 2), (13, 24, 48, 3), (5, 48, 32, 1), (33, 24, 96, 2)])
 def test_ragged_shapes_vs_oracle(B, K, H, L):
-    """Odd batch sizes / widths (nothing a multiple of the 16/32/64 tile sizes), and K = 48 (config 5)."""
+    """Odd batch sizes / widths (nothing a multiple of the 16/32/64 tile sizes), and K = 48 (config 5), on the GENERIC segmented engine:
+    dv = 70, dz = 18 and A = 45 are no multiples of 4, so linear_1 never reaches the fused forward kernel here (asserted below; that
+    kernel's ragged shapes are tests/test_main_fwd_edges_gpu.py)."""
+    from neuralcx import _lib, ops
     d = orc.Dims(K=K, dv=70, dq=50, dz=18, A=45, H=H, L=L)
     params = orc.init_params(d, seed=11 + B, gain=3.0)
     batch = random_case(100 + B, B, d)
     batch["answer_aids"][0] = batch["answer_aids"][B - 1]
+    assert _lib.plan_query(ops.make_dims(to_dev_batch(batch), H=d.H, L=d.L, da=d.da, A=d.A), "FWD_ROUTE")["engine"] == 0
     compare_with_oracle(d, None, params, batch)
 
 

@@ -86,6 +86,27 @@ int ncx_plan_query(const ncx_dims* d, int32_t gemm_id, int32_t* out6) {
         out6[1] = on ? main_adam_passengers() : 0;
         return NCX_OK;
     }
+    if (gemm_id == NCX_QUERY_FWD_ROUTE) {      // the forward's Linear layers, from the functions forward_impl and main_forward launch by
+        const StepRoutes r = routes(*d);
+        GemmUse u[U_COUNT];
+        list_uses(*d, r, u);
+        const long long M = (long long)d->B * d->K;
+        const bool bf16 = d->flags & NCX_F_BF16;
+        for (int i = 0; i < 6; ++i) out6[i] = 0;
+        if (bf16) out6[0] = 3;
+        else if (main_fwd_dims_ok(*d)) {
+            const FwdRoute f = forward_route(*d, r);
+            const int sp = main_split(M, d->H, r.cand_ksteps);
+            out6[0] = f.vfold ? 2 : 1;
+            out6[1] = f.vfold ? main_fold_rows_eff(M, d->H, d->K) : main_chain_form(M, d->H, r.cand_ksteps, sp, false, true);
+            out6[2] = sp;
+            out6[3] = f.dist_in_main ? 1 : 0;
+        } else { out6[1] = u[U_MAIN].plan.cfg; out6[2] = u[U_MAIN].plan.split; }
+        if (d->L < 2) { out6[4] = -1; return NCX_OK; }
+        if (hidden_fwd_dims_ok(*d) && !bf16) { out6[4] = 1; out6[5] = main_split(M, d->H, ksteps(d->H)); }
+        else out6[5] = u[U_FWD_L].plan.split;
+        return NCX_OK;
+    }
     if (gemm_id < 0 || gemm_id >= U_COUNT) return NCX_E_DIMS;
     GemmUse u[U_COUNT];
     list_uses(*d, routes(*d), u);

@@ -225,6 +225,29 @@ __global__ __launch_bounds__(256) void k_scores(const float* __restrict__ h, con
     s = wave_sum(s);
     if (lane == 0) scores[r] = s + bias[0];
 }
+
+// The route of linear_1 on the fused forward kernel (ncx_plan.h): forward_impl launches by it, NCX_QUERY_FWD_ROUTE reports it.
+FwdRoute forward_route(const ncx_dims& d, const StepRoutes& r) {
+    const long long M = (long long)d.B * d.K, H = d.H, din = seg_offsets(d).din;
+    const long long main_T = r.cand_ksteps;
+    FwdRoute f{};
+    // K = 24, whole 32-column tiles, no k-split: the two v segments as one pass with the per-triplet fold (ncx_main.h, MK_VFOLD)
+    // (K = 48: on 96-row tiles only -- two triplets per tile -- so only where those fill the chip)
+    f.vfold = main_fwd_dims_ok(d) && (d.flags & NCX_F_V_MULT) && (d.K == 24 || (d.K == 48 && (main_fold_rows(M, H) >= 96 || hook_env("NCX_FOLD4") || hook_env("NCX_FOLD8")))) && d.dv % 32 == 0 && d.dv >= 64 &&
+              main_split(M, H, main_T) == 1 && !hook_env("NCX_NO_VFOLD") &&
+              (long long)d.n_img * d.dv * 4 < (1ll << 32) - 65536 && (long long)H * din * 4 < (1ll << 32) - 65536;      // (the fold's buffer loads: 32-bit byte offsets)
+    // The pairwise distance rides in the fused forward kernel when that kernel sees whole v rows (no k-split, no slid windows).
+    // Measured at configs[1]: inside the plain chain the distance costs the kernel 12 us and saves k_prep 30; inside the fold's
+    // 48 x 64 tiles (a quarter of the MFMA work per vector instruction) it costs 31 us: there k_prep keeps computing it.
+    // Round 4, measured again for the one-triplet-per-wave fold forms (96 / 192-row tiles, K = 24: a wave's loader holds v_o beside every v_k quad it loads,
+    // the distance is ~14 vector operations per loaded quad and k_prep stops reading the feature rows): the fold loop goes from 5 085 to 5 790 cycles per k-step
+    // (5 740 with the arithmetic spread over the sub-steps) -- vector instructions are not free under fp32 MFMAs, each costs the matrix pipe ~8-15 cycles --
+    // so the kernel loses the 17 us k_prep gains (0.2938 against 0.2771 ms; step 0.8443 / 0.8483 against 0.8489).  Kept behind the hook NCX_DIST_IN_FOLD.
+    f.dist_in_fold = f.vfold && d.K == 24 && main_fold_rows_eff(M, H, d.K) >= 96 && !(d.flags & NCX_F_X6) && hook_env("NCX_DIST_IN_FOLD");
+    f.dist_in_main = main_fwd_dims_ok(d) && (d.flags & NCX_F_V_DIST) && (d.flags & NCX_F_V_MULT) && d.dv % 32 == 0 &&
+                     main_split(M, H, main_T) == 1 && (!f.vfold || f.dist_in_fold) && !(hook_env("NCX_NO_DIST_IN_MAIN"));
+    return f;
+}
 }  // namespace ncx
 
 using namespace ncx;
@@ -300,22 +323,9 @@ static int forward_impl(const ncx_dims* dp, const ncx_inputs* in, const ncx_para
         if (aemb && w.ldgt > d.A) { const int e = pk.n++; pk.src[e] = nullptr; pk.dst[e] = gt; pk.ldd[e] = w.ldgt; pk.zero_from[e] = d.A; pk.cols[e] = 0; }
         if (d.flags & NCX_F_REUSE_GT) pk.n = 0;
     }
-    // the pairwise distance rides in the fused forward kernel when that kernel sees whole v rows (no k-split, no slid windows)
-    const long long main_T = r.cand_ksteps;
-    // K = 24, whole 32-column tiles, no k-split: the two v segments as one pass with the per-triplet fold (ncx_main.h, MK_VFOLD)
-    // (K = 48: on 96-row tiles only -- two triplets per tile -- so only where those fill the chip)
-    const bool vfold = main_fwd_dims_ok(d) && (d.flags & NCX_F_V_MULT) && (d.K == 24 || (d.K == 48 && (main_fold_rows(M, H) >= 96 || hook_env("NCX_FOLD4") || hook_env("NCX_FOLD8")))) && d.dv % 32 == 0 && d.dv >= 64 &&
-                       main_split(M, H, main_T) == 1 && !hook_env("NCX_NO_VFOLD") &&
-                       (long long)d.n_img * d.dv * 4 < (1ll << 32) - 65536 && (long long)H * din * 4 < (1ll << 32) - 65536;      // (the fold's buffer loads: 32-bit byte offsets)
-    // Measured at configs[1]: inside the plain chain the distance costs the kernel 12 us and saves k_prep 30; inside the fold's
-    // 48 x 64 tiles (a quarter of the MFMA work per vector instruction) it costs 31 us: there k_prep keeps computing it.
-    // Round 4, measured again for the one-triplet-per-wave fold forms (96 / 192-row tiles, K = 24: a wave's loader holds v_o beside every v_k quad it loads,
-    // the distance is ~14 vector operations per loaded quad and k_prep stops reading the feature rows): the fold loop goes from 5 085 to 5 790 cycles per k-step
-    // (5 740 with the arithmetic spread over the sub-steps) -- vector instructions are not free under fp32 MFMAs, each costs the matrix pipe ~8-15 cycles --
-    // so the kernel loses the 17 us k_prep gains (0.2938 against 0.2771 ms; step 0.8443 / 0.8483 against 0.8489).  Kept behind the hook NCX_DIST_IN_FOLD.
-    const bool dist_in_fold = vfold && d.K == 24 && main_fold_rows_eff(M, H, d.K) >= 96 && !(d.flags & NCX_F_X6) && hook_env("NCX_DIST_IN_FOLD");
-    const bool dist_in_main = main_fwd_dims_ok(d) && (d.flags & NCX_F_V_DIST) && (d.flags & NCX_F_V_MULT) && d.dv % 32 == 0 &&
-                              main_split(M, H, main_T) == 1 && (!vfold || dist_in_fold) && !(hook_env("NCX_NO_DIST_IN_MAIN"));
+    // the per-triplet fold of the two v segments, and the pairwise distance inside the fused forward kernel (forward_route, above)
+    const FwdRoute fr = forward_route(d, r);
+    const bool vfold = fr.vfold, dist_in_main = fr.dist_in_main;
     ncx_dims dprep = d;
     if (dist_in_main) dprep.flags |= NCX_F_PRIV_DIST_IN_MAIN;
     if (!do_rest) pk.n = 0;                                   // prelude: no weight is read

@@ -122,6 +122,8 @@ int main_forward(MainArgs& a, hipStream_t s);
 int main_forward_rowmap(MainArgs& a, hipStream_t s);
 // a chain of T k-steps over an M x N output takes the 64 x 64 form with three workgroups per CU
 bool main_short_form(long long M, long long N, long long T, int split);
+// the tile form main_forward / main_forward_rowmap launch a chain without the fold on, hooks applied (codes of NCX_QUERY_FWD_ROUTE)
+int main_chain_form(long long M, long long N, long long T, int split, bool single_gather, bool wide_ok);
 // The answer-embedding gradient (two segments, plain or -- rowmap -- over permuted rows) on that form with Adam applied by the same launch
 // (a.adam; WithAdam of ncx_main.h).  NCX_E_FLAGS when the shape does not take the 64 x 64 form: callers ask main_short_form first.
 int main_forward_adam(MainArgs& a, bool rowmap, hipStream_t s);

@@ -54,7 +54,11 @@ struct MainCfg {
     static constexpr int BM_LDS = (BM + RP - 1) / RP * RP;        // A rows held in LDS (a multiple of the loader pass)
     static constexpr int LDS6 = 2 * 3 * (BM_LDS + BN) * MF6_P;      // X6: [2 buffers][3 planes][A rows | W rows][MF6_P]
     static constexpr int LDS_FOLD6 = 2 * (3 * 208 * MF6_P + 8 * 32 * 4 + 128 * MF_P * 4);   // X6 fold: [2][three planes of 208 v_k rows | 8 v_o rows fp32 | W_k, W_m 128 rows fp32]
-    static constexpr int LDS32 = 2 * (BM_LDS + BN) * MF_P * 4;
+    static constexpr int LDS_LOOP = 2 * (BM_LDS + BN) * MF_P * 4;   // the k loop's double-buffered A | W tiles
+    static constexpr int LDS_STAGE = BM * (BN + 4) * 4;             // the epilogue's staged tile [BM][BN + 4] over the same memory
+    // (160 x 128 is the one form whose staged tile is the larger: 84 480 bytes against 82 944.  Sized by the loop alone, the stage's last 384 floats --
+    //  tile rows 157 .. 159 -- lay beyond the allocation: their stores were dropped and their loads read zeros; tests/test_main_fwd_edges_gpu.py, group G)
+    static constexpr int LDS32 = LDS_LOOP > LDS_STAGE ? LDS_LOOP : LDS_STAGE;
     static constexpr int LDS = !X6_ ? LDS32 : (LDS_FOLD6 > LDS6 ? (LDS_FOLD6 > LDS32 ? LDS_FOLD6 : LDS32) : (LDS6 > LDS32 ? LDS6 : LDS32));
     static constexpr int LDS_FOLD = BM % 96 == 0 ? 2 * (32 * (T / 64) + 128) * MF_P * 4   // MK_VFOLD, one triplet per wave: A 32 rows per wave, W_k | W_m 2 x 64 rows
                                                  : 2 * (80 + 2 * 64) * MF_P * 4;          // MK_VFOLD on 48-row tiles: A 80 rows, two effective weight tiles
@@ -1064,6 +1068,7 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
     // epilogue with 16-byte operand loads and stores whole rows.
     constexpr int SP = BN + 4;
     float* const stage = mf_smem;                        // [BM][SP]  (every fragment read is complete: the last step's barrier)
+    static_assert(BM * SP * 4 <= CFG::LDS, "the staged tile lies inside the launch's LDS (MainCfg::LDS_STAGE)");
     constexpr int QR = BN / 4;                            // 16-byte pieces per tile row
     const EpiArgs& e = args.epi;
     float* const dst = S > 1 ? args.slab + (long long)z * M * N : args.out;      // S > 1: raw partial sums; k_main_fixup runs the epilogue

@@ -17,34 +17,41 @@ bool main_short_form(long long M, long long N, long long T, int split) {
     return split <= 1 && T <= 32 && ((M + 63) / 64) * ((N + 63) / 64) >= 2 * num_cus() && !hook_env("NCX_MAIN_CFG");
 }
 
-// The tile form of a chain without the per-triplet fold.  W: the epilogue the kernels are compiled with (AsIs: the standard one; WithRowMap:
-// permuted rows -- the same choice of tile for a shape, so the two forms of the answer-embedding gradient add every element's products in one order)
+// The tile form of a chain without the per-triplet fold, as codes of NCX_QUERY_FWD_ROUTE: 0 48x128, 1 96x64, 2 96x128, 3 160x128, 4 64x64 short.
+// single_gather: the chain is one MK_GATHER segment; wide_ok: the epilogue leaves the 160-row tile its LDS (a forced 3 without it is refused
+// by the launcher).  main_forward_chain launches by it and ncx_plan_query reports it.
+int main_chain_form(long long M, long long N, long long T, int split, bool single_gather, bool wide_ok) {
+    if (main_short_form(M, N, T, split)) return 4;          // a workgroup that short spends as long starting and storing as multiplying: more of them per CU
+    const long long tiles96 = (long long)((M + 95) / 96) * ((N + 127) / 128);
+    if (wide_ok && split <= 1 && single_gather && !hook_env("NCX_MAIN_CFG")) {
+        // x_v of the MUTAN producer at configs[2]: 12 800 x 360 outputs = 402 tiles of 96 x 128 = 1.57 rounds of the one-per-CU slots (the second
+        // round 57 % full); 160-row tiles: 240 workgroups, ONE round
+        const long long cus = num_cus(), tiles160 = (long long)((M + 159) / 160) * ((N + 127) / 128);
+        const double e96 = (double)tiles96 / (double)(((tiles96 + cus - 1) / cus) * cus), e160 = (double)tiles160 / (double)(((tiles160 + cus - 1) / cus) * cus);
+        if (tiles160 * 10 >= cus * 7 && e160 > e96 + 0.1) return 3;
+    }
+    int cfg = (split <= 1 && tiles96 * 10 >= (long long)num_cus() * 9) ? 2 : 0;
+    if (const char* e = hook_env("NCX_MAIN_CFG")) cfg = atoi(e);       // experiment hook (NCX_EXPERIMENT=1)
+    return cfg >= 1 && cfg <= 3 ? cfg : 0;
+}
+
+// W: the epilogue the kernels are compiled with (AsIs: the standard one; WithRowMap: permuted rows -- the same choice of tile for a shape, so
+// the two forms of the answer-embedding gradient add every element's products in one order)
 template <class C> using AsIs = C;
 template <template <class> class W>
 static int main_forward_chain(MainArgs& a, hipStream_t s) {
     long long T = 0;
     for (int i = 0; i < a.nseg; ++i) T += (a.seg[i].klen + MF_BK - 1) / MF_BK;
-    if (main_short_form(a.M, a.N, T, a.split))
-        return launch_main_fwd<W<MainCfg3>>(a, s);          // a workgroup that short spends as long starting and storing as multiplying: more of them per CU
-    const long long tiles96 = (long long)((a.M + 95) / 96) * ((a.N + 127) / 128);
     constexpr bool wide_ok = W<MainCfgW>::EPI != EPI_ROWMAP;      // (the 160-row tile leaves no LDS behind its staged tile for the row table)
-    if constexpr (wide_ok)
-    if (a.split <= 1 && a.nseg == 1 && a.seg[0].kind == MK_GATHER && !hook_env("NCX_MAIN_CFG")) {
-        // x_v of the MUTAN producer at configs[2]: 12 800 x 360 outputs = 402 tiles of 96 x 128 = 1.57 rounds of the one-per-CU slots (the second
-        // round 57 % full); 160-row tiles: 240 workgroups, ONE round
-        const long long cus = num_cus(), tiles160 = (long long)((a.M + 159) / 160) * ((a.N + 127) / 128);
-        const double e96 = (double)tiles96 / (double)(((tiles96 + cus - 1) / cus) * cus), e160 = (double)tiles160 / (double)(((tiles160 + cus - 1) / cus) * cus);
-        if (tiles160 * 10 >= cus * 7 && e160 > e96 + 0.1) return launch_main_fwd<W<MainCfgW>>(a, s);
-    }
-    int cfg = (a.split <= 1 && tiles96 * 10 >= (long long)num_cus() * 9) ? 2 : 0;
-    if (const char* e = hook_env("NCX_MAIN_CFG")) cfg = atoi(e);       // experiment hook (NCX_EXPERIMENT=1)
-    if (cfg == 3) {
+    switch (main_chain_form(a.M, a.N, T, a.split, a.nseg == 1 && a.seg[0].kind == MK_GATHER, wide_ok)) {
+    case 4: return launch_main_fwd<W<MainCfg3>>(a, s);
+    case 3:
         if constexpr (wide_ok) return launch_main_fwd<W<MainCfgW>>(a, s);
         else return NCX_E_FLAGS;
+    case 1: return launch_main_fwd<W<MainCfg1>>(a, s);
+    case 2: return launch_main_fwd<W<MainCfg2>>(a, s);
+    default: return launch_main_fwd<W<MainCfg0>>(a, s);
     }
-    if (cfg == 1) return launch_main_fwd<W<MainCfg1>>(a, s);
-    if (cfg == 2) return launch_main_fwd<W<MainCfg2>>(a, s);
-    return launch_main_fwd<W<MainCfg0>>(a, s);
 }
 
 // Measured inside the training step at configs[1] (B = 512: 256 tiles of 96 x 128): 338 us with one 96 x 128 workgroup per CU,

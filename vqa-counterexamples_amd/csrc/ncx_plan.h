@@ -24,6 +24,10 @@ struct StepRoutes {
     bool dw1ak_on_tn8(bool side) const { return tn8 && emb_nt && !side; }
 };
 StepRoutes routes(const ncx_dims& d);
+// linear_1 on the fused forward kernel (ncx_forward.hip), with the experiment hooks applied: the two v segments as one pass with the
+// per-triplet fold, and the pairwise distance computed by that kernel.  forward_impl launches by it, NCX_QUERY_FWD_ROUTE reports it.
+struct FwdRoute { bool vfold, dist_in_fold, dist_in_main; };
+FwdRoute forward_route(const ncx_dims& d, const StepRoutes& r);
 
 // The GEMMs of one step, so that ws_layout and forward/backward agree on split-K slab sizes.
 struct GemmUse { int form; long long M, N, ksteps; bool allow96; GemmPlan plan; long long slab_elems; long long tiles; long long wgs; };

@@ -409,8 +409,18 @@ DW1_TN_FORMS = ("grouped", "k_dw_tn8", "k_dw_tn8_x6")
 NCX_QUERY_FUSED_ADAM = 33       # include/neuralcx.h
 
 
+NCX_QUERY_FWD_ROUTE = 34        # include/neuralcx.h
+FWD_ENGINES = ("generic", "chain", "fold", "bf16")
+FWD_CHAIN_FORMS = ("48x128", "96x64", "96x128", "160x128", "64x64")
+
+
 def plan_query(d, name):
     out = (C.c_int32 * 6)()
+    if name == "FWD_ROUTE":
+        check(lib().ncx_plan_query(C.byref(d), NCX_QUERY_FWD_ROUTE, out), "ncx_plan_query")
+        return dict(engine=out[0], engine_name=FWD_ENGINES[out[0]], tile=out[1],
+                    tile_name=FWD_CHAIN_FORMS[out[1]] if out[0] == 1 else ("%dx64" % out[1] if out[0] == 2 else None),
+                    split=out[2], dist_in_main=bool(out[3]), hidden_engine=out[4], hidden_split=out[5])
     if name == "FUSED_ADAM":
         check(lib().ncx_plan_query(C.byref(d), NCX_QUERY_FUSED_ADAM, out), "ncx_plan_query")
         return dict(fused=bool(out[0]), passengers=out[1])

@@ -229,6 +229,17 @@ def ws_de_perm_view(d: NcxDims, ws: torch.Tensor) -> torch.Tensor:
     return ws[base + off.value: base + off.value + nbytes.value].view(torch.int32)
 
 
+def ws_h_view(d: NcxDims, ws: torch.Tensor, l: int) -> torch.Tensor:
+    """fp32 view [B*K, H] of the post-dropout activations of linear_l (l = 1 .. L) that the last forward left in the workspace
+    (NCX_WS_H1 / NCX_WS_H2 / NCX_WS_H3): what the tests compare element by element."""
+    if not 1 <= l <= d.L:
+        raise _lib.NcxError("ws_h_view: layer %d of a model with %d" % (l, d.L))
+    off, nbytes = C.c_size_t(0), C.c_size_t(0)
+    _lib.check(_lib.lib().ncx_ws_region(C.byref(d), (2, 5, 6)[l - 1], C.byref(off), C.byref(nbytes)), "ncx_ws_region")
+    base = (ws.data_ptr() + 255) // 256 * 256 - ws.data_ptr()
+    return ws[base + off.value: base + off.value + nbytes.value].view(torch.float32).view(d.B * d.K, d.H)
+
+
 def ranking_loss(scores: torch.Tensor, gt: torch.Tensor, scale: float = 0.0, want_grad: bool = True):
     """Listwise softmax-CE / B + rank of the ground truth + Recall@1/@5 hit counts in one pass."""
     B, K = scores.shape
