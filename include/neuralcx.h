@@ -221,6 +221,10 @@ int ncx_backward_phase(const ncx_dims* d, const ncx_inputs* in, const ncx_params
 #define NCX_WS_DE_PERM 4
 #define NCX_WS_H2 5     /* diagnostics / tests: post-dropout activations of linear_2, [B*K, H] (valid after ncx_forward; size 0 when L < 2) */
 #define NCX_WS_H3 6     /* ... of linear_3 (size 0 when L < 3) */
+/* diagnostics / tests: gradient of linear_2's pre-activations, [B*K, H], valid after ncx_backward when L == 2: the backward's two
+ * ping-pong buffers then hold dpre_2 and dpre_1 (NCX_WS_DPRE1) side by side.  Size 0 for every other L (L == 1 has no such layer; the
+ * region is kept to the one depth whose hidden-layer products the tests judge alone). */
+#define NCX_WS_DPRE2 7
 int ncx_ws_region(const ncx_dims* d, int32_t which, size_t* offset, size_t* bytes);
 
 /* NCX_F_FUSED_TAIL: replaces, in one pass over h_L, the tail of ncx_forward (`out`, cx.py:327), ncx_loss_rank

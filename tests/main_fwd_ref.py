@@ -73,6 +73,7 @@ class MainFwdRef:
         ws = np.concatenate([sl("v_orig", d.dv), sl("q_emb", d.dq), sl("z_orig", d.dz), sl("a_emb_gt", d.da)], 1)
         self.b1 = _f64(params["linear_1.bias"])
         self.sh = xs @ ws.T + self.b1                                                     # [B, H]
+        self.xs = xs                                                                      # (the shared row: tests/main_bwd_ref.py)
         # the candidate row, segment by segment
         dist = np.sqrt(((v_o[:, None, :] - v_k + 1e-6) ** 2).sum(-1, keepdims=True)) if spec["v_dist"] else np.zeros((B, K, 1))
         rank = np.broadcast_to(np.eye(K), (B, K, K)) if spec["v_rank"] else _f64(batch["v_rank"])

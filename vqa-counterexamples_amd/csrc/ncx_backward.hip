@@ -871,7 +871,8 @@ int ncx_backward_phase(const ncx_dims* dp, const ncx_inputs* in, const ncx_param
 int ncx_ws_region(const ncx_dims* dp, int32_t which, size_t* offset, size_t* bytes) {
     if (check_dims(dp) != NCX_OK) return NCX_E_DIMS;
     if (!offset || !bytes) return NCX_E_NULL;
-    if (which != NCX_WS_DGT && which != NCX_WS_H1 && which != NCX_WS_DPRE1 && which != NCX_WS_DE_PERM && which != NCX_WS_H2 && which != NCX_WS_H3) return NCX_E_FLAGS;
+    if (which != NCX_WS_DGT && which != NCX_WS_H1 && which != NCX_WS_DPRE1 && which != NCX_WS_DE_PERM && which != NCX_WS_H2 && which != NCX_WS_H3 &&
+        which != NCX_WS_DPRE2) return NCX_E_FLAGS;
     const StepRoutes r = routes(*dp);
     const WsLayout w = ws_layout(*dp, r);
     if (which == NCX_WS_DE_PERM) {      // (size 0: the shape or the variant keeps the full form of the product)
@@ -881,6 +882,10 @@ int ncx_ws_region(const ncx_dims* dp, int32_t which, size_t* offset, size_t* byt
     if (which == NCX_WS_H2 || which == NCX_WS_H3) {      // (size 0: the model has no such layer)
         const int l = which == NCX_WS_H2 ? 2 : 3;
         *offset = w.h[l - 1]; *bytes = dp->L >= l ? (size_t)dp->B * dp->K * dp->H * 4 : 0;
+        return NCX_OK;
+    }
+    if (which == NCX_WS_DPRE2) {      // (L == 2: dpre_2 stays in the first ping-pong buffer, dpre_1 goes to the second)
+        *offset = w.dpre[0]; *bytes = dp->L == 2 ? (size_t)dp->B * dp->K * dp->H * 4 : 0;
         return NCX_OK;
     }
     if (which == NCX_WS_H1 || which == NCX_WS_DPRE1) {

@@ -342,12 +342,14 @@ __global__ __launch_bounds__(TN8_T, 1) void k_dw_tn8(const Tn8Args a) {
 
 // ---- the same launch on the bf16 matrix path with fp32-grade operands (NCX_F_X6; not the default) -----------------------------------------
 // Every operand element is cut into three bf16 values by truncation, x = x1 + x2 + x3 EXACTLY (x1 = x & 0xFFFF0000, x2 = (x - x1) & 0xFFFF0000,
-// x3 = x - x1 - x2; every residual is exact in fp32), when it is stored to LDS (once per element, as in the fp32 kernel); the six products
-// a1 x1 + (a1 x2 + a2 x1) + (a1 x3 + a2 x2 + a3 x1) run on v_mfma_f32_16x16x32_bf16 with fp32 accumulation (products of bf16 values are exact in
-// fp32): what is dropped is 2^-24 relative, the rounding error of one fp32 operation.  6 MFMAs of 16 cycles replace 8 of 32 per 16 x 16 x 32
+// x3 = x - x1 - x2; every residual is exact in fp32), when it is stored to LDS (once per element, as in the fp32 kernel); the eight products
+// a1 x1 + (a1 x2 + a2 x1) + (a1 x3 + a2 x2 + a3 x1) + (a2 x3 + a3 x2) run on v_mfma_f32_16x16x32_bf16 with fp32 accumulation (products of bf16 values are
+// exact in fp32), a1 x1 on one accumulator and the seven small ones on a second, added when the partial tile leaves: what is dropped is a3 x3, 2^-32
+// relative.  (With six products on one accumulator the form was 2.2 - 2.5 x the fp32 kernel's error on the a_emb lesion's operands:
+// profiles/main_bwd_edges.json.)  8 MFMAs of 16 cycles replace 8 of 32 per 16 x 16 x 32
 // block.  LDS holds three bf16 planes per operand in the global [k][m] layout; fragments come from ds_read_b64_tr_b16 (hardware transpose);
 // row pitches = 32 mod 256 bytes.  Measured on the dGt problem alone (tools/mb/mb_tn.hip): 80 us against 109, same error against fp64 (1.0e-9 on
-// values of 1.9e-3); the kernel is then bound by LDS + global-load return traffic (~3 000 cycles per k-step against 1 536 of MFMA), not by the
+// values of 1.9e-3); the kernel is then bound by LDS + global-load return traffic (~3 000 cycles per k-step against 1 536 of MFMA with six products, 2 048 with eight), not by the
 // matrix cores.  Pieces, slab slots and the reduction are those of k_dw_tn8; the block mapping inside a wave is the plain one (block (i, j) =
 // rows wm0 + 16 i .., columns wn0 + 16 j ..), so the summation order differs from the fp32 kernel's: results agree to fp32 rounding, not bitwise.
 typedef __bf16 tn_bf16x8 __attribute__((ext_vector_type(8)));
@@ -376,11 +378,11 @@ __global__ __launch_bounds__(TN8_T, 1) void k_dw_tn8_x6(const Tn8Args a) {
     const int nseg = s_nseg, V = s_vtot;
     if (V == 0) return;
 
-    f32x4 acc[4][2];
+    f32x4 acc[4][2], acl[4][2];                  // a1 x1 | the seven small plane products (mfma16)
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 2; ++j) { acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f}; acl[i][j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 
     // ---- loader: as in k_dw_tn8 ---------------------------------------------------------------------------------------------------------
     const int arow = tid >> 6, aq = tid & 63;
@@ -522,24 +524,30 @@ __global__ __launch_bounds__(TN8_T, 1) void k_dw_tn8_x6(const Tn8Args a) {
                 bf[p][j] = __builtin_bit_cast(tn_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
             }
     };
-    // the 12 MFMAs of block row i: the two column blocks alternate (a dependent MFMA is two issues away); small terms first
-    auto mfma12 = [&](const tn_bf16x8 (&af)[3], const tn_bf16x8 (&bf)[3][2], f32x4 (&c)[2]) __attribute__((always_inline)) {
+    // the 16 MFMAs of block row i: the two column blocks alternate (a dependent MFMA is two issues away).  The seven small plane products go
+    // to the accumulator `lo`, a1 x1 alone to `c`: the running sum takes ONE rounding per k-step at its full magnitude instead of six, and
+    // a2 x3 + a3 x2 (up to 2^-22 of a term, with the term's sign under truncation) are no longer dropped -- only a3 x3 (2^-32) is.
+    auto mfma16 = [&](const tn_bf16x8 (&af)[3], const tn_bf16x8 (&bf)[3][2], f32x4 (&c)[2], f32x4 (&lo)[2]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) c[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bf[2][j], c[j], 0, 0, 0);
+        for (int j = 0; j < 2; ++j) lo[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bf[2][j], lo[j], 0, 0, 0);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) c[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bf[1][j], c[j], 0, 0, 0);
+        for (int j = 0; j < 2; ++j) lo[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[2], bf[1][j], lo[j], 0, 0, 0);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) c[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[2], bf[0][j], c[j], 0, 0, 0);
+        for (int j = 0; j < 2; ++j) lo[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bf[2][j], lo[j], 0, 0, 0);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) c[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bf[1][j], c[j], 0, 0, 0);
+        for (int j = 0; j < 2; ++j) lo[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bf[1][j], lo[j], 0, 0, 0);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) c[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bf[0][j], c[j], 0, 0, 0);
+        for (int j = 0; j < 2; ++j) lo[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[2], bf[0][j], lo[j], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) lo[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bf[1][j], lo[j], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) lo[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bf[0][j], lo[j], 0, 0, 0);
 #pragma unroll
         for (int j = 0; j < 2; ++j) c[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bf[0][j], c[j], 0, 0, 0);
     };
     auto pin = [&]() __attribute__((always_inline)) {
 #pragma unroll
-        for (int q = 0; q < 12; ++q) {
+        for (int q = 0; q < 16; ++q) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
@@ -571,7 +579,7 @@ __global__ __launch_bounds__(TN8_T, 1) void k_dw_tn8_x6(const Tn8Args a) {
             for (int rg = 0; rg < 4; ++rg) {
                 const int row = wm0 + 16 * i + 4 * lk + rg;
 #pragma unroll
-                for (int j = 0; j < 2; ++j) { slot[row * BN + wn0 + 16 * j + li] = acc[i][j][rg]; acc[i][j][rg] = 0.f; }
+                for (int j = 0; j < 2; ++j) { slot[row * BN + wn0 + 16 * j + li] = acc[i][j][rg] + acl[i][j][rg]; acc[i][j][rg] = 0.f; acl[i][j][rg] = 0.f; }
             }
     };
     auto step = [&](auto par_c, auto mode_c, int v) __attribute__((always_inline)) {
@@ -581,16 +589,16 @@ __global__ __launch_bounds__(TN8_T, 1) void k_dw_tn8_x6(const Tn8Args a) {
         // block row 3 of step v - 1 (zeros at the start and after a flush) over the first reads of this buffer
         read_b(PAR, bfr[PAR]);
         read_a(PAR, 0, afA);
-        mfma12(afB, bfr[PAR ^ 1], acc[3]);
+        mfma16(afB, bfr[PAR ^ 1], acc[3], acl[3]);
 #pragma unroll
-        for (int q = 0; q < 12; ++q) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 2, 0); }
+        for (int q = 0; q < 16; ++q) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 2, 0); }
         __builtin_amdgcn_sched_barrier(0);
-        read_a(PAR, 1, afB); stash(SS{}, MD{}, PAR ^ 1, 0, 2); mfma12(afA, bfr[PAR], acc[0]); pin();
-        read_a(PAR, 2, afA); stash(SS{}, MD{}, PAR ^ 1, 2, NA + 1); mfma12(afB, bfr[PAR], acc[1]); pin();
-        read_a(PAR, 3, afB); issue_fast(SS{}); mfma12(afA, bfr[PAR], acc[2]); pin();       // (virtual step v + 3: the loop made the state valid for it)
+        read_a(PAR, 1, afB); stash(SS{}, MD{}, PAR ^ 1, 0, 2); mfma16(afA, bfr[PAR], acc[0], acl[0]); pin();
+        read_a(PAR, 2, afA); stash(SS{}, MD{}, PAR ^ 1, 2, NA + 1); mfma16(afB, bfr[PAR], acc[1], acl[1]); pin();
+        read_a(PAR, 3, afB); issue_fast(SS{}); mfma16(afA, bfr[PAR], acc[2], acl[2]); pin();       // (virtual step v + 3: the loop made the state valid for it)
         __syncthreads();
         if (v + 1 == vend_c) {                           // the piece ends here (uniform): block row 3, partial tile out, next piece
-            mfma12(afB, bfr[PAR], acc[3]);
+            mfma16(afB, bfr[PAR], acc[3], acl[3]);
 #pragma unroll
             for (int p = 0; p < 3; ++p) afB[p] = zero8;
             flush();

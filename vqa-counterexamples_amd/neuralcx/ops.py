@@ -240,6 +240,17 @@ def ws_h_view(d: NcxDims, ws: torch.Tensor, l: int) -> torch.Tensor:
     return ws[base + off.value: base + off.value + nbytes.value].view(torch.float32).view(d.B * d.K, d.H)
 
 
+def ws_dpre_view(d: NcxDims, ws: torch.Tensor, l: int) -> torch.Tensor:
+    """fp32 view [B*K, H] of the gradient of linear_l's pre-activations that the last backward left in the workspace: l = 1
+    (NCX_WS_DPRE1, any L) or l = 2 (NCX_WS_DPRE2, a model with L == 2 only): what the weight-gradient kernels were handed."""
+    if l not in (1, 2) or (l == 2 and d.L != 2):
+        raise _lib.NcxError("ws_dpre_view: layer %d of a model with %d" % (l, d.L))
+    off, nbytes = C.c_size_t(0), C.c_size_t(0)
+    _lib.check(_lib.lib().ncx_ws_region(C.byref(d), (3, 7)[l - 1], C.byref(off), C.byref(nbytes)), "ncx_ws_region")
+    base = (ws.data_ptr() + 255) // 256 * 256 - ws.data_ptr()
+    return ws[base + off.value: base + off.value + nbytes.value].view(torch.float32).view(d.B * d.K, d.H)
+
+
 def ranking_loss(scores: torch.Tensor, gt: torch.Tensor, scale: float = 0.0, want_grad: bool = True):
     """Listwise softmax-CE / B + rank of the ground truth + Recall@1/@5 hit counts in one pass."""
     B, K = scores.shape
