@@ -80,7 +80,8 @@ template <class CFG> struct WithMlbEpi : CFG { static constexpr int EPI = EPI_ML
 template <class CFG> struct WithRowMap : CFG { static constexpr int EPI = EPI_ROWMAP; };
 // ADAM (the answer-embedding gradient, ncx_backward_adam): nothing after this product reads a weight and every other gradient is final when it is
 // launched, so the launch is also the optimiser step (args.adam, ncx_adam.h).  A tile's epilogue stores its piece of the gradient as always, then
-// updates the parameter and the two moments of the same elements (each is produced exactly once: split == 1); the workgroups
+// updates the parameter and the two moments of the same elements (each is produced exactly once: split == 1) from values it requested before
+// the tile was staged, and its epilogue loop is unrolled over the thread's four pieces; the workgroups
 // [adam.pass_at, adam.pass_at + adam.n_pass) of the grid carry no tile: they update a slice of the rest of the flat buffer, HBM traffic beside
 // short latency-bound tiles.  The workgroup ids on either side of the passengers are the tile ids of the plain form, in order.
 template <class CFG> struct WithAdam : CFG { static constexpr bool ADAM = true; };
@@ -1056,7 +1057,36 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
     if constexpr (NSEG > 2) seg_pass(IntC<2>{});
     if constexpr (NSEG > 3) seg_pass(IntC<3>{});
     if constexpr (NSEG > 4) seg_pass(IntC<4>{});
+    // ADAM: a thread's NP epilogue pieces f = tid + i MT are known at compile time, so the parameter and the two moments of all of them are
+    // requested HERE, before the accumulators go through LDS (3 NP 16-byte loads, 48 registers: the loader's are dead), and the epilogue finds
+    // them landed.  Loaded inside the rolled loop, each piece waited for its own three loads before it could store: four serial HBM round
+    // trips at the end of every workgroup (DESIGN S5d).  pf_row[i]: the OUTPUT row of piece i -- under the row map read from the table in
+    // global memory by the thread itself (the LDS copy lies behind the barrier); the prefetch and every store of the piece use this one value.
+    constexpr int NP = CFG::ADAM ? BM * (BN / 4) / MT : 1;
+    static_assert(!CFG::ADAM || (BM * (BN / 4) % MT == 0 && NP == 4), "ADAM: four 16-byte pieces per thread (64 x 64 tiles, 256 threads)");
+    int pf_row[NP];
+    f32x4 pf_p[NP], pf_m[NP], pf_v[NP];
+    if constexpr (CFG::ADAM) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int rc = min(m0 + (tid + i * MT) / (BN / 4), M - 1);      // (rows beyond the matrix: clamped like the loader's, never used)
+            if constexpr (ROWMAP) pf_row[i] = ((giptr)args.seg[0].idx)[rc];
+            else pf_row[i] = rc;
+        }
+    }
     if constexpr (!X6) mfma(afB, bfB);                   // the last sub-step of the last segment (X6: every segment finishes its own last block row)
+    if constexpr (CFG::ADAM) {
+        // A piece the loop below does not update from these registers (a row beyond M, a quad at or over the right edge: n + 3 >= N) requests the
+        // last whole quad of a row of the matrix instead: inside the buffer (N >= 4: launch_main_fwd_adam), never read.
+        const AdamFuse& ad = args.adam;
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int n = n0 + 4 * ((tid + i * MT) % (BN / 4));
+            const long long off = (long long)pf_row[i] * args.ldo + (n + 3 < N ? n : N - 4);
+            pf_p[i] = *(gf4ptr)(ad.p + off); pf_m[i] = *(gf4ptr)(ad.m + off); pf_v[i] = *(gf4ptr)(ad.v + off);
+        }
+        __builtin_amdgcn_sched_barrier(0);               // (issued before the staging stores below, not between them)
+    }
 
     // ---- epilogue: + Sh[r / K] (+ bias), ReLU, Dropout, store ---------------------------------------------------------
     // Every operand is fetched behind one uniform test per kind (a test per element puts each load in its own basic block:
@@ -1073,7 +1103,8 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
     const EpiArgs& e = args.epi;
     float* const dst = S > 1 ? args.slab + (long long)z * M * N : args.out;      // S > 1: raw partial sums; k_main_fixup runs the epilogue
     const long long ldd = S > 1 ? (long long)N : args.ldo;
-    const bool plain = S > 1 || !(e.rowadd || e.bias || e.relu || e.dropout || e.gate);
+    // (ADAM: no epilogue operand, host-checked -- known here, so the unrolled loop of those forms carries no copy of the operand code)
+    const bool plain = CFG::ADAM || S > 1 || !(e.rowadd || e.bias || e.relu || e.dropout || e.gate);
     // (the row-add operand of piece f + 256 is fetched while piece f is finished: rolled, but never waiting on its own load)
     auto item = [&](int f, int& r, int& n, int& nl) __attribute__((always_inline)) {
         const int rr = f / QR, cq = f - rr * QR;
@@ -1106,7 +1137,7 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
     if (use_add) { add0 = fetch_add(min(tid, LAST_F)); add1 = fetch_add(min(tid + MT, LAST_F)); add2 = fetch_add(min(tid + 2 * MT, LAST_F)); }
     // (the three requests above are in flight while the accumulators go through LDS)
     int orow_v = 0;                                      // ROWMAP: output row of tile row `tid` (in flight with them)
-    if constexpr (ROWMAP) orow_v = ((giptr)args.seg[0].idx)[min(m0 + min(tid, BM - 1), M - 1)];
+    if constexpr (ROWMAP && !CFG::ADAM) orow_v = ((giptr)args.seg[0].idx)[min(m0 + min(tid, BM - 1), M - 1)];
 #pragma unroll
     for (int i = 0; i < WM; ++i)
 #pragma unroll
@@ -1114,19 +1145,19 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
 #pragma unroll
             for (int q = 0; q < 4; ++q) stage[(wm0 + 16 * i + 4 * lk + q) * SP + wn0 + 16 * j + li] = acc[i][j][q];
     int* const orow = (int*)(stage + BM * SP);           // ROWMAP: output row of every tile row, behind the staged tile
-    if constexpr (ROWMAP) {
+    if constexpr (ROWMAP && !CFG::ADAM) {                // (ADAM: every piece has its output row in a register, pf_row)
         static_assert(!ROWMAP || (BM <= MT && (BM * SP + BM) * 4 <= CFG::LDS), "row map: one thread per tile row, table behind the staged tile");
         if (tid < BM) orow[tid] = orow_v;
     }
     __syncthreads();
-#pragma unroll 1
-    for (int f = tid; f < BM * QR; f += MT) {
+    // piece f of the tile; i: its number among the thread's pieces (the ADAM forms: f = tid + i MT, unrolled; otherwise unused)
+    auto piece = [&](const int f, const int i) __attribute__((always_inline)) {
         int r, n, nl;
         const int so = item(f, r, n, nl);
         const f32x4 addv = add0;
         add0 = add1; add1 = add2;
         if (use_add) add2 = fetch_add(min(f + 3 * MT, LAST_F));
-        if (r >= M || n >= N) continue;
+        if (r >= M || n >= N) return;
         f32x4 v = *(const f32x4*)(stage + so);
         const int sh = n - nl;
         if (!plain) {
@@ -1164,10 +1195,11 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
                 if (n + 3 < N) *(f32x4u*)ot = t;
                 else { ot[0] = t[0]; if (n + 1 < N) ot[1] = t[1]; if (n + 2 < N) ot[2] = t[2]; }
             }
-            continue;
+            return;
         }
         float* o = dst + (long long)r * ldd + n;
-        if constexpr (ROWMAP) o = dst + (long long)orow[f / QR] * ldd + n;
+        if constexpr (CFG::ADAM) o = dst + (long long)pf_row[i] * ldd + n;      // (r < M: pf_row[i] is r, or idx[r] under the row map -- the row the prefetch took)
+        else if constexpr (ROWMAP) o = dst + (long long)orow[f / QR] * ldd + n;
         if (n + 3 < N) *(f32x4u*)o = v;
         else { o[0] = v[0]; if (n + 1 < N) o[1] = v[1]; if (n + 2 < N) o[2] = v[2]; }
         if constexpr (CFG::ADAM) {                       // (split == 1, no epilogue operand: host-checked) v is the finished gradient of elements o[0 .. 3]
@@ -1175,7 +1207,7 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
             const long long off = o - dst;
             float* const pp = ad.p + off; float* const pm = ad.m + off; float* const pv = ad.v + off;
             if (n + 3 < N) {
-                f32x4 p4 = *(const f32x4u*)pp, m4 = *(const f32x4u*)pm, v4 = *(const f32x4u*)pv;
+                f32x4 p4 = pf_p[i], m4 = pf_m[i], v4 = pf_v[i];          // requested from these addresses before the tile was staged
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) {
                     float pj = p4[jj], mj = m4[jj], vj = v4[jj];
@@ -1193,6 +1225,13 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
                 }
             }
         }
+    };
+    if constexpr (CFG::ADAM) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) piece(tid + i * MT, i);
+    } else {
+#pragma unroll 1
+        for (int f = tid; f < BM * QR; f += MT) piece(f, 0);
     }
     stamp(8);
     if (stamps && tid == 0) stamps[15] = __builtin_amdgcn_s_memrealtime();
@@ -1323,6 +1362,7 @@ template <class CFG>
 static inline int launch_main_fwd_adam(MainArgs& a, int n_pass, int pass_at_hint, hipStream_t s) {
     static_assert(CFG::ADAM && CFG::EPI != EPI_MLB && !CFG::X6, "the answer-embedding gradient's forms");
     if (a.nseg != 2 || a.M < 1 || a.N < 1 || a.split > 1 || a.dist_out || !a.out) return NCX_E_FLAGS;
+    if (a.N < 4) return NCX_E_DIMS;                   // (the epilogue's clamped prefetch reads the last whole quad of a row; check_dims keeps da >= 4)
     for (int i = 0; i < 2; ++i) if (!main_fwd_operand_ok(a.seg[i].klen)) return NCX_E_DIMS;
     const EpiArgs& e = a.epi;
     if (e.rowadd || e.bias || e.relu || e.dropout || e.gate) return NCX_E_FLAGS;

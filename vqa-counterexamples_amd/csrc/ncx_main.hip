@@ -76,7 +76,8 @@ int main_forward_rowmap(MainArgs& a, hipStream_t s) {
     return main_forward_chain<WithRowMap>(a, s);
 }
 
-// One passenger per CU: the tiles keep their three-per-CU slots and every CU's share of the tail streams beside them.
+// One passenger per CU: every CU's share of the tail streams beside its tiles, in one of its three workgroup slots while it runs (DESIGN 5d;
+// 512 and 1024 passengers measured slower in front of the tiles: 64.5 and 68.3 us against 62.4).
 // Experiment hooks: NCX_ADAM_PASS (their number), NCX_ADAM_PASS_AT (the tile workgroups dispatched before them; negative: all).
 int main_adam_passengers() {
     if (const char* e = hook_env("NCX_ADAM_PASS")) { const int n = atoi(e); if (n > 0) return n; }
@@ -87,9 +88,11 @@ int main_forward_adam(MainArgs& a, bool rowmap, hipStream_t s) {
     long long T = 0;
     for (int i = 0; i < a.nseg; ++i) T += (a.seg[i].klen + MF_BK - 1) / MF_BK;
     if (!main_short_form(a.M, a.N, T, a.split)) return NCX_E_FLAGS;
-    // behind the first round of tiles (three per CU): they start as the first tiles retire and stream under the rest -- 67.6 us against 71.9
-    // behind all tiles at configs[1]; a grid of one round or less has them last
-    int at = 3 * num_cus();
+    // in FRONT of the tiles: the passengers stream while the first round of tiles is in its k loop, when HBM is idle; behind the first round
+    // (three per CU, the earlier default) they start as the first tiles retire, into the burst of the first round's epilogues.  At configs[1],
+    // with the epilogue's loads issued ahead: 62.4 us in front, 64.3 behind 256 tiles, 68.2 behind 512, 70.1 behind 768, 72.3 behind all
+    // (profiles/adam_prefetch_bench.json)
+    int at = 0;
     if (const char* e = hook_env("NCX_ADAM_PASS_AT")) at = atoi(e);
     const int np = main_adam_passengers();
     return rowmap ? launch_main_fwd_adam<WithAdam<WithRowMap<MainCfg3>>>(a, np, at, s) : launch_main_fwd_adam<WithAdam<MainCfg3>>(a, np, at, s);
