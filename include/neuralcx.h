@@ -518,6 +518,19 @@ int ncx_gru_train_forward_flags(const int32_t* wids, int32_t B, int32_t T, const
 int ncx_gru_train_backward(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t dim_emb, int32_t dim_q,
                            const float* packed_t, void* workspace, size_t workspace_bytes, const float* dq_out,
                            float* dW_ih, float* dW_hh, float* db_ih, float* db_hh, float* dE /*nullable*/, void* stream);
+/* ncx_gru_train_backward with `flags`: 0 (the same call, the same launches, the same bits) or NCX_F_X6, which moves the matrix products of
+ * the backward that ncx_gru_bwd_form names onto the bf16 matrix path with three-plane operands (csrc/ncx_gru_train_x6.hip): every operand
+ * element is cut into three exact bf16 planes on its way to LDS, accumulation stays fp32, results agree with the fp32 kernels to fp32
+ * rounding, not bitwise.  The packs, the workspace, its size and the stash layout are unchanged, so either form consumes whichever stash
+ * the forward left (fp32 or X6 forward).  Still no atomics: bit-identical from run to run.  Any other `flags` returns -1 before any
+ * launch or pointer use. */
+int ncx_gru_train_backward_flags(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t dim_emb, int32_t dim_q,
+                                 const float* packed_t, uint32_t flags, void* workspace, size_t workspace_bytes, const float* dq_out,
+                                 float* dW_ih, float* dW_hh, float* db_ih, float* db_hh, float* dE /*nullable*/, void* stream);
+/* Host only, no launch: which products of ncx_gru_train_backward_flags take their X6 kernel for these dims under `flags`, as a bit mask:
+ * bit 0 the reverse sweep (dh_{t-1} = dGh_t . W_hh), bit 1 dX = dGx . W_ih, bit 2 dW_hh, bit 3 dW_ih.  0 under flags 0; -1 = dims or
+ * flags refused. */
+int ncx_gru_bwd_form(int32_t B, int32_t T, int32_t dim_emb, int32_t dim_q, uint32_t flags);
 
 /* ---- the two-layer LSTM question encoder: seq2vec arch `2-lstm` (csrc/ncx_lstm.hip) ------------------------------------------------
  * Takes the role of TwoLSTM.forward in eval mode (seq2vec.py:48-76).  Forward only; gate order i, f, g, o as torch.nn.LSTM:

@@ -9,7 +9,10 @@ HIP events around --steps calls after --warmup calls; --repeats windows per path
 window and the spread (max - min) / median of each path.  The packs are built once (they belong to a weight set, not to a step); the
 workspace is allocated once.  Prints one JSON line; --out writes it.
 --x6: three paths alternate window by window, the forward on the fp32 step kernel (x6=False: the yardstick), on the bf16 x 6 step
-kernel (x6=True, NCX_F_X6: the x6_* fields; the backward is the same code on either stash) and torch."""
+kernel (x6=True, NCX_F_X6: the x6_* fields; the backward is the fp32 one on either stash) and torch.
+--x6_bwd (implies --x6): a fourth path in the same alternation, X6 forward + X6 backward (ops.gru_train_backward x6=True: the x6b_* fields;
+x6b_speedup_vs_x6 compares it with X6 forward + fp32 backward of the same run).
+--steps-only N --path {fp32,x6fwd,x6}: N steps of that one path on the --kind length set and nothing else (the run a kernel trace wraps)."""
 import argparse
 import json
 import os
@@ -35,8 +38,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--x6", action="store_true", help="time the forward on the bf16 x 6 step kernel beside the fp32 one")
+    ap.add_argument("--x6_bwd", action="store_true", help="also time X6 forward + X6 backward (NCX_F_X6 on ncx_gru_train_backward_flags)")
+    ap.add_argument("--steps-only", type=int, default=0, help="run this many steps of --path on --kind and exit (for a kernel trace)")
+    ap.add_argument("--path", default="x6", choices=("fp32", "x6fwd", "x6"))
+    ap.add_argument("--kind", default="all26", choices=("all26", "uniform", "vqa"))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.x6 = a.x6 or a.x6_bwd
     assert torch.cuda.is_available(), "bench_gru_train.py needs the MI355X"
     B, T, de, dq, V = a.batch, 26, 620, 2400, 10000
     torch.manual_seed(1)
@@ -66,6 +74,16 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / a.steps
 
+    if a.steps_only:
+        w, _ = make(a.kind)
+        for _ in range(a.steps_only):
+            ops.gru_train_forward(w, gw, ws, x6=a.path != "fp32")
+            ops.gru_train_backward(w, gw, ws, dq_out, x6=a.path == "x6")
+        torch.cuda.synchronize()
+        ops.check_gru_ids(device=w.device)
+        print(json.dumps(dict(steps_only=a.steps_only, path=a.path, kind=a.kind, bwd_form=ops.gru_bwd_form(de, dq, B, T, x6=a.path == "x6"))))
+        return
+
     res = dict(metric="gru_train_ms", shape=dict(B=B, T=T, dim_emb=de, dim_q=dq), steps=a.steps, warmup=a.warmup, repeats=a.repeats,
                mflop_per_valid_token=flop_token / 1e6, workspace_bytes=ws.numel() - 256, device=torch.cuda.get_device_name(0), cases={})
     for kind in ("all26", "uniform", "vqa"):
@@ -73,11 +91,15 @@ def main():
 
         def hip_step():
             ops.gru_train_forward(w, gw, ws, x6=False if a.x6 else None)
-            return ops.gru_train_backward(w, gw, ws, dq_out)
+            return ops.gru_train_backward(w, gw, ws, dq_out, x6=False if a.x6 else None)
 
         def x6_step():
             ops.gru_train_forward(w, gw, ws, x6=True)
-            return ops.gru_train_backward(w, gw, ws, dq_out)
+            return ops.gru_train_backward(w, gw, ws, dq_out, x6=False)
+
+        def x6b_step():
+            ops.gru_train_forward(w, gw, ws, x6=True)
+            return ops.gru_train_backward(w, gw, ws, dq_out, x6=True)
 
         def torch_step():       # the path GRUEncoder.forward takes with use_hip_train off, and its backward
             out, _ = enc.gru(enc.embedding(w))
@@ -85,11 +107,13 @@ def main():
             q = out[torch.arange(B, device=w.device), last]
             return torch.autograd.grad(q, params, dq_out)
 
-        t_hip, t_x6, t_torch = [], [], []
+        t_hip, t_x6, t_x6b, t_torch = [], [], [], []
         for _ in range(a.repeats):
             t_hip.append(window(hip_step))
             if a.x6:
                 t_x6.append(window(x6_step))
+            if a.x6_bwd:
+                t_x6b.append(window(x6b_step))
             t_torch.append(window(torch_step))
         g, ref = hip_step(), torch_step()
         ops.check_gru_ids(device=w.device)
@@ -107,6 +131,12 @@ def main():
             err6 = {k: float((g6[k] - r).abs().max() / r.abs().max()) for k, r in zip(("E", "w_ih", "w_hh", "b_ih", "b_hh"), ref)}
             res["cases"][kind].update(x6_ms=m6, x6_ms_windows=t_x6, x6_spread=(max(t_x6) - min(t_x6)) / m6, x6_speedup_vs_fp32=mh / m6,
                                       x6_tflops_valid=flops / m6 / 1e9, x6_max_rel_diff_vs_torch=err6)
+        if a.x6_bwd:
+            m6b, g6b = float(np.median(t_x6b)), x6b_step()
+            err6b = {k: float((g6b[k] - r).abs().max() / r.abs().max()) for k, r in zip(("E", "w_ih", "w_hh", "b_ih", "b_hh"), ref)}
+            res["cases"][kind].update(x6b_ms=m6b, x6b_ms_windows=t_x6b, x6b_spread=(max(t_x6b) - min(t_x6b)) / m6b, x6b_speedup_vs_x6=m6 / m6b,
+                                      x6b_speedup_vs_fp32=mh / m6b, x6b_tflops_valid=flops / m6b / 1e9, x6b_max_rel_diff_vs_torch=err6b,
+                                      x6b_bwd_form=ops.gru_bwd_form(de, dq, B, T, x6=True))
     line = json.dumps(res)
     print(line)
     if a.out:

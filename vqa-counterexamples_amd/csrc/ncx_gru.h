@@ -55,6 +55,25 @@ __attribute__((visibility("hidden"))) int gru_steps_x6(const int32_t* wids, int 
                                                        const float* packed, const RnnPlan& p, float* ha, float* hb, float* gates, float* q_out,
                                                        hipStream_t s);
 
+// The arguments of the backward's sweep / dX kernel (k_gru_bgemm, ncx_gru_train.hip) and of its X6 form (k_gru_bgemm_x6, ncx_gru_train_x6.hip)
+struct GruBgArgs {
+    const float* gates; const float* hstash; const float* wT;      // wT: WhhT (sweep) or WihT (dX), [rows][kp]
+    const int* perm; const int* lens; const int* n_t; const float* dq_out;
+    const float* dh_in; float* dh_out;                               // dh_t (read), dh_{t-1} (written)
+    float* dG; float* dX;
+    int B, T, t, dq, dqp, de, tiles_m;
+};
+
+// The bf16 x 6 form of rnn_dw(a, gather, false, s) (ncx_gru_train_x6.hip): the same walk in 256 x 64 output tiles
+__attribute__((visibility("hidden"))) hipError_t gru_dw_x6(const RnnDwArgs& a, bool gather, hipStream_t s);
+// The bf16 x 6 forms of k_gru_bgemm's launches: launch a.t of the reverse sweep; dX of all a.T steps (a.wT = WihT)
+constexpr int GRU_B6_WR = 4;                     // wave rows of their tile: 32 GRU_B6_WR rows x 64 columns (ablation: DESIGN 5w)
+__attribute__((visibility("hidden"))) hipError_t gru_sweep_x6(const GruBgArgs& a, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t gru_dx_x6(const GruBgArgs& a, hipStream_t s);
+// Which products of the backward take an X6 kernel under NCX_F_X6 (ncx_gru_bwd_form's bits)
+constexpr int GRU_BWD_SWEEP = 1, GRU_BWD_DX = 2, GRU_BWD_DWHH = 4, GRU_BWD_DWIH = 8;
+constexpr int GRU_BWD_X6 = GRU_BWD_SWEEP | GRU_BWD_DX | GRU_BWD_DWHH | GRU_BWD_DWIH;
+
 __attribute__((visibility("hidden"))) int gru_forward_keep(const int32_t* wids, int B, int T, const float* E, int V1, int dim_emb, int dim_q,
                                                            const float* packed, const RnnPlan& p, float* hstash, float* gates, float* q_out,
                                                            int32_t* bad_id_flag, uint32_t flags, hipStream_t s);

@@ -1,6 +1,6 @@
 // ncx_gru_train.hip -- training the question encoder (GRUEncoder: embedding -> one-layer GRU -> last valid step): the forward that keeps
 // what the backward needs, and backward through time.  ncx_gru_train_workspace_bytes, ncx_gru_packed_t_bytes, ncx_gru_pack_t,
-// ncx_gru_train_forward, ncx_gru_train_backward.
+// ncx_gru_train_forward, ncx_gru_train_backward, their ..._flags forms and ncx_gru_bwd_form.
 //
 // Reference: vqa/models/seq2vec.py -- process_lengths + select_last (11-25) and factory (79-97); what is replaced is torch autograd
 // through nn.Embedding + nn.GRU + the last-step selection.  With len_b, perm, n_t of ncx_gru.hip, for t from len_b - 1 down to 0:
@@ -21,6 +21,9 @@
 //                       Both share their 64 x 64 tile loop with the LSTM's sweep (rnn_nt_tile, ncx_rnn.h).
 //   k_rnn_dw            (ncx_rnn.hip) dW_hh = sum_{t >= 1} dGh_t^T h_{t-1} (stash rows, the walk skips the da_n block),
 //                       dW_ih = sum_t dGx_t^T E[wid] (gathered rows): TN products whose contraction walks (t, row < n_t[t]).
+//   NCX_F_X6            (ncx_gru_train_backward_flags; ncx_gru_train_x6.hip) the four products above on the bf16 matrix path with three-plane
+//                       operands: k_gru_bgemm_x6<false> / <true> for the sweep and dX, k_gru_dw_x6 for the two walks.  The launches, what
+//                       they read and write and everything else in this plan stay as they are.
 //   k_gru_dbias         column sums of the four blocks over the same ranges (rnn_colsum) -> db_ih, db_hh.
 //   k_rnn_tok, k_rnn_de (ncx_rnn.hip) the word id of every valid pair (or -1); one workgroup per row of E sums the dX rows of its id.
 #include "ncx_gru.h"
@@ -59,13 +62,7 @@ __global__ __launch_bounds__(256) void k_gru_pack_t(const float* __restrict__ w_
     for (int rr = 0; rr < 4; ++rr) packed_t[(size_t)(row0 + ty + 8 * rr) * p.kp + c0 + tx] = tile[tx][ty + 8 * rr];
 }
 
-struct BgArgs {
-    const float* gates; const float* hstash; const float* wT;      // wT: WhhT (sweep) or WihT (dX), [rows][kp]
-    const int* perm; const int* lens; const int* n_t; const float* dq_out;
-    const float* dh_in; float* dh_out;                               // dh_t (read), dh_{t-1} (written)
-    float* dG; float* dX;
-    int B, T, t, dq, dqp, de, tiles_m;
-};
+typedef GruBgArgs BgArgs;      // (ncx_gru.h: shared with the X6 form of this kernel)
 
 // rnn_nt_tile's A rows: dG_t's rows, the k-steps in order; the sweep's k-steps from s_hn on sit one block further (da_hn, after da_n)
 // (the column offset is one int, uniform over the workgroup, before it meets the row pointer: the loop then keeps it in scalar registers)
@@ -211,7 +208,20 @@ int ncx_gru_train_forward_flags(const int32_t* wids, int32_t B, int32_t T, const
 int ncx_gru_train_backward(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t dim_emb, int32_t dim_q,
                            const float* packed_t, void* workspace, size_t workspace_bytes, const float* dq_out,
                            float* dW_ih, float* dW_hh, float* db_ih, float* db_hh, float* dE, void* stream) {
-    if (!gru_train_dims_ok(B, T, dim_emb, dim_q) || V1 < 1) return -1;
+    return ncx_gru_train_backward_flags(wids, B, T, E, V1, dim_emb, dim_q, packed_t, 0, workspace, workspace_bytes, dq_out, dW_ih, dW_hh, db_ih, db_hh,
+                                        dE, stream);
+}
+
+int ncx_gru_bwd_form(int32_t B, int32_t T, int32_t dim_emb, int32_t dim_q, uint32_t flags) {
+    if (!gru_flags_ok(flags) || !gru_train_dims_ok(B, T, dim_emb, dim_q)) return -1;
+    return (flags & NCX_F_X6) ? GRU_BWD_X6 : 0;
+}
+
+int ncx_gru_train_backward_flags(const int32_t* wids, int32_t B, int32_t T, const float* E, int32_t V1, int32_t dim_emb, int32_t dim_q,
+                                 const float* packed_t, uint32_t flags, void* workspace, size_t workspace_bytes, const float* dq_out,
+                                 float* dW_ih, float* dW_hh, float* db_ih, float* db_hh, float* dE, void* stream) {
+    if (!gru_flags_ok(flags) || !gru_train_dims_ok(B, T, dim_emb, dim_q) || V1 < 1) return -1;
+    const int form = (flags & NCX_F_X6) ? GRU_BWD_X6 : 0;
     const GruTrainLayout w = gru_train_layout(B, T, dim_emb, dim_q);
     if (!rnn_args_ok({wids, E, dq_out, dW_ih, dW_hh, db_ih, db_hh}, packed_t, workspace, workspace_bytes, w.total)) return -1;
     hipStream_t s = (hipStream_t)stream;
@@ -230,22 +240,30 @@ int ncx_gru_train_backward(const int32_t* wids, int32_t B, int32_t T, const floa
     const unsigned grid_h = (unsigned)(a.tiles_m * cdiv(dim_q, BG_BN));
     for (int t = T; t >= 1; --t) {             // every launch is issued: how many rows it has is known on the device only
         a.t = t; a.dh_in = dh[t & 1]; a.dh_out = dh[(t + 1) & 1];
+        if (form & GRU_BWD_SWEEP) {
+            NCX_HIP_TRY(gru_sweep_x6(a, s));
+            continue;
+        }
         hipLaunchKernelGGL(k_gru_bgemm<false>, dim3(grid_h), dim3(256), 0, s, a);
         NCX_HIP_TRY(hipGetLastError());
     }
     NCX_HIP_TRY(rnn_tok(wids, B, T, V1, a.perm, n_t, tok, s));
     if (dE) {
         a.wT = packed_t + (size_t)pk.rows_h * pk.kp; a.t = 0;
-        hipLaunchKernelGGL(k_gru_bgemm<true>, dim3((unsigned)(a.tiles_m * cdiv(dim_emb, BG_BN)), (unsigned)T), dim3(256), 0, s, a);
-        NCX_HIP_TRY(hipGetLastError());
+        if (form & GRU_BWD_DX) {
+            NCX_HIP_TRY(gru_dx_x6(a, s));
+        } else {
+            hipLaunchKernelGGL(k_gru_bgemm<true>, dim3((unsigned)(a.tiles_m * cdiv(dim_emb, BG_BN)), (unsigned)T), dim3(256), 0, s, a);
+            NCX_HIP_TRY(hipGetLastError());
+        }
         NCX_HIP_TRY(rnn_embed_grad(tok, a.dX, nullptr, B, T, V1, dim_emb, dE, s));
     }
     RnnDwArgs d{};
     d.dG = a.dG; d.tok = tok; d.n_t = n_t; d.B = B; d.T = T; d.ld = 4 * pk.dqp; d.kp = pk.kp; d.units = dim_q; d.unitsp = pk.dqp;
     d.X = a.hstash; d.out = dW_hh; d.cols = dim_q; d.xshift = 1; d.skip_from = 2 * pk.dqp; d.skip_by = pk.dqp;     // blocks r z hn
-    NCX_HIP_TRY(rnn_dw(d, false, false, s));
+    NCX_HIP_TRY((form & GRU_BWD_DWHH) ? gru_dw_x6(d, false, s) : rnn_dw(d, false, false, s));
     d.X = E; d.out = dW_ih; d.cols = dim_emb; d.xshift = 0; d.skip_from = 0; d.skip_by = 0;                         // blocks r z n
-    NCX_HIP_TRY(rnn_dw(d, true, false, s));
+    NCX_HIP_TRY((form & GRU_BWD_DWIH) ? gru_dw_x6(d, true, s) : rnn_dw(d, true, false, s));
     hipLaunchKernelGGL(k_gru_dbias, dim3((unsigned)(4 * pk.dqp / 32)), dim3(256), 0, s, a.dG, n_t, B, T, dim_q, pk.dqp, db_ih, db_hh);
     NCX_HIP_TRY(hipGetLastError());
     return NCX_OK;

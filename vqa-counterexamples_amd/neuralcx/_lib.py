@@ -23,6 +23,7 @@ EXPORTS = ("ncx_input_size", "ncx_workspace_bytes", "ncx_forward", "ncx_forward_
            "ncx_similarity_scores",
            "ncx_gru_packed_bytes", "ncx_gru_pack", "ncx_gru_workspace_bytes", "ncx_gru_encode", "ncx_gru_encode_flags", "ncx_gru_step_form",
            "ncx_gru_train_workspace_bytes", "ncx_gru_packed_t_bytes", "ncx_gru_pack_t", "ncx_gru_train_forward", "ncx_gru_train_forward_flags", "ncx_gru_train_backward",
+           "ncx_gru_train_backward_flags", "ncx_gru_bwd_form",
            "ncx_lstm2_packed_bytes", "ncx_lstm2_pack", "ncx_lstm2_workspace_bytes", "ncx_lstm2_encode", "ncx_lstm2_encode_flags", "ncx_lstm2_step_form",
            "ncx_lstm2_train_workspace_bytes", "ncx_lstm2_packed_t_bytes", "ncx_lstm2_pack_t", "ncx_lstm2_train_forward", "ncx_lstm2_train_forward_flags", "ncx_lstm2_train_backward",
            "ncx_ws_region", "ncx_wgmap_check",
@@ -241,6 +242,10 @@ def lib():
     L.ncx_gru_train_backward.restype = C.c_int
     L.ncx_gru_train_backward.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                          C.c_size_t] + [C.c_void_p] * 7
+    L.ncx_gru_train_backward_flags.restype = C.c_int
+    L.ncx_gru_train_backward_flags.argtypes = L.ncx_gru_train_backward.argtypes[:8] + [C.c_uint32] + L.ncx_gru_train_backward.argtypes[8:]
+    L.ncx_gru_bwd_form.restype = C.c_int
+    L.ncx_gru_bwd_form.argtypes = L.ncx_gru_step_form.argtypes
     L.ncx_lstm2_packed_bytes.restype = C.c_size_t
     L.ncx_lstm2_packed_bytes.argtypes = [C.c_int32, C.c_int32]
     L.ncx_lstm2_pack.restype = C.c_int

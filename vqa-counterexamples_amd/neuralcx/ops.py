@@ -1037,10 +1037,23 @@ def gru_train_forward(wids: torch.Tensor, gw: GruTrainWeights, ws: torch.Tensor,
     return q
 
 
+GRU_BWD_SWEEP, GRU_BWD_DX, GRU_BWD_DWHH, GRU_BWD_DWIH = 1, 2, 4, 8      # ncx_gru_bwd_form's bits
+
+
+def gru_bwd_form(dim_emb: int, dim_q: int, B: int, T: int, x6=None) -> int:
+    """Which products of gru_train_backward take their bf16 x 6 kernel for this shape (ncx_gru_bwd_form; host only: no launch, no device
+    access), as a bit mask: GRU_BWD_SWEEP | GRU_BWD_DX | GRU_BWD_DWHH | GRU_BWD_DWIH; 0 for the fp32 form.  x6: as gru_step_form."""
+    rc = _lib.lib().ncx_gru_bwd_form(B, T, dim_emb, dim_q, mlb_att_flags(x6))
+    if rc < 0:
+        raise _lib.NcxError("ncx_gru_bwd_form: dims out of range (B %d, T %d, dim_emb %d, dim_q %d)" % (B, T, dim_emb, dim_q))
+    return rc
+
+
 def gru_train_backward(wids: torch.Tensor, gw: GruTrainWeights, ws: torch.Tensor, dq_out: torch.Tensor, want_dE: bool = True,
-                       dE: Optional[torch.Tensor] = None) -> Dict[str, Optional[torch.Tensor]]:
-    """ncx_gru_train_backward on the workspace gru_train_forward left for the same wids: dq_out [B, dim_q] -> {"w_ih", "w_hh", "b_ih",
-    "b_hh", "E"} in torch's layouts; "E" is None when want_dE is off (a fixed embedding).  `dE`: a caller's [V + 1, dim_emb] buffer."""
+                       dE: Optional[torch.Tensor] = None, x6=None) -> Dict[str, Optional[torch.Tensor]]:
+    """ncx_gru_train_backward_flags on the workspace gru_train_forward left for the same wids (under either x6): dq_out [B, dim_q] ->
+    {"w_ih", "w_hh", "b_ih", "b_hh", "E"} in torch's layouts; "E" is None when want_dE is off (a fixed embedding).  `dE`: a caller's
+    [V + 1, dim_emb] buffer.  x6 (gru_bwd_form): the bf16 x 6 form of the products it names -- fp32-grade, not bit-equal to the fp32 form."""
     B, T, wids = _gru_train_args(wids, gw, "gru_train_backward")
     if tuple(dq_out.shape) != (B, gw.dim_q):
         raise ValueError("dq_out must be [%d, %d], got %s" % (B, gw.dim_q, tuple(dq_out.shape)))
@@ -1054,10 +1067,11 @@ def gru_train_backward(wids: torch.Tensor, gw: GruTrainWeights, ws: torch.Tensor
         if tuple(g["E"].shape) != (gw.V1, gw.dim_emb):
             raise ValueError("dE must be [%d, %d], got %s" % (gw.V1, gw.dim_emb, tuple(g["E"].shape)))
     p, n = _ws_ptr(ws)
-    _lib.check(_lib.lib().ncx_gru_train_backward(_ptr(wids, torch.int32, "wids"), B, T, _ptr(gw.E, torch.float32, "E"), gw.V1, gw.dim_emb,
-                                                 gw.dim_q, _ptr(gw.packed_t, torch.float32, "packed_t"), p, n,
-                                                 _ptr(dq_out.float().contiguous(), torch.float32, "dq_out"),
-                                                 *[_ptr(g[k], torch.float32, "d" + k) for k in ("w_ih", "w_hh", "b_ih", "b_hh", "E")], _stream()),
+    _lib.check(_lib.lib().ncx_gru_train_backward_flags(_ptr(wids, torch.int32, "wids"), B, T, _ptr(gw.E, torch.float32, "E"), gw.V1, gw.dim_emb,
+                                                       gw.dim_q, _ptr(gw.packed_t, torch.float32, "packed_t"), mlb_att_flags(x6), p, n,
+                                                       _ptr(dq_out.float().contiguous(), torch.float32, "dq_out"),
+                                                       *[_ptr(g[k], torch.float32, "d" + k) for k in ("w_ih", "w_hh", "b_ih", "b_hh", "E")],
+                                                       _stream()),
                "ncx_gru_train_backward")
     return g
 

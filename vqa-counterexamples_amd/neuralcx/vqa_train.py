@@ -77,7 +77,8 @@ class GruTrainFunction(torch.autograd.Function):
     """q = the hidden state after each question's last word (GRUEncoder below its dropout) through ncx_gru_train_forward / _backward.
     Inputs: wids, E, w_ih, w_hh, b_ih, b_hh and the encoder module, on which the packs are cached (keyed on data_ptr / _version of the
     five tensors, like GRUEncoder._hip_weights: rebuilt after an optimizer step).  Gradients: the five tensors; None for E when it does
-    not require grad (a fixed embedding: the dX product is skipped).  The forward's step kernel follows module.hip_x6 (ops.gru_step_form)."""
+    not require grad (a fixed embedding: the dX product is skipped).  module.hip_x6 is read once, in forward, and picks the form of the
+    forward's step kernel (ops.gru_step_form) and of the backward's products (ops.gru_bwd_form): one step runs under one choice."""
 
     @staticmethod
     def weights(module, tensors):
@@ -93,14 +94,15 @@ class GruTrainFunction(torch.autograd.Function):
     def forward(ctx, wids, E, w_ih, w_hh, b_ih, b_hh, module=None):
         gw = GruTrainFunction.weights(module, (E, w_ih, w_hh, b_ih, b_hh))
         ws = ops.gru_train_workspace(wids.shape[0], wids.shape[1], gw, wids.device)
-        q = ops.gru_train_forward(wids, gw, ws, x6=getattr(module, "hip_x6", None))
-        ctx.hip = (wids, gw, ws)
+        x6 = getattr(module, "hip_x6", None)
+        q = ops.gru_train_forward(wids, gw, ws, x6=x6)
+        ctx.hip = (wids, gw, ws, x6)
         return q
 
     @staticmethod
     def backward(ctx, dq):
-        wids, gw, ws = ctx.hip
-        g = ops.gru_train_backward(wids, gw, ws, dq, want_dE=ctx.needs_input_grad[1])
+        wids, gw, ws, x6 = ctx.hip
+        g = ops.gru_train_backward(wids, gw, ws, dq, want_dE=ctx.needs_input_grad[1], x6=x6)
         ctx.hip = None                                            # the stash is the step's largest buffer: let go of it here
         return None, g["E"], g["w_ih"], g["w_hh"], g["b_ih"], g["b_hh"], None
 

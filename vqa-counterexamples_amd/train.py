@@ -23,7 +23,8 @@ glimpse fusion, classifier; forward with dropout and backward) then runs in HIP 
 product on the bf16 matrix path with three-plane operands (NCX_F_X6: same results to fp32 rounding; not the default), and with
 --hip_att_train the backward runs its twin, d conv_v_att.weight, there as well.  --x6_seq2vec is the same choice for the GRU question
 encoder (any arch): it sets GRUEncoder.hip_x6, and the encoder's HIP forward (eval mode and --hip_seq2vec_train) runs the bf16 x 6 form of
-its step kernel; --x6_2lstm is that choice for the 2-lstm encoder (TwoLSTM.hip_x6: its eval-mode forward and --hip_2lstm_train run
+its step kernel, and with --hip_seq2vec_train its backward through time runs the bf16 x 6 form of its four matrix products -- the
+reverse sweep, dX, dW_hh, dW_ih (ncx_gru_train_backward_flags, ops.gru_bwd_form); --x6_2lstm is that choice for the 2-lstm encoder (TwoLSTM.hip_x6: its eval-mode forward and --hip_2lstm_train run
 k_lstm_step_x6).  The images are a seeded synthetic attention table [syn_images, dim_v, syn_grid, syn_grid].
 """
 import argparse
@@ -237,7 +238,8 @@ class Trainer:
         print("=> route: %s%s%s%s%s" % ("hip" if self.hip else self.route, " (engine: whole step in HIP)" if self.engine else "",
                                     " (question encoder: HIP forward + backward through time)" if getattr(self, "hip_seq2vec", False) else
                                     " (2-lstm question encoder: HIP forward + backward through time, --hip_2lstm_train)" if getattr(self, "hip_2lstm", False)
-                                    else "", " (question encoder: bf16 x 6 step kernel)" if getattr(args, "x6_seq2vec", False) else "",
+                                    else "", (" (question encoder: bf16 x 6 step kernel)" + (" (and the bf16 x 6 products of its backward)" if getattr(self, "hip_seq2vec", False) else ""))
+                                    if getattr(args, "x6_seq2vec", False) else "",
                                       " (2-lstm question encoder: bf16 x 6 step kernel)" if getattr(args, "x6_2lstm", False) else ""), flush=True)
 
     # ---- data ------------------------------------------------------------------------------------------------

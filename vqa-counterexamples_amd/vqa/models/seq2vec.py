@@ -13,7 +13,8 @@ class GRUEncoder(nn.Module):
     `use_hip_train = True` (off by default) also trains it there: a CUDA fp32 module called with grad mode on and a parameter that
     requires grad runs neuralcx.vqa_train.GruTrainFunction (forward with a stash, backward through time); its dropout stays in torch.
     `hip_x6` is handed to both HIP routes and changes no routing decision: None = the process-wide choice (ops.EXTRA_FLAGS, NCX_X6=1),
-    True / False = the bf16 x 6 / the fp32 form of the step kernel (ops.gru_step_form; train.py --x6_seq2vec sets True)."""
+    True / False = the bf16 x 6 / the fp32 form of the step kernel (ops.gru_step_form; train.py --x6_seq2vec sets True) and, on the
+    training route, of the backward's matrix products that have one (ops.gru_bwd_form)."""
     use_hip = True
     use_hip_train = False
     hip_x6 = None
