@@ -19,22 +19,13 @@ import numpy as np
 import torch
 
 from gru_ref import lengths
+from x6_ref import cut
 
 SWEEP, DX, DWHH, DWIH = 1, 2, 4, 8
 SHIPPED_MASK = SWEEP | DX | DWHH | DWIH    # what ncx_gru_bwd_form reports under NCX_F_X6
 SHIPPED_NPROD = 8
 ORDER = ((0, 0), (0, 1), (1, 0), (1, 1), (0, 2), (2, 0), (1, 2), (2, 1))
 GRADS = ("E", "w_ih", "w_hh", "b_ih", "b_hh")
-
-
-def cut(x):
-    """fp32 tensor -> its three truncated bf16 planes (as fp32 tensors); x1 + x2 + x3 == x exactly."""
-    hi = lambda v: (v.contiguous().view(torch.int32) & -65536).view(torch.float32)
-    x1 = hi(x)
-    r1 = x - x1
-    x2 = hi(r1)
-    x3 = r1 - x2
-    return x1, x2, x3
 
 
 def plane_matmul(a, b, nprod):

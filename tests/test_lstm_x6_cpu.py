@@ -20,6 +20,7 @@ import test_lstm_gpu as fwd_suite
 from conftest import ROOT
 from test_gru_x6_cpu import GRU_YAML, SYN
 from test_mlb_att_cpu import _cli
+from x6_ref import cut
 
 SYMS = ("ncx_lstm2_encode_flags", "ncx_lstm2_train_forward_flags", "ncx_lstm2_step_form")
 DIMS = ((512, 26, 620, 1200), (2, 2, 1, 1), (5, 7, 7, 37))          # (B, T, emb, H)
@@ -171,15 +172,6 @@ def test_counterexamples_help_names_both_encoders():
 SIX = ((0, 2), (1, 1), (2, 0), (0, 1), (1, 0), (0, 0))              # (plane of a, plane of b), small terms first: a1 b3 ... a1 b1
 THREE = ((0, 1), (1, 0), (0, 0))
 FIVES = {"no a1 b3": SIX[1:], "no a2 b2": SIX[:1] + SIX[2:], "no a3 b1": SIX[:2] + SIX[3:]}
-
-
-def cut(x):
-    """x (fp32) -> the three planes of rnn_split_store: x1 = x & 0xFFFF0000, x2 = (x - x1) & 0xFFFF0000, x3 = the high half of x - x1 - x2."""
-    hi = lambda v: (v.contiguous().view(torch.int32) & -65536).view(torch.float32)
-    x1 = hi(x)
-    r1 = x - x1
-    x2 = hi(r1)
-    return x1, x2, hi(r1 - x2)
 
 
 def emulate(wids, E, layer0, layer1, products):

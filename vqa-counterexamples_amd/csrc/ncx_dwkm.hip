@@ -16,6 +16,7 @@
 #include <type_traits>
 #include "ncx_internal.h"
 #include "ncx_dwred.h"
+#include "ncx_x6.h"
 
 namespace ncx {
 
@@ -417,16 +418,13 @@ __global__ __launch_bounds__(512, 1) void k_dw_km8(const float* __restrict__ dpr
 }
 
 // ---- the same pass on the bf16 matrix path with fp32-grade operands (NCX_F_X6; not the default) -------------------------------------------
-// Operands as in k_dw_tn8_x6 (ncx_dwtn.hip): every fp32 element is cut into three bf16 values by truncation when it is stored to LDS
-// (x = x1 + x2 + x3 exactly), six products per block on v_mfma_f32_16x16x32_bf16 with fp32 accumulation.  One 8-wave workgroup per CU on a
+// Operands as in k_dw_tn8_x6 (ncx_dwtn.hip): every fp32 element is cut into three bf16 planes when it is stored to LDS, six plane products
+// per block with fp32 accumulation (the cut, the products and the contract: ncx_x6.h).  One 8-wave workgroup per CU on a
 // 256 (all of H) x 64 tile pair; a reduction step is one triplet part of 24 rows in a 32-deep MFMA step (LDS rows 24 .. 31 of the dpre planes
 // are zeroed once and never written: their products vanish whatever the feature planes hold there).  T_b of a 16-row block row comes out of
 // its 12 MFMAs into a scratch accumulator that starts at zero, and is folded into both outputs (acc_k += T_b, acc_m += v_o (.) T_b) under the
 // MFMAs of the NEXT block row; the last block row's MFMAs of a step run after the barrier, over the first fragment reads of the next step.
 // v_o travels in fp32 (a 64-float row per LDS buffer).  Same k-chunks and slab layout as k_dw_km: the reduction that follows is unchanged.
-typedef __bf16 km_bf16x8 __attribute__((ext_vector_type(8)));
-typedef short km_s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int km_u32x2 __attribute__((ext_vector_type(2)));
 constexpr int KM6_PA = 544, KM6_PB = 160;                                    // bytes per row of one plane (512 + 32, 128 + 32)
 constexpr int KM6_PL = 32 * (KM6_PA + KM6_PB), KM6_BUF = 3 * KM6_PL;
 constexpr int KM6_LDS = 2 * KM6_BUF + 2 * 64 * 4 + 64 * 16;                  // planes, v_o rows, a dump row for the stores of threads without a v_o quad
@@ -488,22 +486,6 @@ __global__ __launch_bounds__(512, 1) void k_dw_km_x6(const float* __restrict__ d
         for (int i = 0; i < NA; ++i) va[SS_][i] = __builtin_bit_cast(f32x4, (bu32x4)__builtin_amdgcn_raw_buffer_load_b128(rsD, offA[i], ao, 0));
         vb[SS_] = __builtin_bit_cast(f32x4, (bu32x4)__builtin_amdgcn_raw_buffer_load_b128(rsF, __umul24((unsigned)ix, dv4) + offX, 0, 0));
     };
-    auto split_store = [&](f32x4 v, unsigned char* base) __attribute__((always_inline)) {
-        unsigned p1[4], p2[4], p3[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float xj = v[j];               // (a scalar copy first: __builtin_bit_cast applied to the vector element itself reads element 0 -- hipcc 7.2)
-            p1[j] = __builtin_bit_cast(unsigned, xj) & 0xFFFF0000u;
-            const float r1 = xj - __builtin_bit_cast(float, p1[j]);
-            p2[j] = __builtin_bit_cast(unsigned, r1) & 0xFFFF0000u;
-            const float r2 = r1 - __builtin_bit_cast(float, p2[j]);
-            p3[j] = __builtin_bit_cast(unsigned, r2);
-        }
-        const km_u32x2 w1 = {__builtin_amdgcn_perm(p1[1], p1[0], 0x07060302u), __builtin_amdgcn_perm(p1[3], p1[2], 0x07060302u)};
-        const km_u32x2 w2 = {__builtin_amdgcn_perm(p2[1], p2[0], 0x07060302u), __builtin_amdgcn_perm(p2[3], p2[2], 0x07060302u)};
-        const km_u32x2 w3 = {__builtin_amdgcn_perm(p3[1], p3[0], 0x07060302u), __builtin_amdgcn_perm(p3[3], p3[2], 0x07060302u)};
-        *(km_u32x2*)(base) = w1; *(km_u32x2*)(base + PL) = w2; *(km_u32x2*)(base + 2 * PL) = w3;
-    };
     // the fp32 v_o quad goes to the buffer's v_o row from the threads that hold one (rows >= 24; eight copies of the same value), to the dump row from the others: no branch
     float* const vo_dst0 = brow >= K ? lds_vo + 4 * bq : lds_dump + 4 * lane;
     const int vo_step = brow >= K ? 64 : 0;
@@ -513,38 +495,27 @@ __global__ __launch_bounds__(512, 1) void k_dw_km_x6(const float* __restrict__ d
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             if (i < h0 || i >= h1) continue;
-            split_store(va[SS_][i], base + (arow + 8 * i) * PA + aq * 8);
+            x6_split_store(va[SS_][i], base + (arow + 8 * i) * PA + aq * 8, PL);
         }
         if (NA >= h0 && NA < h1) {
-            split_store(vb[SS_], base + A_PL + brow * PB + bq * 8);
+            x6_split_store(vb[SS_], base + A_PL + brow * PB + bq * 8, PL);
             *(f32x4*)(vo_dst0 + buf * vo_step) = vb[SS_];
         }
     };
-    typedef __attribute__((address_space(3))) km_s16x4* lds_s16x4;
     const int tq = li >> 2, tp = li & 3;
     const int fragA = (4 * lk + tq) * PA + (wm0 + 4 * tp) * 2, fragB = A_PL + (4 * lk + tq) * PB + (wn0 + 4 * tp) * 2;
-    auto read_a = [&](int buf, int i, km_bf16x8 (&af)[3]) __attribute__((always_inline)) {
+    auto read_a = [&](int buf, int i, x6_bf16x8 (&af)[3]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int p = 0; p < 3; ++p) {
-            const unsigned char* ta = km6_smem + buf * BUF + p * PL + fragA + i * 32;
-            const km_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(ta));
-            const km_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(ta + 16 * PA));
-            af[p] = __builtin_bit_cast(km_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-        }
+        for (int p = 0; p < 3; ++p) af[p] = x6_frag_tr(km6_smem + buf * BUF + p * PL + fragA + i * 32, PA);
     };
-    auto read_b = [&](int buf, km_bf16x8 (&bf)[3][2]) __attribute__((always_inline)) {
+    auto read_b = [&](int buf, x6_bf16x8 (&bf)[3][2]) __attribute__((always_inline)) {
 #pragma unroll
         for (int p = 0; p < 3; ++p)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const unsigned char* tb = km6_smem + buf * BUF + p * PL + fragB + j * 32;
-                const km_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(tb));
-                const km_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(tb + 16 * PB));
-                bf[p][j] = __builtin_bit_cast(km_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-            }
+            for (int j = 0; j < 2; ++j) bf[p][j] = x6_frag_tr(km6_smem + buf * BUF + p * PL + fragB + j * 32, PB);
     };
     // T of one block row: 12 MFMAs from zero, the two column blocks alternate, small terms first
-    auto mfma12z = [&](const km_bf16x8 (&af)[3], const km_bf16x8 (&bf)[3][2], f32x4 (&c)[2]) __attribute__((always_inline)) {
+    auto mfma12z = [&](const x6_bf16x8 (&af)[3], const x6_bf16x8 (&bf)[3][2], f32x4 (&c)[2]) __attribute__((always_inline)) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) c[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bf[2][j], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
 #pragma unroll
@@ -579,9 +550,9 @@ __global__ __launch_bounds__(512, 1) void k_dw_km_x6(const float* __restrict__ d
         __builtin_amdgcn_sched_barrier(0);
     };
     typedef std::integral_constant<int, 0> S0; typedef std::integral_constant<int, 1> S1;
-    km_bf16x8 afA[3], afB[3], bfr[2][3][2];
+    x6_bf16x8 afA[3], afB[3], bfr[2][3][2];
     float vo[2][2] = {{0.f, 0.f}, {0.f, 0.f}};                      // [parity of the step][column block]: v_o of the lane's columns
-    const km_bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    const x6_bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int p = 0; p < 3; ++p) {
         afB[p] = zero8;

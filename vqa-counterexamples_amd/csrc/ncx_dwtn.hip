@@ -28,6 +28,7 @@
 #include <type_traits>
 #include "ncx_internal.h"
 #include "ncx_dwred.h"
+#include "ncx_x6.h"
 
 namespace ncx {
 
@@ -341,20 +342,15 @@ __global__ __launch_bounds__(TN8_T, 1) void k_dw_tn8(const Tn8Args a) {
 
 
 // ---- the same launch on the bf16 matrix path with fp32-grade operands (NCX_F_X6; not the default) -----------------------------------------
-// Every operand element is cut into three bf16 values by truncation, x = x1 + x2 + x3 EXACTLY (x1 = x & 0xFFFF0000, x2 = (x - x1) & 0xFFFF0000,
-// x3 = x - x1 - x2; every residual is exact in fp32), when it is stored to LDS (once per element, as in the fp32 kernel); the eight products
-// a1 x1 + (a1 x2 + a2 x1) + (a1 x3 + a2 x2 + a3 x1) + (a2 x3 + a3 x2) run on v_mfma_f32_16x16x32_bf16 with fp32 accumulation (products of bf16 values are
-// exact in fp32), a1 x1 on one accumulator and the seven small ones on a second, added when the partial tile leaves: what is dropped is a3 x3, 2^-32
-// relative.  (With six products on one accumulator the form was 2.2 - 2.5 x the fp32 kernel's error on the a_emb lesion's operands:
-// profiles/main_bwd_edges.json.)  8 MFMAs of 16 cycles replace 8 of 32 per 16 x 16 x 32
-// block.  LDS holds three bf16 planes per operand in the global [k][m] layout; fragments come from ds_read_b64_tr_b16 (hardware transpose);
+// Every operand element is cut into three bf16 planes when it is stored to LDS (once per element, as in the fp32 kernel), and the EIGHT plane
+// products of ncx_x6.h run with fp32 accumulation, a1 x1 on one accumulator and the seven small ones on a second, added when the partial tile
+// leaves -- the cut, the order, what is dropped and what is outside the contract: ncx_x6.h.  (With six products on one accumulator the form was
+// 2.2 - 2.5 x the fp32 kernel's error on the a_emb lesion's operands: profiles/main_bwd_edges.json.)  8 MFMAs of 16 cycles replace 8 of 32 per
+// 16 x 16 x 32 block.  LDS holds three bf16 planes per operand in the global [k][m] layout; fragments come from ds_read_b64_tr_b16 (hardware transpose);
 // row pitches = 32 mod 256 bytes.  Measured on the dGt problem alone (tools/mb/mb_tn.hip): 80 us against 109, same error against fp64 (1.0e-9 on
 // values of 1.9e-3); the kernel is then bound by LDS + global-load return traffic (~3 000 cycles per k-step against 1 536 of MFMA with six products, 2 048 with eight), not by the
 // matrix cores.  Pieces, slab slots and the reduction are those of k_dw_tn8; the block mapping inside a wave is the plain one (block (i, j) =
 // rows wm0 + 16 i .., columns wn0 + 16 j ..), so the summation order differs from the fp32 kernel's: results agree to fp32 rounding, not bitwise.
-typedef __bf16 tn_bf16x8 __attribute__((ext_vector_type(8)));
-typedef short tn_s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int tn_u32x2 __attribute__((ext_vector_type(2)));
 constexpr int TN6_PA = 544, TN6_PB = 160;                                    // bytes per k-row of one plane (512 + 32, 128 + 32)
 constexpr int TN6_PL = TN8_BK * (TN6_PA + TN6_PB), TN6_BUF = 3 * TN6_PL;    // one plane (A rows | X rows), one buffer
 
@@ -464,31 +460,13 @@ __global__ __launch_bounds__(TN8_T, 1) void k_dw_tn8_x6(const Tn8Args a) {
         if (v >= l_vend) loader_switch(v);
         issue_fast(set_c);
     };
-    // x -> three bf16 planes (four values: one 8-byte store per plane)
-    auto split_store = [&](f32x4 v, unsigned char* base) __attribute__((always_inline)) {
-        unsigned p1[4], p2[4], p3[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float xj = v[j];               // (a scalar copy first: __builtin_bit_cast applied to the vector element itself reads element 0 -- hipcc 7.2)
-            p1[j] = __builtin_bit_cast(unsigned, xj) & 0xFFFF0000u;
-            const float r1 = xj - __builtin_bit_cast(float, p1[j]);
-            p2[j] = __builtin_bit_cast(unsigned, r1) & 0xFFFF0000u;
-            const float r2 = r1 - __builtin_bit_cast(float, p2[j]);
-            p3[j] = __builtin_bit_cast(unsigned, r2);            // (at most 8 significant bits are left: the high half holds them all)
-        }
-        // v_perm_b32: the high halves of two dwords -> one dword (the even element in the low half)
-        const tn_u32x2 w1 = {__builtin_amdgcn_perm(p1[1], p1[0], 0x07060302u), __builtin_amdgcn_perm(p1[3], p1[2], 0x07060302u)};
-        const tn_u32x2 w2 = {__builtin_amdgcn_perm(p2[1], p2[0], 0x07060302u), __builtin_amdgcn_perm(p2[3], p2[2], 0x07060302u)};
-        const tn_u32x2 w3 = {__builtin_amdgcn_perm(p3[1], p3[0], 0x07060302u), __builtin_amdgcn_perm(p3[3], p3[2], 0x07060302u)};
-        *(tn_u32x2*)(base) = w1; *(tn_u32x2*)(base + PL) = w2; *(tn_u32x2*)(base + 2 * PL) = w3;
-    };
     auto stash = [&](auto set_c, auto mode_c, int buf, int h0, int h1) __attribute__((always_inline)) {      // MODE: as k_dw_tn8 (0 select, 1 softmax, 2 plain)
         constexpr int S = decltype(set_c)::value, MODE = decltype(mode_c)::value;
         unsigned char* const base = tn6_smem + buf * BUF;
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             if (i < h0 || i >= h1) continue;
-            split_store(va[S][i], base + (arow + 8 * i) * PA + aq * 8);
+            x6_split_store(va[S][i], base + (arow + 8 * i) * PA + aq * 8, PL);
         }
         if (NA >= h0 && NA < h1) {
             f32x4 v = vb[S], e;
@@ -498,50 +476,29 @@ __global__ __launch_bounds__(TN8_T, 1) void k_dw_tn8_x6(const Tn8Args a) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { const float xj = v[j], ej = e[j]; v[j] = MODE == 1 ? ej : (vs[S] != 0.f ? ej : xj); }
             }
-            split_store(v, base + A_PL + brow * PB + bq * 8);
+            x6_split_store(v, base + A_PL + brow * PB + bq * 8, PL);
         }
     };
-    typedef __attribute__((address_space(3))) tn_s16x4* lds_s16x4;
     const int tq = li >> 2, tp = li & 3;
     const int fragA = (4 * lk + tq) * PA + (wm0 + 4 * tp) * 2, fragB = A_PL + (4 * lk + tq) * PB + (wn0 + 4 * tp) * 2;
-    auto read_a = [&](int buf, int i, tn_bf16x8 (&af)[3]) __attribute__((always_inline)) {
+    auto read_a = [&](int buf, int i, x6_bf16x8 (&af)[3]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int p = 0; p < 3; ++p) {
-            const unsigned char* ta = tn6_smem + buf * BUF + p * PL + fragA + i * 32;
-            const tn_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(ta));
-            const tn_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(ta + 16 * PA));
-            af[p] = __builtin_bit_cast(tn_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-        }
+        for (int p = 0; p < 3; ++p) af[p] = x6_frag_tr(tn6_smem + buf * BUF + p * PL + fragA + i * 32, PA);
     };
-    auto read_b = [&](int buf, tn_bf16x8 (&bf)[3][2]) __attribute__((always_inline)) {
+    auto read_b = [&](int buf, x6_bf16x8 (&bf)[3][2]) __attribute__((always_inline)) {
 #pragma unroll
         for (int p = 0; p < 3; ++p)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const unsigned char* tb = tn6_smem + buf * BUF + p * PL + fragB + j * 32;
-                const tn_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(tb));
-                const tn_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(tb + 16 * PB));
-                bf[p][j] = __builtin_bit_cast(tn_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-            }
+            for (int j = 0; j < 2; ++j) bf[p][j] = x6_frag_tr(tn6_smem + buf * BUF + p * PL + fragB + j * 32, PB);
     };
     // the 16 MFMAs of block row i: the two column blocks alternate (a dependent MFMA is two issues away).  The seven small plane products go
-    // to the accumulator `lo`, a1 x1 alone to `c`: the running sum takes ONE rounding per k-step at its full magnitude instead of six, and
-    // a2 x3 + a3 x2 (up to 2^-22 of a term, with the term's sign under truncation) are no longer dropped -- only a3 x3 (2^-32) is.
-    auto mfma16 = [&](const tn_bf16x8 (&af)[3], const tn_bf16x8 (&bf)[3][2], f32x4 (&c)[2], f32x4 (&lo)[2]) __attribute__((always_inline)) {
+    // to the accumulator `lo`, a1 x1 alone to `c` (the eight-product order of ncx_x6.h): a2 x3 + a3 x2 (up to 2^-22 of a term, with the
+    // term's sign under truncation) are not dropped.
+    auto mfma16 = [&](const x6_bf16x8 (&af)[3], const x6_bf16x8 (&bf)[3][2], f32x4 (&c)[2], f32x4 (&lo)[2]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) lo[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bf[2][j], lo[j], 0, 0, 0);
+        for (int q = 0; q < 7; ++q)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) lo[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[2], bf[1][j], lo[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) lo[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bf[2][j], lo[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) lo[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bf[1][j], lo[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) lo[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[2], bf[0][j], lo[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) lo[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bf[1][j], lo[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) lo[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bf[0][j], lo[j], 0, 0, 0);
+            for (int j = 0; j < 2; ++j) lo[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[X6S_A[q]], bf[X6S_B[q]][j], lo[j], 0, 0, 0);
 #pragma unroll
         for (int j = 0; j < 2; ++j) c[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bf[0][j], c[j], 0, 0, 0);
     };
@@ -557,8 +514,8 @@ __global__ __launch_bounds__(TN8_T, 1) void k_dw_tn8_x6(const Tn8Args a) {
         __builtin_amdgcn_sched_barrier(0);
     };
     typedef std::integral_constant<int, 0> S0; typedef std::integral_constant<int, 1> S1;
-    tn_bf16x8 afA[3], afB[3], bfr[2][3][2];
-    const tn_bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    x6_bf16x8 afA[3], afB[3], bfr[2][3][2];
+    const x6_bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int p = 0; p < 3; ++p) {
         afB[p] = zero8;

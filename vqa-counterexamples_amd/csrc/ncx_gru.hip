@@ -62,8 +62,7 @@ __global__ __launch_bounds__(256) void k_gru_step(const int* __restrict__ wids, 
     __shared__ __attribute__((aligned(16))) float lds[2][GRU_TILE_ROWS * GRU_P];
     // workgroup ids are dealt round-robin over the 8 XCDs: consecutive work items (the row tiles of one unit tile, which share its
     // weight rows) go to the same XCD's L2
-    const int per = (total + 7) >> 3;
-    const int w = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+    const int w = rnn_work_item(blockIdx.x, total);
     if (w >= total) return;
     const int nt = n_t[t];
     const int j = w / tiles_m, m0 = (w - j * tiles_m) * RNN_BM;

@@ -8,11 +8,10 @@
 // are zeroed on the load side BEFORE the cut (the workspace may hold anything there, and the cut of a NaN is NaN), X rows beyond n_t are
 // read from the clamped row n_t - 1 (a valid stash row or a row of E), gathered rows go through the tok table (-1 is never an address), one
 // workgroup walks the whole contraction in order (no slabs, no reduction launch, no atomics), and with no k-step at all the tile is
-// exactly 0.  What differs is the product, as in k_dw_tn8_x6 (ncx_dwtn.hip): every operand element is cut into three bf16 values by
-// truncation when its tile is stored to LDS (rnn_split_store, ncx_rnn.h: x = x1 + x2 + x3 exactly), and eight plane products per
-// 16 x 16 x 32 block, a1 x1 + (a1 x2 + a2 x1) + (a1 x3 + a2 x2 + a3 x1) + (a2 x3 + a3 x2), run with fp32 accumulation: a1 x1 on one
-// accumulator and the seven small ones on a second, added when the tile leaves (six products on one accumulator were 2.2 - 2.5 x the
-// fp32 error there); what is dropped is a3 x3, 2^-32 relative.
+// exactly 0.  What differs is the product, as in k_dw_tn8_x6 (ncx_dwtn.hip): the operands are cut into three bf16 planes when their tile
+// is stored to LDS and EIGHT plane products per 16 x 16 x 32 block run with fp32 accumulation, a1 x1 on one accumulator and the seven
+// small ones on a second, added when the tile leaves (six products on one accumulator were 2.2 - 2.5 x the fp32 error there) -- the cut,
+// the order of the products, what is dropped and what is outside the contract: ncx_x6.h.
 // One workgroup: 8 waves in a 4 x 2 grid, 256 gate rows x 64 feature columns, a wave 64 x 32 = 4 x 2 MFMA blocks.  LDS, double buffered:
 // three planes of [32 k-rows][256 | 64] bf16 in the global row-is-k layout, row pitches 544 / 160 bytes (= 32 mod 256: the eight k-rows
 // that one 32-lane half of a ds_read_b64_tr_b16 touches fall on disjoint banks); fragments come from the transposing read, so lane group
@@ -32,20 +31,17 @@ constexpr int W6_PL = GEMM_BK * (W6_PA + W6_PB), W6_BUF = 3 * W6_PL, W6_LDS = 2 
 static_assert(GEMM_BK == 32, "one k-step is one MFMA depth");
 static_assert(W6_LDS <= 160 * 1024, "LDS");
 static_assert(W6_T * 4 == GEMM_BK * W6_BM / 4 && W6_T == GEMM_BK * W6_BN / 4, "the loader: 4 quads of the gate-gradient tile, 1 of the X tile per thread");
-
-typedef short w6_s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) w6_s16x4* w6_lds_s16x4;
 }  // namespace
 
 template <bool GATHER>
 __global__ __launch_bounds__(W6_T, 1) void k_gru_dw_x6(const RnnDwArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char w6_smem[];
-    // Workgroup ids are dealt round-robin over the 8 XCDs, so work item w = (id & 7) per + (id >> 3): consecutive work items run on the
-    // same XCD at the same time, and they are ordered so that 32 of them (an XCD's CUs) form W6_GM gate-row tiles x 8 column tiles: per
+    // Consecutive work items run on the same XCD at the same time (rnn_work_item), and they are ordered so that 32 of them (an XCD's
+    // CUs) form W6_GM gate-row tiles x 8 column tiles: per
     // k-step that L2 then fetches 4 gate-gradient tiles and 8 X tiles (192 KB) for its 32 workgroups instead of 32 of each (1 280 KB).
     // The operands are far larger than an L2 (dG 511 MB at B = 512, T = 26), so what is not shared there comes from beyond it.
-    const int tiles_n = (a.cols + W6_BN - 1) / W6_BN, total = a.tiles_m * tiles_n, per = (total + 7) >> 3;
-    const int w = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+    const int tiles_n = (a.cols + W6_BN - 1) / W6_BN, total = a.tiles_m * tiles_n;
+    const int w = rnn_work_item(blockIdx.x, total);
     if (w >= total) return;                      // (uniform: before any barrier)
     const int grp = w / (W6_GM * tiles_n), rest = w - grp * (W6_GM * tiles_n), gm = min(W6_GM, a.tiles_m - grp * W6_GM);
     const int tn = rest / gm, m0 = (grp * W6_GM + (rest - tn * gm)) * W6_BM, n0 = tn * W6_BN;
@@ -79,8 +75,8 @@ __global__ __launch_bounds__(W6_T, 1) void k_gru_dw_x6(const RnnDwArgs a) {
     auto store = [&](int buf) __attribute__((always_inline)) {
         unsigned char* const base = w6_smem + buf * W6_BUF;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) rnn_split_store(a_ok[i] ? va[i] : zero, base + (arow + 8 * i) * W6_PA + 8 * aq, W6_PL);
-        rnn_split_store(vb, base + W6_APL + brow * W6_PB + 8 * bq, W6_PL);
+        for (int i = 0; i < 4; ++i) x6_split_store(a_ok[i] ? va[i] : zero, base + (arow + 8 * i) * W6_PA + 8 * aq, W6_PL);
+        x6_split_store(vb, base + W6_APL + brow * W6_PB + 8 * bq, W6_PL);
     };
 
     f32x4 acc[4][2], acl[4][2];                  // a1 x1 | the seven small plane products
@@ -89,33 +85,26 @@ __global__ __launch_bounds__(W6_T, 1) void k_gru_dw_x6(const RnnDwArgs a) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) { acc[i][j] = zero; acl[i][j] = zero; }
 
-    // ds_read_b64_tr_b16: lane 4 q + p of a 16-lane group gives the address of k-row q, columns 4 p .. + 3 of a 4 x 16 block; lane i
-    // receives column i of the four k-rows.  Two reads (k-rows 4 lk .., 16 + 4 lk ..) make one 8-deep fragment.
+    // fragments through x6_frag_tr (ncx_x6.h): lane 4 tq + tp of a 16-lane group points at k-row 4 lk + tq, columns 4 tp .. + 3
     const int tq = li >> 2, tp = li & 3;
     const int fragA = (4 * lk + tq) * W6_PA + 2 * (wm0 + 4 * tp), fragB = W6_APL + (4 * lk + tq) * W6_PB + 2 * (wn0 + 4 * tp);
-    auto frag = [&](const unsigned char* p, int pitch) __attribute__((always_inline)) -> rnn_bf16x8 {
-        const w6_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w6_lds_s16x4)(p));
-        const w6_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w6_lds_s16x4)(p + 16 * pitch));
-        return __builtin_bit_cast(rnn_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-    };
     auto compute = [&](int buf) __attribute__((always_inline)) {
         const unsigned char* const base = w6_smem + buf * W6_BUF;
-        rnn_bf16x8 bf[3][2];
+        x6_bf16x8 bf[3][2];
 #pragma unroll
         for (int p = 0; p < 3; ++p)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) bf[p][j] = frag(base + p * W6_PL + fragB + 32 * j, W6_PB);
+            for (int j = 0; j < 2; ++j) bf[p][j] = x6_frag_tr(base + p * W6_PL + fragB + 32 * j, W6_PB);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            rnn_bf16x8 af[3];
+            x6_bf16x8 af[3];
 #pragma unroll
-            for (int p = 0; p < 3; ++p) af[p] = frag(base + p * W6_PL + fragA + 32 * i, W6_PA);
+            for (int p = 0; p < 3; ++p) af[p] = x6_frag_tr(base + p * W6_PL + fragA + 32 * i, W6_PA);
             // small terms first; the two column blocks alternate (a dependent MFMA is two issues away)
-            constexpr int PA[7] = {1, 2, 0, 1, 2, 0, 1}, PB[7] = {2, 1, 2, 1, 0, 1, 0};
 #pragma unroll
             for (int c = 0; c < 7; ++c)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acl[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[PA[c]], bf[PB[c]][j], acl[i][j], 0, 0, 0);
+                for (int j = 0; j < 2; ++j) acl[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[X6S_A[c]], bf[X6S_B[c]][j], acl[i][j], 0, 0, 0);
 #pragma unroll
             for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bf[0][j], acc[i][j], 0, 0, 0);
         }
@@ -159,30 +148,23 @@ __global__ __launch_bounds__(W6_T, 1) void k_gru_dw_x6(const RnnDwArgs a) {
 // The NT product acc = dG_t[m0 .. + BM][K = 3 dqp] . wT[n0 .. + 64]^T of rnn_nt_tile, both operands col-is-k, cut from fp32 on the way to LDS
 // (the transposed pack is read as ncx_gru_pack_t left it); everything around it is k_gru_bgemm's: n_t read on the device, workgroups beyond
 // it exit before their first barrier, rows beyond n_t clamped to row n_t - 1 and never stored, the sweep's k-steps from s_hn on one block
-// further (da_hn after da_n), and the epilogue line for line.  LDS as in k_gru_step_x6 (ncx_gru_x6.hip): three planes of
-// [BM rows | 64 weight rows][32 k] bf16 at 80 bytes per row, plain 16-byte fragment reads (lane group lk holds k = 8 lk .. + 7 of both
-// operands), double buffered, register-staged, one barrier per k-step.  The waves form a WR x 2 grid, 32 rows x 32 columns each (2 x 2
-// MFMA blocks, eight plane products per block on two accumulators as in the walk); a wave whose 32 rows all lie beyond n_t takes part in the
-// loads, the stores and the barriers and multiplies nothing.  Work items are dealt to the XCDs in contiguous runs, row tiles of a column
+// further (da_hn after da_n), and the epilogue line for line.  The LDS row tile is RnnX6Tile<WR, 64> (ncx_rnn.h), as in k_gru_step_x6.
+// The waves form a WR x 2 grid, 32 rows x 32 columns each (2 x 2 MFMA blocks, eight plane products per block on two accumulators as in
+// the walk).  Work items are dealt to the XCDs in contiguous runs, row tiles of a column
 // tile next to each other: an XCD's L2 fetches its share of the weight rows once per launch.
 namespace {
-constexpr int B6_BN = 64, B6_PB = 80;
-template <int WR> struct B6 {
-    static constexpr int BM = 32 * WR, T = 128 * WR, LR = T / 8, NB = (B6_BN + LR - 1) / LR;
-    static constexpr int ROWS = BM + B6_BN, PL = ROWS * B6_PB, BUF = 3 * PL, LDS = 2 * BUF;
-    static_assert(BM == 2 * LR, "the loader takes the A tile in two passes");
-    static_assert(LDS <= 160 * 1024, "LDS");
-};
+constexpr int B6_BN = 64;
+template <int WR> using B6 = RnnX6Tile<WR, B6_BN>;
 }  // namespace
 
 template <bool DX, int WR>
 __global__ __launch_bounds__(128 * WR, 1) void k_gru_bgemm_x6(const GruBgArgs a, int tiles_n) {
-    typedef B6<WR> Cfg;
-    constexpr int BM = Cfg::BM, LR = Cfg::LR, NB = Cfg::NB, PL = Cfg::PL, BUF = Cfg::BUF;
+    typedef B6<WR> Tile;
+    constexpr int BM = Tile::BM, NB = Tile::NB;
     extern __shared__ __attribute__((aligned(16))) unsigned char b6_smem[];
     const int t = DX ? (int)blockIdx.y : a.t;
-    const int total = a.tiles_m * tiles_n, per = (total + 7) >> 3;
-    const int w = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+    const int total = a.tiles_m * tiles_n;
+    const int w = rnn_work_item(blockIdx.x, total);
     if (w >= total) return;
     const int tn = w / a.tiles_m, m0 = (w - tn * a.tiles_m) * BM, n0 = tn * B6_BN;       // row tiles of a column tile share its weight rows
     const int nprod = t < a.T ? a.n_t[t] : 0;
@@ -192,7 +174,6 @@ __global__ __launch_bounds__(128 * WR, 1) void k_gru_bgemm_x6(const GruBgArgs a,
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lk = lane >> 4;
     const int wr = wave >> 1, wu = wave & 1;   // wave tile: rows 32 wr .. + 32, columns 32 wu .. + 32
-    const int c4 = 4 * (tid & 7), lr = tid >> 3;
     const int kp = 3 * a.dqp, dg_ld = 4 * a.dqp;
     const int ns = m0 < nprod ? kp / GEMM_BK : 0;
     const bool live = m0 + 32 * wr < nprod;    // (wave-uniform)
@@ -200,70 +181,39 @@ __global__ __launch_bounds__(128 * WR, 1) void k_gru_bgemm_x6(const GruBgArgs a,
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     f32x4 acc[2][2] = {{zero, zero}, {zero, zero}}, acl[2][2] = {{zero, zero}, {zero, zero}};     // a1 w1 | the seven small plane products
     if (ns > 0) {
-        // loader: thread owns column quad c4 of tile rows lr + LR i: 2 of the A tile, NB of the weight tile (while inside its 64 rows)
+        const Tile tile(b6_smem);
+        // loader: the gate-gradient rows behind the A tile's rows, the column tile's rows of the transposed pack
         const float* aptr[2]; const float* bptr[NB];
-        bool bok[NB];
 #pragma unroll
-        for (int i = 0; i < 2; ++i) aptr[i] = a.dG + ((size_t)t * a.B + rnn_clamp_row(m0 + lr + LR * i, nprod)) * dg_ld + c4;
+        for (int i = 0; i < 2; ++i) aptr[i] = a.dG + ((size_t)t * a.B + rnn_clamp_row(m0 + tile.arow(i), nprod)) * dg_ld + tile.c4;
 #pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            bok[i] = lr + LR * i < B6_BN;                                        // (uniform over a wave: 8 rows per wave and pass)
-            bptr[i] = a.wT + (size_t)(n0 + (bok[i] ? lr + LR * i : lr)) * kp + c4;
-        }
+        for (int i = 0; i < NB; ++i) bptr[i] = a.wT + (size_t)(n0 + tile.wrow(i)) * kp + tile.c4;
         const int s_hn = 2 * a.dqp / GEMM_BK, skip = DX ? 0 : a.dqp;
         f32x4 va[2], vb[NB];
         auto issue = [&](int s) __attribute__((always_inline)) {
             const int ka = s * GEMM_BK + (s >= s_hn ? skip : 0);                 // (uniform)
 #pragma unroll
             for (int i = 0; i < 2; ++i) va[i] = *(const f32x4*)(aptr[i] + ka);
-#pragma unroll
-            for (int i = 0; i < NB; ++i)
-                if (bok[i]) vb[i] = *(const f32x4*)(bptr[i] + s * GEMM_BK);
+            tile.load_w(bptr, s, vb);
         };
-        auto store = [&](int buf) __attribute__((always_inline)) {
-            unsigned char* const base = b6_smem + buf * BUF + 2 * c4;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) rnn_split_store(va[i], base + (lr + LR * i) * B6_PB, PL);
-#pragma unroll
-            for (int i = 0; i < NB; ++i)
-                if (bok[i]) rnn_split_store(vb[i], base + (BM + lr + LR * i) * B6_PB, PL);
-        };
-        const int fragA = (32 * wr + li) * B6_PB + 16 * lk, fragB = (BM + 32 * wu + li) * B6_PB + 16 * lk;
-        auto compute = [&](int buf) __attribute__((always_inline)) {
-            const unsigned char* const base = b6_smem + buf * BUF;
-            rnn_bf16x8 af[2][3], bf[2][3];
-#pragma unroll
-            for (int p = 0; p < 3; ++p)
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    af[i][p] = *(const rnn_bf16x8*)(base + p * PL + fragA + 16 * i * B6_PB);
-                    bf[i][p] = *(const rnn_bf16x8*)(base + p * PL + fragB + 16 * i * B6_PB);
-                }
+        const int fragA = tile.frag_at(32 * wr + li), fragB = tile.frag_at(BM + 32 * wu + li);
+        auto compute = [&](int buf, int) __attribute__((always_inline)) {
+            x6_bf16x8 af[2][3], bf[2][3];
+            tile.read_a(buf, fragA, af);
+            tile.read_a(buf, fragB, bf);
             // small terms first; inside one product the four blocks alternate (a dependent MFMA is four issues away)
-            constexpr int PA[7] = {1, 2, 0, 1, 2, 0, 1}, PB[7] = {2, 1, 2, 1, 0, 1, 0};
 #pragma unroll
             for (int c = 0; c < 7; ++c)
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) acl[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][PA[c]], bf[j][PB[c]], acl[i][j], 0, 0, 0);
+                    for (int j = 0; j < 2; ++j) acl[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][X6S_A[c]], bf[j][X6S_B[c]], acl[i][j], 0, 0, 0);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][0], bf[j][0], acc[i][j], 0, 0, 0);
         };
-        // register-staged double-buffered LDS, one barrier per k-step: the loads of step s + 1 fly over the MFMAs of step s
-        issue(0); store(0);
-        __syncthreads();
-        int buf = 0;
-        for (int s = 0; s < ns; ++s) {
-            const bool more = s + 1 < ns;
-            if (more) issue(s + 1);
-            if (live) compute(buf);
-            if (more) store(buf ^ 1);
-            __syncthreads();
-            buf ^= 1;
-        }
+        tile.run(ns, live, va, vb, issue, [](int) {}, compute);
     }
 
     // epilogue (k_gru_bgemm's): C layout col = lane & 15, row = 4 (lane >> 4) + reg

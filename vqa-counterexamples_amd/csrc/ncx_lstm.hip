@@ -84,8 +84,7 @@ __global__ __launch_bounds__(256) void k_lstm_step(LstmStep a, int s, int layer_
     const int t = s - layer;
     // workgroup ids are dealt round-robin over the 8 XCDs (grid1 is a multiple of 8): the row tiles of one unit tile, which share its
     // weight rows, go to the same XCD's L2
-    const int per = (a.total + 7) >> 3;
-    const int w = (bid & 7) * per + (bid >> 3);
+    const int w = rnn_work_item(bid, a.total);
     if (w >= a.total) return;
     const int nt = a.n_t[t];
     const int j = w / a.tiles_m, m0 = (w - j * a.tiles_m) * RNN_BM;

@@ -7,19 +7,16 @@
 // exit before their first barrier, rows of E gathered by (clamped) word id on the load side, rows beyond n_t clamped to row n_t - 1 and
 // never stored, the ragged last k-step of the x and of the h segment zero filled, step 0 of a layer stops after the x columns, one
 // accumulator per gate, the layer's pointers picked by selects, and the epilogue is the shared one (lstm_cell_store, ncx_lstm.h).  What
-// differs is the product, which is k_gru_step_x6's (ncx_gru_x6.hip): every operand element is cut into three bf16 values by truncation
-// when its tile is stored to LDS (rnn_split_store, ncx_rnn.h; layer 0's tanh is taken before the cut, tanh(0) = 0 keeps the zero fill),
-// and six products per 16 x 16 x 32 block, a1 b3 + a2 b2 + a3 b1 + a1 b2 + a2 b1 + a1 b1 (small terms first), run on
-// v_mfma_f32_16x16x32_bf16 with fp32 accumulation; what is dropped is 2^-24 relative.  A non-finite table or weight value is outside the
-// contract (the cut computes Inf - Inf).
+// differs is the product, which is k_gru_step_x6's (ncx_gru_x6.hip): the operands are cut into three bf16 planes when their tile is stored
+// to LDS (layer 0's tanh is taken before the cut, tanh(0) = 0 keeps the zero fill) and six plane products per 16 x 16 x 32 block run with
+// fp32 accumulation -- the cut, the order of the products, what is dropped and what is outside the contract: ncx_x6.h.
 // One workgroup: 12 waves, 192 rows x the 128 weight rows (i, f, g, o) of one 32-unit block of the packed layout, read as ncx_lstm2_pack
-// left them.  The waves form a 6 x 2 grid, 32 rows x 16 units x 4 gates each (k_lstm_step's wave tile): per 32-deep k-step a wave reads 6
-// row and 12 weight fragments of 16 bytes and issues 48 MFMAs, one gate at a time so that only that gate's weight fragments are live
-// beside the eight accumulators; a wave whose 32 rows all lie beyond n_t takes part in the loads, the stores and the barriers and
-// multiplies nothing.  LDS, double buffered: three planes of [192 rows | 128 weight rows][32 k] bf16 at 80 bytes per row (plain 16-byte
-// fragment reads; lane group lk holds k = 8 lk .. 8 lk + 7 of both operands): 153 600 bytes, one workgroup per CU.  Register-staged, one
-// barrier per k-step: the loads of step s + 1 fly over the MFMAs of step s and are cut and stored to the other buffer after them; a
-// thread loads two quads of the row tile and up to two of the weight tile per k-step.
+// left them, in the LDS row tile RnnX6Tile<6, 128> (ncx_rnn.h), whose geometry, cut-and-store, weight loads and x-then-h loads this
+// kernel uses; the loader coordinates, the fragment reads and the one-barrier loop are written out here, because on the tile's shared
+// loop this kernel measured 1.4 - 1.8 % slower; 153 600 bytes, one workgroup per CU.  The waves form a 6 x 2 grid,
+// 32 rows x 16 units x 4 gates each (k_lstm_step's wave tile): per 32-deep k-step a wave reads 6 row and 12 weight fragments of 16 bytes
+// and issues 48 MFMAs, one gate at a time so that only that gate's weight fragments are live beside the eight accumulators; a thread
+// loads two quads of the row tile and up to two of the weight tile.
 // Measured (B = 512, T = 26, 620 -> 1200, ms per encode, every question 26 words / uniform 3..26 / VQA-like; the fp32 kernel 6.54 / 6.33 /
 // 2.64, torch 6.37 / 6.34 / 6.30 in the same run): 128 rows with 8 waves 5.64 / 5.13 / 2.00 -- 2 layers x 4 row tiles x 38 unit blocks = 304
 // workgroups for 256 CUs, a second round of 48; 192 rows with 12 waves 3.84 / 3.59 / 1.53 -- 228 workgroups, one round.  Two gates at a
@@ -36,35 +33,21 @@ using namespace ncx;
 #endif
 
 namespace {
-constexpr int L6_WR = NCX_LSTM_X6_WR;                    // wave rows of the L6_WR x 2 wave grid
-constexpr int L6_BM = 32 * L6_WR;                        // rows (questions) per workgroup
-constexpr int L6_T = 128 * L6_WR;                        // threads
-constexpr int L6_LR = L6_T / 8;                          // tile rows one pass of the loader covers (8 threads per row)
-constexpr int L6_WROWS = 4 * RNN_BU;                     // weight rows of a tile
-constexpr int L6_NB = (L6_WROWS + L6_LR - 1) / L6_LR;    // passes over the 128 weight rows
-constexpr int L6_PB = 80;                                // bytes per LDS row of one plane: 32 bf16 + 16 (k_gru_step_x6's pitch)
-constexpr int L6_ROWS = L6_BM + L6_WROWS;                // 320 tile rows: the A rows, then the weight rows
-constexpr int L6_PL = L6_ROWS * L6_PB, L6_BUF = 3 * L6_PL;      // one plane, one buffer (three planes)
-constexpr int L6_LDS = 2 * L6_BUF;                       // 153 600 bytes
-static_assert(GEMM_BK == 32, "one k-step is one MFMA depth");
-static_assert(L6_LDS <= 160 * 1024, "LDS");
-static_assert(L6_BM == 2 * L6_LR, "the loader takes the A tile in two passes");
+typedef RnnX6Tile<NCX_LSTM_X6_WR, 4 * RNN_BU> L6;        // 192 rows | the 128 weight rows of a unit block: 153 600 bytes
 }  // namespace
 
 // grid = (layers of this launch) x grid1; workgroups [0, grid1) run layer `layer_base`, [grid1, 2 grid1) layer 1.  KEEP as k_lstm_step.
 template <bool KEEP>
-__global__ __launch_bounds__(L6_T, 1) void k_lstm_step_x6(LstmStep a, int s, int layer_base, LstmKeep<KEEP> keep) {
+__global__ __launch_bounds__(L6::T, 1) void k_lstm_step_x6(LstmStep a, int s, int layer_base, LstmKeep<KEEP> keep) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds6[];
     const int second = (int)blockIdx.x >= a.grid1;
     const int layer = layer_base + second, bid = (int)blockIdx.x - second * a.grid1;
     const int t = s - layer;
-    // workgroup ids are dealt round-robin over the 8 XCDs (grid1 is a multiple of 8): the row tiles of one unit block, which share its
-    // weight rows, go to the same XCD's L2
-    const int per = (a.total + 7) >> 3;
-    const int w = (bid & 7) * per + (bid >> 3);
+    // (grid1 is a multiple of 8) the row tiles of one unit block, which share its weight rows, go to the same XCD's L2
+    const int w = rnn_work_item(bid, a.total);
     if (w >= a.total) return;
     const int nt = a.n_t[t];
-    const int j = w / a.tiles_m, m0 = (w - j * a.tiles_m) * L6_BM;
+    const int j = w / a.tiles_m, m0 = (w - j * a.tiles_m) * L6::BM;
     if (m0 >= nt) return;                      // (uniform: before any barrier)
 
     const int H = a.H, in = layer ? H : a.emb;
@@ -86,14 +69,16 @@ __global__ __launch_bounds__(L6_T, 1) void k_lstm_step_x6(LstmStep a, int s, int
     const int li = lane & 15, lk = lane >> 4;
     const int wr = wave >> 1, wu = wave & 1;   // wave tile: rows 32 wr .. + 32, units 16 wu .. + 16
     const int c4 = 4 * (tid & 7), lr = tid >> 3;
+    const L6 tile(lds6);
     const bool live = m0 + 32 * wr < nt;       // (wave-uniform) a wave whose 32 rows are all beyond n_t loads and stores, and multiplies nothing
 
-    // loader: thread owns column quad c4 of tile rows lr + L6_LR i: 2 of the A tile, L6_NB of the weight tile (while inside its 128 rows)
-    const float* xptr[2]; const float* hptr[2]; const float* bptr[L6_NB];
-    bool bok[L6_NB];
+    // loader: thread owns column quad c4 of tile rows lr + L6::LR i: 2 of the A tile, L6::NB of the weight tile (while inside its 128 rows;
+    // c4, lr and bok are the tile's own values, restated: see the file header)
+    const float* xptr[2]; const float* hptr[2]; const float* bptr[L6::NB];
+    bool bok[L6::NB];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        const int row = min(m0 + lr + L6_LR * i, nt - 1);                    // rows beyond n_t: clamped here, never stored
+        const int row = min(m0 + lr + L6::LR * i, nt - 1);                    // rows beyond n_t: clamped here, never stored
         if (layer == 0) {
             int wid = a.wids[(size_t)a.perm[row] * a.T + t];
             wid = min(max(wid, 0), a.V1 - 1);                                // an id out of range is never an address (k_rnn_plan flags it)
@@ -105,26 +90,16 @@ __global__ __launch_bounds__(L6_T, 1) void k_lstm_step_x6(LstmStep a, int s, int
         hptr[i] = h_prev + (size_t)row * H;
     }
 #pragma unroll
-    for (int i = 0; i < L6_NB; ++i) {
-        bok[i] = lr + L6_LR * i < L6_WROWS;                                  // (uniform over a wave: 8 rows per wave and pass)
-        bptr[i] = packed + ((size_t)j * L6_WROWS + (bok[i] ? lr + L6_LR * i : lr)) * kp + c4;
+    for (int i = 0; i < L6::NB; ++i) {
+        bok[i] = lr + L6::LR * i < L6::WROWS;                                  // (uniform over a wave: 8 rows per wave and pass)
+        bptr[i] = packed + ((size_t)j * L6::WROWS + (bok[i] ? lr + L6::LR * i : lr)) * kp + c4;
     }
     const int nx = kx / GEMM_BK, ns = nx + (t > 0 ? (kp - kx) / GEMM_BK : 0);
 
-    f32x4 va[2], vb[L6_NB];
+    f32x4 va[2], vb[L6::NB];
     auto issue = [&](int ks) __attribute__((always_inline)) {
-        const bool ish = ks >= nx;
-        const int k = (ish ? ks - nx : ks) * GEMM_BK + c4, cols = ish ? H : in;
-        if (k - c4 + GEMM_BK <= cols) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) va[i] = *(const f32x4u*)((ish ? hptr[i] : xptr[i]) + k);
-        } else {                               // the ragged last k-step of a segment: guarded, zero filled
-#pragma unroll
-            for (int i = 0; i < 2; ++i) va[i] = load4(ish ? hptr[i] : xptr[i], k, cols);
-        }
-#pragma unroll
-        for (int i = 0; i < L6_NB; ++i)
-            if (bok[i]) vb[i] = *(const f32x4*)(bptr[i] + ks * GEMM_BK);
+        rnn_xh_load(ks, nx, c4, xptr, in, hptr, H, va);
+        tile.load_w(bptr, ks, vb);
     };
     auto store = [&](int buf, int ks) __attribute__((always_inline)) {
         if (layer == 0 && ks < nx) {           // x = tanh(E[wid]), before the cut; tanh(0) = 0 keeps the zero fill
@@ -133,36 +108,30 @@ __global__ __launch_bounds__(L6_T, 1) void k_lstm_step_x6(LstmStep a, int s, int
 #pragma unroll
                 for (int e = 0; e < 4; ++e) va[i][e] = tanhf(va[i][e]);
         }
-        unsigned char* const base = lds6 + buf * L6_BUF + 2 * c4;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) rnn_split_store(va[i], base + (lr + L6_LR * i) * L6_PB, L6_PL);
-#pragma unroll
-        for (int i = 0; i < L6_NB; ++i)
-            if (bok[i]) rnn_split_store(vb[i], base + (L6_BM + lr + L6_LR * i) * L6_PB, L6_PL);
+        tile.store(buf, va, vb);
     };
 
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     f32x4 acc[4][2] = {{zero, zero}, {zero, zero}, {zero, zero}, {zero, zero}};     // [gate i f g o][row half]
-    const int fragA = (32 * wr + li) * L6_PB + 16 * lk, fragB = (L6_BM + 16 * wu + li) * L6_PB + 16 * lk;
+    const int fragA = (32 * wr + li) * L6::PB + 16 * lk, fragB = (L6::BM + 16 * wu + li) * L6::PB + 16 * lk;
     auto compute = [&](int buf) __attribute__((always_inline)) {
-        const unsigned char* const base = lds6 + buf * L6_BUF;
-        rnn_bf16x8 af[2][3];
+        const unsigned char* const base = lds6 + buf * L6::BUF;
+        x6_bf16x8 af[2][3];
 #pragma unroll
         for (int p = 0; p < 3; ++p)
 #pragma unroll
-            for (int i = 0; i < 2; ++i) af[i][p] = *(const rnn_bf16x8*)(base + p * L6_PL + fragA + 16 * i * L6_PB);
+            for (int i = 0; i < 2; ++i) af[i][p] = *(const x6_bf16x8*)(base + p * L6::PL + fragA + 16 * i * L6::PB);
         // the six plane products, small terms first, one gate at a time: only that gate's weight fragments are live, and its two
         // accumulators alternate
-        constexpr int PA[6] = {0, 1, 2, 0, 1, 0}, PB[6] = {2, 1, 0, 1, 0, 0};
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            rnn_bf16x8 bf[3];
+            x6_bf16x8 bf[3];
 #pragma unroll
-            for (int p = 0; p < 3; ++p) bf[p] = *(const rnn_bf16x8*)(base + p * L6_PL + fragB + g * RNN_BU * L6_PB);
+            for (int p = 0; p < 3; ++p) bf[p] = *(const x6_bf16x8*)(base + p * L6::PL + fragB + g * RNN_BU * L6::PB);
 #pragma unroll
             for (int c = 0; c < 6; ++c)
 #pragma unroll
-                for (int i = 0; i < 2; ++i) acc[g][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][PA[c]], bf[PB[c]], acc[g][i], 0, 0, 0);
+                for (int i = 0; i < 2; ++i) acc[g][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][X6_A[c]], bf[X6_B[c]], acc[g][i], 0, 0, 0);
         }
     };
 
@@ -205,11 +174,11 @@ namespace ncx {
 template <bool KEEP>
 static int lstm2_launch_x6(int B, int T, LstmStep a, const LstmKeep<KEEP>& keep, hipStream_t st) {
     static DevMask attr_set{0};
-    NCX_HIP_TRY(set_max_lds_once(attr_set, (const void*)k_lstm_step_x6<KEEP>, L6_LDS));
-    a.tiles_m = (int)cdiv(B, L6_BM); a.total = a.tiles_m * (int)cdiv(a.H, RNN_BU); a.grid1 = (int)(8 * cdiv(a.total, 8));
+    NCX_HIP_TRY(set_max_lds_once(attr_set, (const void*)k_lstm_step_x6<KEEP>, L6::LDS));
+    a.tiles_m = (int)cdiv(B, L6::BM); a.total = a.tiles_m * (int)cdiv(a.H, RNN_BU); a.grid1 = (int)(8 * cdiv(a.total, 8));
     for (int s = 0; s <= T; ++s) {             // every launch is issued: how many rows a step has is known on the device only
         const int layers = (s < T) + (s >= 1);
-        hipLaunchKernelGGL(k_lstm_step_x6<KEEP>, dim3((unsigned)(layers * a.grid1)), dim3(L6_T), L6_LDS, st, a, s, s < T ? 0 : 1, keep);
+        hipLaunchKernelGGL(k_lstm_step_x6<KEEP>, dim3((unsigned)(layers * a.grid1)), dim3(L6::T), L6::LDS, st, a, s, s < T ? 0 : 1, keep);
         NCX_HIP_TRY(hipGetLastError());
     }
     return NCX_OK;

@@ -30,6 +30,7 @@
 #pragma once
 #include "ncx_internal.h"
 #include "ncx_adam.h"
+#include "ncx_x6.h"
 #include <type_traits>
 
 namespace ncx {
@@ -171,59 +172,33 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
                 for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i][e], bf[j][e], acc[i][j], 0, 0, 0);
     };
 
-    // ---- X6: operands as three bf16 planes (x = x1 + x2 + x3 exactly, by truncation, cut when the tile is stored to LDS), six products per
-    // 16 x 16 x 32 block on v_mfma_f32_16x16x32_bf16 with fp32 accumulation: what is dropped is 2^-24 relative.  A sub-step is one 16-row block
+    // ---- X6: operands as three bf16 planes, cut when the tile is stored to LDS, six plane products per 16 x 16 x 32 block with fp32
+    // accumulation (the cut, the products and the contract: ncx_x6.h).  A sub-step is one 16-row block
     // row of the wave (6 WN MFMAs); the last block row of a step runs after the barrier, over the first reads of the next buffer.
     constexpr bool X6 = CFG::X6;
     static_assert(!X6 || (VFOLD && BM == 192 && WM == 3 && WN == 2 && DEPTH == 2), "X6: the 8-wave 192 x 64 fold form only");
-    typedef __bf16 mbf16x8 __attribute__((ext_vector_type(8)));
-    typedef unsigned int mu32x2 __attribute__((ext_vector_type(2)));
     constexpr int P6 = MF6_P, A6_PL = BML * P6, PL6 = (BML + BN) * P6, BUF6 = 3 * PL6;
     unsigned char* const lds6 = (unsigned char*)mf_smem;
-    mbf16x8 xa[2][3], xb[2][X6 ? WN : 1][3];             // [alternating set][plane]; [parity of the step][column block][plane]
-    auto split_store6 = [&](f32x4 v, unsigned char* base) __attribute__((always_inline)) {
-        unsigned p1[4], p2[4], p3[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float xj = v[j];               // (a scalar copy first: __builtin_bit_cast applied to the vector element itself reads element 0 -- hipcc 7.2)
-            p1[j] = __builtin_bit_cast(unsigned, xj) & 0xFFFF0000u;
-            const float r1 = xj - __builtin_bit_cast(float, p1[j]);
-            p2[j] = __builtin_bit_cast(unsigned, r1) & 0xFFFF0000u;
-            const float r2 = r1 - __builtin_bit_cast(float, p2[j]);
-            p3[j] = __builtin_bit_cast(unsigned, r2);
-        }
-        const mu32x2 w1 = {__builtin_amdgcn_perm(p1[1], p1[0], 0x07060302u), __builtin_amdgcn_perm(p1[3], p1[2], 0x07060302u)};
-        const mu32x2 w2 = {__builtin_amdgcn_perm(p2[1], p2[0], 0x07060302u), __builtin_amdgcn_perm(p2[3], p2[2], 0x07060302u)};
-        const mu32x2 w3 = {__builtin_amdgcn_perm(p3[1], p3[0], 0x07060302u), __builtin_amdgcn_perm(p3[3], p3[2], 0x07060302u)};
-        *(mu32x2*)(base) = w1; *(mu32x2*)(base + PL6) = w2; *(mu32x2*)(base + 2 * PL6) = w3;
-    };
-    auto read_a6 = [&](int buf, int i, mbf16x8 (&f)[3]) __attribute__((always_inline)) {
+    x6_bf16x8 xa[2][3], xb[2][X6 ? WN : 1][3];             // [alternating set][plane]; [parity of the step][column block][plane]
+    auto read_a6 = [&](int buf, int i, x6_bf16x8 (&f)[3]) __attribute__((always_inline)) {
         const unsigned char* a = lds6 + buf * BUF6 + (wm0 + 16 * i + li) * P6 + 16 * lk;
 #pragma unroll
-        for (int p = 0; p < 3; ++p) f[p] = *(const mbf16x8*)(a + p * PL6);
+        for (int p = 0; p < 3; ++p) f[p] = *(const x6_bf16x8*)(a + p * PL6);
     };
-    auto read_b6 = [&](int buf, mbf16x8 (&f)[X6 ? WN : 1][3]) __attribute__((always_inline)) {
+    auto read_b6 = [&](int buf, x6_bf16x8 (&f)[X6 ? WN : 1][3]) __attribute__((always_inline)) {
         const unsigned char* b = lds6 + buf * BUF6 + A6_PL + (wn0 + li) * P6 + 16 * lk;
 #pragma unroll
         for (int j = 0; j < (X6 ? WN : 1); ++j)
 #pragma unroll
-            for (int p = 0; p < 3; ++p) f[j][p] = *(const mbf16x8*)(b + j * 16 * P6 + p * PL6);
+            for (int p = 0; p < 3; ++p) f[j][p] = *(const x6_bf16x8*)(b + j * 16 * P6 + p * PL6);
     };
     // the 6 WN MFMAs of block row i; the column blocks alternate (a dependent MFMA is WN issues away); small terms first
-    auto mfma6 = [&](const mbf16x8 (&a)[3], const mbf16x8 (&b)[X6 ? WN : 1][3], f32x4 (&c)[WN]) __attribute__((always_inline)) {
+    auto mfma6 = [&](const x6_bf16x8 (&a)[3], const x6_bf16x8 (&b)[X6 ? WN : 1][3], f32x4 (&c)[WN]) __attribute__((always_inline)) {
         if constexpr (X6) {
 #pragma unroll
-            for (int j = 0; j < WN; ++j) c[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[j][2], c[j], 0, 0, 0);
+            for (int q = 0; q < 6; ++q)
 #pragma unroll
-            for (int j = 0; j < WN; ++j) c[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[j][1], c[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < WN; ++j) c[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[j][0], c[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < WN; ++j) c[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[j][1], c[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < WN; ++j) c[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[j][0], c[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < WN; ++j) c[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[j][0], c[j], 0, 0, 0);
+                for (int j = 0; j < WN; ++j) c[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[X6_A[q]], b[j][X6_B[q]], c[j], 0, 0, 0);
         }
     };
 
@@ -320,14 +295,14 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
 #pragma unroll
                     for (int j = 0; j < 4; ++j) v[j] = __builtin_amdgcn_exp2f(__builtin_fmaf(v[j], 1.44269504088896341f, -lse_c[i]));
                 }
-                if constexpr (X6) split_store6(v, lds6 + buf * BUF6 + (trow + RP * i) * P6 + 8 * quad);
+                if constexpr (X6) x6_split_store(v, lds6 + buf * BUF6 + (trow + RP * i) * P6 + 8 * quad, PL6);
                 else
                 *(f32x4*)(lds_a + buf * BML * P + (trow + RP * i) * P + 4 * quad) = v;       // (rows >= BM: spare LDS rows, never read)
             }
 #pragma unroll
             for (int i = 0; i < NB; ++i) {
                 if (i + NA < h0 || i + NA >= h1) continue;
-                if constexpr (X6) split_store6(vb[S][i], lds6 + buf * BUF6 + A6_PL + (trow + RP * i) * P6 + 8 * quad);
+                if constexpr (X6) x6_split_store(vb[S][i], lds6 + buf * BUF6 + A6_PL + (trow + RP * i) * P6 + 8 * quad, PL6);
                 else
                 *(f32x4*)(lds_b + buf * BN * P + (trow + RP * i) * P + 4 * quad) = vb[S][i];
             }
@@ -395,7 +370,7 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
                 }
                 if (LAST) {                              // nothing is carried over a segment switch: block row 2 now, zeros into the set the next segment's first step multiplies first
                     mfma6(xa[PAR], xb[PAR], acc[2]);
-                    const mbf16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
+                    const x6_bf16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
                     for (int p = 0; p < 3; ++p) { xa[0][p] = z8; xa[1][p] = z8; }
                 }
@@ -835,16 +810,12 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
             vb4[SS_][0] = __builtin_bit_cast(f32x4, (bu32x4)__builtin_amdgcn_raw_buffer_load_b128(rsK, voB, so, 0));
             vb4[SS_][1] = __builtin_bit_cast(f32x4, (bu32x4)__builtin_amdgcn_raw_buffer_load_b128(rsM, voB, so, 0));
         };
-        auto split3 = [&](const float (&x)[4], unsigned (&w1)[2], unsigned (&w2)[2], unsigned (&w3)[2]) __attribute__((always_inline)) {
+        // x6_cut4 (ncx_x6.h) with the three planes' v_perm_b32 interleaved: this fold's schedule follows the order they are written in
+        // (with x6_cut4's order 4 278 lines of the unit's assembly move), so it keeps the order it was measured with
+        auto cut4_fold = [&](const float (&x)[4], unsigned (&w1)[2], unsigned (&w2)[2], unsigned (&w3)[2]) __attribute__((always_inline)) {
             unsigned p1[4], p2[4], p3[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                p1[j] = __builtin_bit_cast(unsigned, x[j]) & 0xFFFF0000u;
-                const float r1 = x[j] - __builtin_bit_cast(float, p1[j]);
-                p2[j] = __builtin_bit_cast(unsigned, r1) & 0xFFFF0000u;
-                const float r2 = r1 - __builtin_bit_cast(float, p2[j]);
-                p3[j] = __builtin_bit_cast(unsigned, r2);
-            }
+            for (int j = 0; j < 4; ++j) x6_cut1(x[j], p1[j], p2[j], p3[j]);
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 w1[h] = __builtin_amdgcn_perm(p1[2 * h + 1], p1[2 * h], 0x07060302u);
@@ -861,9 +832,9 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
                 const f32x4 v = va4[SS_][i];
                 const float x[4] = {v[0], v[1], v[2], v[3]};
                 unsigned w1[2], w2[2], w3[2];
-                split3(x, w1, w2, w3);
+                cut4_fold(x, w1, w2, w3);
                 unsigned char* d = bb + (trow + 64 * i) * P6 + 8 * quad;
-                *(mu32x2*)(d) = mu32x2{w1[0], w1[1]}; *(mu32x2*)(d + A_PLX) = mu32x2{w2[0], w2[1]}; *(mu32x2*)(d + 2 * A_PLX) = mu32x2{w3[0], w3[1]};
+                *(x6_u32x2*)(d) = x6_u32x2{w1[0], w1[1]}; *(x6_u32x2*)(d + A_PLX) = x6_u32x2{w2[0], w2[1]}; *(x6_u32x2*)(d + 2 * A_PLX) = x6_u32x2{w3[0], w3[1]};
             }
             if (part == 1) *(float*)(bb + VO_OFF + (vo_t * 32 + vo_c) * 4) = vv[SS_];
             if (part == 2) {
@@ -877,18 +848,18 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc4[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         struct Raw { f32x4 wk[2], wm[2]; };                          // W_k / W_m [n = 16 j + li][k = 8 lk .. 8 lk + 7] of one column block
-        const mbf16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
-        mbf16x8 af[2][2][3];                                        // [set][block row][plane]: A fragments of a step (set = parity of the step)
-        mbf16x8 bq[2][3];                                           // effective-weight planes of a column block, two in flight
+        const x6_bf16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
+        x6_bf16x8 af[2][2][3];                                        // [set][block row][plane]: A fragments of a step (set = parity of the step)
+        x6_bf16x8 bq[2][3];                                           // effective-weight planes of a column block, two in flight
         f32x4 vo[2];                                                // v_o[w][8 lk .. 8 lk + 7]
 #pragma unroll
         for (int p = 0; p < 3; ++p) { af[1][0][p] = z8; af[1][1][p] = z8; bq[1][p] = z8; }
-        auto read_af = [&](int buf, mbf16x8 (&f)[2][3]) __attribute__((always_inline)) {
+        auto read_af = [&](int buf, x6_bf16x8 (&f)[2][3]) __attribute__((always_inline)) {
             const unsigned char* a = lds6 + buf * BUFX + (24 * wave + li) * P6 + 16 * lk;
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int p = 0; p < 3; ++p) f[i][p] = *(const mbf16x8*)(a + i * 16 * P6 + p * A_PLX);
+                for (int p = 0; p < 3; ++p) f[i][p] = *(const x6_bf16x8*)(a + i * 16 * P6 + p * A_PLX);
         };
         auto read_vo = [&](int buf) __attribute__((always_inline)) {
             const unsigned char* v = lds6 + buf * BUFX + VO_OFF + (wave * 32 + 8 * lk) * 4;
@@ -899,7 +870,7 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
             r.wk[0] = *(const f32x4*)(b); r.wk[1] = *(const f32x4*)(b + 16);
             r.wm[0] = *(const f32x4*)(b + 64 * P * 4); r.wm[1] = *(const f32x4*)(b + 64 * P * 4 + 16);
         };
-        auto build = [&](const Raw& r, mbf16x8 (&o)[3]) __attribute__((always_inline)) {
+        auto build = [&](const Raw& r, x6_bf16x8 (&o)[3]) __attribute__((always_inline)) {
             unsigned w1[4], w2[4], w3[4];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -907,28 +878,20 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { const float v_ = vo[h][e], m_ = r.wm[h][e], k_ = r.wk[h][e]; x[e] = __builtin_fmaf(v_, m_, k_); }
                 unsigned a1[2], a2[2], a3[2];
-                split3(x, a1, a2, a3);
+                cut4_fold(x, a1, a2, a3);
                 w1[2 * h] = a1[0]; w1[2 * h + 1] = a1[1]; w2[2 * h] = a2[0]; w2[2 * h + 1] = a2[1]; w3[2 * h] = a3[0]; w3[2 * h + 1] = a3[1];
             }
             typedef unsigned int mu32x4 __attribute__((ext_vector_type(4)));
-            o[0] = __builtin_bit_cast(mbf16x8, mu32x4{w1[0], w1[1], w1[2], w1[3]});
-            o[1] = __builtin_bit_cast(mbf16x8, mu32x4{w2[0], w2[1], w2[2], w2[3]});
-            o[2] = __builtin_bit_cast(mbf16x8, mu32x4{w3[0], w3[1], w3[2], w3[3]});
+            o[0] = __builtin_bit_cast(x6_bf16x8, mu32x4{w1[0], w1[1], w1[2], w1[3]});
+            o[1] = __builtin_bit_cast(x6_bf16x8, mu32x4{w2[0], w2[1], w2[2], w2[3]});
+            o[2] = __builtin_bit_cast(x6_bf16x8, mu32x4{w3[0], w3[1], w3[2], w3[3]});
         };
         // the 12 MFMAs of column block j: the two block rows alternate; small terms first
-        auto fmfma = [&](const mbf16x8 (&a)[2][3], const mbf16x8 (&b)[3], int j) __attribute__((always_inline)) {
+        auto fmfma = [&](const x6_bf16x8 (&a)[2][3], const x6_bf16x8 (&b)[3], int j) __attribute__((always_inline)) {
 #pragma unroll
-            for (int i = 0; i < 2; ++i) acc4[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][0], b[2], acc4[i][j], 0, 0, 0);
+            for (int q = 0; q < 6; ++q)
 #pragma unroll
-            for (int i = 0; i < 2; ++i) acc4[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][1], b[1], acc4[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) acc4[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][2], b[0], acc4[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) acc4[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][0], b[1], acc4[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) acc4[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][1], b[0], acc4[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) acc4[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][0], b[0], acc4[i][j], 0, 0, 0);
+                for (int i = 0; i < 2; ++i) acc4[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][X6_A[q]], b[X6_B[q]], acc4[i][j], 0, 0, 0);
         };
         auto pin6 = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -1036,7 +999,7 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
     if constexpr (VFOLD) {
         if constexpr (X6) {
             run_vfold6(args.seg[0], NSEG > 1);
-            const mbf16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};       // (here, not at the top: 72 registers of zeros would live through the fold)
+            const x6_bf16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};       // (here, not at the top: 72 registers of zeros would live through the fold)
 #pragma unroll
             for (int q = 0; q < 2; ++q)
 #pragma unroll

@@ -3,6 +3,7 @@
 #pragma once
 #include "ncx_internal.h"
 #include "ncx_wave.h"
+#include "ncx_x6.h"
 
 using namespace ncx;
 
@@ -188,11 +189,9 @@ __global__ __launch_bounds__(256, 2) void k_att_logits(const AttArgs a, const At
 }
 
 // ---- the same product on the bf16 matrix path with fp32-grade operands (NCX_F_X6; not the default) ----------------------------------
-// As k_dw_tn8_x6 and the X6 form of k_main_fwd: every operand element is cut into three bf16 values by truncation, x = x1 + x2 + x3
-// exactly (x1 = x & 0xFFFF0000, x2 = (x - x1) & 0xFFFF0000, x3 = x - x1 - x2), when the tile is stored to LDS; six products per
-// 16 x 16 x 32 block, a1 x3 + a2 x2 + a3 x1 + a1 x2 + a2 x1 + a1 x1 (small terms first), run on v_mfma_f32_16x16x32_bf16 with fp32
-// accumulation.  What is dropped is 2^-24 relative.  A non-finite map or weight value is outside the contract: the cut computes
-// Inf - Inf.
+// As k_dw_tn8_x6 and the X6 form of k_main_fwd: the operands are cut into three bf16 planes when the tile is stored to LDS and six plane
+// products per 16 x 16 x 32 block run with fp32 accumulation -- the cut, the order of the products, what is dropped and what is outside
+// the contract (a non-finite map or weight value): ncx_x6.h.
 // One workgroup: 8 waves, TM positions of one image x 128 hidden columns (two slab slots), one 32-channel step = one MFMA depth.
 // The waves form a 2 x 4 grid: 7 (TM = 208: a 224-row grid, the last 16 rows are loader padding and are dropped) or 2 block rows x 2
 // column blocks each, so a map fragment is read by 4 waves and serves 12 MFMAs.  LDS, double-buffered: three planes of the map tile in
@@ -205,9 +204,6 @@ __global__ __launch_bounds__(256, 2) void k_att_logits(const AttArgs a, const At
 // form 199 VGPRs, 153 600 bytes of LDS, 2 waves per SIMD; 64-row form 111 VGPRs, 92 160 bytes, 4 waves per SIMD by registers; by LDS
 // both run one workgroup per CU, i.e. 2 resident waves per SIMD; no scratch, for both values of TRAIN.  The epilogue, the slab layout and the order k_att_pool sums it in are those of the fp32 kernel.
 constexpr int ATT6_BN = 128, ATT6_T = 512, ATT6_PB = 80;
-typedef __bf16 att_bf16x8 __attribute__((ext_vector_type(8)));
-typedef short att_s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int att_u32x2 __attribute__((ext_vector_type(2)));
 
 template <int TM> struct AttCfg6 {
     static constexpr int LOAD_M = (TM + 31) / 32 * 32;
@@ -282,24 +278,6 @@ __global__ __launch_bounds__(ATT6_T, 1) void k_att_logits_x6(const AttArgs a, co
             for (int i = 0; i < NB; ++i) vb[S][i] = load_window(brp[i], k + 4 * bq, dv);
         }
     };
-    // x -> three bf16 planes (four values: one 8-byte store per plane)
-    auto split_store = [&](f32x4 v, unsigned char* base) __attribute__((always_inline)) {
-        unsigned p1[4], p2[4], p3[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float xj = v[j];               // (a scalar copy first: __builtin_bit_cast applied to the vector element itself reads element 0 -- hipcc 7.2)
-            p1[j] = __builtin_bit_cast(unsigned, xj) & 0xFFFF0000u;
-            const float r1 = xj - __builtin_bit_cast(float, p1[j]);
-            p2[j] = __builtin_bit_cast(unsigned, r1) & 0xFFFF0000u;
-            const float r2 = r1 - __builtin_bit_cast(float, p2[j]);
-            p3[j] = __builtin_bit_cast(unsigned, r2);            // (at most 8 significant bits are left: the high half holds them all)
-        }
-        // v_perm_b32: the high halves of two dwords -> one dword (the even element in the low half)
-        const att_u32x2 w1 = {__builtin_amdgcn_perm(p1[1], p1[0], 0x07060302u), __builtin_amdgcn_perm(p1[3], p1[2], 0x07060302u)};
-        const att_u32x2 w2 = {__builtin_amdgcn_perm(p2[1], p2[0], 0x07060302u), __builtin_amdgcn_perm(p2[3], p2[2], 0x07060302u)};
-        const att_u32x2 w3 = {__builtin_amdgcn_perm(p3[1], p3[0], 0x07060302u), __builtin_amdgcn_perm(p3[3], p3[2], 0x07060302u)};
-        *(att_u32x2*)(base) = w1; *(att_u32x2*)(base + PL) = w2; *(att_u32x2*)(base + 2 * PL) = w3;
-    };
     // part s < NA: map item s; part NA + i: weight item i.  Positions beyond P, channels beyond dv and hidden rows beyond dh_att are zero.
     auto store = [&](auto set_c, int k, int buf, int s0, int s1) __attribute__((always_inline)) {
         constexpr int S = decltype(set_c)::value;
@@ -315,7 +293,7 @@ __global__ __launch_bounds__(ATT6_T, 1) void k_att_logits_x6(const AttArgs a, co
             if (NA * T != QA && tid + T * i >= QA) continue;
             f32x4 v = fix_window(va[S][i], acol[i], P);
             if (ragged && k + arow[i] >= dv) v = zero;
-            split_store(v, base + adst[i]);
+            x6_split_store(v, base + adst[i], PL);
         }
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
@@ -323,7 +301,7 @@ __global__ __launch_bounds__(ATT6_T, 1) void k_att_logits_x6(const AttArgs a, co
             f32x4 v = vb[S][i];
             if (ragged) v = fix_window(v, k + 4 * bq, dv);
             if (!bok[i]) v = zero;
-            split_store(v, base + bdst[i]);
+            x6_split_store(v, base + bdst[i], PL);
         }
     };
 
@@ -333,7 +311,6 @@ __global__ __launch_bounds__(ATT6_T, 1) void k_att_logits_x6(const AttArgs a, co
 #pragma unroll
         for (int j = 0; j < WN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    typedef __attribute__((address_space(3))) att_s16x4* lds_s16x4;
     const int tq = li >> 2, tp = li & 3;
     const int fragA = (4 * lk + tq) * PA + (wm0 + 4 * tp) * 2, fragB = A_PL + (wn0 + li) * PB + 16 * lk;
     constexpr int NP = NA + NB;                        // parts of the next tile's store, spread over the block rows of this step
@@ -347,21 +324,16 @@ __global__ __launch_bounds__(ATT6_T, 1) void k_att_logits_x6(const AttArgs a, co
         const bool has_next = k + BK < dv;
         if (k + 2 * BK < dv) issue(par_c, k + 2 * BK);
         const unsigned char* const base = lds + PAR * BUF;
-        att_bf16x8 bf[WN][3];
+        x6_bf16x8 bf[WN][3];
 #pragma unroll
         for (int j = 0; j < WN; ++j)
 #pragma unroll
-            for (int p = 0; p < 3; ++p) bf[j][p] = *(const att_bf16x8*)(base + p * PL + fragB + j * 16 * PB);
+            for (int p = 0; p < 3; ++p) bf[j][p] = *(const x6_bf16x8*)(base + p * PL + fragB + j * 16 * PB);
 #pragma unroll
         for (int i = 0; i < WM; ++i) {
-            att_bf16x8 af[3];
+            x6_bf16x8 af[3];
 #pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                const unsigned char* ta = base + p * PL + fragA + i * 32;
-                const att_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(ta));
-                const att_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(ta + 16 * PA));
-                af[p] = __builtin_bit_cast(att_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-            }
+            for (int p = 0; p < 3; ++p) af[p] = x6_frag_tr(base + p * PL + fragA + i * 32, PA);
             // the 12 MFMAs of block row i: the two column blocks alternate (a dependent MFMA is two issues away); small terms first
 #ifdef NCX_ATT6_ABLATE_MFMA      // timing experiment only: one product of the six (every fragment read stays live)
 #pragma unroll
@@ -370,17 +342,9 @@ __global__ __launch_bounds__(ATT6_T, 1) void k_att_logits_x6(const AttArgs a, co
             for (int j = 0; j < WN; ++j) asm volatile("" :: "v"(af[1]), "v"(af[2]), "v"(bf[j][1]), "v"(bf[j][2]));
 #else
 #pragma unroll
-            for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bf[j][2], acc[i][j], 0, 0, 0);
+            for (int c = 0; c < 6; ++c)
 #pragma unroll
-            for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bf[j][1], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[2], bf[j][0], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bf[j][1], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bf[j][0], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bf[j][0], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[X6_A[c]], bf[j][X6_B[c]], acc[i][j], 0, 0, 0);
 #endif
             if (has_next) store(SN{}, k + BK, PAR ^ 1, i * NP / WM, (i + 1) * NP / WM);
         }

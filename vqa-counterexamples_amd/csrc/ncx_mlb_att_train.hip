@@ -334,8 +334,8 @@ __global__ __launch_bounds__(256, 2) void k_att_dwv(const DwvArgs a) {
             }
 }
 // ---- the same product on the bf16 matrix path with fp32-grade operands (NCX_F_X6; not the default) ----------------------------------
-// The cut, the six products and their order are those of k_att_logits_x6 (ncx_mlb_att.h), and so is the LDS image, with the roles
-// renamed: the operand whose k runs along rows is dXv [P positions][dh_att] (there the map [dv channels][P]) and goes to LDS in the
+// The cut, the six products and their order are those of ncx_x6.h, and the LDS image is that of k_att_logits_x6 (ncx_mlb_att.h) with
+// the roles renamed: the operand whose k runs along rows is dXv [P positions][dh_att] (there the map [dv channels][P]) and goes to LDS in the
 // global layout, three planes of [32 positions][DWV6_TH hidden] at a pitch of DWV6_TH * 2 + 32 bytes (8 consecutive position rows on
 // 8 distinct 32-byte bank groups), read through ds_read_b64_tr_b16; the operand whose k is contiguous is the map [dv][P] (there the
 // weight [dh_att][dv]), three planes of [128 channels][32 positions] at 80 bytes per row, read with plain 16-byte loads.  A transposed
@@ -417,23 +417,6 @@ __global__ __launch_bounds__(DWV6_T, 1) void k_att_dwv_x6(const DwvArgs a) {
             for (int i = 0; i < NB; ++i) vb[S][i] = load_window(mb + boff[i], k + 4 * bq, P);
         }
     };
-    // x -> three bf16 planes (four values: one 8-byte store per plane)
-    auto split_store = [&](f32x4 v, unsigned char* base) __attribute__((always_inline)) {
-        unsigned p1[4], p2[4], p3[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float xj = v[j];               // (a scalar copy first: __builtin_bit_cast applied to the vector element itself reads element 0 -- hipcc 7.2)
-            p1[j] = __builtin_bit_cast(unsigned, xj) & 0xFFFF0000u;
-            const float r1 = xj - __builtin_bit_cast(float, p1[j]);
-            p2[j] = __builtin_bit_cast(unsigned, r1) & 0xFFFF0000u;
-            const float r2 = r1 - __builtin_bit_cast(float, p2[j]);
-            p3[j] = __builtin_bit_cast(unsigned, r2);            // (at most 8 significant bits are left: the high half holds them all)
-        }
-        const att_u32x2 w1 = {__builtin_amdgcn_perm(p1[1], p1[0], 0x07060302u), __builtin_amdgcn_perm(p1[3], p1[2], 0x07060302u)};
-        const att_u32x2 w2 = {__builtin_amdgcn_perm(p2[1], p2[0], 0x07060302u), __builtin_amdgcn_perm(p2[3], p2[2], 0x07060302u)};
-        const att_u32x2 w3 = {__builtin_amdgcn_perm(p3[1], p3[0], 0x07060302u), __builtin_amdgcn_perm(p3[3], p3[2], 0x07060302u)};
-        *(att_u32x2*)(base) = w1; *(att_u32x2*)(base + PL) = w2; *(att_u32x2*)(base + 2 * PL) = w3;
-    };
     // part s < NA: dXv item s; part NA + i: map item i.  Positions beyond P, hidden units beyond dh_att and channels beyond dv are zero.
     auto store = [&](auto set_c, int k, int buf, int s0, int s1) __attribute__((always_inline)) {
         constexpr int S = decltype(set_c)::value;
@@ -446,7 +429,7 @@ __global__ __launch_bounds__(DWV6_T, 1) void k_att_dwv_x6(const DwvArgs a) {
             if (NA * T != QA && tid + T * i >= QA) continue;
             f32x4 v = fix_window(va[S][i], acol[i], dh);
             if (ragged && k + arow[i] >= P) v = zero;
-            split_store(v, base + adst[i]);
+            x6_split_store(v, base + adst[i], PL);
         }
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
@@ -454,7 +437,7 @@ __global__ __launch_bounds__(DWV6_T, 1) void k_att_dwv_x6(const DwvArgs a) {
             f32x4 v = vb[S][i];
             if (ragged) v = fix_window(v, k + 4 * bq, P);
             if (!bok[i]) v = zero;
-            split_store(v, base + bdst[i]);
+            x6_split_store(v, base + bdst[i], PL);
         }
     };
 
@@ -464,7 +447,6 @@ __global__ __launch_bounds__(DWV6_T, 1) void k_att_dwv_x6(const DwvArgs a) {
 #pragma unroll
         for (int j = 0; j < WN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    typedef __attribute__((address_space(3))) att_s16x4* lds_s16x4;
     const int tq = li >> 2, tp = li & 3;
     const int fragA = (4 * lk + tq) * PA + (wm0 + 4 * tp) * 2, fragB = A_PL + (wn0 + li) * PB + 16 * lk;
     constexpr int NP = NA + NB;                        // parts of the next tile's store, spread over the block rows of this step
@@ -478,34 +460,21 @@ __global__ __launch_bounds__(DWV6_T, 1) void k_att_dwv_x6(const DwvArgs a) {
         const bool has_next = t + 1 < nsteps;
         if (t + 2 < nsteps) { issue(par_c, b2, k2); advance(b2, k2); }
         const unsigned char* const base = lds + PAR * BUF;
-        att_bf16x8 bf[WN][3];
+        x6_bf16x8 bf[WN][3];
 #pragma unroll
         for (int j = 0; j < WN; ++j)
 #pragma unroll
-            for (int p = 0; p < 3; ++p) bf[j][p] = *(const att_bf16x8*)(base + p * PL + fragB + j * 16 * PB);
+            for (int p = 0; p < 3; ++p) bf[j][p] = *(const x6_bf16x8*)(base + p * PL + fragB + j * 16 * PB);
 #pragma unroll
         for (int i = 0; i < WM; ++i) {
-            att_bf16x8 af[3];
+            x6_bf16x8 af[3];
 #pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                const unsigned char* ta = base + p * PL + fragA + i * 32;
-                const att_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(ta));
-                const att_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(ta + 16 * PA));
-                af[p] = __builtin_bit_cast(att_bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-            }
+            for (int p = 0; p < 3; ++p) af[p] = x6_frag_tr(base + p * PL + fragA + i * 32, PA);
             // the 12 MFMAs of block row i: the two column blocks alternate (a dependent MFMA is two issues away); small terms first
 #pragma unroll
-            for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bf[j][2], acc[i][j], 0, 0, 0);
+            for (int c = 0; c < 6; ++c)
 #pragma unroll
-            for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bf[j][1], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[2], bf[j][0], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bf[j][1], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bf[j][0], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bf[j][0], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < WN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[X6_A[c]], bf[j][X6_B[c]], acc[i][j], 0, 0, 0);
             if (has_next) store(SN{}, k1, PAR ^ 1, i * NP / WM, (i + 1) * NP / WM);
         }
         __syncthreads();

@@ -1,10 +1,12 @@
 // ncx_rnn.h -- the recurrent core that the GRU encoder (ncx_gru*.hip) and the two-layer LSTM encoder (ncx_lstm*.hip) share: the length
 // plan, the workspace carver and the entry points' argument check, the launchers of the shared kernels (ncx_rnn.hip), and the device code
-// that is inlined into the encoders' own kernels (the 64 x 64 NT tile loop of the backward sweeps, the bias column sum).  The forward step
-// kernels and the pack kernels are not here: their LDS layouts, accumulators and packed layouts differ.
+// that is inlined into the encoders' own kernels (the 64 x 64 NT tile loop of the backward sweeps, the LDS row tile of the bf16 x 6
+// kernels, the work-item numbering, the bias column sum).  The fp32 forward step kernels and the pack kernels are not here: their LDS
+// layouts, accumulators and packed layouts differ.
 #pragma once
 #include <initializer_list>
 #include "ncx_internal.h"
+#include "ncx_x6.h"
 
 namespace ncx {
 
@@ -73,29 +75,6 @@ __attribute__((visibility("hidden"))) hipError_t rnn_dw(const RnnDwArgs& a, bool
 // A row index at or beyond n is read from row n - 1 (row 0 when n is 0): such rows are never stored, or are zeroed on the way to LDS
 __device__ __forceinline__ int rnn_clamp_row(int r, int n) { return max(min(r, n - 1), 0); }
 
-// The cut of the bf16 x 6 step kernels (ncx_gru_x6.hip, ncx_lstm_x6.hip): x -> three bf16 values by truncation, x = x1 + x2 + x3 exactly
-// (x1 = x & 0xFFFF0000, x2 = (x - x1) & 0xFFFF0000, x3 = x - x1 - x2), as split_store of k_att_logits_x6.  Four values: one 8-byte store
-// per plane, the planes `plane` bytes apart.
-typedef __bf16 rnn_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int rnn_u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void rnn_split_store(f32x4 v, unsigned char* base, int plane) {
-    unsigned p1[4], p2[4], p3[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float xj = v[j];               // (a scalar copy first: __builtin_bit_cast applied to the vector element itself reads element 0 -- hipcc 7.2)
-        p1[j] = __builtin_bit_cast(unsigned, xj) & 0xFFFF0000u;
-        const float r1 = xj - __builtin_bit_cast(float, p1[j]);
-        p2[j] = __builtin_bit_cast(unsigned, r1) & 0xFFFF0000u;
-        const float r2 = r1 - __builtin_bit_cast(float, p2[j]);
-        p3[j] = __builtin_bit_cast(unsigned, r2);            // (at most 8 significant bits are left: the high half holds them all)
-    }
-    // v_perm_b32: the high halves of two dwords -> one dword (the even element in the low half)
-    const rnn_u32x2 w1 = {__builtin_amdgcn_perm(p1[1], p1[0], 0x07060302u), __builtin_amdgcn_perm(p1[3], p1[2], 0x07060302u)};
-    const rnn_u32x2 w2 = {__builtin_amdgcn_perm(p2[1], p2[0], 0x07060302u), __builtin_amdgcn_perm(p2[3], p2[2], 0x07060302u)};
-    const rnn_u32x2 w3 = {__builtin_amdgcn_perm(p3[1], p3[0], 0x07060302u), __builtin_amdgcn_perm(p3[3], p3[2], 0x07060302u)};
-    *(rnn_u32x2*)(base) = w1; *(rnn_u32x2*)(base + plane) = w2; *(rnn_u32x2*)(base + 2 * plane) = w3;
-}
-
 // The 64 x 64 NT tile of the backward sweeps and the dX products: acc += A[m0 .. + 64][k-steps s0 .. s1) . W[n0 .. + 64]^T on
 // v_mfma_f32_16x16x4_f32, both operands col-is-k at LDS pitch RNN_NT_P (conflict-free ds_read_b64 fragments, ncx_gemm.h).
 //   src.ptr(s, i)   where the loader's quad of A row lr + 32 i sits at k-step s (an aligned, readable 16 bytes)
@@ -156,6 +135,98 @@ __device__ __forceinline__ void rnn_nt_tile(float (&lds)[2][RNN_NT_LDS], const A
         if (more) store(buf ^ 1, s + 1);
         __syncthreads();
         buf ^= 1;
+    }
+}
+
+// Workgroup ids are dealt round-robin over the 8 XCDs, so work item (id & 7) per + (id >> 3), per = ceil(total / 8): consecutive work
+// items run on the same XCD at the same time and share its L2.  The grid is a multiple of 8; an item at or beyond `total` has no work.
+template <class Id>                           // (blockIdx.x as it is, or an int)
+__device__ __forceinline__ int rnn_work_item(Id id, int total) { return (int)(id & 7) * ((total + 7) >> 3) + (int)(id >> 3); }
+
+// The LDS row tile of the bf16 x 6 recurrent kernels (k_gru_step_x6, k_lstm_step_x6, k_gru_bgemm_x6; the cut and the products: ncx_x6.h):
+// acc += A[32 WR rows][k-steps 0 .. ns) . W[NW weight rows]^T, both operands col-is-k in fp32 and cut on the way to LDS.  The workgroup
+// is a WR x 2 grid of waves, wave row wr owns tile rows 32 wr .. + 32.  LDS, double buffered: three planes of [BM rows | NW weight
+// rows][32 k] bf16 at 80 bytes per row (32 bf16 + 16: plain, conflict-free 16-byte fragment reads; lane group lk holds k = 8 lk .. + 7
+// of both operands).  Loader: thread owns column quad c4 of tile rows lr + LR i, 2 of the A tile and NB of the weight tile while inside
+// its NW rows (bok[i]; uniform over a wave: 8 rows per wave and pass).  What is the kernel's: where the quads come from (issue), the
+// MFMA schedule (compute) and the epilogue.  (k_lstm_step_x6 also keeps its fragment reads and its loop: DESIGN 5x has the timing.)
+template <int WR, int NW>
+struct RnnX6Tile {
+    static constexpr int BM = 32 * WR, T = 128 * WR;         // rows per workgroup, threads
+    static constexpr int LR = T / 8;                         // tile rows one pass of the loader covers (8 threads per row)
+    static constexpr int NB = (NW + LR - 1) / LR;            // passes over the weight rows
+    static constexpr int PB = 80;                            // bytes per LDS row of one plane
+    static constexpr int WROWS = NW, ROWS = BM + NW;         // weight rows; tile rows: the A rows, then the weight rows
+    static constexpr int PL = ROWS * PB, BUF = 3 * PL, LDS = 2 * BUF;        // one plane, one buffer (three planes), both buffers
+    static_assert(GEMM_BK == 32, "one k-step is one MFMA depth");
+    static_assert(BM == 2 * LR, "the loader takes the A tile in two passes");
+    static_assert(LDS <= 160 * 1024, "LDS");
+
+    unsigned char* const lds;
+    const int c4, lr, lk;
+    bool bok[NB];
+    __device__ __forceinline__ explicit RnnX6Tile(unsigned char* lds_) : lds(lds_), c4(4 * (threadIdx.x & 7)), lr(threadIdx.x >> 3), lk((threadIdx.x & 63) >> 4) {
+#pragma unroll
+        for (int i = 0; i < NB; ++i) bok[i] = lr + LR * i < NW;
+    }
+    // the tile row of the loader's pass i over the A rows / the weight rows (a pass beyond them points at row lr and is never loaded)
+    __device__ __forceinline__ int arow(int i) const { return lr + LR * i; }
+    __device__ __forceinline__ int wrow(int i) const { return bok[i] ? lr + LR * i : lr; }
+    // the weight quads of k-step s; w[i] points at this thread's quad of weight row wrow(i) at k-step 0
+    __device__ __forceinline__ void load_w(const float* const (&w)[NB], int s, f32x4 (&vb)[NB]) const {
+#pragma unroll
+        for (int i = 0; i < NB; ++i)
+            if (bok[i]) vb[i] = *(const f32x4*)(w[i] + s * GEMM_BK);
+    }
+    __device__ __forceinline__ void store(int buf, const f32x4 (&va)[2], const f32x4 (&vb)[NB]) const {
+        unsigned char* const base = lds + buf * BUF + 2 * c4;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) x6_split_store(va[i], base + (lr + LR * i) * PB, PL);
+#pragma unroll
+        for (int i = 0; i < NB; ++i)
+            if (bok[i]) x6_split_store(vb[i], base + (BM + lr + LR * i) * PB, PL);
+    }
+    // byte offset of this lane's fragment of tile row `row` inside a plane; the fragment of plane p in buffer buf
+    __device__ __forceinline__ int frag_at(int row) const { return row * PB + 16 * lk; }
+    __device__ __forceinline__ x6_bf16x8 frag(int buf, int p, int at) const { return *(const x6_bf16x8*)(lds + buf * BUF + p * PL + at); }
+    // the A fragments of the wave's two 16-row blocks (at = frag_at(32 wr + li)), every plane
+    __device__ __forceinline__ void read_a(int buf, int at, x6_bf16x8 (&af)[2][3]) const {
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int i = 0; i < 2; ++i) af[i][p] = frag(buf, p, at + 16 * i * PB);
+    }
+    // Register-staged, one barrier per k-step: issue(s + 1) loads into va / vb over the MFMAs of step s (compute(buf, s)), then
+    // pre(s + 1) may transform the loaded quads before they are cut and stored to the other buffer.  A wave that is not `live` (its 32
+    // rows all beyond n_t) takes part in the loads, the stores and the barriers and multiplies nothing.  ns >= 1.
+    template <class Issue, class Pre, class Compute>
+    __device__ __forceinline__ void run(int ns, bool live, f32x4 (&va)[2], f32x4 (&vb)[NB], const Issue& issue, const Pre& pre, const Compute& compute) const {
+        issue(0); pre(0); store(0, va, vb);
+        __syncthreads();
+        int buf = 0;
+        for (int s = 0; s < ns; ++s) {
+            const bool more = s + 1 < ns;
+            if (more) issue(s + 1);
+            if (live) compute(buf, s);
+            if (more) { pre(s + 1); store(buf ^ 1, va, vb); }
+            __syncthreads();
+            buf ^= 1;
+        }
+    }
+};
+
+// The A quads of k-step s of a step kernel's x-then-h walk: k-steps [0, nx) run over the xcols columns of the rows at x[i], the rest
+// over the hcols columns of the rows at h[i]; the ragged last k-step of either segment is guarded and zero filled.  c4: the quad.
+__device__ __forceinline__ void rnn_xh_load(int s, int nx, int c4, const float* const (&x)[2], int xcols, const float* const (&h)[2], int hcols,
+                                            f32x4 (&va)[2]) {
+    const bool ish = s >= nx;
+    const int k = (ish ? s - nx : s) * GEMM_BK + c4, cols = ish ? hcols : xcols;
+    if (k - c4 + GEMM_BK <= cols) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) va[i] = *(const f32x4u*)((ish ? h[i] : x[i]) + k);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) va[i] = load4(ish ? h[i] : x[i], k, cols);
     }
 }
 
