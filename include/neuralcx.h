@@ -225,6 +225,14 @@ int ncx_backward_phase(const ncx_dims* d, const ncx_inputs* in, const ncx_params
  * ping-pong buffers then hold dpre_2 and dpre_1 (NCX_WS_DPRE1) side by side.  Size 0 for every other L (L == 1 has no such layer; the
  * region is kept to the one depth whose hidden-layer products the tests judge alone). */
 #define NCX_WS_DPRE2 7
+/* diagnostics / tests, NCX_F_BF16 only (size 0 without the flag): the packed bf16 operands of linear_1's candidate product, as raw uint16
+ * bit patterns in the column layout ncx_bf16_layout reports.  NCX_WS_XC: the candidate rows, [B*K][kc], valid after ncx_forward or its
+ * PRELUDE phase.  NCX_WS_WC: the weights [W1 column slices | Gt], [Hp][kc], valid after ncx_forward. */
+#define NCX_WS_XC 8
+#define NCX_WS_WC 9
+/* diagnostics / tests: the fp32 Gt = W1[:, a_emb_other] . E^T the last ncx_forward produced, [H][ld] with the leading dimension
+ * ld = A under NCX_F_BF16 and A rounded up to a multiple of 32 otherwise (bytes = H * ld * 4 tells which). */
+#define NCX_WS_GT 10
 int ncx_ws_region(const ncx_dims* d, int32_t which, size_t* offset, size_t* bytes);
 
 /* NCX_F_FUSED_TAIL: replaces, in one pass over h_L, the tail of ncx_forward (`out`, cx.py:327), ncx_loss_rank
@@ -879,6 +887,15 @@ int ncx_mlb_att_train_ws_region(const ncx_mlb_att_dims* d, const ncx_mlb_att_tra
  *         the hidden layers' engine: 0 generic, 1 the fused forward kernel, -1 when L == 1;
  *         their k-chunks per output tile (0 when L == 1)} */
 #define NCX_QUERY_FWD_ROUTE 34
+/* Not a GEMM id either: the kernels the bf16 variant (NCX_F_BF16) launches for these dims, as launched (experiment hooks applied; read
+ * from the one function its launchers call).  Without the flag out6 = {-1, 0, 0, 0, 0, 0}.
+ * out6 = {h_1 = Xc . Wc^T: gemm_bf16_nt_kernel on 0 128x128, 1 64x128, 2 128x64, 3 64x64 tiles, or 8 gemm_bf16_nt8_kernel (192x256);
+ *         dWc = dpre_1^T . Xc: 1 gemm_bf16_tn8_kernel (256x128 tiles), 0 gemm_bf16_tn_kernel (128x128);
+ *         the k-chunks of that launch's grid; the rows per k-chunk; the chunks that hold rows (= the slabs the reduction sums);
+ *         bits 1 / 2 / 4 / 8: the 4-columns-per-thread form of k_dpre_to_bf16 / of k_pack2d on E / on [W1ak; W1agt] / on [dGt; dGgt] --
+ *         the part of that choice the SHAPE decides; the launchers also require 16-byte aligned pointers, which a workspace region
+ *         always is and a caller's weight tensor need not be} */
+#define NCX_QUERY_BF16_ROUTE 35
 int ncx_profile_begin(uint32_t gemm_mask /* bit i = gemm id i */, int32_t max_launches);
 int ncx_profile_end(float* ms, int32_t* ids, int32_t cap);
 /* In-kernel clock diagnostics of the MAIN launch (the fused forward kernel of linear_1): while `stamps` is non-NULL
@@ -893,6 +910,12 @@ int ncx_profile_stamps(unsigned long long* stamps, int64_t words);
 /* out6 = {form (0 NT,1 TN,2 NN), M, N, 32-deep k-steps, tile cfg (0 64x64, 1 128x128, 2 96x128, 3 96x64, 4 128x64; the fused forward
  *         kernel: 5 48x128, 6 / 7 / 8 the per-triplet fold on 48x64 / 96x64 / 192x64 tiles), aligned k-chunks per output tile (1 = no split)} */
 int ncx_plan_query(const ncx_dims* d, int32_t gemm_id, int32_t* out6);
+/* The column layout of the bf16 variant's packed operands (NCX_WS_XC, NCX_WS_WC) and the padded extents of its other bf16 images:
+ * out10 = {c_vk, c_vm, c_misc, c_z, c_p: the first column of v_k | v_o * v_k | dist, one-hot rank | z_k | softmax(a_k) (weights: of the
+ *          matching W1 slices and Gt), each a multiple of 8, the gaps zero; raw: one past the last used column; kc: the row length (raw
+ *          rounded up to 128, zero beyond raw); Hp: rows of Wc and columns of the bf16 dpre_1 image (H rounded up to 128); dap, Ap: da and A
+ *          rounded up to 128}.  Defined for any valid dims, with or without NCX_F_BF16. */
+int ncx_bf16_layout(const ncx_dims* d, int32_t* out10);
 /* Host-only self-check of the workgroup-id <-> (tile, k-chunk) maps (XCD-aware interleaved layout, chunk-per-XCD
  * layout with its padding ids): 0 when decode/encode are mutually inverse and cover every (tile, chunk) exactly once. */
 int ncx_wgmap_check(int32_t tiles_m, int32_t tiles_n, int32_t S);

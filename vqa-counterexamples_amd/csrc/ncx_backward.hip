@@ -872,9 +872,19 @@ int ncx_ws_region(const ncx_dims* dp, int32_t which, size_t* offset, size_t* byt
     if (check_dims(dp) != NCX_OK) return NCX_E_DIMS;
     if (!offset || !bytes) return NCX_E_NULL;
     if (which != NCX_WS_DGT && which != NCX_WS_H1 && which != NCX_WS_DPRE1 && which != NCX_WS_DE_PERM && which != NCX_WS_H2 && which != NCX_WS_H3 &&
-        which != NCX_WS_DPRE2) return NCX_E_FLAGS;
+        which != NCX_WS_DPRE2 && which != NCX_WS_XC && which != NCX_WS_WC && which != NCX_WS_GT) return NCX_E_FLAGS;
     const StepRoutes r = routes(*dp);
     const WsLayout w = ws_layout(*dp, r);
+    if (which == NCX_WS_XC || which == NCX_WS_WC) {      // (size 0 without NCX_F_BF16: the fp32 path packs no operands)
+        const bool bf16 = dp->flags & NCX_F_BF16;
+        *offset = which == NCX_WS_XC ? w.xc : w.wc;
+        *bytes = !bf16 ? 0 : which == NCX_WS_XC ? bf16_xc_bytes(*dp) : bf16_wc_bytes(*dp);
+        return NCX_OK;
+    }
+    if (which == NCX_WS_GT) {      // [H][ldgt] (ws_layout: A under NCX_F_BF16, else pad_to(A, 32))
+        *offset = w.gt; *bytes = (size_t)dp->H * w.ldgt * 4;
+        return NCX_OK;
+    }
     if (which == NCX_WS_DE_PERM) {      // (size 0: the shape or the variant keeps the full form of the product)
         *offset = w.de_perm; *bytes = r.de_skip ? ((size_t)dp->A + 1) * 4 : 0;
         return NCX_OK;

@@ -29,6 +29,24 @@ static inline Bf16Cols bf16_cols(const ncx_dims& d) {
     return c;
 }
 constexpr int BF16_SPLIT = 8;                 // k-chunks of the weight-gradient GEMM: one per XCD
+static inline int bf16_hp(const ncx_dims& d) { return (d.H + 127) / 128 * 128; }     // rows of Wc / columns of dpre_bf: whole 128-wide tiles
+
+// The kernel selections of the variant, taken ONCE (ncx_bf16.hip: from the CU count and, under NCX_EXPERIMENT=1, the hooks
+// NCX_BF16_NT_CFG, NCX_BF16_TN8, NCX_BF16_NO_TN8): bf16_main_forward, bf16_dw1c and the packers launch by this struct and
+// ncx_plan_query(NCX_QUERY_BF16_ROUTE) reports it, so they cannot disagree.
+enum { BF16_VEC_DPRE = 1, BF16_VEC_E = 2, BF16_VEC_W1A = 4, BF16_VEC_DG = 8 };
+struct Bf16Route {
+    int nt_form;        // h_1 = Xc . Wc^T: gemm_bf16_nt_kernel on 0 128x128, 1 64x128, 2 128x64, 3 64x64 tiles; 8 gemm_bf16_nt8_kernel (192x256)
+    int tn8;            // dWc: 1 gemm_bf16_tn8_kernel (256x128 tiles), 0 gemm_bf16_tn_kernel<128, 128>
+    int S;              // ... k-chunks of its grid (workgroups per output tile; chunks past the last row return at once)
+    int chunk;          // ... rows per k-chunk, a multiple of 64
+    int nz;             // ... chunks that hold rows = slabs k_bf16_reduce_dwc sums
+    int vec;            // BF16_VEC_* bits: the SHAPE's half of the 4-columns-per-thread choice of k_dpre_to_bf16, of k_pack2d on E,
+                        // on [W1ak; W1agt] and on [dGt; dGgt]; the launchers also ask for 16-byte aligned pointers (workspace regions are)
+};
+Bf16Route bf16_route(const ncx_dims& d);
+// the shape's half of k_pack2d's VEC form: C columns of a source with leading dimension ld into an image Cp wide
+static inline bool bf16_pack_vec_shape(int C, int Cp, long long ld) { return C % 4 == 0 && Cp % 4 == 0 && ld % 4 == 0; }
 
 // bytes of the bf16 workspace regions
 static inline size_t bf16_xc_bytes(const ncx_dims& d) { return (size_t)d.B * d.K * bf16_cols(d).kc * 2; }

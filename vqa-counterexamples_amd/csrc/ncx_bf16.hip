@@ -524,7 +524,7 @@ __global__ __launch_bounds__(256) void k_bf16_reduce_dwc(ncx_dims d, Bf16Cols cc
 // ---- host side -------------------------------------------------------------------------------------------------
 int bf16_pack_wc(const ncx_dims& d, const float* w1, const float* gt, u16* wc, hipStream_t s) {
     const Bf16Cols cc = bf16_cols(d);
-    const int Hp = (d.H + 127) / 128 * 128;
+    const int Hp = bf16_hp(d);
     const long long n = (long long)Hp * cc.kc;
     hipLaunchKernelGGL(k_pack_wc, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, cc, seg_offsets(d), w1, gt, wc, Hp);
     NCX_HIP_TRY(hipGetLastError());
@@ -543,26 +543,48 @@ static int launch_bf16_nt(const u16* xc, int M, const u16* wc, int N, int kc, co
     return NCX_OK;
 }
 
+// The selections (ncx_bf16.h).  NT: the product is bound by operand delivery (global-load latency x bytes in flight), not by the MFMA
+// pipe: prefer the tile that puts >= 2 workgroups on every CU; one 192 x 256 workgroup per CU (LDS-DMA staged) where all of H is one
+// tile and >= 3/4 of the CUs get one.  NCX_BF16_NT_CFG (0..3, 8) overrides for experiments.  TN: all 256 output rows in one workgroup
+// (the packed rows read once), S k-chunks so that tiles x S fills one round of the CUs.
+Bf16Route bf16_route(const ncx_dims& d) {
+    Bf16Route r{};
+    const Bf16Cols cc = bf16_cols(d);
+    const int M = d.B * d.K, Hp = bf16_hp(d);
+    int cfg = -1;
+    { const char* e = hook_env("NCX_BF16_NT_CFG"); if (e) cfg = atoi(e); }
+    if ((cfg < 0 || cfg == 8) && d.H <= N8_BN && Hp == N8_BN && (cfg == 8 || (long long)(M + N8_BM - 1) / N8_BM * 4 >= 3LL * num_cus())) r.nt_form = 8;
+    else {
+        if (cfg < 0) {
+            const long long t128 = (long long)((M + 127) / 128) * ((d.H + 127) / 128);
+            cfg = t128 >= 2LL * num_cus() ? 0 : 3;
+        }
+        r.nt_form = cfg == 0 || cfg == 1 || cfg == 2 ? cfg : 3;
+    }
+    const int tiles_n8 = cc.kc / 128;
+    int S8 = num_cus() / tiles_n8; if (S8 > BF16_SPLIT) S8 = BF16_SPLIT;
+    r.tn8 = Hp == 256 && S8 >= 2 && ((long long)M >= 64LL * 16 * S8 || hook_env("NCX_BF16_TN8")) && !hook_env("NCX_BF16_NO_TN8");
+    r.S = r.tn8 ? S8 : BF16_SPLIT;
+    r.chunk = (int)(((long long)(M + r.S - 1) / r.S + 63) / 64 * 64);
+    r.nz = (M + r.chunk - 1) / r.chunk;
+    const int dap = bf16_up128(d.da), Ap = bf16_up128(d.A);
+    r.vec = (d.H % 4 == 0 ? BF16_VEC_DPRE : 0) | (bf16_pack_vec_shape(d.da, dap, d.da) ? BF16_VEC_E : 0) |
+            (bf16_pack_vec_shape(d.da, dap, seg_offsets(d).din) ? BF16_VEC_W1A : 0) | (bf16_pack_vec_shape(d.A, Ap, d.A) ? BF16_VEC_DG : 0);
+    return r;
+}
+
 int bf16_main_forward(const ncx_dims& d, const u16* xc, const u16* wc, const EpiArgs& epi, float* h1, hipStream_t s) {
     const Bf16Cols cc = bf16_cols(d);
     const int M = d.B * d.K;
-    // The product is bound by operand delivery (global-load latency x bytes in flight), not by the MFMA pipe: prefer the
-    // tile that puts >= 2 workgroups on every CU.  NCX_BF16_NT_CFG (0..3) overrides for experiments.
-    int cfg = -1;
-    { const char* e = hook_env("NCX_BF16_NT_CFG"); if (e) cfg = atoi(e); }
-    // one 192 x 256 workgroup per CU (LDS-DMA staged): all of H in one tile, >= 3/4 of the CUs busy
-    if ((cfg < 0 || cfg == 8) && d.H <= N8_BN && (d.H + 127) / 128 * 128 == N8_BN && (cfg == 8 || (long long)(M + N8_BM - 1) / N8_BM * 4 >= 3LL * num_cus())) {
+    const Bf16Route rt = bf16_route(d);
+    if (rt.nt_form == 8) {
         static DevMask attr8{0};
         NCX_HIP_TRY(set_max_lds_once(attr8, (const void*)gemm_bf16_nt8_kernel, N8_LDS));
         hipLaunchKernelGGL(gemm_bf16_nt8_kernel, dim3((M + N8_BM - 1) / N8_BM), dim3(512), N8_LDS, s, xc, M, wc, N8_BN, d.H, cc.kc, h1, (long long)d.H, epi);
         NCX_HIP_TRY(hipGetLastError());
         return NCX_OK;
     }
-    if (cfg < 0) {
-        const long long t128 = (long long)((M + 127) / 128) * ((d.H + 127) / 128);
-        cfg = t128 >= 2LL * num_cus() ? 0 : 3;
-    }
-    switch (cfg) {
+    switch (rt.nt_form) {
     case 0:  return launch_bf16_nt<128, 128>(xc, M, wc, d.H, cc.kc, epi, h1, s);
     case 1:  return launch_bf16_nt<64, 128>(xc, M, wc, d.H, cc.kc, epi, h1, s);
     case 2:  return launch_bf16_nt<128, 64>(xc, M, wc, d.H, cc.kc, epi, h1, s);
@@ -573,41 +595,33 @@ int bf16_main_forward(const ncx_dims& d, const u16* xc, const u16* wc, const Epi
 int bf16_dw1c(const ncx_dims& d, const float* dpre, u16* dpre_bf, const u16* xc, float* slab, float* g_w1, float* dgt,
               hipStream_t s) {
     const Bf16Cols cc = bf16_cols(d);
-    const int M = d.B * d.K, Hp = (d.H + 127) / 128 * 128;
+    const int M = d.B * d.K, Hp = bf16_hp(d);
+    const Bf16Route rt = bf16_route(d);
     {
         const long long n = (long long)M * Hp;
-        if (d.H % 4 == 0 && (((uintptr_t)dpre | (uintptr_t)dpre_bf) & 15) == 0)
+        if ((rt.vec & BF16_VEC_DPRE) && (((uintptr_t)dpre | (uintptr_t)dpre_bf) & 15) == 0)
             hipLaunchKernelGGL(k_dpre_to_bf16<true>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, dpre, M, d.H, Hp, dpre_bf);
         else
             hipLaunchKernelGGL(k_dpre_to_bf16<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dpre, M, d.H, Hp, dpre_bf);
         NCX_HIP_TRY(hipGetLastError());
     }
-    int nz;
-    // all 256 output rows in one workgroup (the packed rows read once), S k-chunks so that tiles x S fills one round of the CUs
-    const int tiles_n8 = cc.kc / 128;
-    int S8 = num_cus() / tiles_n8; if (S8 > BF16_SPLIT) S8 = BF16_SPLIT;
-    const bool tn8 = Hp == 256 && S8 >= 2 && ((long long)M >= 64LL * 16 * S8 || hook_env("NCX_BF16_TN8")) && !hook_env("NCX_BF16_NO_TN8");
-    if (tn8) {
+    if (rt.tn8) {
         static DevMask attr8{0};
         NCX_HIP_TRY(set_max_lds_once(attr8, (const void*)gemm_bf16_tn8_kernel, TN8_LDS));
-        const int chunk = (int)(((long long)(M + S8 - 1) / S8 + 63) / 64 * 64);
-        nz = (M + chunk - 1) / chunk;
-        hipLaunchKernelGGL(gemm_bf16_tn8_kernel, dim3(tiles_n8 * S8), dim3(512), TN8_LDS, s, (const u16*)dpre_bf, Hp, xc, cc.kc, M, chunk, S8, slab, d.H, cc.kc);
+        hipLaunchKernelGGL(gemm_bf16_tn8_kernel, dim3(cc.kc / 128 * rt.S), dim3(512), TN8_LDS, s, (const u16*)dpre_bf, Hp, xc, cc.kc, M, rt.chunk, rt.S, slab, d.H, cc.kc);
         NCX_HIP_TRY(hipGetLastError());
     } else {
-    constexpr int BM = 128, BN = 128;
-    const int lds = 4 * 64 * TN_PITCH;
-    static DevMask attr{0};
-    NCX_HIP_TRY(set_max_lds_once(attr, (const void*)gemm_bf16_tn_kernel<BM, BN>, lds));
-    const int chunk = (int)(((long long)(M + BF16_SPLIT - 1) / BF16_SPLIT + 63) / 64 * 64);
-    nz = (M + chunk - 1) / chunk;
-    const int tiles_m = Hp / BM, tiles_n = cc.kc / BN;
-    hipLaunchKernelGGL((gemm_bf16_tn_kernel<BM, BN>), dim3(tiles_m * tiles_n * BF16_SPLIT), dim3(256), lds, s, (const u16*)dpre_bf, Hp,
-                       xc, cc.kc, M, chunk, tiles_m, BF16_SPLIT, slab, d.H, cc.kc);
-    NCX_HIP_TRY(hipGetLastError());
+        constexpr int BM = 128, BN = 128;
+        const int lds = 4 * 64 * TN_PITCH;
+        static DevMask attr{0};
+        NCX_HIP_TRY(set_max_lds_once(attr, (const void*)gemm_bf16_tn_kernel<BM, BN>, lds));
+        const int tiles_m = Hp / BM, tiles_n = cc.kc / BN;
+        hipLaunchKernelGGL((gemm_bf16_tn_kernel<BM, BN>), dim3(tiles_m * tiles_n * rt.S), dim3(256), lds, s, (const u16*)dpre_bf, Hp,
+                           xc, cc.kc, M, rt.chunk, tiles_m, rt.S, slab, d.H, cc.kc);
+        NCX_HIP_TRY(hipGetLastError());
     }
     const long long n = (long long)d.H * cc.raw;
-    hipLaunchKernelGGL(k_bf16_reduce_dwc, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, cc, seg_offsets(d), (const float*)slab, nz,
+    hipLaunchKernelGGL(k_bf16_reduce_dwc, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, cc, seg_offsets(d), (const float*)slab, rt.nz,
                        g_w1, dgt);
     NCX_HIP_TRY(hipGetLastError());
     return NCX_OK;
@@ -647,7 +661,7 @@ __global__ __launch_bounds__(256) void k_pack_transposed(const float* __restrict
 
 static int pack2d(const float* src, long long ld, int R, int C, u16* dst, int Rp, int Cp, hipStream_t s) {
     const long long n = (long long)Rp * Cp;
-    if (C % 4 == 0 && Cp % 4 == 0 && ld % 4 == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0)
+    if (bf16_pack_vec_shape(C, Cp, ld) && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0)
         hipLaunchKernelGGL(k_pack2d<true>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, src, ld, R, C, dst, Rp, Cp);
     else
         hipLaunchKernelGGL(k_pack2d<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, ld, R, C, dst, Rp, Cp);

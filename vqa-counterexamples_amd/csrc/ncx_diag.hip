@@ -1,5 +1,6 @@
 // ncx_diag.hip -- the diagnostics ABI: launch timing, in-kernel stamps, the WgMap self-check and the plan query.
 #include "ncx_driver.h"
+#include "ncx_bf16.h"
 #include <stdlib.h>
 
 using namespace ncx;
@@ -65,6 +66,15 @@ int ncx_wgmap_check(int32_t tiles_m, int32_t tiles_n, int32_t S) {
     return bad;
 }
 
+int ncx_bf16_layout(const ncx_dims* d, int32_t* out10) {
+    if (check_dims(d) != NCX_OK) return NCX_E_DIMS;
+    if (!out10) return NCX_E_NULL;
+    const Bf16Cols c = bf16_cols(*d);
+    const int32_t v[10] = {c.c_vk, c.c_vm, c.c_misc, c.c_z, c.c_p, c.raw, c.kc, bf16_hp(*d), bf16_up128(d->da), bf16_up128(d->A)};
+    for (int i = 0; i < 10; ++i) out10[i] = v[i];
+    return NCX_OK;
+}
+
 int ncx_plan_query(const ncx_dims* d, int32_t gemm_id, int32_t* out6) {
     if (check_dims(d) != NCX_OK || !out6) return NCX_E_DIMS;
     if (gemm_id == NCX_QUERY_DW1_ROUTE) {      // the routes of linear_1's weight gradient, from the predicates backward_impl launches by
@@ -84,6 +94,13 @@ int ncx_plan_query(const ncx_dims* d, int32_t gemm_id, int32_t* out6) {
         for (int i = 0; i < 6; ++i) out6[i] = 0;
         out6[0] = on ? 1 : 0;
         out6[1] = on ? main_adam_passengers() : 0;
+        return NCX_OK;
+    }
+    if (gemm_id == NCX_QUERY_BF16_ROUTE) {     // the kernel selections of the bf16 variant, from the function its launchers launch by
+        for (int i = 0; i < 6; ++i) out6[i] = 0;
+        if (!(d->flags & NCX_F_BF16)) { out6[0] = -1; return NCX_OK; }
+        const Bf16Route b = bf16_route(*d);
+        out6[0] = b.nt_form; out6[1] = b.tn8; out6[2] = b.S; out6[3] = b.chunk; out6[4] = b.nz; out6[5] = b.vec;
         return NCX_OK;
     }
     if (gemm_id == NCX_QUERY_FWD_ROUTE) {      // the forward's Linear layers, from the functions forward_impl and main_forward launch by

@@ -26,7 +26,7 @@ EXPORTS = ("ncx_input_size", "ncx_workspace_bytes", "ncx_forward", "ncx_forward_
            "ncx_gru_train_backward_flags", "ncx_gru_bwd_form",
            "ncx_lstm2_packed_bytes", "ncx_lstm2_pack", "ncx_lstm2_workspace_bytes", "ncx_lstm2_encode", "ncx_lstm2_encode_flags", "ncx_lstm2_step_form",
            "ncx_lstm2_train_workspace_bytes", "ncx_lstm2_packed_t_bytes", "ncx_lstm2_pack_t", "ncx_lstm2_train_forward", "ncx_lstm2_train_forward_flags", "ncx_lstm2_train_backward",
-           "ncx_ws_region", "ncx_wgmap_check",
+           "ncx_ws_region", "ncx_wgmap_check", "ncx_bf16_layout",
            "ncx_comm_unique_id", "ncx_comm_create", "ncx_comm_destroy", "ncx_allreduce", "ncx_train_tail", "ncx_profile_stamps",
            "ncx_pairlin_workspace_bytes", "ncx_pairlin_forward", "ncx_pairlin_backward",
            "ncx_linctx_workspace_bytes", "ncx_linctx_forward", "ncx_linctx_backward",
@@ -285,6 +285,8 @@ def lib():
     L.ncx_comm_create.restype = C.c_int; L.ncx_comm_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
     L.ncx_comm_destroy.restype = C.c_int; L.ncx_comm_destroy.argtypes = [C.c_void_p]
     L.ncx_allreduce.restype = C.c_int; L.ncx_allreduce.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.ncx_bf16_layout.restype = C.c_int
+    L.ncx_bf16_layout.argtypes = [C.POINTER(NcxDims), C.POINTER(C.c_int32)]
     L.ncx_plan_query.restype = C.c_int
     L.ncx_plan_query.argtypes = [C.POINTER(NcxDims), C.c_int32, C.POINTER(C.c_int32)]
     P_SD = C.POINTER(NcxScorerDims)
@@ -419,8 +421,25 @@ FWD_ENGINES = ("generic", "chain", "fold", "bf16")
 FWD_CHAIN_FORMS = ("48x128", "96x64", "96x128", "160x128", "64x64")
 
 
+NCX_QUERY_BF16_ROUTE = 35       # include/neuralcx.h
+BF16_NT_FORMS = {0: "128x128", 1: "64x128", 2: "128x64", 3: "64x64", 8: "nt8"}
+
+
+def bf16_layout(d):
+    """ncx_bf16_layout: the column layout of the packed bf16 operands and the padded extents, by name."""
+    out = (C.c_int32 * 10)()
+    check(lib().ncx_bf16_layout(C.byref(d), out), "ncx_bf16_layout")
+    return dict(zip(("c_vk", "c_vm", "c_misc", "c_z", "c_p", "raw", "kc", "Hp", "dap", "Ap"), (int(v) for v in out)))
+
+
 def plan_query(d, name):
     out = (C.c_int32 * 6)()
+    if name == "BF16_ROUTE":
+        check(lib().ncx_plan_query(C.byref(d), NCX_QUERY_BF16_ROUTE, out), "ncx_plan_query")
+        if out[0] < 0:
+            return None
+        return dict(nt=out[0], nt_name=BF16_NT_FORMS[out[0]], tn8=bool(out[1]), S=out[2], chunk=out[3], nz=out[4],
+                    vec_dpre=bool(out[5] & 1), vec_e=bool(out[5] & 2), vec_w1a=bool(out[5] & 4), vec_dg=bool(out[5] & 8))
     if name == "FWD_ROUTE":
         check(lib().ncx_plan_query(C.byref(d), NCX_QUERY_FWD_ROUTE, out), "ncx_plan_query")
         return dict(engine=out[0], engine_name=FWD_ENGINES[out[0]], tile=out[1],

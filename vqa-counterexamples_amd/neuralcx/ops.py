@@ -251,6 +251,33 @@ def ws_dpre_view(d: NcxDims, ws: torch.Tensor, l: int) -> torch.Tensor:
     return ws[base + off.value: base + off.value + nbytes.value].view(torch.float32).view(d.B * d.K, d.H)
 
 
+def bf16_layout(d: NcxDims) -> dict:
+    """The column layout of the bf16 variant's packed operands (ncx_bf16_layout): c_vk, c_vm, c_misc, c_z, c_p, raw, kc, Hp, dap, Ap."""
+    return _lib.bf16_layout(d)
+
+
+def _ws_region(d: NcxDims, ws: torch.Tensor, which: int) -> torch.Tensor:
+    off, nbytes = C.c_size_t(0), C.c_size_t(0)
+    _lib.check(_lib.lib().ncx_ws_region(C.byref(d), which, C.byref(off), C.byref(nbytes)), "ncx_ws_region")
+    base = (ws.data_ptr() + 255) // 256 * 256 - ws.data_ptr()
+    return ws[base + off.value: base + off.value + nbytes.value]
+
+
+def ws_xc_view(d: NcxDims, ws: torch.Tensor) -> torch.Tensor:
+    """int16 view [B*K, kc] of the bf16 bit patterns of the packed candidate rows (NCX_WS_XC; NCX_F_BF16 only, else empty)."""
+    return _ws_region(d, ws, 8).view(torch.int16).view(-1, bf16_layout(d)["kc"])
+
+
+def ws_wc_view(d: NcxDims, ws: torch.Tensor) -> torch.Tensor:
+    """int16 view [Hp, kc] of the bf16 bit patterns of the packed weights [W1 slices | Gt] (NCX_WS_WC; NCX_F_BF16 only, else empty)."""
+    return _ws_region(d, ws, 9).view(torch.int16).view(-1, bf16_layout(d)["kc"])
+
+
+def ws_gt_view(d: NcxDims, ws: torch.Tensor) -> torch.Tensor:
+    """fp32 view [H, ld] of the Gt the last forward produced (NCX_WS_GT): ld = A under NCX_F_BF16, A rounded up to 32 otherwise."""
+    return _ws_region(d, ws, 10).view(torch.float32).view(d.H, -1)
+
+
 def ranking_loss(scores: torch.Tensor, gt: torch.Tensor, scale: float = 0.0, want_grad: bool = True):
     """Listwise softmax-CE / B + rank of the ground truth + Recall@1/@5 hit counts in one pass."""
     B, K = scores.shape
