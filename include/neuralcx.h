@@ -896,6 +896,15 @@ int ncx_mlb_att_train_ws_region(const ncx_mlb_att_dims* d, const ncx_mlb_att_tra
  *         the part of that choice the SHAPE decides; the launchers also require 16-byte aligned pointers, which a workspace region
  *         always is and a caller's weight tensor need not be} */
 #define NCX_QUERY_BF16_ROUTE 35
+/* Not a GEMM id either: Gt and Sh, the two short products in front of linear_1, as ONE launch of the fused forward kernel's 64 x 64 form with
+ * one fix-up behind it (fp32 path with the a_emb segment, widths multiples of 4, no NCX_F_REUSE_GT, no side stream, a joint plan that splits at
+ * least one of the two; hook NCX_NO_GTSH_PAIR: off).
+ * out6 = {1 when ncx_forward takes that launch for these dims, else 0 (the two launches of the generic engine);
+ *         the k-chunks per 64 x 64 tile of Gt and of Sh: those of the two launches (ncx_plan_query NCX_GEMM_GT / NCX_GEMM_SH), so that the
+ *         results are theirs bit for bit;
+ *         the workgroups that share a tile's chunks, for Gt and for Sh (divisors of the chunk counts: a workgroup runs chunks / workgroups
+ *         consecutive chunks; 0, 0: no joint plan); the workgroup slots of one round (3 per CU)} */
+#define NCX_QUERY_GTSH_PAIR 36
 int ncx_profile_begin(uint32_t gemm_mask /* bit i = gemm id i */, int32_t max_launches);
 int ncx_profile_end(float* ms, int32_t* ids, int32_t cap);
 /* In-kernel clock diagnostics of the MAIN launch (the fused forward kernel of linear_1): while `stamps` is non-NULL

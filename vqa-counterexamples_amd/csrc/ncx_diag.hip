@@ -103,6 +103,15 @@ int ncx_plan_query(const ncx_dims* d, int32_t gemm_id, int32_t* out6) {
         out6[0] = b.nt_form; out6[1] = b.tn8; out6[2] = b.S; out6[3] = b.chunk; out6[4] = b.nz; out6[5] = b.vec;
         return NCX_OK;
     }
+    if (gemm_id == NCX_QUERY_GTSH_PAIR) {      // Gt and Sh as one launch: the route forward_impl takes and the joint plan it launches by
+        const StepRoutes r = routes(*d);
+        SideStream* ss = side_stream();
+        out6[0] = r.gtsh_pair(*d, ss && ss->mode != 3) ? 1 : 0;
+        out6[1] = r.pair_s_gt; out6[2] = r.pair_s_sh;
+        out6[3] = r.pair_w_gt; out6[4] = r.pair_w_sh;
+        out6[5] = 3 * num_cus();
+        return NCX_OK;
+    }
     if (gemm_id == NCX_QUERY_FWD_ROUTE) {      // the forward's Linear layers, from the functions forward_impl and main_forward launch by
         const StepRoutes r = routes(*d);
         GemmUse u[U_COUNT];

@@ -23,11 +23,14 @@ __device__ __forceinline__ void store_bf16x4(u16* p, const float (&v)[4], int va
     else { for (int j = 0; j < valid; ++j) p[j] = f32_to_bf16(v[j]); }
 }
 
-struct PackArgs { const float* src[WPAD_N + 1]; float* dst[WPAD_N + 1]; long long lds[WPAD_N + 1]; int cols[WPAD_N + 1], ldd[WPAD_N + 1], zero_from[WPAD_N + 1]; int n, H; int nprep; };   // nprep: row blocks (4 candidate rows each) in front of the pack blocks
-// dst[e][h][0 .. cols) = src[e][h][0 .. cols);  dst[e][h][zero_from .. ldd) = 0.   One block per (h, e): H * n blocks, which
+constexpr int PACK_N = WPAD_N + 1 + PAIR_WPAD_N;      // the padded weight copies of linear_1 / the hidden layers, Gt's pad columns, those of the Gt + Sh pair launch
+struct PackArgs { const float* src[PACK_N]; float* dst[PACK_N]; long long lds[PACK_N]; int cols[PACK_N], ldd[PACK_N], zero_from[PACK_N], first[PACK_N + 1]; int n; int nprep; };   // first[e]: entry e's first pack block (its rows follow; first[n]: all of them); nprep: row blocks (4 candidate rows each) in front of the pack blocks
+// dst[e][h][0 .. cols) = src[e][h][0 .. cols);  dst[e][h][zero_from .. ldd) = 0.   One block per row h of entry e, which
 // ride at the end of k_prep's grid (a launch of their own cost 5 us for 0.5 MB of copies).
 __device__ __forceinline__ void pack_rows_block(const PackArgs& a, int idx) {
-    const int h = idx % a.H, e = idx / a.H;
+    int e = 0;
+    while (e + 1 < a.n && idx >= a.first[e + 1]) ++e;
+    const int h = idx - a.first[e];
     float* drow = a.dst[e] + (long long)h * a.ldd[e];
     if (a.src[e]) {
         const float* srow = a.src[e] + (long long)h * a.lds[e];
@@ -309,18 +312,36 @@ static int forward_impl(const ncx_dims* dp, const ncx_inputs* in, const ncx_para
     // zero-padded copies of the weight slices the fused forward kernel reads past their width (+ the pad columns of Gt):
     // functions of the weights only, like Gt -- evaluation passes reuse them (NCX_F_REUSE_GT)
     struct { const float* ptr[WPAD_N]; int width[WPAD_N]; } wp{};
-    PackArgs pk{}; pk.H = H;
+    // Gt and Sh as one launch of the fused forward kernel's 64 x 64 form (StepRoutes::gtsh_pair); its weight sides are padded like linear_1's
+    const bool pair = r.gtsh_pair(d, ss != nullptr);
+    struct { const float* ptr[PAIR_WPAD_N]; int width[PAIR_WPAD_N]; } pw{};
+    PackArgs pk{};
+    auto pack = [&](const float* src, long long lds, int cols, float* dst, int ldd, int zero_from, int rows) {
+        const int e = pk.n++;
+        pk.src[e] = src; pk.lds[e] = lds; pk.cols[e] = cols; pk.dst[e] = dst; pk.ldd[e] = ldd; pk.zero_from[e] = zero_from; pk.first[e + 1] = pk.first[e] + rows;
+    };
     {
         const float* srcs[WPAD_N] = {p->w1 + o.v_other, p->w1 + o.v_mult, p->w1 + o.v_dist, p->w1 + o.z_other, p->w1 + o.a_other, p->w2, p->w3};
         float* cur = (float*)(ws + w.wpad);
         for (int i = 0; i < WPAD_N; ++i) {
             wp.width[i] = wpad_width(d, i); wp.ptr[i] = cur;
             if (!wp.width[i]) continue;
-            const int e = pk.n++;
-            pk.src[e] = srcs[i]; pk.lds[e] = (i == 5 || i == 6) ? H : din; pk.cols[e] = wpad_cols(d, i); pk.dst[e] = cur; pk.ldd[e] = wp.width[i]; pk.zero_from[e] = pk.cols[e];
+            pack(srcs[i], (i == 5 || i == 6) ? H : din, wpad_cols(d, i), cur, wp.width[i], wpad_cols(d, i), H);
             cur += (size_t)H * wp.width[i];
         }
-        if (aemb && w.ldgt > d.A) { const int e = pk.n++; pk.src[e] = nullptr; pk.dst[e] = gt; pk.ldd[e] = w.ldgt; pk.zero_from[e] = d.A; pk.cols[e] = 0; }
+        if (aemb && w.ldgt > d.A) pack(nullptr, 0, 0, gt, w.ldgt, d.A, H);
+        if (pair) {
+            const float* psrc[PAIR_WPAD_N] = {p->w1 + o.v_orig, p->w1 + o.q_emb, p->w1 + o.z_orig, p->w1 + o.a_gt, p->answer_embedding};
+            const int pcols[PAIR_WPAD_N] = {d.dv, d.dq, d.dz, d.da, d.da};
+            float* pcur = (float*)(ws + w.pwpad);
+            for (int i = 0; i < PAIR_WPAD_N; ++i) {
+                const int rows = i == 4 ? d.A : H;
+                pw.width[i] = pair_wpad_width(d, r, i); pw.ptr[i] = pcur;
+                if (!pw.width[i]) continue;
+                pack(psrc[i], i == 4 ? d.da : din, pcols[i], pcur, pw.width[i], pcols[i], rows);
+                pcur += (size_t)rows * pw.width[i];
+            }
+        }
         if (d.flags & NCX_F_REUSE_GT) pk.n = 0;
     }
     // the per-triplet fold of the two v segments, and the pairwise distance inside the fused forward kernel (forward_route, above)
@@ -330,7 +351,7 @@ static int forward_impl(const ncx_dims* dp, const ncx_inputs* in, const ncx_para
     if (dist_in_main) dprep.flags |= NCX_F_PRIV_DIST_IN_MAIN;
     if (!do_rest) pk.n = 0;                                   // prelude: no weight is read
     pk.nprep = do_pre ? (int)cdiv(M, 4) : 0;                  // rest: the pack blocks alone
-    const unsigned prep_grid = (unsigned)(pk.nprep + (long long)H * pk.n);
+    const unsigned prep_grid = (unsigned)(pk.nprep + (long long)pk.first[pk.n]);
     if (prep_grid > 0) {
         if (d.dv <= 2048 && d.A <= 2048)
             hipLaunchKernelGGL(k_prep<true>, dim3(prep_grid), dim3(256), 0, s, dprep, *in, idx_k, idx_o, idx_ob, mx, inv, misc, xc, bf16_cols(d), pk);
@@ -348,6 +369,30 @@ static int forward_impl(const ncx_dims* dp, const ncx_inputs* in, const ncx_para
     const bool merge_fix = !ss && !bf16 && aemb && !(d.flags & NCX_F_REUSE_GT) && u[U_GT].plan.cfg == u[U_SH].plan.cfg &&
                            !hook_env("NCX_NO_MERGE_FIX");
     // Gt[H, A] = W1[:, a_other] . E^T   (weights only: evaluation passes reuse it, NCX_F_REUSE_GT)
+    if (pair) {
+        // ... and Sh in ONE launch of 64 x 64 tiles split by the joint plan, one fix-up behind it: the two products are independent, and on launches
+        // of their own each pays the chip's ramp and drain for k-chunks too short to amortise it
+        auto seg = [&](MainArgs& a, int i, int kind, const float* x, long long lda, int klen, const int* idx, int slot, const float* wgt, long long ldb) {
+            MainSeg& g = a.seg[i]; g.kind = kind; g.a = x; g.lda = lda; g.idx = idx; g.klen = klen;
+            if (slot >= 0 && pw.width[slot]) { g.b = pw.ptr[slot]; g.ldb = pw.width[slot]; } else { g.b = wgt; g.ldb = ldb; } };
+        float* const pslab = (float*)(ws + w.slab2);
+        const size_t gt_elems = (size_t)r.pair_s_gt * H * d.A, sh_elems = (size_t)r.pair_s_sh * d.B * H;
+        if ((gt_elems + sh_elems) * 4 > w.slab2_bytes) return NCX_E_WORKSPACE;
+        MainArgs ag{}; ag.M = H; ag.N = d.A; ag.nseg = 4;          // Gt rides in the plain slot of the one kind sequence; its other segments are empty
+        seg(ag, 0, MK_GATHER, nullptr, 0, 0, nullptr, -1, nullptr, 0);
+        seg(ag, 1, MK_PLAIN, p->w1 + o.a_other, din, d.da, nullptr, 4, p->answer_embedding, d.da);
+        seg(ag, 2, MK_PLAIN, nullptr, 0, 0, nullptr, -1, nullptr, 0);
+        seg(ag, 3, MK_GATHER, nullptr, 0, 0, nullptr, -1, nullptr, 0);
+        ag.out = gt; ag.ldo = w.ldgt; ag.split = r.pair_s_gt; ag.slab = pslab;
+        MainArgs as{}; as.M = d.B; as.N = H; as.nseg = 4;
+        seg(as, 0, MK_GATHER, in->feats, d.dv, d.dv, idx_ob, 0, p->w1 + o.v_orig, din);
+        seg(as, 1, MK_PLAIN, in->q_emb, d.dq, d.dq, nullptr, 1, p->w1 + o.q_emb, din);
+        seg(as, 2, MK_PLAIN, in->z_orig, d.dz, d.dz, nullptr, 2, p->w1 + o.z_orig, din);
+        seg(as, 3, MK_GATHER, p->answer_embedding, d.da, d.da, in->answer_aids, 3, p->w1 + o.a_gt, din);
+        as.out = sh; as.ldo = H; as.split = r.pair_s_sh; as.slab = pslab + gt_elems; as.epi.bias = p->b1;
+        // (the chunks are the generic engine's, so Gt and Sh are the bits of the two launches below; the joint plan only shares them among fewer workgroups)
+        rc = profiled(U_SH, s, [&] { return main_forward_pair(ag, as, r.pair_s_gt / r.pair_w_gt, r.pair_s_sh / r.pair_w_sh, s); }); if (rc) return rc;
+    } else
     if (aemb && bf16 && !(d.flags & NCX_F_REUSE_GT)) {       // bf16 copies of E / W1[:, a_*] (also the backward's operands)
         const Bf16Emb m = bf16_emb_layout(d, ws + w.bf_emb);
         rc = bf16_pack_embedding(d, p->answer_embedding, p->w1, m, s2); if (rc) return rc;
@@ -363,7 +408,7 @@ static int forward_impl(const ncx_dims* dp, const ncx_inputs* in, const ncx_para
         if (rc) return rc;
     }
     // Sh[B, H] = b1 + shared segments
-    {
+    if (!pair) {
         GemmArgs a{}; a.mode = MODE_CHAIN; a.nseg = 4; a.M = d.B;
         a.a[0] = ss ? x_gather_strided(in->feats, d.dv, in->img_idx, d.K + 1, d.B, d.dv)      // (idx_ob is written by k_prep, concurrently)
                     : x_gather(in->feats, d.dv, idx_ob, d.B, d.dv);

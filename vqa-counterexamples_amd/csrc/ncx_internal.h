@@ -78,6 +78,7 @@ struct WsLayout {
     size_t km_slab;                     // k-chunk slabs of the fused v_other / v_mult weight gradient (ncx_dwkm.hip)
     size_t mslab, mslab_bytes;          // [split][M][N] partial sums of the fused forward kernel's split problems (max over its uses)
     size_t wpad;                        // zero-padded copies of the weight slices whose width is not a multiple of 32 (ncx_main.h)
+    size_t pwpad;                       // ... of the Gt + Sh pair launch's weight sides (W1[:, v_orig | q_emb | z_orig | a_gt], answer_embedding): ncx_plan.h
     int ldm;                            // leading dimension of misc: K + 1 rounded up to a multiple of 4 (zero padded)
     int ldgt;                           // leading dimension of Gt: A rounded up to a multiple of 32 (zero padded); bf16 variant: A
     size_t total;
@@ -128,6 +129,12 @@ int main_chain_form(long long M, long long N, long long T, int split, bool singl
 // (a.adam; WithAdam of ncx_main.h).  NCX_E_FLAGS when the shape does not take the 64 x 64 form: callers ask main_short_form first.
 int main_forward_adam(MainArgs& a, bool rowmap, hipStream_t s);
 int main_adam_passengers();          // passenger workgroups of that launch
+// Gt and Sh, the two short products in front of linear_1, as ONE launch of that 64 x 64 form plus one fix-up (the PAIR form of k_main_fwd, ncx_main.h).
+// Both argument sets are {G, P, P, G} chains with split and slab set: Sh fills all four segments, Gt the plain segment 1 with the others at
+// zero length.  Raw partial tiles go to each set's slab[z][M][N]; the fix-up sums them z ascending and applies each set's epilogue (bias only).
+// reps: consecutive chunks one workgroup runs (a divisor of the set's split): the chunks, and with them the bits of the sums, stay those of
+// `split` workgroups per tile -- the generic engine's for the same split -- while split / reps workgroups per tile share the round.
+int main_forward_pair(const MainArgs& gt, const MainArgs& sh, int reps_gt, int reps_sh, hipStream_t s);
 // The MLB producer's x_v product (ncx_mlb.hip): one MK_GATHER segment with the EPI_MLB epilogue of ncx_main.h
 int main_forward_mlb(MainArgs& a, hipStream_t s);
 // k-split of a problem for the fused forward kernel (48 x 128 tiles): 1 when its tiles already give every CU a workgroup,

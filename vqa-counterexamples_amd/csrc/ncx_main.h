@@ -45,12 +45,15 @@ template <int V> struct IntC { static constexpr int value = V; };
 // budget is sized for (workgroups per CU x T / 256)
 // X6 (NCX_F_X6; not the default): the plain / softmax segments run on the bf16 matrix path with three-plane fp32-grade operands (see run_seg)
 constexpr int MF6_P = 80;                                            // bytes per 32-deep row of one bf16 plane (64 + 16: conflict-free ds_read_b128)
+struct MainPairArgs { MainArgs p[2]; int wg0, reps[2]; };     // the PAIR form's kernel arguments (WithPair below): workgroups [0, wg0) run p[0], [wg0, grid) p[1] (wg0 % 8 == 0: ids keep their XCD); reps[q]: consecutive k-chunks a workgroup of p[q] runs
 template <int BM_, int BN_, int WGM_, int WGN_, int DEPTH_, int OCC_, int T_ = MF_T, bool X6_ = false>
 struct MainCfg {
+    typedef MainArgs KArgs;                                         // what the kernel is launched with
     static constexpr int BM = BM_, BN = BN_, WGM = WGM_, WGN = WGN_, DEPTH = DEPTH_, OCC = OCC_, T = T_;
     static constexpr bool X6 = X6_;
     static constexpr int EPI = 0;                                   // which epilogue the kernel is compiled with (EPI_MLB: WithMlbEpi below)
     static constexpr bool ADAM = false;                             // the launch also applies Adam (WithAdam below)
+    static constexpr bool PAIR = false;                             // the launch runs two problems, each workgroup one of them (WithPair below)
     static constexpr int RP = T / 8;                                // tile rows per loader pass (8 threads x 16 bytes per 32-float row)
     static constexpr int BM_LDS = (BM + RP - 1) / RP * RP;        // A rows held in LDS (a multiple of the loader pass)
     static constexpr int LDS6 = 2 * 3 * (BM_LDS + BN) * MF6_P;      // X6: [2 buffers][3 planes][A rows | W rows][MF6_P]
@@ -86,13 +89,32 @@ template <class CFG> struct WithRowMap : CFG { static constexpr int EPI = EPI_RO
 // [adam.pass_at, adam.pass_at + adam.n_pass) of the grid carry no tile: they update a slice of the rest of the flat buffer, HBM traffic beside
 // short latency-bound tiles.  The workgroup ids on either side of the passengers are the tile ids of the plain form, in order.
 template <class CFG> struct WithAdam : CFG { static constexpr bool ADAM = true; };
+// PAIR (Gt and Sh in front of linear_1): two independent short products share ONE launch, so the chip ramps up and drains
+// once for both.  Each workgroup picks its argument set by a scalar test on its id and is from there on a workgroup of the split form: it
+// stores its raw partial tile to slab[z][M][N] (also when its problem has a single chunk) and k_main_fixup_pair sums both problems in one
+// launch.  Both argument sets run the ONE kind sequence {G, P, P, G}: Sh fills all four segments, Gt the plain slot 1 with the others at
+// zero length (admitted in this form only: launch_main_fwd_pair), so the registers are those of a single role.  A workgroup runs reps[q]
+// consecutive chunks of its tile, each from zero accumulators to its own slab: the chunks stay those of the launches the pair replaces
+// (same bits), the workgroups per tile are what the joint plan fits into one round of every XCD (plan_gtsh_pair).
+template <class CFG> struct WithPair : CFG { static constexpr bool PAIR = true; typedef MainPairArgs KArgs; };
 
 typedef const __attribute__((address_space(1))) float* gfptr;      // global address space: global_load, never flat_load
 typedef const __attribute__((address_space(1))) int* giptr;
 typedef const __attribute__((address_space(1))) f32x4u* gf4ptr;
 
+// the argument set of this workgroup, (wg) its id within that set's problem and (reps) the chunks it runs: a scalar test on the workgroup id in the PAIR form
+__device__ __forceinline__ const MainArgs& main_args_of(const MainArgs& a, int&, int&) { return a; }
+__device__ __forceinline__ const MainArgs& main_args_of(const MainPairArgs& pa, int& wg, int& reps) {
+    const int sel = wg >= pa.wg0 ? 1 : 0;                // uniform: the kernel arguments are read through a scalar offset
+    wg -= sel ? pa.wg0 : 0;
+    reps = pa.reps[sel];
+    return pa.p[sel];
+}
+
 template <class CFG, bool DIST, int K0, int K1 = -1, int K2 = -1, int K3 = -1, int K4 = -1>
-__global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs args) {
+__global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const typename CFG::KArgs kargs) {
+    int wg = blockIdx.x, reps = 1;
+    const MainArgs& args = main_args_of(kargs, wg, reps);
     constexpr bool VFOLD = K0 == MK_VFOLD;
     constexpr int DIST_SEG = VFOLD ? 1 : 2;              // the (dist | rank) segment: right after the one that streams v_o and v_k
     static_assert(!DIST || (VFOLD ? K1 == MK_PLAIN : (K1 == MK_GATHER_MUL && K2 == MK_PLAIN)), "DIST: v_o, v_k segment followed by the dist | rank segment");
@@ -122,7 +144,7 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
     // accumulators to slab[z][M][N]; k_main_fixup sums the S slabs in fixed order and applies the epilogue.
     const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
     const int S = args.split > 1 ? args.split : 1;
-    int bid = blockIdx.x;
+    int bid = wg;
     if constexpr (CFG::ADAM) {                           // passengers leave here (uniform per workgroup), before any barrier and before the tile map
         const int pa = args.adam.pass_at, np = args.adam.n_pass;
         if (bid >= pa && bid < pa + np) { adam_passenger(args.adam, bid - pa, tid, MT); return; }
@@ -131,8 +153,12 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
     // (row tile, k-chunk) units are dealt over the XCDs; the column tiles of a unit are consecutive ids on one XCD
     const int id = bid, xcd = id & 7, local = id >> 3;
     const int tn = local % tiles_n, unit = (local / tiles_n) * 8 + xcd;
-    if (unit >= tiles_m * S) return;
-    const int tm = unit / S, z = unit - tm * S;
+    // PAIR: a tile's S chunks are shared by S / reps workgroups, each running `reps` consecutive chunks one after the other, every chunk from zero
+    // accumulators to its own slab: the partial tiles -- hence the bits of their sum -- are those of S workgroups, the round holds S / reps per tile
+    int wpt = S;                                         // workgroups per tile
+    if constexpr (CFG::PAIR) wpt = S / reps;
+    if (unit >= tiles_m * wpt) return;
+    const int tm = unit / wpt, z0 = (unit - tm * wpt) * (CFG::PAIR ? reps : 1);
     const int m0 = tm * BM, n0 = tn * BN;
     const int quad = tid & 7, trow = tid >> 3;
     unsigned long long* const stamps = args.stamps ? args.stamps + (size_t)blockIdx.x * 16 : nullptr;
@@ -142,6 +168,9 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
     if (stamps && tid == 0) { stamps[14] = __builtin_amdgcn_s_memrealtime(); stamps[13] = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20); }   // XCC_ID
     stamp(0);
 
+    int rep = 0;
+    do {                                                 // one pass unless PAIR (the body below keeps its indentation)
+    const int z = z0 + rep;
     f32x4 acc[WM][WN];
 #pragma unroll
     for (int i = 0; i < WM; ++i)
@@ -1064,10 +1093,11 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
     static_assert(BM * SP * 4 <= CFG::LDS, "the staged tile lies inside the launch's LDS (MainCfg::LDS_STAGE)");
     constexpr int QR = BN / 4;                            // 16-byte pieces per tile row
     const EpiArgs& e = args.epi;
-    float* const dst = S > 1 ? args.slab + (long long)z * M * N : args.out;      // S > 1: raw partial sums; k_main_fixup runs the epilogue
-    const long long ldd = S > 1 ? (long long)N : args.ldo;
+    const bool to_slab = CFG::PAIR || S > 1;             // raw partial sums; k_main_fixup (PAIR: k_main_fixup_pair, one chunk included) runs the epilogue
+    float* const dst = to_slab ? args.slab + (long long)z * M * N : args.out;
+    const long long ldd = to_slab ? (long long)N : args.ldo;
     // (ADAM: no epilogue operand, host-checked -- known here, so the unrolled loop of those forms carries no copy of the operand code)
-    const bool plain = CFG::ADAM || S > 1 || !(e.rowadd || e.bias || e.relu || e.dropout || e.gate);
+    const bool plain = CFG::ADAM || to_slab || !(e.rowadd || e.bias || e.relu || e.dropout || e.gate);
     // (the row-add operand of piece f + 256 is fetched while piece f is finished: rolled, but never waiting on its own load)
     auto item = [&](int f, int& r, int& n, int& nl) __attribute__((always_inline)) {
         const int rr = f / QR, cq = f - rr * QR;
@@ -1196,19 +1226,31 @@ __global__ __launch_bounds__(CFG::T, CFG::OCC) void k_main_fwd(const MainArgs ar
 #pragma unroll 1
         for (int f = tid; f < BM * QR; f += MT) piece(f, 0);
     }
+    if constexpr (CFG::PAIR) __syncthreads();            // (the next chunk's first tiles go where the staged tile is still being read)
+    } while (CFG::PAIR && ++rep < reps);
     stamp(8);
     if (stamps && tid == 0) stamps[15] = __builtin_amdgcn_s_memrealtime();
 }
 
 // out[r][n] = epilogue(sum_z slab[z][r][n]): 4 consecutive n per thread (N % 4 != 0: scalar tail), z ascending (deterministic)
-__global__ __launch_bounds__(256) void k_main_fixup(const MainArgs a) {
-    const int M = a.M, N = a.N, S = a.split;
+// VEC (the pair's fix-up): N % 4 == 0 reads each slab with one 16-byte load, four slabs in flight; the same sums in the same order
+template <bool VEC>
+__device__ __forceinline__ void main_fixup_body(const MainArgs& a, const int block, const int S) {
+    const int M = a.M, N = a.N;
     const int nq = (N + 3) / 4;
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long i = (long long)block * 256 + threadIdx.x;
     if (i >= (long long)M * nq) return;
     const int r = (int)(i / nq), n0 = (int)(i - (long long)r * nq) * 4;
     float v[4] = {0.f, 0.f, 0.f, 0.f};
     const long long mn = (long long)M * N, off = (long long)r * N + n0;
+    if (VEC && (N & 3) == 0) {
+#pragma unroll 4
+        for (int z = 0; z < S; ++z) {
+            const f32x4 w = *(const f32x4u*)(a.slab + z * mn + off);     // (4-byte aligned only: Sh's slab follows Gt's [S][H][A])
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] += w[j];
+        }
+    } else
     for (int z = 0; z < S; ++z)
 #pragma unroll
         for (int j = 0; j < 4; ++j) if (n0 + j < N) v[j] += a.slab[z * mn + off + j];
@@ -1219,6 +1261,13 @@ __global__ __launch_bounds__(256) void k_main_fixup(const MainArgs a) {
         if (n >= N) break;
         a.out[(long long)r * a.ldo + n] = apply_epilogue(e, v[j], r, n, N);
     }
+}
+__global__ __launch_bounds__(256) void k_main_fixup(const MainArgs a) { main_fixup_body<false>(a, (int)blockIdx.x, a.split); }
+// ... of both problems of the PAIR form in one launch: blocks [0, blocks0) finish p[0], the rest p[1] (a problem with one chunk: a copy with its epilogue)
+__global__ __launch_bounds__(256) void k_main_fixup_pair(const MainPairArgs pa, const int blocks0) {
+    const int sel = (int)blockIdx.x >= blocks0 ? 1 : 0;
+    const MainArgs& a = pa.p[sel];
+    main_fixup_body<true>(a, (int)blockIdx.x - (sel ? blocks0 : 0), a.split > 1 ? a.split : 1);
 }
 
 // Operand requirements of the kernel (see the header comment): klen >= 4 and a multiple of 4; weight rows readable (zero
@@ -1317,6 +1366,47 @@ static inline int launch_main_fwd(MainArgs& a, hipStream_t s) {
     }
 }
 
+
+// The pair form (WithPair): pa.p[0] / pa.p[1] in dispatch order, each {G, P, P, G} with its split and its slab set; a problem of one chunk goes
+// through the slab too.  A zero-length segment is admitted HERE only, and only around a lone plain segment 1 (Gt): the workgroups of such a
+// problem never hand over to another segment, so no step prefetches from an empty one.  Sets pa.wg0; launches the kernel and the one fix-up.
+template <class CFG>
+static inline int launch_main_fwd_pair(MainPairArgs& pa, hipStream_t s) {
+    static_assert(CFG::PAIR && sizeof(MainPairArgs) <= 4096, "the pair form; its arguments fit the kernel-argument segment");
+    long long wgs[2], blocks[2];
+    for (int q = 0; q < 2; ++q) {
+        const MainArgs& a = pa.p[q];
+        if (a.nseg != 4 || a.M < 1 || a.N < 1) return NCX_E_DIMS;
+        if (a.seg[0].kind != MK_GATHER || a.seg[1].kind != MK_PLAIN || a.seg[2].kind != MK_PLAIN || a.seg[3].kind != MK_GATHER) return NCX_E_FLAGS;
+        if (!a.slab || !a.out) return NCX_E_WORKSPACE;
+        const EpiArgs& e = a.epi;
+        if (a.dist_out || a.stamps || e.rowadd || e.relu || e.dropout || e.gate) return NCX_E_FLAGS;
+        const bool lone = a.seg[0].klen == 0 && a.seg[2].klen == 0 && a.seg[3].klen == 0;
+        long long T = 0;
+        for (int i = 0; i < 4; ++i) {
+            if (lone && i != 1) continue;
+            if (!main_fwd_operand_ok(a.seg[i].klen)) return NCX_E_DIMS;
+            if (a.seg[i].kind == MK_GATHER && !a.seg[i].idx) return NCX_E_NULL;
+            T += (a.seg[i].klen + MF_BK - 1) / MF_BK;
+        }
+        const long long S = a.split > 1 ? a.split : 1;
+        const long long R = pa.reps[q];
+        if (S > T || R < 1 || S % R) return NCX_E_DIMS;                    // (every chunk holds a step; whole workgroups)
+        const long long tiles_m = (a.M + CFG::BM - 1) / CFG::BM, tiles_n = (a.N + CFG::BN - 1) / CFG::BN;
+        wgs[q] = ((tiles_m * (S / R) + 7) / 8) * 8 * tiles_n;
+        blocks[q] = ((long long)a.M * ((a.N + 3) / 4) + 255) / 256;
+    }
+    if (wgs[0] + wgs[1] > (1ll << 30) || blocks[0] + blocks[1] > (1ll << 30)) return NCX_E_DIMS;
+    pa.wg0 = (int)wgs[0];
+    constexpr int lds = CFG::LDS;
+    static DevMask attr{0};
+    NCX_HIP_TRY(set_max_lds_once(attr, (const void*)k_main_fwd<CFG, false, MK_GATHER, MK_PLAIN, MK_PLAIN, MK_GATHER>, lds));
+    hipLaunchKernelGGL((k_main_fwd<CFG, false, MK_GATHER, MK_PLAIN, MK_PLAIN, MK_GATHER>), dim3((unsigned)(wgs[0] + wgs[1])), dim3(CFG::T), lds, s, pa);
+    NCX_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_main_fixup_pair, dim3((unsigned)(blocks[0] + blocks[1])), dim3(256), 0, s, pa, (int)blocks[0]);
+    NCX_HIP_TRY(hipGetLastError());
+    return NCX_OK;
+}
 
 // The forms with Adam (WithAdam): the answer-embedding gradient's two-segment chain, plain rows or permuted rows (WithRowMap), unsplit, no
 // epilogue operand.  a.adam carries the optimiser's buffers; n_pass and pass_at are set here: n_pass workgroups for the tail (none when it is

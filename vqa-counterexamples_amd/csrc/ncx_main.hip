@@ -98,6 +98,22 @@ int main_forward_adam(MainArgs& a, bool rowmap, hipStream_t s) {
     return rowmap ? launch_main_fwd_adam<WithAdam<WithRowMap<MainCfg3>>>(a, np, at, s) : launch_main_fwd_adam<WithAdam<MainCfg3>>(a, np, at, s);
 }
 
+// Gt and Sh as one launch of 64 x 64 tiles, three workgroups per CU (WithPair, ncx_main.h).  A workgroup of Gt / Sh runs reps_gt / reps_sh
+// consecutive chunks of its tile.  The problem whose workgroups run the more k-steps is dispatched first.
+int main_forward_pair(const MainArgs& gt, const MainArgs& sh, int reps_gt, int reps_sh, hipStream_t s) {
+    auto steps = [](const MainArgs& a, int reps) {
+        long long T = 0;
+        for (int i = 0; i < a.nseg; ++i) T += (a.seg[i].klen + MF_BK - 1) / MF_BK;
+        const long long S = a.split > 1 ? a.split : 1, W = S / (reps > 0 ? reps : 1);
+        return (T + W - 1) / (W > 0 ? W : 1);
+    };
+    MainPairArgs pa{};
+    const bool gt_first = steps(gt, reps_gt) >= steps(sh, reps_sh);
+    pa.p[0] = gt_first ? gt : sh; pa.p[1] = gt_first ? sh : gt;
+    pa.reps[0] = gt_first ? reps_gt : reps_sh; pa.reps[1] = gt_first ? reps_sh : reps_gt;
+    return launch_main_fwd_pair<WithPair<MainCfg3>>(pa, s);
+}
+
 // x_v of the MLB producer: 96 x 128 tiles, one workgroup per CU, once they fill the chip (12 800 x 1200 at B = 512: 1340 tiles), else 48 x 128
 int main_forward_mlb(MainArgs& a, hipStream_t s) {
     const long long tiles96 = (long long)((a.M + 95) / 96) * ((a.N + 127) / 128);

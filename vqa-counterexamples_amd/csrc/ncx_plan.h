@@ -22,7 +22,20 @@ struct StepRoutes {
     long long cand_ksteps;  // k-steps of linear_1's candidate chain: v_other (| v_mult) | dist, rank | z_other | softmax(a) or a_other
     // dW1[:, a_other] = dGt . E on the balanced TN kernel (not with the side stream: the kernel's slab is the main stream's)
     bool dw1ak_on_tn8(bool side) const { return tn8 && emb_nt && !side; }
+    // Gt and Sh as one launch of the fused forward kernel's 64 x 64 form (main_forward_pair).  pair_ok: what the shape, the variant and the hook
+    // decide -- the workspace is sized by it, with or without NCX_F_REUSE_GT (an evaluation pass finds the padded weights where the step left
+    // them); pair_s_gt / pair_s_sh: k-chunks per tile (the generic engine's plans); pair_w_gt / pair_w_sh: the joint plan's workgroups per tile
+    bool pair_ok; int pair_s_gt, pair_s_sh, pair_w_gt, pair_w_sh;
+    bool gtsh_pair(const ncx_dims& d, bool side) const { return pair_ok && !(d.flags & NCX_F_REUSE_GT) && !side; }
 };
+// The joint plan of the pair (ncx_plan.hip): s_gt / s_sh k-chunks per tile as on the generic engine, shared by w_gt / w_sh workgroups per
+// tile such that the workgroups of both problems fill at most one round of the 3 x CUs slots ON EVERY XCD.  w_gt == 0: no plan.
+struct PairPlan { int s_gt, s_sh, w_gt, w_sh; long long tiles_gt, tiles_sh, t_gt, t_sh, slots; };
+PairPlan plan_gtsh_pair(const ncx_dims& d, const StepRoutes& r);
+// padded copies of the weight sides of the pair whose width is not a multiple of 32 (ncx_main.h reads whole k-steps): slot 0 .. 3 the W1 slices
+// v_orig, q_emb, z_orig, a_gt ([H] rows), 4 answer_embedding ([A] rows); 0: used in place
+constexpr int PAIR_WPAD_N = 5;
+int pair_wpad_width(const ncx_dims& d, const StepRoutes& r, int i);
 StepRoutes routes(const ncx_dims& d);
 // linear_1 on the fused forward kernel (ncx_forward.hip), with the experiment hooks applied: the two v segments as one pass with the
 // per-triplet fold, and the pairwise distance computed by that kernel.  forward_impl launches by it, NCX_QUERY_FWD_ROUTE reports it.

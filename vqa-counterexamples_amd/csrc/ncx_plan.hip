@@ -114,7 +114,66 @@ StepRoutes routes(const ncx_dims& d) {
     // ... over rows permuted so that the answers of the batch come first: the row tiles behind them skip the dGgt^T segment (all zeros there)
     r.de_skip = r.emb_nt && d.A <= NCX_PERM_MAX_A && !hook_env("NCX_NO_DE_SKIP");
     r.cand_ksteps = ksteps(d.dv) * ((d.flags & NCX_F_V_MULT) ? 2 : 1) + ksteps(d.K + 1) + ksteps(d.dz) + ksteps(aemb ? d.A : d.da);
+    // Gt and Sh as one launch: fp32 path with the a_emb segment on, every reduction extent a multiple of 4 (16-byte operand windows), operand
+    // extents below 4 GiB, and a joint plan that splits at least one of the two (else today's launches already fill the chip or have nothing to cut)
+    r.pair_s_gt = r.pair_s_sh = 1; r.pair_w_gt = r.pair_w_sh = 0;
+    r.pair_ok = false;
+    if (aemb && !bf16 && d.dv % 4 == 0 && d.dq % 4 == 0 && d.dz % 4 == 0 && d.da % 4 == 0 && main_fwd_extents_ok(d) &&
+        (long long)d.B * d.dq * 4 < (1ll << 32) - 65536 && !hook_env("NCX_NO_GTSH_PAIR")) {
+        const PairPlan p = plan_gtsh_pair(d, r);
+        r.pair_s_gt = p.s_gt; r.pair_s_sh = p.s_sh; r.pair_w_gt = p.w_gt; r.pair_w_sh = p.w_sh;
+        r.pair_ok = p.w_gt > 0 && (p.s_gt > 1 || p.s_sh > 1);
+    }
     return r;
+}
+
+// The splits of the pair are those the generic engine's plans give the two problems on launches of their own (list_uses: U_GT, U_SH; both cut a
+// chain of T steps into S chunks [T z / S, T (z + 1) / S) and sum a 32-deep step in one order), and the fix-up adds the partial tiles z
+// ascending like split_fixup2_kernel: Gt and Sh are then the two-launch path's bit for bit, and a training run keeps its trajectory.  What
+// the joint plan chooses is how many WORKGROUPS share a tile's chunks: w_gt | S_gt, w_sh | S_sh, a workgroup running S / w consecutive chunks.
+// The kernel deals its (row tile, workgroup) units round-robin over the 8 XCDs and keeps a unit's column tiles on one XCD, so the round that
+// must hold is the round of EVERY XCD: ceil(units / 8) x column tiles of both problems together within 3 x CUs / 8 slots -- with Gt's 32
+// column tiles per unit a plan that fits the chip as a whole (3 and 10 workgroups per tile at configs[1]: 704 of 768 slots) still puts 104
+// workgroups on the 96 slots of four XCDs, and the launch waits for their second round (measured: 58.5 us against 65.9 for the two launches
+// it replaces).  Among the (w_gt, w_sh) that fit every XCD's round: the pair whose longest workgroup is shortest (the launch is as
+// long as its slowest workgroup and what shares its CU), then the one that leaves the fullest XCD the fewest tile-steps.  configs[1]: S = 4 /
+// 16 as on the generic engine, 4 / 8 workgroups per tile, 768 in all, 64 + 32 on every XCD (two of Gt and one of Sh per CU).
+// w_gt == 0: no plan (another tile form, or even one workgroup per tile overfills an XCD).
+PairPlan plan_gtsh_pair(const ncx_dims& d, const StepRoutes& r) {
+    PairPlan p{};
+    const long long tm_gt = cdiv(d.H, 64), tn_gt = cdiv(d.A, 64), tm_sh = cdiv(d.B, 64), tn_sh = cdiv(d.H, 64);
+    p.tiles_gt = tm_gt * tn_gt; p.t_gt = ksteps(d.da);
+    p.tiles_sh = tm_sh * tn_sh; p.t_sh = ksteps(d.dv) + ksteps(d.dq) + ksteps(d.dz) + ksteps(d.da);
+    p.slots = 3ll * num_cus();
+    p.s_gt = p.s_sh = 1; p.w_gt = p.w_sh = 0;
+    GemmUse u[U_COUNT];
+    list_uses(d, r, u);
+    if (u[U_GT].plan.cfg != CFG_64x64 || u[U_SH].plan.cfg != CFG_64x64) return p;
+    p.s_gt = u[U_GT].plan.split > 1 ? u[U_GT].plan.split : 1;
+    p.s_sh = u[U_SH].plan.split > 1 ? u[U_SH].plan.split : 1;
+    if (p.s_gt > p.t_gt || p.s_sh > p.t_sh) return p;
+    if (const char* e = hook_env("NCX_PAIR_WPT")) {      // experiment hook (NCX_EXPERIMENT=1): "w_gt,w_sh", the workgroups per tile (divisors of the splits, else no plan)
+        int wg = 0, ws = 0;
+        if (sscanf(e, "%d,%d", &wg, &ws) == 2 && wg >= 1 && ws >= 1 && p.s_gt % wg == 0 && p.s_sh % ws == 0) { p.w_gt = wg; p.w_sh = ws; }
+        return p;
+    }
+    const long long xcd_slots = p.slots / 8;
+    long long best_work = -1, best_long = 0;
+    for (long long wg = 1; wg <= p.s_gt; ++wg)
+        for (long long ws = 1; ws <= p.s_sh; ++ws) {
+            if (p.s_gt % wg || p.s_sh % ws) continue;
+            const long long n_gt = cdiv(tm_gt * wg, 8) * tn_gt, n_sh = cdiv(tm_sh * ws, 8) * tn_sh;      // workgroups of the fullest XCD
+            if (n_gt + n_sh > xcd_slots) continue;
+            const long long cg = cdiv(p.t_gt, wg), cs = cdiv(p.t_sh, ws), lng = cg > cs ? cg : cs;
+            const long long work = n_gt * cg + n_sh * cs;                                                // ... and its tile-steps
+            if (best_work < 0 || lng < best_long || (lng == best_long && work < best_work)) { best_work = work; best_long = lng; p.w_gt = (int)wg; p.w_sh = (int)ws; }
+        }
+    return p;
+}
+
+int pair_wpad_width(const ncx_dims& d, const StepRoutes& r, int i) {
+    const int c[PAIR_WPAD_N] = {d.dv, d.dq, d.dz, d.da, d.da};
+    return (!r.pair_ok || c[i] % 32 == 0) ? 0 : pad_to(c[i], 32);
 }
 
 // Split of one candidate-column problem of the grouped dW1 launch.  The big problems (2048 / 2000 columns) fill whole
@@ -259,6 +318,9 @@ WsLayout ws_layout(const ncx_dims& d, const StepRoutes& r) {
         if (u[U_SH].slab_elems > s2) s2 = u[U_SH].slab_elems;
         if (u[U_DW1AK].slab_elems > s2) s2 = u[U_DW1AK].slab_elems;
         if (u[U_DE].slab_elems > s2) s2 = u[U_DE].slab_elems;
+        // ... which also holds the partial tiles of the Gt + Sh pair launch: [S_gt][H][A], then [S_sh][B][H]
+        const long long pair = r.pair_ok ? (long long)r.pair_s_gt * d.H * d.A + (long long)r.pair_s_sh * d.B * d.H : 0;
+        if (pair > s2) s2 = pair;
         w.slab2_bytes = (size_t)s2 * 4;
         w.slab2 = take(w.slab2_bytes);
     }
@@ -279,6 +341,11 @@ WsLayout ws_layout(const ncx_dims& d, const StepRoutes& r) {
         w.xc = take(bf16_xc_bytes(d)); w.wc = take(bf16_wc_bytes(d));
         w.dpre_bf = take(bf16_dpre_bytes(d)); w.bf_slab = take(bf16_slab_bytes(d));
         w.bf_emb = take(bf16_emb_bytes(d));
+    }
+    {   // padded weight copies of the Gt + Sh pair launch (last: every other region keeps its place)
+        size_t e = 0;
+        for (int i = 0; i < PAIR_WPAD_N; ++i) e += (size_t)(i == 4 ? d.A : d.H) * pair_wpad_width(d, r, i);
+        w.pwpad = take(e * 4);
     }
     w.total = off;
     return w;

@@ -425,6 +425,9 @@ NCX_QUERY_BF16_ROUTE = 35       # include/neuralcx.h
 BF16_NT_FORMS = {0: "128x128", 1: "64x128", 2: "128x64", 3: "64x64", 8: "nt8"}
 
 
+NCX_QUERY_GTSH_PAIR = 36        # include/neuralcx.h
+
+
 def bf16_layout(d):
     """ncx_bf16_layout: the column layout of the packed bf16 operands and the padded extents, by name."""
     out = (C.c_int32 * 10)()
@@ -445,6 +448,9 @@ def plan_query(d, name):
         return dict(engine=out[0], engine_name=FWD_ENGINES[out[0]], tile=out[1],
                     tile_name=FWD_CHAIN_FORMS[out[1]] if out[0] == 1 else ("%dx64" % out[1] if out[0] == 2 else None),
                     split=out[2], dist_in_main=bool(out[3]), hidden_engine=out[4], hidden_split=out[5])
+    if name == "GTSH_PAIR":
+        check(lib().ncx_plan_query(C.byref(d), NCX_QUERY_GTSH_PAIR, out), "ncx_plan_query")
+        return dict(taken=bool(out[0]), s_gt=out[1], s_sh=out[2], w_gt=out[3], w_sh=out[4], slots=out[5])
     if name == "FUSED_ADAM":
         check(lib().ncx_plan_query(C.byref(d), NCX_QUERY_FUSED_ADAM, out), "ncx_plan_query")
         return dict(fused=bool(out[0]), passengers=out[1])
