@@ -9,29 +9,12 @@ import pytest
 import torch
 
 import mlb_att_ref as R
+from trainer_edge_cases import ACT_CODE, ACT_FIELD
+from trainer_edge_cases import att_weights as weights_of
 from test_mlb_att_cpu import WORDS, YAML, _cli, att_opt, load_case
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-ACT_CODE = {None: 0, "": 0, "tanh": 2}
-ACT_FIELD = dict(att_v="act_v_att", att_q="act_q_att", att_mm="act_mm", v="act_v", q="act_q", c="act_c")
-
-
-def weights_of(state, acts=None):
-    from neuralcx import ops
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-    G = state["conv_att.weight"].shape[0]
-    tens = dict(wv_att=t(state["conv_v_att.weight"].reshape(state["conv_v_att.weight"].shape[0], -1)), bv_att=t(state["conv_v_att.bias"]),
-                wq_att=t(state["linear_q_att.weight"]), bq_att=t(state["linear_q_att.bias"]),
-                wa=t(state["conv_att.weight"].reshape(G, -1)), ba=t(state["conv_att.bias"]),
-                wg=t(np.stack([state["list_linear_v_fusion.%d.weight" % g] for g in range(G)])),
-                bg=t(np.stack([state["list_linear_v_fusion.%d.bias" % g] for g in range(G)])),
-                wqf=t(state["linear_q_fusion.weight"]), bqf=t(state["linear_q_fusion.bias"]),
-                wc=t(state["linear_classif.weight"]), bc=t(state["linear_classif.bias"]))
-    codes = {ACT_FIELD[k]: ACT_CODE[v] for k, v in (acts or {}).items()}
-    return ops.MlbAttWeights.from_tensors(tens, **codes)
-
 
 def check(got_logits, got_att, ref_logits, ref_att, floor, what):
     """max|got - ref| <= 1e-4 max(floor, max|ref|) for the logits and for each glimpse's map; prints every figure before it asserts."""

@@ -13,6 +13,7 @@ import torch
 
 import mlb_att_ref as R
 import mlb_att_train_ref as TR
+import trainer_edge_cases as E
 from helpers import grad_tol
 from test_mlb_att_cpu import YAML, _cli
 from test_mlb_att_gpu import ACT_FIELD, module_on_gpu, weights_of
@@ -127,12 +128,7 @@ def test_hip_step_vs_golden(name):
 
 
 # ---- 2. fp64 parity on edge shapes -------------------------------------------------------------------------------------------------
-EDGE = [(5, 64, 48, 32, 2, 24, 40, 5, 7),           # P = 35, ragged 64-row tile
-        (3, 36, 20, 70, 3, 12, 9, 14, 14),          # P = 196: the 208-row tile; two hidden tiles, the second ragged; dv = one whole step + 4
-        (4, 33, 12, 65, 8, 5, 7, 5, 13),            # P = 65, two position tiles; G = 8; odd widths
-        (2, 8, 8, 4, 1, 4, 4, 1, 2),                # the P < 4 kernel; minimal widths; G = 1
-        (2, 8, 8, 8, 2, 4, 4, 1, 1),                # P = 1: ds is exactly zero
-        (13, 40, 16, 48, 2, 8, 6, 3, 3)]            # repeated, non-identity img_idx; uneven image groups of the dWv_att split
+EDGE = E.ATT_EDGE
 
 
 @pytest.mark.parametrize("mode", [0, 2], ids=["mode0", "mode2_p0.5"])

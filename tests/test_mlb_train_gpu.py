@@ -12,32 +12,21 @@ import pytest
 import torch
 
 import mlb_train_ref as R
+import trainer_edge_cases as E
 from conftest import GOLDEN, PKG
 from helpers import grad_tol
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 # (B, dv, dq, dh, A)
-EDGE_SHAPES = [(1, 36, 20, 4, 8), (33, 100, 68, 20, 52), (70, 132, 96, 44, 100), (130, 64, 48, 36, 2000), (48, 2048, 2400, 1200, 2000)]
+EDGE_SHAPES = E.MLB_EDGE + [E.MLB_RAGGED, (48, 2048, 2400, 1200, 2000)]
+_case = E.mlb_case
 ALL_ON = (True, True, True)
 _ids = lambda s: "x".join(map(str, s))
 
 
 def _t(a, dt=torch.float32):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV, dt)
-
-
-def _case(shape, seed=0, gain=2.0, n_extra=3):
-    """Seeded inputs: a feature table with n_extra spare rows, an identity index, q, targets, p = 0.5 keep masks."""
-    B, dv, dq, dh, A = shape
-    rng = np.random.default_rng(seed + B)
-    P = R.init_params(seed + 1, dv, dq, dh, A, gain=gain)
-    feats = (np.abs(rng.standard_normal((B + n_extra, dv))) * 0.45).astype(np.float32)
-    q = (rng.standard_normal((B, dq)) * 0.3).astype(np.float32)
-    idx = np.arange(B, dtype=np.int32)
-    target = rng.integers(0, A, size=B).astype(np.int32)
-    masks = tuple((rng.random((B, w)) >= 0.5).astype(np.float32) for w in (dv, dq, dh))
-    return P, feats, q, idx, target, masks
 
 
 def _weights(P, acts=ALL_ON):
@@ -135,9 +124,7 @@ def test_parity_with_reference_fixture(case):
 def _edge_inputs(shape):
     P, feats, q, idx, target, masks = _case(shape)
     if shape[0] == 33:                       # a non-identity index: a repeated image, an all-zero feature row, ids outside the table (clamped)
-        feats[35] = 0.0
-        idx = np.random.default_rng(5).permutation(33).astype(np.int32)
-        idx[3] = idx[7]; idx[11] = 35; idx[20] = -4; idx[21] = 99
+        idx = E.gathered_33(feats, out_of_table=True)
     return P, feats, q, idx, target, masks
 
 
@@ -160,7 +147,7 @@ def test_edge_shapes_explicit_masks(shape, want_dq):
 @pytest.mark.parametrize("off", [0, 1, 2], ids=["no_act_v", "no_act_q", "no_act_c"])
 @pytest.mark.parametrize("shape", EDGE_SHAPES[:3], ids=_ids)
 def test_edge_shapes_one_activation_off(shape, off, want_dq):
-    """each activation switched off removes one factor of k_mt_dfuse (and act_c the stored t)"""
+    """each activation switched off removes one factor of k_train_dfuse (and act_c the stored t)"""
     _edge(shape, want_dq, tuple(i != off for i in range(3)))
 
 

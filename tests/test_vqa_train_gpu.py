@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import trainer_edge_cases as E
 import vqa_train_ref as R
 from conftest import GOLDEN, PKG
 from helpers import grad_tol
@@ -16,25 +17,12 @@ from loss_adam_ref import ce_ref as _ce_ref
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 # (B, dv, dq, dhv, dhq, dz, R, A)
-EDGE_SHAPES = [(1, 36, 20, 12, 8, 4, 1, 8), (33, 100, 68, 36, 44, 20, 3, 52), (70, 132, 96, 44, 40, 40, 10, 100),
-               (130, 64, 48, 32, 32, 36, 10, 2000), (48, 2048, 2400, 360, 360, 360, 10, 2000)]
+EDGE_SHAPES = E.MUTAN_EDGE + [E.MUTAN_RAGGED, (48, 2048, 2400, 360, 360, 360, 10, 2000)]
+_case = E.mutan_case
 
 
 def _t(a, dt=torch.float32):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV, dt)
-
-
-def _case(shape, seed=0, gain=2.0, n_extra=3):
-    """Seeded inputs: a feature table with n_extra spare rows, an identity index, q, targets, p = 0.5 keep masks."""
-    B, dv, dq, dhv, dhq, dz, Rk, A = shape
-    rng = np.random.default_rng(seed + B)
-    P = R.init_params(seed + 1, dv, dq, dhv, dhq, dz, Rk, A, gain=gain)
-    feats = (np.abs(rng.standard_normal((B + n_extra, dv))) * 0.45).astype(np.float32)
-    q = (rng.standard_normal((B, dq)) * 0.3).astype(np.float32)
-    idx = np.arange(B, dtype=np.int32)
-    target = rng.integers(0, A, size=B).astype(np.int32)
-    masks = tuple((rng.random((B, w)) >= 0.5).astype(np.float32) for w in (dv, dq, dz))
-    return P, feats, q, idx, target, masks
 
 
 def _weights(P, Rk, act_v=True, act_q=True):
@@ -134,9 +122,7 @@ def test_parity_with_reference_fixture(case):
 def test_edge_shapes_explicit_masks(shape, want_dq):
     P, feats, q, idx, target, masks = _case(shape)
     if shape[0] == 33:                       # a non-identity index: a repeated image and an all-zero feature row
-        feats[35] = 0.0
-        idx = np.random.default_rng(5).permutation(33).astype(np.int32)
-        idx[3] = idx[7]; idx[11] = 35
+        idx = E.gathered_33(feats, out_of_table=False)
     out = _run(shape, P, feats, q, idx, target, masks=masks, p=(0.5, 0.5, 0.5), mode=2, want_dq=want_dq)
     ref = R.step(P, feats[idx], q, target, masks=masks, p=(0.5, 0.5, 0.5))
     assert (out["dq"] is None) == (not want_dq)

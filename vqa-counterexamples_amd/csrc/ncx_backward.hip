@@ -477,7 +477,7 @@ int ncx_train_tail(const ncx_dims* dp, const ncx_params* p, void* workspace, siz
     if (d.K > 32 || d.H > 256) return NCX_E_DIMS;            // the K rows of a triplet live in registers, one lane per 4 columns
     const StepRoutes r = routes(d);
     const WsLayout w = ws_layout(d, r);
-    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) return NCX_E_WORKSPACE;
+    if (!ws_ok(workspace, workspace_bytes, w.total)) return NCX_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream_;
     char* ws = (char*)workspace;
     const int H = d.H;
@@ -535,7 +535,7 @@ static int backward_impl(const ncx_dims* dp, const ncx_inputs* in, const ncx_par
     if (d.L >= 3 && (!g->w3 || !g->b3)) return NCX_E_NULL;
     const StepRoutes r = routes(d);
     const WsLayout w = ws_layout(d, r);
-    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) return NCX_E_WORKSPACE;
+    if (!ws_ok(workspace, workspace_bytes, w.total)) return NCX_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream_;
     char* ws = (char*)workspace;
     const int M = d.B * d.K, H = d.H;

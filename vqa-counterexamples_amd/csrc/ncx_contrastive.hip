@@ -63,16 +63,15 @@ static GemmArgs ct_gemm_dw(const ncx_contrastive_dims& d, const CtPtrs& p, GemmP
 }
 
 static CtLayout ct_layout(const ncx_contrastive_dims& d) {
-    CtLayout w{}; size_t o = 0;
+    CtLayout w{}; WsCarver cv;
     const size_t M = (size_t)d.B * d.P;
-    auto take = [&](size_t bytes) { const size_t r = o; o = align_up(o + bytes, 256); return r; };
-    w.idx = take(M * 4); w.zall = take(M * d.dz * 4); w.h = take(M * CT_H * 4); w.dpre = take(M * CT_H * 4);
-    w.per = take((size_t)d.B * 16);
+    w.idx = cv.take(M * 4); w.zall = cv.take(M * d.dz * 4); w.h = cv.take(M * CT_H * 4); w.dpre = cv.take(M * CT_H * 4);
+    w.per = cv.take((size_t)d.B * 16);
     CtPtrs p{}; GemmPlan pl; size_t sb, t;
     GemmArgs a = ct_gemm_h(d, p, &pl); sb = gemm_slab_bytes(a, pl);
     a = ct_gemm_dw(d, p, &pl);         t = gemm_slab_bytes(a, pl); sb = t > sb ? t : sb;
-    w.slab = take(sb); w.slab_bytes = sb;
-    w.total = o;
+    w.slab = cv.take(sb); w.slab_bytes = sb;
+    w.total = cv.off;
     return w;
 }
 
@@ -196,7 +195,7 @@ extern "C" int ncx_contrastive_forward(const ncx_contrastive_dims* dp, const ncx
     if (!ct_dims_ok(dp)) return NCX_E_DIMS;
     const ncx_contrastive_dims& d = *dp;
     const CtLayout l = ct_layout(d);
-    if (ws_bytes < l.total || ((uintptr_t)ws & 255)) return NCX_E_WORKSPACE;
+    if (!ws_ok(ws, ws_bytes, l.total)) return NCX_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream_;
     char* base = (char*)ws;
     const long long M = (long long)d.B * d.P, n = M * d.dz;
@@ -217,7 +216,7 @@ extern "C" int ncx_contrastive_distances(const ncx_contrastive_dims* dp, const f
     if (!ct_dims_ok(dp)) return NCX_E_DIMS;
     if (!h) {
         const CtLayout l = ct_layout(*dp);
-        if (ws_bytes < l.total || ((uintptr_t)ws & 255)) return NCX_E_WORKSPACE;
+        if (!ws_ok(ws, ws_bytes, l.total)) return NCX_E_WORKSPACE;
         h = (const float*)((char*)ws + l.h);
     } else if ((uintptr_t)h & 15) return NCX_E_DIMS;
     const long long n = (long long)dp->B * (dp->P - 1);
@@ -231,7 +230,7 @@ extern "C" int ncx_contrastive_loss(const ncx_contrastive_dims* dp, void* ws, si
     if (!dp || !ws || !losses4) return NCX_E_NULL;
     if (!ct_dims_ok(dp) || dp->P != 3) return NCX_E_DIMS;
     const CtLayout l = ct_layout(*dp);
-    if (ws_bytes < l.total || ((uintptr_t)ws & 255)) return NCX_E_WORKSPACE;
+    if (!ws_ok(ws, ws_bytes, l.total)) return NCX_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream_;
     char* base = (char*)ws;
     float* per = (float*)(base + l.per);
@@ -249,7 +248,7 @@ extern "C" int ncx_contrastive_backward(const ncx_contrastive_dims* dp, const nc
     if (!ct_dims_ok(dp)) return NCX_E_DIMS;
     const ncx_contrastive_dims& d = *dp;
     const CtLayout l = ct_layout(d);
-    if (ws_bytes < l.total || ((uintptr_t)ws & 255)) return NCX_E_WORKSPACE;
+    if (!ws_ok(ws, ws_bytes, l.total)) return NCX_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream_;
     char* base = (char*)ws;
     const long long M = (long long)d.B * d.P;

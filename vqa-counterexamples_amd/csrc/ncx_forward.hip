@@ -287,7 +287,7 @@ static int forward_impl(const ncx_dims* dp, const ncx_inputs* in, const ncx_para
     if (d.L >= 3 && (!p->w3 || !p->b3)) return NCX_E_NULL;
     const StepRoutes r = routes(d);
     const WsLayout w = ws_layout(d, r);
-    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) return NCX_E_WORKSPACE;
+    if (!ws_ok(workspace, workspace_bytes, w.total)) return NCX_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream_;
     char* ws = (char*)workspace;
     const int M = d.B * d.K, H = d.H;

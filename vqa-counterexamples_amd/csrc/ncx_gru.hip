@@ -189,7 +189,7 @@ struct GruLayout { RnnPlanOff plan; size_t h0, h1, total; };
 static GruLayout gru_layout(int B, int dim_q) {
     GruLayout w{};
     WsCarver c;
-    w.plan = c.take_plan(B);
+    w.plan = take_plan(c, B);
     w.h0 = c.take((size_t)B * dim_q * 4); w.h1 = c.take((size_t)B * dim_q * 4);
     w.total = c.off;
     return w;

@@ -152,7 +152,7 @@ static GruTrainLayout gru_train_layout(int B, int T, int dim_emb, int dim_q) {
     GruTrainLayout w{};
     WsCarver c;
     const size_t pairs = (size_t)B * T, dqp = pad_to(dim_q, GEMM_BK);
-    w.plan = c.take_plan(B);
+    w.plan = take_plan(c, B);
     w.tok = c.take(pairs * 4);
     w.h = c.take(pairs * dim_q * 4); w.gates = c.take(pairs * 4 * dqp * 4); w.dg = c.take(pairs * 4 * dqp * 4);
     w.dh0 = c.take((size_t)B * dim_q * 4); w.dh1 = c.take((size_t)B * dim_q * 4);

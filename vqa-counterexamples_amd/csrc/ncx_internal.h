@@ -53,6 +53,14 @@ __attribute__((visibility("hidden"))) int run_gemm_planned(GemmArgs& a, int form
 // ncx_scorers.hip: out[c] = sum over rows r < R of in[r * ld + c], c < cols, in a fixed order (k_colsum)
 __attribute__((visibility("hidden"))) hipError_t colsum_rows(const float* in, long long ld, int R, int cols, float* out, hipStream_t s);
 
+// Byte offsets of a workspace's regions, each 256-byte aligned, in the order they are taken (off: the bytes taken so far)
+struct WsCarver {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; }
+};
+// what every entry point asks of the workspace it is handed: 256-byte aligned and at least `total` bytes (else NCX_E_WORKSPACE)
+static inline bool ws_ok(const void* ws, size_t bytes, size_t total) { return bytes >= total && !((uintptr_t)ws & 255); }
+
 // Workspace partition (byte offsets from a 256-byte aligned base).  Saved-for-backward part first.
 struct WsLayout {
     size_t idx_k, idx_o, idx_ob;        // int32 [M], [M], [B]: feature-table rows per logical row

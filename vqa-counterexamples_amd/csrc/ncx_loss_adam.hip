@@ -1,5 +1,5 @@
-// ncx_loss_adam.hip -- the two entry points every scorer shares: the listwise loss / rank (ncx_loss_rank) and the Adam update
-// (ncx_adam_step).
+// ncx_loss_adam.hip -- the losses and the optimiser every model shares: the scorers' listwise loss / rank (ncx_loss_rank), the VQA
+// trainers' cross-entropy over the answers (ncx_ce_loss) and the Adam update (ncx_adam_step).
 #include "ncx_wave.h"
 #include "ncx_adam.h"
 
@@ -48,6 +48,73 @@ __global__ __launch_bounds__(256) void k_loss_finish(const float* __restrict__ l
     }
 }
 
+// Mean cross-entropy over A answers (the loss of the three VQA trainers): one workgroup per example.  rows[b] = CE_b scale,
+// rows[B + b] (as int) = hit bits (1: top-1, 2: top-5).
+__device__ __forceinline__ float ce_block_max(float v, float* red) {
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+__device__ __forceinline__ float ce_block_sum(float v, float* red) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__global__ __launch_bounds__(256) void k_ce_rows(const float* __restrict__ logits, const int* __restrict__ target, int B, int A, float scale,
+                                                 float* __restrict__ dlogits, float* __restrict__ rows, int* __restrict__ bad) {
+    __shared__ float red[4];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const float* x = logits + (long long)b * A;
+    const int tg = target[b];
+    const bool ok = tg >= 0 && tg < A;
+    if (!ok) {                                           // never used as an address: the row contributes nothing
+        if (t == 0) { *bad = 1; rows[b] = 0.f; ((int*)rows)[B + b] = 0; }
+        if (dlogits) for (int c = t; c < A; c += 256) dlogits[(long long)b * A + c] = 0.f;
+        return;
+    }
+    const float xt = x[tg];
+    float mx = -INFINITY; int ahead = 0;
+    for (int c = t; c < A; c += 256) {
+        const float v = x[c];
+        mx = fmaxf(mx, v);
+        ahead += (v > xt || (v == xt && c < tg)) ? 1 : 0;
+    }
+    mx = ce_block_max(mx, red);
+    float se = 0.f;
+    for (int c = t; c < A; c += 256) se += __expf(x[c] - mx);
+    se = ce_block_sum(se, red);
+    const int rank = (int)ce_block_sum((float)ahead, red);
+    if (dlogits) {
+        const float inv = 1.f / se;
+        for (int c = t; c < A; c += 256) dlogits[(long long)b * A + c] = (__expf(x[c] - mx) * inv - (c == tg ? 1.f : 0.f)) * scale;
+    }
+    if (t == 0) {
+        rows[b] = (logf(se) - (xt - mx)) * scale;              // (xt - mx first: the row's offset never meets the small log term)
+        ((int*)rows)[B + b] = (rank < 1 ? 1 : 0) | (rank < 5 ? 2 : 0);
+    }
+}
+// loss = sum_b rows[b]; the hit counts: single workgroup, fixed order
+__global__ __launch_bounds__(256) void k_ce_finish(const float* __restrict__ rows, int B, float* __restrict__ loss, int* __restrict__ h1,
+                                                   int* __restrict__ h5) {
+    __shared__ float red[4];
+    float acc = 0.f, c1 = 0.f, c5 = 0.f;
+    for (int i = threadIdx.x; i < B; i += 256) {
+        acc += rows[i];
+        const int bits = ((const int*)rows)[B + i];
+        c1 += (float)(bits & 1); c5 += (float)((bits >> 1) & 1);
+    }
+    acc = ce_block_sum(acc, red); c1 = ce_block_sum(c1, red); c5 = ce_block_sum(c5, red);
+    if (threadIdx.x == 0) {
+        if (loss) loss[0] = acc;
+        if (h1) h1[0] = (int)c1;
+        if (h5) h5[0] = (int)c5;
+    }
+}
+
 // torch.optim.Adam on a flat buffer: the update itself is adam_update (ncx_adam.h), shared with the launch that applies it where the
 // answer-embedding gradient is produced.
 __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -82,6 +149,21 @@ int ncx_loss_rank(const float* scores, const int32_t* gt, int32_t B, int32_t K, 
     NCX_HIP_TRY(hipGetLastError());
     if (loss || hits) {
         hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(256), 0, s, (const float*)loss_rows, (const int*)rank, B, loss, hits);
+        NCX_HIP_TRY(hipGetLastError());
+    }
+    return NCX_OK;
+}
+
+int ncx_ce_loss(const float* logits, const int32_t* target, int32_t B, int32_t A, float scale, float* loss, float* dlogits,
+                int32_t* hits_top1, int32_t* hits_top5, int32_t* bad_flag, float* rows, void* stream_) {
+    if (!logits || !target || !bad_flag || !rows) return NCX_E_NULL;
+    if (B < 1 || A < 1 || (long long)B * A >= (1ll << 31)) return NCX_E_DIMS;
+    hipStream_t s = (hipStream_t)stream_;
+    if (scale <= 0.f) scale = 1.f / (float)B;
+    hipLaunchKernelGGL(k_ce_rows, dim3(B), dim3(256), 0, s, logits, target, B, A, scale, dlogits, rows, bad_flag);
+    NCX_HIP_TRY(hipGetLastError());
+    if (loss || hits_top1 || hits_top5) {
+        hipLaunchKernelGGL(k_ce_finish, dim3(1), dim3(256), 0, s, (const float*)rows, B, loss, hits_top1, hits_top5);
         NCX_HIP_TRY(hipGetLastError());
     }
     return NCX_OK;

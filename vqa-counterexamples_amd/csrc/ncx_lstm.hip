@@ -263,7 +263,7 @@ struct Lstm2Layout { RnnPlanOff plan; size_t h[2][2], c[2], total; };
 static Lstm2Layout lstm2_layout(int B, int H) {
     Lstm2Layout w{};
     WsCarver c;
-    w.plan = c.take_plan(B);
+    w.plan = take_plan(c, B);
     for (int l = 0; l < 2; ++l) {
         w.h[l][0] = c.take((size_t)B * H * 4); w.h[l][1] = c.take((size_t)B * H * 4); w.c[l] = c.take((size_t)B * H * 4);
     }

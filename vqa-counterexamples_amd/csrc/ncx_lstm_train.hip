@@ -192,7 +192,7 @@ static Lstm2TrainLayout lstm2_train_layout(int B, int T, int emb, int H) {
     Lstm2TrainLayout w{};
     WsCarver c;
     const size_t pairs = (size_t)B * T, Hp = pad_to(H, GEMM_BK);
-    w.plan = c.take_plan(B);
+    w.plan = take_plan(c, B);
     w.tok = c.take(pairs * 4);
     for (int l = 0; l < 2; ++l) {
         w.h[l] = c.take(pairs * H * 4); w.c[l] = c.take(pairs * H * 4);

@@ -12,7 +12,7 @@
 // DESIGN 4f); the classifier on the fused forward kernel over the B K neighbour rows, the B original rows only on request.
 // Widths the fused kernel does not take (dv not a multiple of 32, dh or A not a multiple of 4) run on the generic engine: x_v with
 // its activation goes to the workspace and k_mlb_mul finishes it.
-#include "ncx_internal.h"
+#include "ncx_train.h"
 
 using namespace ncx;
 
@@ -47,17 +47,16 @@ static int check_mlb(const ncx_dims* d, const ncx_mlb_params* m) {
 
 static MlbLayout mlb_layout(const ncx_dims& d, const ncx_mlb_params& m, GemmPlan* plans /*[3]*/) {
     MlbLayout w{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+    WsCarver cv;
     const long long Mv = (long long)d.B * (d.K + 1), Mk = (long long)d.B * d.K, lim = (1ll << 32) - 65536;
     // the fused forward kernel reads with 32-bit byte offsets and whole 32-column k-steps on the weight side (ncx_main.h)
     w.main_v = d.dv % 32 == 0 && d.dv >= 64 && (long long)d.n_img * d.dv * 4 < lim && (long long)d.dz * d.dv * 4 < lim && !hook_env("NCX_VQA_NO_MAIN");
     w.main_c = d.dz % 4 == 0 && d.A % 4 == 0 && Mk * d.dz * 4 < lim && (long long)d.A * pad_to(d.dz, 32) * 4 < lim && !hook_env("NCX_VQA_NO_MAIN");
-    w.xq = take((size_t)d.B * d.dz * 4);
-    w.t_knns = take(m.act_c ? (size_t)Mk * d.dz * 4 : 0);
-    w.t_orig = take(m.act_c ? (size_t)d.B * d.dz * 4 : 0);
-    w.xv = take(w.main_v ? 0 : (size_t)Mv * d.dz * 4);
-    w.wcp = take(w.main_c && d.dz % 32 ? (size_t)d.A * pad_to(d.dz, 32) * 4 : 0);
+    w.xq = cv.take((size_t)d.B * d.dz * 4);
+    w.t_knns = cv.take(m.act_c ? (size_t)Mk * d.dz * 4 : 0);
+    w.t_orig = cv.take(m.act_c ? (size_t)d.B * d.dz * 4 : 0);
+    w.xv = cv.take(w.main_v ? 0 : (size_t)Mv * d.dz * 4);
+    w.wcp = cv.take(w.main_c && d.dz % 32 ? (size_t)d.A * pad_to(d.dz, 32) * 4 : 0);
     // 0: xq = act_q(q Wq^T)   1: xv = act_v(gather(v) Wv^T) (generic route)   2: a_knns = t Wc^T (generic route)
     const long long shp[3][3] = {{d.B, d.dz, ksteps(d.dq)}, {Mv, d.dz, ksteps(d.dv)}, {Mk, d.A, ksteps(d.dz)}};
     long long slab = 0;
@@ -68,8 +67,8 @@ static MlbLayout mlb_layout(const ncx_dims& d, const ncx_mlb_params& m, GemmPlan
         if (e > slab) slab = e;
     }
     w.slab_bytes = (size_t)slab * 4;
-    w.slab = take(w.slab_bytes);
-    w.total = off;
+    w.slab = cv.take(w.slab_bytes);
+    w.total = cv.off;
     return w;
 }
 
@@ -88,16 +87,14 @@ int ncx_mlb_forward(const ncx_dims* dp, const float* feats, const int32_t* img_i
     const ncx_dims& d = *dp; const ncx_mlb_params& m = *mp;
     GemmPlan plans[3];
     const MlbLayout w = mlb_layout(d, m, plans);
-    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) return NCX_E_WORKSPACE;
+    if (!ws_ok(workspace, workspace_bytes, w.total)) return NCX_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream_;
     char* ws = (char*)workspace;
     float* xq = (float*)(ws + w.xq); float* slab = (float*)(ws + w.slab);
     float* t_knns = m.act_c ? (float*)(ws + w.t_knns) : nullptr; float* t_orig = m.act_c ? (float*)(ws + w.t_orig) : nullptr;
     const int Mv = d.B * (d.K + 1), Mk = d.B * d.K, dh = d.dz;
     {   // x_q = act_q(q . Wq^T + bq), once per question                                fusion.py:41-47
-        GemmArgs a{}; a.mode = MODE_CHAIN; a.nseg = 1; a.M = d.B;
-        a.a[0] = x_plain(q_emb, d.dq, d.B, d.dq); a.b[0] = x_plain(m.wq, d.dq, dh, d.dq); a.klen[0] = d.dq;
-        a.out[0] = xq; a.ldo[0] = dh; a.n_cols[0] = dh; a.epi.relu = m.act_q;
+        GemmArgs a = gemm_nt(d.B, dh, d.dq, q_emb, m.wq, xq, m.act_q);
         rc = run_gemm_planned(a, FORM_NT, plans[0], slab, w.slab_bytes, m.bq, s); if (rc) return rc;
     }
     if (w.main_v) {
@@ -136,15 +133,12 @@ int ncx_mlb_forward(const ncx_dims* dp, const float* feats, const int32_t* img_i
         a.out = a_knns; a.ldo = d.A; a.epi.bias = m.bc; a.split = 1;
         rc = main_forward(a, s); if (rc) return rc;
     } else {
-        GemmArgs a{}; a.mode = MODE_CHAIN; a.nseg = 1; a.M = Mk;
-        a.a[0] = x_plain(ck, dh, Mk, dh); a.b[0] = x_plain(m.wc, dh, d.A, dh); a.klen[0] = dh;
-        a.out[0] = a_knns; a.ldo[0] = d.A; a.n_cols[0] = d.A;
+        GemmArgs a = gemm_nt(Mk, d.A, dh, ck, m.wc, a_knns, 0);
         rc = run_gemm_planned(a, FORM_NT, plans[2], slab, w.slab_bytes, m.bc, s); if (rc) return rc;
     }
     if (a_orig) {   // the B original rows, only on request (NeuralModel never reads a_orig)
-        GemmArgs a{}; a.mode = MODE_CHAIN; a.nseg = 1; a.M = d.B;
-        a.a[0] = x_plain(co, dh, d.B, dh); a.b[0] = x_plain(m.wc, dh, d.A, dh); a.klen[0] = dh;
-        a.out[0] = a_orig; a.ldo[0] = d.A; a.n_cols[0] = d.A; a.split[0] = 1;
+        GemmArgs a = gemm_nt(d.B, d.A, dh, co, m.wc, a_orig, 0);
+        a.split[0] = 1;
         GemmPlan pl; pl.cfg = CFG_64x64; pl.split = 1;
         rc = run_gemm_planned(a, FORM_NT, pl, slab, w.slab_bytes, m.bc, s); if (rc) return rc;
     }

@@ -1,7 +1,7 @@
 // ncx_mlb_att.h -- the kernels and host helpers that the eval-mode forward (ncx_mlb_att.hip) and the training step
 // (ncx_mlb_att_train.hip) of the MLB attention model share.  Included by those two translation units only.
 #pragma once
-#include "ncx_internal.h"
+#include "ncx_train.h"
 #include "ncx_wave.h"
 #include "ncx_x6.h"
 
@@ -20,17 +20,9 @@ struct AttArgs {
     int P, dv, dh, G, n_img, HT, PT, act_v, act_mm;
 };
 
-// The six dropouts of the training step (ncx_mlb_att_train.hip): layer ids 1 .. 6 of the counter-based generator, p[layer - 1].
-struct AttDrop { int mode; float p[6]; unsigned lo, hi; };
-__device__ __forceinline__ bool att_keep(const AttDrop& k, int layer, const float* mask, long long i) {
-    if (k.mode == 1) return k.p[layer - 1] > 0.f ? dropout_keep(k.lo, k.hi, (unsigned)layer, (unsigned long long)i, k.p[layer - 1]) : true;
-    if (k.mode == 2) return mask[i] != 0.f;
-    return true;
-}
-__device__ __forceinline__ float att_scale(const AttDrop& k, int layer) { return k.mode ? 1.f / (1.f - k.p[layer - 1]) : 1.f; }
 // What the training form of the logits kernels adds: the stash of Xv = act_v_att(conv_v_att(.)) [B, P, dh_att], layer 3's dropout on
 // x_att before the contraction, and the map read from the dropped copy Vd [B, dv, P] with the identity index (identity != 0).
-struct AttTrain { float* xv_stash; const float* mask3; AttDrop drop; int identity; };
+struct AttTrain { float* xv_stash; const float* mask3; TrainDrop drop; int identity; };
 
 // TM: positions per tile, 208 or 64
 template <int TM> struct AttCfg {
@@ -47,7 +39,6 @@ template <int TM> struct AttCfg {
 };
 
 __device__ __forceinline__ float att_act(float v, int act) { return act == 2 ? tanhf(v) : v; }
-__device__ __forceinline__ int clamp_img(int i, int n) { return i < 0 ? 0 : i >= n ? n - 1 : i; }
 
 // The epilogue the logits kernels share: the x_att tile -> LDS, then the contraction with conv_att.weight over the tile's hidden
 // columns in groups of 64; group c of the tile goes to slab slot ht0 + c.  BN: hidden columns per workgroup; T: threads; GUARD: the
@@ -80,14 +71,14 @@ __device__ __forceinline__ void att_epilogue(float* const smem, const f32x4 (&ac
         __syncthreads();
         const int hl = tid % BN, h = h0 + hl;
         if (h < a.dh) {
-            const float xq = a.xq[(long long)b * a.dh + h], sc = att_scale(tr.drop, 3);
+            const float xq = a.xq[(long long)b * a.dh + h], sc = train_scale(tr.drop, 3);
             float* const st = tr.xv_stash + (long long)b * a.P * a.dh;
             for (int pl = tid / BN; pl < TM && p0 + pl < a.P; pl += T / BN) {
                 const int e = (p0 + pl) * a.dh + h;
                 const float xv = xs[pl * XP + hl];
                 st[e] = xv;
                 const float v = att_act(xv * xq, a.act_mm);
-                xs[pl * XP + hl] = att_keep(tr.drop, 3, tr.mask3, (long long)b * a.P * a.dh + e) ? v * sc : 0.f;      // index over [B, P, dh_att]
+                xs[pl * XP + hl] = train_keep(tr.drop, 3, tr.mask3, (long long)b * a.P * a.dh + e) ? v * sc : 0.f;      // index over [B, P, dh_att]
             }
         }
     }
@@ -382,7 +373,7 @@ __global__ __launch_bounds__(256) void k_att_logits_small(const AttArgs a, const
         const long long e = ((long long)b * a.P + p) * a.dh + h;
         if constexpr (TRAIN) tr.xv_stash[e] = x;
         x = att_act(x * a.xq[(long long)b * a.dh + h], a.act_mm);
-        if constexpr (TRAIN) x = att_keep(tr.drop, 3, tr.mask3, e) ? x * att_scale(tr.drop, 3) : 0.f;
+        if constexpr (TRAIN) x = train_keep(tr.drop, 3, tr.mask3, e) ? x * train_scale(tr.drop, 3) : 0.f;
 #pragma unroll
         for (int g = 0; g < ATT_MAX_G; ++g)
             if (g < a.G) t[g] = __builtin_fmaf(a.wa[(long long)g * a.dh + h], x, t[g]);
@@ -513,12 +504,6 @@ GemmArgs glimpse_gemm(const ncx_mlb_att_dims& d, const float* v_att, const float
         a.klen[g] = d.dv;
         a.out[g] = xv ? xv + (long long)g * d.dh_f : nullptr; a.ldo[g] = (long long)d.G * d.dh_f; a.n_cols[g] = d.dh_f;
     }
-    return a;
-}
-GemmArgs linear_gemm(int M, int N, int K, const float* x, const float* w, float* out, int act) {
-    GemmArgs a{}; a.mode = MODE_CHAIN; a.nseg = 1; a.M = M;
-    a.a[0] = x_plain(x, K, M, K); a.b[0] = x_plain(w, K, N, K); a.klen[0] = K;
-    a.out[0] = out; a.ldo[0] = N; a.n_cols[0] = N; a.epi.relu = act;
     return a;
 }
 

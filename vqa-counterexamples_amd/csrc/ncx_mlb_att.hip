@@ -31,8 +31,7 @@ struct AttLayout {
 
 AttLayout att_layout(const ncx_mlb_att_dims& d) {
     AttLayout w{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+    WsCarver cv;
     const int GF = d.G * d.dh_f;
     if (d.P >= 4) {
         w.TM = cdiv(d.P, 208) * 208 < cdiv(d.P, 64) * 64 ? 208 : 64;
@@ -40,23 +39,23 @@ AttLayout att_layout(const ncx_mlb_att_dims& d) {
     } else {
         w.TM = 0; w.HT = 1; w.PT = 1;
     }
-    w.xq = take((size_t)d.B * d.dh_att * 4);
-    w.aslab = take((size_t)d.B * w.HT * d.G * d.P * 4);
-    w.v_att = take((size_t)d.B * d.G * d.dv * 4);
-    w.xv = take((size_t)d.B * GF * 4);
-    w.xqf = take((size_t)d.B * GF * 4);
+    w.xq = cv.take((size_t)d.B * d.dh_att * 4);
+    w.aslab = cv.take((size_t)d.B * w.HT * d.G * d.P * 4);
+    w.v_att = cv.take((size_t)d.B * d.G * d.dv * 4);
+    w.xv = cv.take((size_t)d.B * GF * 4);
+    w.xqf = cv.take((size_t)d.B * GF * 4);
     w.plan[0] = plan_gemm(FORM_NT, d.B, d.dh_att, ksteps(d.dq), true);
     w.plan[1] = plan_gemm(FORM_NT, d.B, d.dh_f, ksteps(d.dv), true);
     w.plan[2] = plan_gemm(FORM_NT, d.B, GF, ksteps(d.dq), true);
     w.plan[3] = plan_gemm(FORM_NT, d.B, d.A, ksteps(GF), true);
-    const GemmArgs probe[4] = {linear_gemm(d.B, d.dh_att, d.dq, nullptr, nullptr, nullptr, 0), glimpse_gemm(d, nullptr, nullptr, nullptr),
-                               linear_gemm(d.B, GF, d.dq, nullptr, nullptr, nullptr, 0), linear_gemm(d.B, d.A, GF, nullptr, nullptr, nullptr, 0)};
+    const GemmArgs probe[4] = {gemm_nt(d.B, d.dh_att, d.dq, nullptr, nullptr, nullptr, 0), glimpse_gemm(d, nullptr, nullptr, nullptr),
+                               gemm_nt(d.B, GF, d.dq, nullptr, nullptr, nullptr, 0), gemm_nt(d.B, d.A, GF, nullptr, nullptr, nullptr, 0)};
     for (int i = 0; i < 4; ++i) {
         const size_t e = gemm_slab_bytes(probe[i], w.plan[i]);
         if (e > w.slab_bytes) w.slab_bytes = e;
     }
-    w.slab = take(w.slab_bytes);
-    w.total = off;
+    w.slab = cv.take(w.slab_bytes);
+    w.total = cv.off;
     return w;
 }
 }  // namespace
@@ -89,14 +88,14 @@ int ncx_mlb_att_forward_flags(const ncx_mlb_att_dims* dp, const float* feats, co
     if (!feats || !img_idx || !q_emb || !workspace || !logits || !att) return NCX_E_NULL;
     const ncx_mlb_att_dims& d = *dp; const ncx_mlb_att_params& m = *mp;
     const AttLayout w = att_layout(d);
-    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) return NCX_E_WORKSPACE;
+    if (!ws_ok(workspace, workspace_bytes, w.total)) return NCX_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream_;
     char* ws = (char*)workspace;
     float* xq = (float*)(ws + w.xq); float* aslab = (float*)(ws + w.aslab); float* v_att = (float*)(ws + w.v_att);
     float* xv = (float*)(ws + w.xv); float* xqf = (float*)(ws + w.xqf); float* slab = (float*)(ws + w.slab);
     const int GF = d.G * d.dh_f;
     {   // a. x_q = act(q . Wq_att^T + b)                                               att.py:58-63
-        GemmArgs a = linear_gemm(d.B, d.dh_att, d.dq, q_emb, m.wq_att, xq, m.act_q_att);
+        GemmArgs a = gemm_nt(d.B, d.dh_att, d.dq, q_emb, m.wq_att, xq, m.act_q_att);
         rc = run_gemm_planned(a, FORM_NT, w.plan[0], slab, w.slab_bytes, m.bq_att, s); if (rc) return rc;
     }
     {   // b. partial position logits of every dh_att tile                              att.py:46-57,71-90
@@ -123,14 +122,14 @@ int ncx_mlb_att_forward_flags(const ncx_mlb_att_dims* dp, const float* feats, co
     {   // d. the glimpse Linears (pre-activation, column slices of x_v), x_qf, the second fusion      att.py:120-143,145-148
         GemmArgs a = glimpse_gemm(d, v_att, m.wg, xv);
         rc = run_gemm_planned(a, FORM_NT, w.plan[1], slab, w.slab_bytes, nullptr, s); if (rc) return rc;
-        GemmArgs q = linear_gemm(d.B, GF, d.dq, q_emb, m.wqf, xqf, m.act_q);
+        GemmArgs q = gemm_nt(d.B, GF, d.dq, q_emb, m.wqf, xqf, m.act_q);
         rc = run_gemm_planned(q, FORM_NT, w.plan[2], slab, w.slab_bytes, m.bqf, s); if (rc) return rc;
         const long long total = (long long)d.B * GF;
         hipLaunchKernelGGL(k_att_fuse, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, xv, m.bg, xqf, GF, total, m.act_v, m.act_c);
         NCX_HIP_TRY(hipGetLastError());
     }
     {   // e. logits = t . Wc^T + bc                                                     att.py:149-153
-        GemmArgs a = linear_gemm(d.B, d.A, GF, xv, m.wc, logits, 0);
+        GemmArgs a = gemm_nt(d.B, d.A, GF, xv, m.wc, logits, 0);
         rc = run_gemm_planned(a, FORM_NT, w.plan[3], slab, w.slab_bytes, m.bc, s); if (rc) return rc;
     }
     return NCX_OK;

@@ -1,6 +1,8 @@
 // ncx_mlb_att_train.hip -- the trainable MLB attention model (MLBAtt in training mode) below the question encoder:
 // ncx_mlb_att_train_workspace_bytes, _forward[_flags], _backward[_flags], _ws_region, ncx_mlb_att_dwv_form.  Reference: vqa/models/att.py:39-163 with F.dropout active;
-// the kernels of the eval-mode forward are shared through ncx_mlb_att.h.  DESIGN 5r.
+// the kernels of the eval-mode forward are shared through ncx_mlb_att.h; the dropout front end (TrainDrop), the GEMM request builders, the
+// runner and the element-wise kernels drop_flat, dfuse and dact (k_train_* of ncx_train.hip) are the ones all three VQA trainers use
+// (ncx_train.h).  DESIGN 5r, 5y.
 //
 // Dropout layers (generator layer id, element index = linear index in the tensor): 1 the map fed to conv_v_att [B, dv, P] (the pooled
 // map is not dropped), 2 q fed to linear_q_att [B, dq], 3 x_att [B, P, dh_att], 4 v_att [B, G, dv], 5 q fed to linear_q_fusion
@@ -8,19 +10,19 @@
 //
 // Forward:
 //   k_at_dropmap        Vd = drop1(feats[img_idx]) [B, dv, P]  (only when layer 1 is on; else the table is read in place)
-//   k_at_droprows x 2   q2 = drop2(q), q5 = drop5(q)           (only when on)
+//   drop_flat x 2       q2 = drop2(q), q5 = drop5(q)           (only when on)
 //   NT                  x_q = act(q2 Wq_att^T + b)
 //   k_att_logits<TRAIN> the eval kernel + the Xv stash [B, P, dh_att] written from the LDS tile + drop3 before the contraction
 //   k_att_pool          softmax, pooling of the UNDROPPED map -> att, v_att
-//   k_at_droprows       v4 = drop4(v_att)                       (only when on)
+//   drop_flat           v4 = drop4(v_att)                       (only when on)
 //   NT group, NT        the glimpse Linears (pre-activation), x_qf
 //   k_att_fuse_train    x_v = act_v(. + bg) in place; t = act_c(x_v x_qf); tc = drop6(t)
 //   NT                  logits = tc Wc^T + bc
 // Backward from dlogits:
 //   TN, NN + drop6      dWc = dlogits^T tc;  dt = (dlogits Wc) m6
-//   k_at_dfuse          dz = dt (1 - t^2); dpv = dz x_qf (1 - x_v^2); dpqf = dz x_v (1 - x_qf^2)
+//   dfuse               dz = dt (1 - t^2); dpv = dz x_qf (1 - x_v^2); dpqf = dz x_v (1 - x_qf^2)
 //   TN group, TN        dWg[g] = dpv[:, g]^T v4[:, g];  dWqf = dpqf^T q5
-//   NN x G              dv_att[:, g] = dpv[:, g] Wg[g];  k_at_droprows applies m4 (its index runs over [B, G, dv])
+//   NN x G              dv_att[:, g] = dpv[:, g] Wg[g];  drop_flat applies m4 (its index runs over [B, G, dv])
 //   k_at_datt           partial[b][chunk][g][p] = sum over the chunk's channels of dv_att[b, g, c] V[b, c, p]   (undropped map)
 //   k_at_ds             datt = sum of the chunks in order; ds = att (datt - sum_p att datt); per-question partial of dba
 //   k_at_head           a workgroup owns (b, 64 hidden units) and walks p over the stash: recomputes a = act_mm(Xv x_q) and m3, da =
@@ -31,7 +33,7 @@
 //                       (NCX_F_X6 on the backward: k_att_dwv_x6, the same product and slab on the bf16 matrix path with three-plane
 //                       operands; a non-finite map or dXv value is outside that contract)
 //   k_at_sumrows        fixed-order sums over b / S: dWv_att, dWa, dbv_att, dba, and the bias gradients of the tail
-//   k_at_dact, TN       dpq = dxq (1 - x_q^2);  dWq_att = dpq^T q2
+//   dact, TN            dpq = dxq (1 - x_q^2);  dWq_att = dpq^T q2
 //   NN + drop2, NN + drop5, k_at_add      dq_emb, on request
 // No atomics; every reduction in a fixed order; tanh only in epilogues and element-wise kernels.
 #include "ncx_mlb_att.h"
@@ -45,23 +47,17 @@ constexpr int DWV_MAX_S = 8;
 // ---- element-wise kernels ----------------------------------------------------------------------------------------------------
 // Vd[b, c, p] = drop1(feats[clamp(img_idx[b]), c, p]); per = dv P elements per image
 __global__ __launch_bounds__(256) void k_at_dropmap(const float* __restrict__ feats, const int* __restrict__ img_idx, int n_img, long long per,
-                                                    long long total, AttDrop k, const float* __restrict__ mask, float* __restrict__ vd) {
+                                                    long long total, TrainDrop k, const float* __restrict__ mask, float* __restrict__ vd) {
     const long long i = blockIdx.x * 256ll + threadIdx.x;
     if (i >= total) return;
     const long long b = i / per, r = i - b * per;
     const int img = clamp_img(img_idx[b], n_img);
     const float v = feats[(long long)img * per + r];
-    vd[i] = att_keep(k, 1, mask, i) ? v * att_scale(k, 1) : 0.f;
-}
-// out[i] = drop_layer(in[i]), i < n (in == out allowed)
-__global__ __launch_bounds__(256) void k_at_droprows(const float* in, float* out, long long n, AttDrop k, int layer, const float* __restrict__ mask) {
-    const long long i = blockIdx.x * 256ll + threadIdx.x;
-    if (i >= n) return;
-    out[i] = att_keep(k, layer, mask, i) ? in[i] * att_scale(k, layer) : 0.f;
+    vd[i] = train_keep(k, 1, mask, i) ? v * train_scale(k, 1) : 0.f;
 }
 // x_v = act_v(xv + bg) (in place), t = act_c(x_v x_qf), tc = drop6(t); n = G dh_f columns
 __global__ __launch_bounds__(256) void k_att_fuse_train(float* __restrict__ xv, const float* __restrict__ bg, const float* __restrict__ xqf, int n,
-                                                        long long total, int act_v, int act_c, AttDrop k, const float* __restrict__ mask6,
+                                                        long long total, int act_v, int act_c, TrainDrop k, const float* __restrict__ mask6,
                                                         float* __restrict__ t, float* __restrict__ tc) {
     const long long i = blockIdx.x * 256ll + threadIdx.x;
     if (i >= total) return;
@@ -69,23 +65,7 @@ __global__ __launch_bounds__(256) void k_att_fuse_train(float* __restrict__ xv, 
     const float x = att_act(xv[i] + bg[c], act_v);
     const float tt = att_act(x * xqf[i], act_c);
     xv[i] = x; t[i] = tt;
-    tc[i] = att_keep(k, 6, mask6, i) ? tt * att_scale(k, 6) : 0.f;
-}
-__global__ __launch_bounds__(256) void k_at_dfuse(const float* __restrict__ dt, const float* __restrict__ t, const float* __restrict__ xv,
-                                                  const float* __restrict__ xqf, long long total, int act_v, int act_q, int act_c,
-                                                  float* __restrict__ dpv, float* __restrict__ dpqf) {
-    const long long i = blockIdx.x * 256ll + threadIdx.x;
-    if (i >= total) return;
-    const float a = xv[i], q = xqf[i], tt = t[i];
-    const float dz = act_c == 2 ? dt[i] * (1.f - tt * tt) : dt[i];
-    const float gv = dz * q, gq = dz * a;
-    dpv[i] = act_v == 2 ? gv * (1.f - a * a) : gv;
-    dpqf[i] = act_q == 2 ? gq * (1.f - q * q) : gq;
-}
-// d[i] *= 1 - y[i]^2
-__global__ __launch_bounds__(256) void k_at_dact(float* __restrict__ d, const float* __restrict__ y, long long n) {
-    const long long i = blockIdx.x * 256ll + threadIdx.x;
-    if (i < n) d[i] *= 1.f - y[i] * y[i];
+    tc[i] = train_keep(k, 6, mask6, i) ? tt * train_scale(k, 6) : 0.f;
 }
 __global__ __launch_bounds__(256) void k_at_add(float* __restrict__ d, const float* __restrict__ x, long long n) {
     const long long i = blockIdx.x * 256ll + threadIdx.x;
@@ -169,7 +149,7 @@ __global__ __launch_bounds__(256) void k_at_ds(const float* __restrict__ partial
 struct HeadArgs {
     float* stash; const float* xq; const float* ds; const float* wa; const float* mask3;
     float* dxq; float* dwa_p; float* dbv_p;
-    AttDrop drop;
+    TrainDrop drop;
     int P, dh, G, act_v, act_mm;
 };
 // grid (h tiles of 64, B); thread (pq = t >> 6, hl = t & 63) walks p = pq, pq + 4, ...; the four partial sums are added in pq order
@@ -193,12 +173,12 @@ __global__ __launch_bounds__(256) void k_at_head(const HeadArgs a) {
     if (hv) {
         const long long base = (long long)b * P * a.dh;
         float* const st = a.stash + base;
-        const float xq = a.xq[(long long)b * a.dh + h], sc = att_scale(a.drop, 3);
+        const float xq = a.xq[(long long)b * a.dh + h], sc = train_scale(a.drop, 3);
         for (int p = pq; p < P; p += 4) {
             const int e = p * a.dh + h;
             const float x = st[e];
             const float av = att_act(x * xq, a.act_mm);
-            const float m = att_keep(a.drop, 3, a.mask3, base + e) ? sc : 0.f;       // index over [B, P, dh_att]
+            const float m = train_keep(a.drop, 3, a.mask3, base + e) ? sc : 0.f;       // index over [B, P, dh_att]
             const float ad = av * m;
             float s = 0.f;
 #pragma unroll
@@ -528,20 +508,14 @@ struct AtPtrs {
     float *xq, *xv, *xqf, *logits, *dt, *dvatt, *dq, *dq2;
     ncx_mlb_att_grads g;
 };
-inline const float* at_off(const float* p, long long n) { return p ? p + n : nullptr; }
-inline float* at_off(float* p, long long n) { return p ? p + n : nullptr; }
-inline unsigned at_grid(long long n) { return (unsigned)((n + 255) / 256); }
-
-bool at_on(const ncx_mlb_att_train& t, int layer) {
+// the step's six p, in layer order
+inline float at_p(const ncx_mlb_att_train& t, int layer) {
     const float p[6] = {t.p_att_v, t.p_att_q, t.p_att_mm, t.p_v, t.p_q, t.p_c};
-    return t.dropout_mode == 2 || (t.dropout_mode == 1 && p[layer - 1] > 0.f);
+    return p[layer - 1];
 }
-AttDrop at_drop(const ncx_mlb_att_train& t) {
-    AttDrop k{};
-    k.mode = t.dropout_mode;
-    if (k.mode) { k.p[0] = t.p_att_v; k.p[1] = t.p_att_q; k.p[2] = t.p_att_mm; k.p[3] = t.p_v; k.p[4] = t.p_q; k.p[5] = t.p_c; }
-    k.lo = (unsigned)(t.seed & 0xFFFFFFFFull); k.hi = (unsigned)(t.seed >> 32);
-    return k;
+inline bool at_on(const ncx_mlb_att_train& t, int layer) { return drop_on(t.dropout_mode, at_p(t, layer)); }
+inline TrainDrop at_drop(const ncx_mlb_att_train& t) {
+    return train_drop(t.dropout_mode, t.seed, {t.p_att_v, t.p_att_q, t.p_att_mm, t.p_v, t.p_q, t.p_c});
 }
 
 // the limits the training step adds to check_att_dims (d has passed it)
@@ -566,73 +540,50 @@ int at_check(const ncx_mlb_att_dims* d, const ncx_mlb_att_train* t, const ncx_ml
         const int rc = check_att(d, &probe); if (rc != NCX_OK) return rc;
     }
     if (t->dropout_mode < 0 || t->dropout_mode > 2) return NCX_E_DIMS;
-    const float ps[6] = {t->p_att_v, t->p_att_q, t->p_att_mm, t->p_v, t->p_q, t->p_c};
-    for (int i = 0; i < 6; ++i) if (!(ps[i] >= 0.f && ps[i] < 1.f)) return NCX_E_DIMS;
+    if (!probs_ok({t->p_att_v, t->p_att_q, t->p_att_mm, t->p_v, t->p_q, t->p_c})) return NCX_E_DIMS;
     return at_check_dims(d);
 }
 
 // The products of the step on the generic engine (pointers may be NULL when only sizing the slab).  AT_DVATT: problem `gi` of G.
-GemmArgs at_gemm(const ncx_mlb_att_dims& d, const ncx_mlb_att_train& t, const ncx_mlb_att_params& m, const AtLayout& w, const AtPtrs& p, int which,
-                 int gi, int* form, GemmPlan* pl, const float** bias) {
+GemmReq at_gemm(const ncx_mlb_att_dims& d, const ncx_mlb_att_train& t, const ncx_mlb_att_params& m, const AtLayout& w, const AtPtrs& p, int which,
+                int gi) {
     const int B = d.B, GF = d.G * d.dh_f;
-    GemmArgs a{};
-    *bias = nullptr;
-    auto nt = [&](const float* X, int K, const float* W, int N, float* out, int act, const float* bs) {
-        a = linear_gemm(B, N, K, X, W, out, act);
-        *form = FORM_NT; *pl = plan_gemm(FORM_NT, B, N, ksteps(K), true); *bias = bs;
-    };
-    auto tn = [&](int i, const float* D, long long ldd, int Mo, const float* X, long long ldx, int N, float* out) {   // out [Mo, N] = D^T . X over B rows
-        a.mode = MODE_GROUP; a.nseg = i + 1; a.M = Mo;
-        a.a[i] = x_plain(D, ldd, B, Mo); a.b[i] = x_plain(X, ldx, B, N); a.klen[i] = B;
-        a.out[i] = out; a.ldo[i] = N; a.n_cols[i] = N;
-        *form = FORM_TN;
-    };
-    auto nn = [&](const float* D, long long ldd, int K, const float* W, int N, float* out, long long ldo) {           // out [B, N] = D [B, K] . W [K, N], unsplit
-        a.mode = MODE_CHAIN; a.nseg = 1; a.M = B;
-        a.a[0] = x_plain(D, ldd, B, K); a.b[0] = x_plain(W, N, K, N); a.klen[0] = K;
-        a.out[0] = out; a.ldo[0] = ldo; a.n_cols[0] = N;
-        *form = FORM_NN; *pl = plan_gemm(FORM_NN, B, N, ksteps(K), false);
-        a.split[0] = 1; pl->split = 1;
-    };
-    auto drop = [&](int layer, float pr, long long ld) {
-        if (!at_on(t, layer)) return;
-        EpiArgs& e = a.epi;
-        e.dropout = t.dropout_mode; e.drop_p = pr; e.drop_scale = 1.f / (1.f - pr);
-        e.seed_lo = (unsigned)(t.seed & 0xFFFFFFFFull); e.seed_hi = (unsigned)(t.seed >> 32); e.layer = (unsigned)layer;
-        e.keep_mask = at_off(p.masks, w.m_off[layer - 1]); e.ld_mask = ld;
+    GemmReq r{};
+    GemmArgs& a = r.a;
+    auto drop = [&](int layer, long long ld) {
+        epi_dropout(a.epi, t.dropout_mode, t.seed, at_p(t, layer), (unsigned)layer, ptr_off(p.masks, w.m_off[layer - 1]), ld);
     };
     switch (which) {
-    case AT_XQ: nt(p.q2, d.dq, m.wq_att, d.dh_att, p.xq, m.act_q_att, m.bq_att); break;
+    case AT_XQ: req_nt(r, B, d.dh_att, d.dq, p.q2, m.wq_att, p.xq, m.act_q_att, m.bq_att); break;
     case AT_GLIMPSE:
         a = glimpse_gemm(d, p.v4, m.wg, p.xv);
-        *form = FORM_NT; *pl = plan_gemm(FORM_NT, B, d.dh_f, ksteps(d.dv), true);
+        r.form = FORM_NT; r.pl = plan_gemm(FORM_NT, B, d.dh_f, ksteps(d.dv), true);
         break;
-    case AT_XQF: nt(p.q5, d.dq, m.wqf, GF, p.xqf, m.act_q, m.bqf); break;
-    case AT_LOGITS: nt(p.tc, GF, m.wc, d.A, p.logits, 0, m.bc); break;
-    case AT_DWC: tn(0, p.dlogits, d.A, d.A, p.tc, GF, GF, p.g.wc); *pl = plan_gemm(FORM_TN, d.A, GF, ksteps(B), false); break;
-    case AT_DT: nn(p.dlogits, d.A, d.A, m.wc, GF, p.dt, GF); drop(6, t.p_c, GF); break;
+    case AT_XQF: req_nt(r, B, GF, d.dq, p.q5, m.wqf, p.xqf, m.act_q, m.bqf); break;
+    case AT_LOGITS: req_nt(r, B, d.A, GF, p.tc, m.wc, p.logits, 0, m.bc); break;
+    case AT_DWC: gemm_tn_piece(a, 0, p.dlogits, d.A, d.A, p.tc, GF, GF, p.g.wc, B); req_tn(r, d.A, GF, B); break;
+    case AT_DT: req_nn_unsplit(r, B, p.dlogits, d.A, d.A, m.wc, GF, p.dt, GF); drop(6, GF); break;
     case AT_DWG:
         for (int g = 0; g < d.G; ++g)
-            tn(g, at_off(p.dpv, (long long)g * d.dh_f), GF, d.dh_f, at_off(p.v4, (long long)g * d.dv), (long long)d.G * d.dv, d.dv,
-               at_off(p.g.wg, (long long)g * d.dh_f * d.dv));
-        *pl = plan_gemm(FORM_TN, d.dh_f, (long long)d.G * d.dv, ksteps(B), false);
+            gemm_tn_piece(a, g, ptr_off(p.dpv, (long long)g * d.dh_f), GF, d.dh_f, ptr_off(p.v4, (long long)g * d.dv), (long long)d.G * d.dv, d.dv,
+                          ptr_off(p.g.wg, (long long)g * d.dh_f * d.dv), B);
+        req_tn(r, d.dh_f, (long long)d.G * d.dv, B);
         break;
-    case AT_DWQF: tn(0, p.dpqf, GF, GF, p.q5, d.dq, d.dq, p.g.wqf); *pl = plan_gemm(FORM_TN, GF, d.dq, ksteps(B), false); break;
+    case AT_DWQF: gemm_tn_piece(a, 0, p.dpqf, GF, GF, p.q5, d.dq, d.dq, p.g.wqf, B); req_tn(r, GF, d.dq, B); break;
     case AT_DVATT:
-        nn(at_off(p.dpv, (long long)gi * d.dh_f), GF, d.dh_f, at_off(m.wg, (long long)gi * d.dh_f * d.dv), d.dv,
-           at_off(p.dvatt, (long long)gi * d.dv), (long long)d.G * d.dv);
+        req_nn_unsplit(r, B, ptr_off(p.dpv, (long long)gi * d.dh_f), GF, d.dh_f, ptr_off(m.wg, (long long)gi * d.dh_f * d.dv), d.dv,
+                       ptr_off(p.dvatt, (long long)gi * d.dv), (long long)d.G * d.dv);
         break;
-    case AT_DWQ: tn(0, p.dxq, d.dh_att, d.dh_att, p.q2, d.dq, d.dq, p.g.wq_att); *pl = plan_gemm(FORM_TN, d.dh_att, d.dq, ksteps(B), false); break;
-    case AT_DQ1: nn(p.dxq, d.dh_att, d.dh_att, m.wq_att, d.dq, p.dq, d.dq); drop(2, t.p_att_q, d.dq); break;
-    default: nn(p.dpqf, GF, GF, m.wqf, d.dq, p.dq2, d.dq); drop(5, t.p_q, d.dq); break;
+    case AT_DWQ: gemm_tn_piece(a, 0, p.dxq, d.dh_att, d.dh_att, p.q2, d.dq, d.dq, p.g.wq_att, B); req_tn(r, d.dh_att, d.dq, B); break;
+    case AT_DQ1: req_nn_unsplit(r, B, p.dxq, d.dh_att, d.dh_att, m.wq_att, d.dq, p.dq, d.dq); drop(2, d.dq); break;
+    default: req_nn_unsplit(r, B, p.dpqf, GF, GF, m.wqf, d.dq, p.dq2, d.dq); drop(5, d.dq); break;
     }
-    return a;
+    return r;
 }
 
 AtLayout at_layout(const ncx_mlb_att_dims& d, const ncx_mlb_att_train& t, const ncx_mlb_att_params& m) {
     AtLayout w{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+    WsCarver cv;
     const size_t B = d.B, P = d.P, GF = (size_t)d.G * d.dh_f, G = d.G;
     if (d.P >= 4) {
         w.TM = cdiv(d.P, 208) * 208 < cdiv(d.P, 64) * 64 ? 208 : 64;
@@ -653,43 +604,36 @@ AtLayout at_layout(const ncx_mlb_att_dims& d, const ncx_mlb_att_train& t, const 
                               (long long)(B * d.dq), (long long)(B * GF)};
     for (int i = 0; i < 6; ++i) { w.m_off[i] = mo; mo += msz[i]; }
     w.vd_bytes = at_on(t, 1) ? B * d.dv * P * 4 : 0;
-    w.vd = take(w.vd_bytes);
-    w.q2 = take(at_on(t, 2) ? B * d.dq * 4 : 0);
-    w.q5 = take(at_on(t, 5) ? B * d.dq * 4 : 0);
-    w.xq = take(B * d.dh_att * 4);
-    w.stash = take(B * P * d.dh_att * 4);
-    w.aslab = take(B * w.HT * G * P * 4);
-    w.v_att = take(B * G * d.dv * 4);
-    w.v4 = take(at_on(t, 4) ? B * G * d.dv * 4 : 0);
-    w.xv = take(B * GF * 4); w.xqf = take(B * GF * 4); w.t = take(B * GF * 4); w.tc = take(B * GF * 4);
-    w.dt = take(B * GF * 4); w.dpv = take(B * GF * 4); w.dpqf = take(B * GF * 4);
-    w.dvatt = take(B * G * d.dv * 4);
-    w.dattp = take(B * w.chunks * G * P * 4);
-    w.ds = take(B * G * P * 4);
-    w.dba_p = take(B * G * 4);
-    w.dxq = take(B * d.dh_att * 4);
-    w.dwa_p = take(B * G * d.dh_att * 4);
-    w.dbv_p = take(B * d.dh_att * 4);
+    w.vd = cv.take(w.vd_bytes);
+    w.q2 = cv.take(at_on(t, 2) ? B * d.dq * 4 : 0);
+    w.q5 = cv.take(at_on(t, 5) ? B * d.dq * 4 : 0);
+    w.xq = cv.take(B * d.dh_att * 4);
+    w.stash = cv.take(B * P * d.dh_att * 4);
+    w.aslab = cv.take(B * w.HT * G * P * 4);
+    w.v_att = cv.take(B * G * d.dv * 4);
+    w.v4 = cv.take(at_on(t, 4) ? B * G * d.dv * 4 : 0);
+    w.xv = cv.take(B * GF * 4); w.xqf = cv.take(B * GF * 4); w.t = cv.take(B * GF * 4); w.tc = cv.take(B * GF * 4);
+    w.dt = cv.take(B * GF * 4); w.dpv = cv.take(B * GF * 4); w.dpqf = cv.take(B * GF * 4);
+    w.dvatt = cv.take(B * G * d.dv * 4);
+    w.dattp = cv.take(B * w.chunks * G * P * 4);
+    w.ds = cv.take(B * G * P * 4);
+    w.dba_p = cv.take(B * G * 4);
+    w.dxq = cv.take(B * d.dh_att * 4);
+    w.dwa_p = cv.take(B * G * d.dh_att * 4);
+    w.dbv_p = cv.take(B * d.dh_att * 4);
     w.dwv_bytes = d.P >= 4 ? (size_t)w.S * d.dh_att * d.dv * 4 : 0;
-    w.dwv = take(w.dwv_bytes);
-    w.dq2 = take(B * d.dq * 4);
-    AtPtrs p{};
-    for (int i = 0; i < AT_COUNT; ++i) {
-        int form; GemmPlan pl; const float* bias;
-        GemmArgs a = at_gemm(d, t, m, w, p, i, 0, &form, &pl, &bias);
-        const size_t e = gemm_slab_bytes(a, pl);
-        if (e > w.slab_bytes) w.slab_bytes = e;
-    }
-    w.slab = take(w.slab_bytes);
-    w.total = off;
+    w.dwv = cv.take(w.dwv_bytes);
+    w.dq2 = cv.take(B * d.dq * 4);
+    const AtPtrs p{};
+    w.slab_bytes = max_slab_bytes<AT_COUNT>([&](int which) { return at_gemm(d, t, m, w, p, which, 0); });
+    w.slab = cv.take(w.slab_bytes);
+    w.total = cv.off;
     return w;
 }
 
 int at_run(const ncx_mlb_att_dims& d, const ncx_mlb_att_train& t, const ncx_mlb_att_params& m, const AtLayout& w, const AtPtrs& p, int which, int gi,
            char* ws, hipStream_t s) {
-    int form; GemmPlan pl; const float* bias;
-    GemmArgs a = at_gemm(d, t, m, w, p, which, gi, &form, &pl, &bias);
-    return run_gemm_planned(a, form, pl, (float*)(ws + w.slab), w.slab_bytes, bias, s);
+    return run_request(at_gemm(d, t, m, w, p, which, gi), ws, w.slab, w.slab_bytes, s);
 }
 
 // which kernel d conv_v_att.weight takes (ncx_mlb_att_dwv_form): 0 k_att_dwv_small, 1 fp32 k_att_dwv, 2 k_att_dwv_x6
@@ -738,11 +682,11 @@ int ncx_mlb_att_train_forward_flags(const ncx_mlb_att_dims* dp, const ncx_mlb_at
     const ncx_mlb_att_dims& d = *dp; const ncx_mlb_att_train& t = *tp; const ncx_mlb_att_params& m = *mp;
     if (t.dropout_mode == 2 && !masks) return NCX_E_NULL;
     const AtLayout w = at_layout(d, t, m);
-    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) return NCX_E_WORKSPACE;
+    if (!ws_ok(workspace, workspace_bytes, w.total)) return NCX_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream_;
     char* ws = (char*)workspace;
     auto F = [&](size_t o) { return (float*)(ws + o); };
-    const AttDrop k = at_drop(t);
+    const TrainDrop k = at_drop(t);
     const float* mk = t.dropout_mode == 2 ? masks : nullptr;
     const int GF = d.G * d.dh_f;
     const long long nq = (long long)d.B * d.dq, nmap = (long long)d.B * d.dv * d.P, nva = (long long)d.B * d.G * d.dv;
@@ -750,18 +694,16 @@ int ncx_mlb_att_train_forward_flags(const ncx_mlb_att_dims* dp, const ncx_mlb_at
     p.masks = mk; p.q2 = q_emb; p.q5 = q_emb; p.v4 = F(w.v_att);
     p.xq = F(w.xq); p.xv = F(w.xv); p.xqf = F(w.xqf); p.tc = F(w.tc); p.logits = logits;
     if (at_on(t, 1)) {
-        hipLaunchKernelGGL(k_at_dropmap, dim3(at_grid(nmap)), dim3(256), 0, s, feats, img_idx, d.n_img, (long long)d.dv * d.P, nmap, k,
-                           at_off(mk, w.m_off[0]), F(w.vd));
+        hipLaunchKernelGGL(k_at_dropmap, dim3(grid256(nmap)), dim3(256), 0, s, feats, img_idx, d.n_img, (long long)d.dv * d.P, nmap, k,
+                           ptr_off(mk, w.m_off[0]), F(w.vd));
         NCX_HIP_TRY(hipGetLastError());
     }
     if (at_on(t, 2)) {
-        hipLaunchKernelGGL(k_at_droprows, dim3(at_grid(nq)), dim3(256), 0, s, q_emb, F(w.q2), nq, k, 2, at_off(mk, w.m_off[1]));
-        NCX_HIP_TRY(hipGetLastError());
+        NCX_HIP_TRY(train_drop_flat(q_emb, F(w.q2), nq, k, 2, ptr_off(mk, w.m_off[1]), s));
         p.q2 = F(w.q2);
     }
     if (at_on(t, 5)) {
-        hipLaunchKernelGGL(k_at_droprows, dim3(at_grid(nq)), dim3(256), 0, s, q_emb, F(w.q5), nq, k, 5, at_off(mk, w.m_off[4]));
-        NCX_HIP_TRY(hipGetLastError());
+        NCX_HIP_TRY(train_drop_flat(q_emb, F(w.q5), nq, k, 5, ptr_off(mk, w.m_off[4]), s));
         p.q5 = F(w.q5);
     }
     rc = at_run(d, t, m, w, p, AT_XQ, 0, ws, s); if (rc) return rc;
@@ -772,7 +714,7 @@ int ncx_mlb_att_train_forward_flags(const ncx_mlb_att_dims* dp, const ncx_mlb_at
         a.P = d.P; a.dv = d.dv; a.dh = d.dh_att; a.G = d.G; a.n_img = d.n_img; a.HT = w.HT; a.PT = w.PT;
         a.act_v = m.act_v_att; a.act_mm = m.act_mm;
         AttTrain tr{};
-        tr.xv_stash = F(w.stash); tr.mask3 = at_off(mk, w.m_off[2]); tr.drop = k; tr.identity = at_on(t, 1) ? 1 : 0;
+        tr.xv_stash = F(w.stash); tr.mask3 = ptr_off(mk, w.m_off[2]); tr.drop = k; tr.identity = at_on(t, 1) ? 1 : 0;
         rc = run_att_logits<true>(a, tr, d.B, flags, s);
         if (rc) return rc;
     }
@@ -789,15 +731,14 @@ int ncx_mlb_att_train_forward_flags(const ncx_mlb_att_dims* dp, const ncx_mlb_at
         NCX_HIP_TRY(hipGetLastError());
     }
     if (at_on(t, 4)) {
-        hipLaunchKernelGGL(k_at_droprows, dim3(at_grid(nva)), dim3(256), 0, s, (const float*)F(w.v_att), F(w.v4), nva, k, 4, at_off(mk, w.m_off[3]));
-        NCX_HIP_TRY(hipGetLastError());
+        NCX_HIP_TRY(train_drop_flat(F(w.v_att), F(w.v4), nva, k, 4, ptr_off(mk, w.m_off[3]), s));
         p.v4 = F(w.v4);
     }
     rc = at_run(d, t, m, w, p, AT_GLIMPSE, 0, ws, s); if (rc) return rc;
     rc = at_run(d, t, m, w, p, AT_XQF, 0, ws, s); if (rc) return rc;
     const long long total = (long long)d.B * GF;
-    hipLaunchKernelGGL(k_att_fuse_train, dim3(at_grid(total)), dim3(256), 0, s, p.xv, m.bg, (const float*)p.xqf, GF, total, m.act_v, m.act_c, k,
-                       at_off(mk, w.m_off[5]), F(w.t), F(w.tc));
+    hipLaunchKernelGGL(k_att_fuse_train, dim3(grid256(total)), dim3(256), 0, s, p.xv, m.bg, (const float*)p.xqf, GF, total, m.act_v, m.act_c, k,
+                       ptr_off(mk, w.m_off[5]), F(w.t), F(w.tc));
     NCX_HIP_TRY(hipGetLastError());
     return at_run(d, t, m, w, p, AT_LOGITS, 0, ws, s);
 }
@@ -828,11 +769,11 @@ int ncx_mlb_att_train_backward_flags(const ncx_mlb_att_dims* dp, const ncx_mlb_a
     const ncx_mlb_att_dims& d = *dp; const ncx_mlb_att_train& t = *tp; const ncx_mlb_att_params& m = *mp;
     if ((t.dropout_mode == 2 && !masks) || (t.want_dq && !dq_emb)) return NCX_E_NULL;
     const AtLayout w = at_layout(d, t, m);
-    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) return NCX_E_WORKSPACE;
+    if (!ws_ok(workspace, workspace_bytes, w.total)) return NCX_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream_;
     char* ws = (char*)workspace;
     auto F = [&](size_t o) { return (float*)(ws + o); };
-    const AttDrop k = at_drop(t);
+    const TrainDrop k = at_drop(t);
     const float* mk = t.dropout_mode == 2 ? masks : nullptr;
     const int GF = d.G * d.dh_f, B = d.B;
     const long long total = (long long)B * GF, nva = (long long)B * d.G * d.dv, nxq = (long long)B * d.dh_att, nq = (long long)B * d.dq;
@@ -842,15 +783,13 @@ int ncx_mlb_att_train_backward_flags(const ncx_mlb_att_dims* dp, const ncx_mlb_a
     p.tc = F(w.tc); p.dt = F(w.dt); p.dpv = F(w.dpv); p.dpqf = F(w.dpqf); p.dvatt = F(w.dvatt); p.dxq = F(w.dxq);
     p.dq = dq_emb; p.dq2 = F(w.dq2);
     auto sumrows = [&](const float* in, long long n, int R, float* out) {
-        hipLaunchKernelGGL(k_at_sumrows, dim3(at_grid(n)), dim3(256), 0, s, in, n, R, out);
+        hipLaunchKernelGGL(k_at_sumrows, dim3(grid256(n)), dim3(256), 0, s, in, n, R, out);
         return (int)hipGetLastError();
     };
     // the classifier and the glimpse fusion
     rc = at_run(d, t, m, w, p, AT_DWC, 0, ws, s); if (rc) return rc;
     rc = at_run(d, t, m, w, p, AT_DT, 0, ws, s); if (rc) return rc;
-    hipLaunchKernelGGL(k_at_dfuse, dim3(at_grid(total)), dim3(256), 0, s, (const float*)F(w.dt), (const float*)F(w.t), (const float*)F(w.xv),
-                       (const float*)F(w.xqf), total, m.act_v, m.act_q, m.act_c, F(w.dpv), F(w.dpqf));
-    NCX_HIP_TRY(hipGetLastError());
+    NCX_HIP_TRY(train_dfuse(F(w.dt), F(w.t), F(w.xv), F(w.xqf), total, m.act_v, m.act_q, m.act_c, F(w.dpv), F(w.dpqf), s));
     rc = at_run(d, t, m, w, p, AT_DWG, 0, ws, s); if (rc) return rc;
     rc = at_run(d, t, m, w, p, AT_DWQF, 0, ws, s); if (rc) return rc;
     rc = sumrows(dlogits, d.A, B, g->bc); if (rc) return rc;
@@ -858,8 +797,7 @@ int ncx_mlb_att_train_backward_flags(const ncx_mlb_att_dims* dp, const ncx_mlb_a
     rc = sumrows(p.dpqf, GF, B, g->bqf); if (rc) return rc;
     for (int gi = 0; gi < d.G; ++gi) { rc = at_run(d, t, m, w, p, AT_DVATT, gi, ws, s); if (rc) return rc; }
     if (at_on(t, 4)) {
-        hipLaunchKernelGGL(k_at_droprows, dim3(at_grid(nva)), dim3(256), 0, s, (const float*)p.dvatt, p.dvatt, nva, k, 4, at_off(mk, w.m_off[3]));
-        NCX_HIP_TRY(hipGetLastError());
+        NCX_HIP_TRY(train_drop_flat(p.dvatt, p.dvatt, nva, k, 4, ptr_off(mk, w.m_off[3]), s));
     }
     {   // the pooling and the softmax over positions
         DattArgs a{};
@@ -874,7 +812,7 @@ int ncx_mlb_att_train_backward_flags(const ncx_mlb_att_dims* dp, const ncx_mlb_a
     }
     {   // the attention head, element-wise over the stash
         HeadArgs a{};
-        a.stash = F(w.stash); a.xq = F(w.xq); a.ds = F(w.ds); a.wa = m.wa; a.mask3 = at_off(mk, w.m_off[2]);
+        a.stash = F(w.stash); a.xq = F(w.xq); a.ds = F(w.ds); a.wa = m.wa; a.mask3 = ptr_off(mk, w.m_off[2]);
         a.dxq = F(w.dxq); a.dwa_p = F(w.dwa_p); a.dbv_p = F(w.dbv_p); a.drop = k;
         a.P = d.P; a.dh = d.dh_att; a.G = d.G; a.act_v = m.act_v_att; a.act_mm = m.act_mm;
         const size_t lds = ((size_t)d.G * d.P + (size_t)d.G * 64 + 4 * 64 * (size_t)(d.G + 2)) * 4;
@@ -900,21 +838,20 @@ int ncx_mlb_att_train_backward_flags(const ncx_mlb_att_dims* dp, const ncx_mlb_a
             NCX_HIP_TRY(hipGetLastError());
             rc = sumrows(F(w.dwv), (long long)d.dh_att * d.dv, w.S, g->wv_att); if (rc) return rc;
         } else {
-            hipLaunchKernelGGL(k_att_dwv_small, dim3(at_grid((long long)d.dh_att * d.dv)), dim3(256), 0, s, a, g->wv_att);
+            hipLaunchKernelGGL(k_att_dwv_small, dim3(grid256((long long)d.dh_att * d.dv)), dim3(256), 0, s, a, g->wv_att);
             NCX_HIP_TRY(hipGetLastError());
         }
     }
     // the question side
     if (m.act_q_att == 2) {
-        hipLaunchKernelGGL(k_at_dact, dim3(at_grid(nxq)), dim3(256), 0, s, F(w.dxq), (const float*)F(w.xq), nxq);
-        NCX_HIP_TRY(hipGetLastError());
+        NCX_HIP_TRY(train_dact(F(w.dxq), F(w.xq), nxq, 2, nullptr, nullptr, 0, 0, s));
     }
     rc = at_run(d, t, m, w, p, AT_DWQ, 0, ws, s); if (rc) return rc;
     rc = sumrows(p.dxq, d.dh_att, B, g->bq_att); if (rc) return rc;
     if (t.want_dq) {
         rc = at_run(d, t, m, w, p, AT_DQ1, 0, ws, s); if (rc) return rc;
         rc = at_run(d, t, m, w, p, AT_DQ2, 0, ws, s); if (rc) return rc;
-        hipLaunchKernelGGL(k_at_add, dim3(at_grid(nq)), dim3(256), 0, s, dq_emb, (const float*)p.dq2, nq);
+        hipLaunchKernelGGL(k_at_add, dim3(grid256(nq)), dim3(256), 0, s, dq_emb, (const float*)p.dq2, nq);
         NCX_HIP_TRY(hipGetLastError());
     }
     return NCX_OK;

@@ -286,33 +286,32 @@ WsLayout ws_layout(const ncx_dims& d) { return ws_layout(d, routes(d)); }
 WsLayout ws_layout(const ncx_dims& d, const StepRoutes& r) {
     WsLayout w{};
     const size_t M = (size_t)d.B * d.K, H = d.H;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    w.idx_k = take(M * 4); w.idx_o = take(M * 4); w.idx_ob = take((size_t)d.B * 4);
-    w.mx = take(M * 4); w.inv = take(M * 4);
+    WsCarver cv;
+    w.idx_k = cv.take(M * 4); w.idx_o = cv.take(M * 4); w.idx_ob = cv.take((size_t)d.B * 4);
+    w.mx = cv.take(M * 4); w.inv = cv.take(M * 4);
     w.ldm = pad_to(d.K + 1, 4);
     w.ldgt = (d.flags & NCX_F_BF16) ? d.A : pad_to(d.A, 32);
-    w.misc = take(M * w.ldm * 4);
-    w.gt = take(H * w.ldgt * 4);
-    w.sh = take((size_t)d.B * H * 4);
-    for (int l = 0; l < 3; ++l) w.h[l] = l < d.L ? take(M * H * 4) : 0;
-    w.dpre[0] = take(M * H * 4);
-    w.dpre[1] = d.L >= 2 ? take(M * H * 4) : 0;
-    w.dsh = take((size_t)d.B * H * 4);
-    w.dgt = take(2 * H * d.A * 4);                      // dGt[H][A], then (contiguous: one all-reduce bucket under DP)
+    w.misc = cv.take(M * w.ldm * 4);
+    w.gt = cv.take(H * w.ldgt * 4);
+    w.sh = cv.take((size_t)d.B * H * 4);
+    for (int l = 0; l < 3; ++l) w.h[l] = l < d.L ? cv.take(M * H * 4) : 0;
+    w.dpre[0] = cv.take(M * H * 4);
+    w.dpre[1] = d.L >= 2 ? cv.take(M * H * 4) : 0;
+    w.dsh = cv.take((size_t)d.B * H * 4);
+    w.dgt = cv.take(2 * H * d.A * 4);                      // dGt[H][A], then (contiguous: one all-reduce bucket under DP)
     w.dagt = w.dgt + H * d.A * 4;                       // dGgt[H][A] = one-hot(aid)^T dSh, transposed
-    w.dgtT = take((size_t)2 * d.A * pad_to(d.H, 4) * 4);
-    w.w1aT = take((size_t)2 * d.da * pad_to(d.H, 32) * 4);
-    w.dgtT2 = take(r.tn8 ? (size_t)pad_to(d.A, 32) * pad_to(d.H, 4) * 4 : 0);
-    w.de_perm = take(r.emb_nt ? ((size_t)d.A + 1) * 4 : 0);
-    w.partial = take((size_t)NCX_PRELUDE_WAVES * H * 4 * 2 + (size_t)NCX_PRELUDE_WAVES * 4 + 256);     // (>= NCX_COLSUM_CHUNKS rows)
+    w.dgtT = cv.take((size_t)2 * d.A * pad_to(d.H, 4) * 4);
+    w.w1aT = cv.take((size_t)2 * d.da * pad_to(d.H, 32) * 4);
+    w.dgtT2 = cv.take(r.tn8 ? (size_t)pad_to(d.A, 32) * pad_to(d.H, 4) * 4 : 0);
+    w.de_perm = cv.take(r.emb_nt ? ((size_t)d.A + 1) * 4 : 0);
+    w.partial = cv.take((size_t)NCX_PRELUDE_WAVES * H * 4 * 2 + (size_t)NCX_PRELUDE_WAVES * 4 + 256);     // (>= NCX_COLSUM_CHUNKS rows)
     GemmUse u[U_COUNT];
     list_uses(d, r, u);
     long long slab = 0;
     for (int i = 0; i < U_COUNT; ++i) slab = u[i].slab_elems > slab ? u[i].slab_elems : slab;
     w.slab_bytes = (size_t)slab * 4;
     if (dw_tn8_slab_bytes(d) > w.slab_bytes) w.slab_bytes = dw_tn8_slab_bytes(d);      // ncx_dwtn.hip: its partial tiles live here too
-    w.slab = take(w.slab_bytes);
+    w.slab = cv.take(w.slab_bytes);
     {   // side-stream GEMMs (Gt, Sh forward; dW1ak, dE backward) get their own slab
         long long s2 = u[U_GT].slab_elems;
         if (u[U_SH].slab_elems > s2) s2 = u[U_SH].slab_elems;
@@ -322,32 +321,32 @@ WsLayout ws_layout(const ncx_dims& d, const StepRoutes& r) {
         const long long pair = r.pair_ok ? (long long)r.pair_s_gt * d.H * d.A + (long long)r.pair_s_sh * d.B * d.H : 0;
         if (pair > s2) s2 = pair;
         w.slab2_bytes = (size_t)s2 * 4;
-        w.slab2 = take(w.slab2_bytes);
+        w.slab2 = cv.take(w.slab2_bytes);
     }
-    w.km_slab = take(dw_km_slab_bytes(d));
+    w.km_slab = cv.take(dw_km_slab_bytes(d));
     {   // split-K slabs of the fused forward kernel: linear_1 / hidden layers at small batches
         auto need = [&](long long m, long long n, long long t) { const int sp = main_split(m, n, t); return sp > 1 ? (size_t)sp * m * n * 4 : (size_t)0; };
         size_t b = need((long long)M, (long long)H, r.cand_ksteps);
         if (d.L >= 2) b = b > need((long long)M, (long long)H, ksteps(H)) ? b : need((long long)M, (long long)H, ksteps(H));
         w.mslab_bytes = b;
-        w.mslab = take(b);
+        w.mslab = cv.take(b);
     }
     {   // padded weight copies for the fused forward kernel: [H][pad32(width)] each, in the order pack_wpad fills them
         size_t e = 0;
         for (int i = 0; i < WPAD_N; ++i) e += (size_t)H * wpad_width(d, i);
-        w.wpad = take(e * 4);
+        w.wpad = cv.take(e * 4);
     }
     if (d.flags & NCX_F_BF16) {                          // packed bf16 operands of the two dominant GEMMs (ncx_bf16.h)
-        w.xc = take(bf16_xc_bytes(d)); w.wc = take(bf16_wc_bytes(d));
-        w.dpre_bf = take(bf16_dpre_bytes(d)); w.bf_slab = take(bf16_slab_bytes(d));
-        w.bf_emb = take(bf16_emb_bytes(d));
+        w.xc = cv.take(bf16_xc_bytes(d)); w.wc = cv.take(bf16_wc_bytes(d));
+        w.dpre_bf = cv.take(bf16_dpre_bytes(d)); w.bf_slab = cv.take(bf16_slab_bytes(d));
+        w.bf_emb = cv.take(bf16_emb_bytes(d));
     }
     {   // padded weight copies of the Gt + Sh pair launch (last: every other region keeps its place)
         size_t e = 0;
         for (int i = 0; i < PAIR_WPAD_N; ++i) e += (size_t)(i == 4 ? d.A : d.H) * pair_wpad_width(d, r, i);
-        w.pwpad = take(e * 4);
+        w.pwpad = cv.take(e * 4);
     }
-    w.total = off;
+    w.total = cv.off;
     return w;
 }
 }  // namespace ncx

@@ -22,12 +22,10 @@ struct RnnPlanOff {
     RnnPlan at(void* ws) const { char* b = (char*)ws; return {(int*)(b + perm), (int*)(b + lens), (int*)(b + lens_tmp), (int*)(b + n_t)}; }
 };
 
-// Byte offsets of a workspace's regions, each 256-byte aligned, in the order they are taken
-struct WsCarver {
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; }
-    RnnPlanOff take_plan(int B) { return {take((size_t)B * 4), take((size_t)B * 4), take((size_t)B * 4), take(RNN_MAX_T * 4)}; }
-};
+// the plan's four regions, first in every encoder's workspace (WsCarver: ncx_internal.h)
+static inline RnnPlanOff take_plan(WsCarver& c, int B) {
+    return {c.take((size_t)B * 4), c.take((size_t)B * 4), c.take((size_t)B * 4), c.take(RNN_MAX_T * 4)};
+}
 
 // Sizes that every index, offset and the step launch's grid (rows / RNN_BM x units / RNN_BU workgroups) of either encoder can hold
 __attribute__((visibility("hidden"))) bool rnn_dims_ok(long long B, long long T, long long emb, long long units);

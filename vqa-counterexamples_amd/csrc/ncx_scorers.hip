@@ -117,19 +117,18 @@ static GemmArgs pl_gemm_da(const ncx_scorer_dims& d, const PlPtrs& p, GemmPlan* 
 }
 
 static PlLayout pl_layout(const ncx_scorer_dims& d) {
-    PlLayout w{}; size_t o = 0;
+    PlLayout w{}; WsCarver cv;
     const size_t B = d.B, M = (size_t)d.B * d.K;
-    auto take = [&](size_t bytes) { const size_t r = o; o = align_up(o + bytes, 256); return r; };
-    w.idx_o = take(B * 4); w.aid = take(B * 4); w.idx_k = take(M * 4);
-    w.P = take(B * PL_H * 4); w.h = take(M * PL_H * 4); w.s = take(M * 4); w.dpre = take(M * PL_H * 4);
-    w.dP = take(B * PL_H * 4); w.pw = take(B * PL_H * 4); w.pg = take(B * 4); w.dA = take(B * PL_DA * 4);
+    w.idx_o = cv.take(B * 4); w.aid = cv.take(B * 4); w.idx_k = cv.take(M * 4);
+    w.P = cv.take(B * PL_H * 4); w.h = cv.take(M * PL_H * 4); w.s = cv.take(M * 4); w.dpre = cv.take(M * PL_H * 4);
+    w.dP = cv.take(B * PL_H * 4); w.pw = cv.take(B * PL_H * 4); w.pg = cv.take(B * 4); w.dA = cv.take(B * PL_DA * 4);
     PlPtrs p{}; GemmPlan pl; size_t sb = 0, t;
     GemmArgs a = pl_gemm_p(d, p, &pl);   t = gemm_slab_bytes(a, pl); sb = t > sb ? t : sb;
     a = pl_gemm_dwc(d, p, &pl);          t = gemm_slab_bytes(a, pl); sb = t > sb ? t : sb;
     a = pl_gemm_dwq(d, p, &pl);          t = gemm_slab_bytes(a, pl); sb = t > sb ? t : sb;
     a = pl_gemm_da(d, p, &pl);           t = gemm_slab_bytes(a, pl); sb = t > sb ? t : sb;
-    w.slab = take(sb); w.slab_bytes = sb;
-    w.total = o;
+    w.slab = cv.take(sb); w.slab_bytes = sb;
+    w.total = cv.off;
     return w;
 }
 
@@ -272,13 +271,12 @@ static GemmArgs lc_gemm_dw(const ncx_scorer_dims& d, const float* z, const float
 }
 struct LcLayout { size_t pad, slab, slab_bytes, total; };
 static LcLayout lc_layout(const ncx_scorer_dims& d) {
-    LcLayout w{}; size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o = align_up(o + bytes, 256); return r; };
-    w.pad = take(d.K < 4 ? (size_t)d.B * 16 : 0);
+    LcLayout w{}; WsCarver cv;
+    w.pad = cv.take(d.K < 4 ? (size_t)d.B * 16 : 0);
     GemmPlan pl; size_t sb, t;
     GemmArgs a = lc_gemm_fwd(d, nullptr, nullptr, nullptr, nullptr, &pl); sb = gemm_slab_bytes(a, pl);
     a = lc_gemm_dw(d, nullptr, nullptr, d.K < 4 ? 4 : d.K, nullptr, &pl); t = gemm_slab_bytes(a, pl); sb = t > sb ? t : sb;
-    w.slab = take(sb); w.slab_bytes = sb; w.total = o > 256 ? o : 256;      // (0 is the "unsupported dims" answer)
+    w.slab = cv.take(sb); w.slab_bytes = sb; w.total = cv.off > 256 ? cv.off : 256;      // (0 is the "unsupported dims" answer)
     return w;
 }
 
@@ -299,7 +297,7 @@ extern "C" int ncx_pairlin_forward(const ncx_scorer_dims* dp, const ncx_inputs* 
     if (!scorer_dims_ok(dp, true)) return NCX_E_DIMS;
     const ncx_scorer_dims& d = *dp;
     const PlLayout w = pl_layout(d);
-    if (ws_bytes < w.total || ((uintptr_t)ws & 255)) return NCX_E_WORKSPACE;
+    if (!ws_ok(ws, ws_bytes, w.total)) return NCX_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream_;
     char* base = (char*)ws;
     const int M = d.B * d.K;
@@ -331,7 +329,7 @@ extern "C" int ncx_pairlin_backward(const ncx_scorer_dims* dp, const ncx_inputs*
     if (!scorer_dims_ok(dp, true)) return NCX_E_DIMS;
     const ncx_scorer_dims& d = *dp;
     const PlLayout w = pl_layout(d);
-    if (ws_bytes < w.total || ((uintptr_t)ws & 255)) return NCX_E_WORKSPACE;
+    if (!ws_ok(ws, ws_bytes, w.total)) return NCX_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream_;
     char* base = (char*)ws;
     PlPtrs q{};
@@ -368,7 +366,7 @@ extern "C" int ncx_linctx_forward(const ncx_scorer_dims* dp, const float* z_knns
     if (!dp || !z_knns || !w || !b || !ws || !scores) return NCX_E_NULL;
     if (!scorer_dims_ok(dp, false)) return NCX_E_DIMS;
     const LcLayout l = lc_layout(*dp);
-    if (ws_bytes < l.total || ((uintptr_t)ws & 255)) return NCX_E_WORKSPACE;
+    if (!ws_ok(ws, ws_bytes, l.total)) return NCX_E_WORKSPACE;
     GemmPlan pl;
     GemmArgs a = lc_gemm_fwd(*dp, z_knns, w, b, scores, &pl);
     return run_gemm_planned(a, FORM_NT, pl, (float*)((char*)ws + l.slab), l.slab_bytes, nullptr, (hipStream_t)stream_);
@@ -380,7 +378,7 @@ extern "C" int ncx_linctx_backward(const ncx_scorer_dims* dp, const float* z_knn
     if (!scorer_dims_ok(dp, false)) return NCX_E_DIMS;
     const ncx_scorer_dims& d = *dp;
     const LcLayout l = lc_layout(d);
-    if (ws_bytes < l.total || ((uintptr_t)ws & 255)) return NCX_E_WORKSPACE;
+    if (!ws_ok(ws, ws_bytes, l.total)) return NCX_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream_;
     const float* ds = dscores;
     long long ld = d.K;

@@ -1,5 +1,5 @@
 // ncx_vqa.hip -- the fused MUTAN producer: ncx_vqa_workspace_bytes, ncx_vqa_forward.
-#include "ncx_internal.h"
+#include "ncx_train.h"
 #include <stdio.h>
 
 using namespace ncx;
@@ -23,13 +23,12 @@ hipError_t pad_rows(const float* src, long long ld_src, int cols, float* dst, in
 extern "C" {
 static VqaLayout vqa_layout(const ncx_dims& d, const ncx_mutan_params& m, GemmPlan* plans /*[5]*/) {
     VqaLayout w{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+    WsCarver cv;
     const long long Mv = (long long)d.B * (d.K + 1), RZ = (long long)m.R * d.dz;
-    w.xq = take((size_t)d.B * m.dhq * 4);
-    w.hq = take((size_t)d.B * RZ * 4);
-    w.xv = take((size_t)Mv * m.dhv * 4);
-    w.wcp = take(d.dz % 32 ? (size_t)d.A * pad_to(d.dz, 32) * 4 : 0);
+    w.xq = cv.take((size_t)d.B * m.dhq * 4);
+    w.hq = cv.take((size_t)d.B * RZ * 4);
+    w.xv = cv.take((size_t)Mv * m.dhv * 4);
+    w.wcp = cv.take(d.dz % 32 ? (size_t)d.A * pad_to(d.dz, 32) * 4 : 0);
     // 0: xq = act(q Wq^T)  1: hq = xq Whq^T  2: xv = act(gather(v) Wv^T)  3: z (fold, never split)  4: a = z Wc^T
     const long long shp[5][3] = {{d.B, m.dhq, ksteps(d.dq)}, {d.B, RZ, ksteps(m.dhq)}, {Mv, m.dhv, ksteps(d.dv)}, {Mv, d.dz, 0}, {(long long)d.B * d.K, d.A, ksteps(d.dz)}};
     long long slab = 0;
@@ -46,8 +45,8 @@ static VqaLayout vqa_layout(const ncx_dims& d, const ncx_mutan_params& m, GemmPl
         if (e > slab) slab = e;
     }
     w.slab_bytes = (size_t)slab * 4;
-    w.slab = take(w.slab_bytes);
-    w.total = off;
+    w.slab = cv.take(w.slab_bytes);
+    w.total = cv.off;
     return w;
 }
 static int check_mutan(const ncx_dims* d, const ncx_mutan_params* m) {
@@ -74,22 +73,18 @@ int ncx_vqa_forward(const ncx_dims* dp, const float* feats, const int32_t* img_i
     const ncx_dims& d = *dp; const ncx_mutan_params& m = *mp;
     GemmPlan plans[5];
     const VqaLayout w = vqa_layout(d, m, plans);
-    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) return NCX_E_WORKSPACE;
+    if (!ws_ok(workspace, workspace_bytes, w.total)) return NCX_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream_;
     char* ws = (char*)workspace;
     float* xq = (float*)(ws + w.xq); float* hq = (float*)(ws + w.hq); float* xv = (float*)(ws + w.xv);
     float* slab = (float*)(ws + w.slab);
     const int Mv = d.B * (d.K + 1), RZ = m.R * d.dz;
     {   // x_q = act_q(q . Wq^T + bq)                                            fusion.py:88-93
-        GemmArgs a{}; a.mode = MODE_CHAIN; a.nseg = 1; a.M = d.B;
-        a.a[0] = x_plain(q_emb, d.dq, d.B, d.dq); a.b[0] = x_plain(m.wq, d.dq, m.dhq, d.dq); a.klen[0] = d.dq;
-        a.out[0] = xq; a.ldo[0] = m.dhq; a.n_cols[0] = m.dhq; a.epi.relu = m.act_q;
+        GemmArgs a = gemm_nt(d.B, m.dhq, d.dq, q_emb, m.wq, xq, m.act_q);
         rc = run_gemm_planned(a, FORM_NT, plans[0], slab, w.slab_bytes, m.bq, s); if (rc) return rc;
     }
     {   // hq[b][r*dz + j] = x_q . Whq_r^T + bhq_r   (all R at once)               fusion.py:103-107
-        GemmArgs a{}; a.mode = MODE_CHAIN; a.nseg = 1; a.M = d.B;
-        a.a[0] = x_plain(xq, m.dhq, d.B, m.dhq); a.b[0] = x_plain(m.whq, m.dhq, RZ, m.dhq); a.klen[0] = m.dhq;
-        a.out[0] = hq; a.ldo[0] = RZ; a.n_cols[0] = RZ;
+        GemmArgs a = gemm_nt(d.B, RZ, m.dhq, xq, m.whq, hq, 0);
         rc = run_gemm_planned(a, FORM_NT, plans[1], slab, w.slab_bytes, m.bhq, s); if (rc) return rc;
     }
     if (d.dv % 32 == 0 && d.dv >= 64 && m.dhv >= 4 && !hook_env("NCX_VQA_NO_MAIN")) {
@@ -139,15 +134,12 @@ int ncx_vqa_forward(const ncx_dims* dp, const float* feats, const int32_t* img_i
         rc = main_forward(a, s); if (rc) return rc;
     } else
     {   // a_knns = z_knns . Wc^T + bc                                               noatt.py:24-29 (dropout off in eval)
-        GemmArgs a{}; a.mode = MODE_CHAIN; a.nseg = 1; a.M = d.B * d.K;
-        a.a[0] = x_plain(z_knns, d.dz, d.B * d.K, d.dz); a.b[0] = x_plain(m.wc, d.dz, d.A, d.dz); a.klen[0] = d.dz;
-        a.out[0] = a_knns; a.ldo[0] = d.A; a.n_cols[0] = d.A;
+        GemmArgs a = gemm_nt(d.B * d.K, d.A, d.dz, z_knns, m.wc, a_knns, 0);
         rc = run_gemm_planned(a, FORM_NT, plans[4], slab, w.slab_bytes, m.bc, s); if (rc) return rc;
     }
     if (a_orig) {
-        GemmArgs a{}; a.mode = MODE_CHAIN; a.nseg = 1; a.M = d.B;
-        a.a[0] = x_plain(z_orig, d.dz, d.B, d.dz); a.b[0] = x_plain(m.wc, d.dz, d.A, d.dz); a.klen[0] = d.dz;
-        a.out[0] = a_orig; a.ldo[0] = d.A; a.n_cols[0] = d.A; a.split[0] = 1;
+        GemmArgs a = gemm_nt(d.B, d.A, d.dz, z_orig, m.wc, a_orig, 0);
+        a.split[0] = 1;
         GemmPlan pl; pl.cfg = CFG_64x64; pl.split = 1;
         rc = run_gemm_planned(a, FORM_NT, pl, slab, w.slab_bytes, m.bc, s); if (rc) return rc;
     }
