@@ -312,6 +312,21 @@ size_t ncx_vqa_workspace_bytes(const ncx_dims* d, const ncx_mutan_params* m);
 int ncx_vqa_forward(const ncx_dims* d, const float* feats, const int32_t* img_idx, const float* q_emb,
                     const ncx_mutan_params* m, void* workspace, size_t workspace_bytes,
                     float* z_orig, float* z_knns, float* a_knns, float* a_orig, void* stream);
+/* Diagnostics / tests: what ncx_vqa_forward launches for these dims and parameters, from the function the launcher itself asks
+ * (experiment hooks applied).  Host only: launches nothing, needs no device (256 CUs are assumed without one).
+ *   out4[0]  x_v:        1 the fused forward kernel (one gathered segment), 0 the generic engine's gather
+ *   out4[1]  fusion:     1 k_mutan_fold (one product per question; K + 1 <= 32, dhv % 4 == 0), 0 the generic engine's fold chain of R pairs
+ *   out4[2]  classifier: 0 the generic engine, 1 the fused forward kernel on linear_classif.weight in place (dz % 32 == 0),
+ *                        2 the fused forward kernel on a copy with rows zero-padded to a multiple of 32
+ *   out4[3]  the tile form of the fused x_v launch (the codes of NCX_QUERY_FWD_ROUTE), -1 on the generic engine
+ * The fused forward kernel addresses its operands with 32-bit byte offsets: a feature table, weight matrix or z_knns of 4 GiB
+ * or more takes the generic engine. */
+int ncx_vqa_route(const ncx_dims* d, const ncx_mutan_params* m, int32_t* out4);
+/* Diagnostics / tests: byte offset and size of the intermediate tensors ncx_vqa_forward leaves in the workspace. */
+#define NCX_VQA_WS_XQ 1   /* x_q = act_q(q Wq^T + bq)                          [B, dhq]        */
+#define NCX_VQA_WS_HQ 2   /* hq[b][r dz + j] = x_q[b] . Whq_r[j] + bhq_r[j]    [B, R dz]       */
+#define NCX_VQA_WS_XV 3   /* x_v = act_v(feats[img_idx] Wv^T + bv)             [B (K + 1), dhv] */
+int ncx_vqa_ws_region(const ncx_dims* d, const ncx_mutan_params* m, int32_t which, size_t* offset, size_t* bytes);
 
 /* ---- the frozen MLB producer: the reference factory's second no-attention model (vqa/models/utils.py:7) ----
  * Replaces CXModelBase.vqa_forward (vqa/models/cx.py:64-104) for the MLBNoAtt model (vqa/models/noatt.py:38-46) in eval mode:
@@ -336,6 +351,19 @@ size_t ncx_mlb_workspace_bytes(const ncx_dims* d, const ncx_mlb_params* m);
 int ncx_mlb_forward(const ncx_dims* d, const float* feats, const int32_t* img_idx, const float* q_emb,
                     const ncx_mlb_params* m, void* workspace, size_t workspace_bytes,
                     float* z_orig, float* z_knns, float* a_knns, float* a_orig, void* stream);
+/* The sibling of ncx_vqa_route for ncx_mlb_forward (host only, launches nothing):
+ *   out4[0]  x_v:        1 the fused forward kernel with the product, row split and tanh in its epilogue, 0 the generic engine + k_mlb_mul
+ *   out4[1]  the tile form of that launch: 2 (96 x 128) or 0 (48 x 128), by the CU count; -1 on the generic engine
+ *   out4[2]  classifier: 0 generic engine, 1 fused forward kernel on the weights in place, 2 ... on a zero-padded copy (as ncx_vqa_route)
+ *   out4[3]  1 when t = act_c(z) is stored beside z (act_c != 0) */
+int ncx_mlb_route(const ncx_dims* d, const ncx_mlb_params* m, int32_t* out4);
+/* Intermediate tensors of ncx_mlb_forward in the workspace.  NCX_E_FLAGS for a tensor the route does not store: t_* without
+ * act_c, x_v on the fused route (there it exists only inside the kernel). */
+#define NCX_MLB_WS_XQ 1       /* x_q = act_q(q Wq^T + bq)                      [B, dh]         */
+#define NCX_MLB_WS_T_KNNS 2   /* act_c(z_knns)                                 [B K, dh]       */
+#define NCX_MLB_WS_T_ORIG 3   /* act_c(z_orig)                                 [B, dh]         */
+#define NCX_MLB_WS_XV 4       /* x_v = act_v(feats[img_idx] Wv^T + bv)         [B (K + 1), dh] */
+int ncx_mlb_ws_region(const ncx_dims* d, const ncx_mlb_params* m, int32_t which, size_t* offset, size_t* bytes);
 
 /* ---- the MLB attention model (MLBAtt, vqa/models/att.py:11-192) in eval mode, below the question encoder -------------------
  * Every dropout is the identity.  V[b] = feats[img_idx[b]] is the image's NCHW map [dv, P] (P = W H positions, p = w H + h), read

@@ -145,6 +145,7 @@ int main_adam_passengers();          // passenger workgroups of that launch
 int main_forward_pair(const MainArgs& gt, const MainArgs& sh, int reps_gt, int reps_sh, hipStream_t s);
 // The MLB producer's x_v product (ncx_mlb.hip): one MK_GATHER segment with the EPI_MLB epilogue of ncx_main.h
 int main_forward_mlb(MainArgs& a, hipStream_t s);
+int main_mlb_form(long long M, long long N);       // ... its tile form, as a code of NCX_QUERY_FWD_ROUTE: 2 (96 x 128) or 0 (48 x 128)
 // k-split of a problem for the fused forward kernel (48 x 128 tiles): 1 when its tiles already give every CU a workgroup,
 // else as many k-chunks as keep all workgroups resident at once (two per CU), at least 8 k-steps each.  T: k-steps of the whole chain.
 int main_split(long long M, long long N, long long T);
@@ -209,6 +210,21 @@ static inline bool main_fwd_dims_ok(const ncx_dims& d) {
     return d.dv % 4 == 0 && d.dz % 4 == 0 && ((d.flags & NCX_F_A_EMB) ? d.A : d.da) % 4 == 0 && !(d.flags & NCX_F_BF16) && main_fwd_extents_ok(d);
 }
 static inline bool hidden_fwd_dims_ok(const ncx_dims& d) { return d.H % 4 == 0 && main_fwd_extents_ok(d); }
+// The two products the frozen VQA producers (ncx_vqa.hip, ncx_mlb.hip) put on the fused forward kernel, by the width rules above and by
+// what that kernel addresses with 32-bit byte offsets (ncx_main.h, setup / issue: operand row x lda x 4 + the column window, weight row x
+// ldb x 4 + the k-step's offset; bias, x_q and every store take 64-bit addresses):
+//   v: x_v = feats[img_idx] . Wv^T   operand: the feature table [n_img][dv] (whole 32-column rows, at least two k-steps), weights [n_xv][dv]
+//   c: a = z_knns . Wc^T             operand: [B K][dz], weights [A][dz rounded up to 32] (whole 16-byte pieces on both sides)
+// Anything else runs on the generic engine, whose loaders take 64-bit addresses (OpLoader, ncx_gemm.h).  n_xv: rows of Wv.
+struct ProducerMainRoutes { bool v, c; };
+static inline ProducerMainRoutes producer_main_routes(const ncx_dims& d, int n_xv) {
+    const long long lim = (1ll << 32) - 65536, Mk = (long long)d.B * d.K;
+    const bool on = !hook_env("NCX_VQA_NO_MAIN");
+    ProducerMainRoutes r;
+    r.v = on && d.dv % 32 == 0 && d.dv >= 64 && (long long)d.n_img * d.dv * 4 < lim && (long long)n_xv * d.dv * 4 < lim;
+    r.c = on && d.dz % 4 == 0 && d.A % 4 == 0 && Mk * d.dz * 4 < lim && (long long)d.A * pad_to(d.dz, 32) * 4 < lim;
+    return r;
+}
 // private flag bit (never set by callers: check_dims rejects it): the pairwise distance is computed inside the fused forward
 // kernel, k_prep leaves the feature rows alone
 constexpr uint32_t NCX_F_PRIV_DIST_IN_MAIN = 1u << 30;

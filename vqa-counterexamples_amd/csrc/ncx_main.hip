@@ -115,9 +115,12 @@ int main_forward_pair(const MainArgs& gt, const MainArgs& sh, int reps_gt, int r
 }
 
 // x_v of the MLB producer: 96 x 128 tiles, one workgroup per CU, once they fill the chip (12 800 x 1200 at B = 512: 1340 tiles), else 48 x 128
+int main_mlb_form(long long M, long long N) {
+    const long long tiles96 = ((M + 95) / 96) * ((N + 127) / 128);
+    return tiles96 * 10 >= (long long)num_cus() * 9 ? 2 : 0;
+}
 int main_forward_mlb(MainArgs& a, hipStream_t s) {
-    const long long tiles96 = (long long)((a.M + 95) / 96) * ((a.N + 127) / 128);
-    if (tiles96 * 10 >= (long long)num_cus() * 9) return launch_main_fwd<WithMlbEpi<MainCfg2>>(a, s);
+    if (main_mlb_form(a.M, a.N) == 2) return launch_main_fwd<WithMlbEpi<MainCfg2>>(a, s);
     return launch_main_fwd<WithMlbEpi<MainCfg0>>(a, s);
 }
 

@@ -48,10 +48,10 @@ static int check_mlb(const ncx_dims* d, const ncx_mlb_params* m) {
 static MlbLayout mlb_layout(const ncx_dims& d, const ncx_mlb_params& m, GemmPlan* plans /*[3]*/) {
     MlbLayout w{};
     WsCarver cv;
-    const long long Mv = (long long)d.B * (d.K + 1), Mk = (long long)d.B * d.K, lim = (1ll << 32) - 65536;
+    const long long Mv = (long long)d.B * (d.K + 1), Mk = (long long)d.B * d.K;
     // the fused forward kernel reads with 32-bit byte offsets and whole 32-column k-steps on the weight side (ncx_main.h)
-    w.main_v = d.dv % 32 == 0 && d.dv >= 64 && (long long)d.n_img * d.dv * 4 < lim && (long long)d.dz * d.dv * 4 < lim && !hook_env("NCX_VQA_NO_MAIN");
-    w.main_c = d.dz % 4 == 0 && d.A % 4 == 0 && Mk * d.dz * 4 < lim && (long long)d.A * pad_to(d.dz, 32) * 4 < lim && !hook_env("NCX_VQA_NO_MAIN");
+    const ProducerMainRoutes pr = producer_main_routes(d, d.dz);
+    w.main_v = pr.v; w.main_c = pr.c;
     w.xq = cv.take((size_t)d.B * d.dz * 4);
     w.t_knns = cv.take(m.act_c ? (size_t)Mk * d.dz * 4 : 0);
     w.t_orig = cv.take(m.act_c ? (size_t)d.B * d.dz * 4 : 0);
@@ -76,6 +76,34 @@ size_t ncx_mlb_workspace_bytes(const ncx_dims* d, const ncx_mlb_params* m) {
     if (check_mlb(d, m) != NCX_OK) return 0;
     GemmPlan plans[3];
     return mlb_layout(*d, *m, plans).total;
+}
+
+int ncx_mlb_route(const ncx_dims* d, const ncx_mlb_params* m, int32_t* out4) {
+    if (!out4) return NCX_E_NULL;
+    const int rc = check_mlb(d, m);
+    if (rc != NCX_OK) return rc;
+    GemmPlan plans[3];
+    const MlbLayout w = mlb_layout(*d, *m, plans);
+    out4[0] = w.main_v;
+    out4[1] = w.main_v ? main_mlb_form((long long)d->B * (d->K + 1), d->dz) : -1;
+    out4[2] = w.main_c ? (d->dz % 32 ? 2 : 1) : 0;
+    out4[3] = m->act_c != 0;
+    return NCX_OK;
+}
+
+int ncx_mlb_ws_region(const ncx_dims* d, const ncx_mlb_params* m, int32_t which, size_t* offset, size_t* bytes) {
+    if (!offset || !bytes) return NCX_E_NULL;
+    const int rc = check_mlb(d, m);
+    if (rc != NCX_OK) return rc;
+    GemmPlan plans[3];
+    const MlbLayout w = mlb_layout(*d, *m, plans);
+    const size_t B = d->B, row = (size_t)d->dz * 4;
+    if (which == NCX_MLB_WS_XQ) { *offset = w.xq; *bytes = B * row; }
+    else if (which == NCX_MLB_WS_T_KNNS && m->act_c) { *offset = w.t_knns; *bytes = B * d->K * row; }
+    else if (which == NCX_MLB_WS_T_ORIG && m->act_c) { *offset = w.t_orig; *bytes = B * row; }
+    else if (which == NCX_MLB_WS_XV && !w.main_v) { *offset = w.xv; *bytes = B * (d->K + 1) * row; }
+    else return NCX_E_FLAGS;         // (an unknown id, or a tensor this route never stores)
+    return NCX_OK;
 }
 
 int ncx_mlb_forward(const ncx_dims* dp, const float* feats, const int32_t* img_idx, const float* q_emb,

@@ -5,6 +5,13 @@
 using namespace ncx;
 extern "C" {
 struct VqaLayout { size_t xq, hq, xv, wcp, slab, slab_bytes, total; };
+// What ncx_vqa_forward launches for a shape; ncx_vqa_route reports it from here.
+struct VqaRoute {
+    bool main_v;     // x_v on the fused forward kernel (one gathered segment), else the generic engine's gather
+    bool fold;       // the fusion on k_mutan_fold (one product per question), else the generic engine's FOLD chain of R pairs
+    bool main_c;     // a_knns on the fused forward kernel, else the generic engine
+    bool pad_c;      // ... against a copy of the classifier weights with rows zero-padded to whole 32-column k-steps
+};
 // dst[r][0 .. cols) = src[r][0 .. cols), dst[r][cols .. ldd) = 0: the classifier weights with their rows zero-padded to whole 32-column
 // k-steps for the fused forward kernel (ncx_main.h reads the weight side of a segment up to the next multiple of 32 columns)
 __global__ __launch_bounds__(256) void k_pad_rows(const float* __restrict__ src, long long lds_, int cols, float* __restrict__ dst, int ldd, int rows) {
@@ -21,6 +28,12 @@ hipError_t pad_rows(const float* src, long long ld_src, int cols, float* dst, in
 }
 }  // namespace ncx
 extern "C" {
+static VqaRoute vqa_route(const ncx_dims& d, const ncx_mutan_params& m) {
+    const ProducerMainRoutes p = producer_main_routes(d, m.dhv);
+    VqaRoute r;
+    r.main_v = p.v; r.fold = mutan_fold_supported(d, m); r.main_c = p.c; r.pad_c = p.c && d.dz % 32 != 0;
+    return r;
+}
 static VqaLayout vqa_layout(const ncx_dims& d, const ncx_mutan_params& m, GemmPlan* plans /*[5]*/) {
     VqaLayout w{};
     WsCarver cv;
@@ -53,6 +66,7 @@ static int check_mutan(const ncx_dims* d, const ncx_mutan_params* m) {
     if (!d || !m) return NCX_E_NULL;
     if (d->B < 1 || d->K < 1 || d->dv < 4 || d->dq < 4 || d->dz < 4 || d->A < 4 || d->n_img < 1) return NCX_E_DIMS;
     if (m->dhv < 4 || m->dhq < 4 || m->R < 1 || m->R > NCX_MAX_SEG) return NCX_E_DIMS;
+    if ((long long)d->B * (d->K + 1) * (long long)(d->dz > d->A ? d->dz : d->A) >= (1ll << 31)) return NCX_E_DIMS;      // (row and element counts are ints)
     if ((m->act_v != 0 && m->act_v != 2) || (m->act_q != 0 && m->act_q != 2)) return NCX_E_FLAGS;
     if (!m->wv || !m->bv || !m->wq || !m->bq || !m->whv || !m->bhv || !m->whq || !m->bhq || !m->wc || !m->bc) return NCX_E_NULL;
     return NCX_OK;
@@ -64,6 +78,30 @@ size_t ncx_vqa_workspace_bytes(const ncx_dims* d, const ncx_mutan_params* m) {
     return vqa_layout(*d, *m, plans).total;
 }
 
+int ncx_vqa_route(const ncx_dims* d, const ncx_mutan_params* m, int32_t* out4) {
+    if (!out4) return NCX_E_NULL;
+    const int rc = check_mutan(d, m);
+    if (rc != NCX_OK) return rc;
+    const VqaRoute r = vqa_route(*d, *m);
+    out4[0] = r.main_v; out4[1] = r.fold; out4[2] = r.main_c ? (r.pad_c ? 2 : 1) : 0;
+    out4[3] = r.main_v ? main_chain_form((long long)d->B * (d->K + 1), m->dhv, ksteps(d->dv), 1, true, true) : -1;
+    return NCX_OK;
+}
+
+int ncx_vqa_ws_region(const ncx_dims* d, const ncx_mutan_params* m, int32_t which, size_t* offset, size_t* bytes) {
+    if (!offset || !bytes) return NCX_E_NULL;
+    const int rc = check_mutan(d, m);
+    if (rc != NCX_OK) return rc;
+    GemmPlan plans[5];
+    const VqaLayout w = vqa_layout(*d, *m, plans);
+    const size_t B = d->B;
+    if (which == NCX_VQA_WS_XQ) { *offset = w.xq; *bytes = B * m->dhq * 4; }
+    else if (which == NCX_VQA_WS_HQ) { *offset = w.hq; *bytes = B * m->R * d->dz * 4; }
+    else if (which == NCX_VQA_WS_XV) { *offset = w.xv; *bytes = B * (d->K + 1) * m->dhv * 4; }
+    else return NCX_E_FLAGS;
+    return NCX_OK;
+}
+
 int ncx_vqa_forward(const ncx_dims* dp, const float* feats, const int32_t* img_idx, const float* q_emb,
                     const ncx_mutan_params* mp, void* workspace, size_t workspace_bytes,
                     float* z_orig, float* z_knns, float* a_knns, float* a_orig, void* stream_) {
@@ -73,6 +111,7 @@ int ncx_vqa_forward(const ncx_dims* dp, const float* feats, const int32_t* img_i
     const ncx_dims& d = *dp; const ncx_mutan_params& m = *mp;
     GemmPlan plans[5];
     const VqaLayout w = vqa_layout(d, m, plans);
+    const VqaRoute route = vqa_route(d, m);
     if (!ws_ok(workspace, workspace_bytes, w.total)) return NCX_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream_;
     char* ws = (char*)workspace;
@@ -87,7 +126,7 @@ int ncx_vqa_forward(const ncx_dims* dp, const float* feats, const int32_t* img_i
         GemmArgs a = gemm_nt(d.B, RZ, m.dhq, xq, m.whq, hq, 0);
         rc = run_gemm_planned(a, FORM_NT, plans[1], slab, w.slab_bytes, m.bhq, s); if (rc) return rc;
     }
-    if (d.dv % 32 == 0 && d.dv >= 64 && m.dhv >= 4 && !hook_env("NCX_VQA_NO_MAIN")) {
+    if (route.main_v) {
         // x_v on the fused forward kernel (ncx_main.h): one gathered segment, bias + activation in the epilogue (round 3: 249 -> see DESIGN 5b)
         MainArgs a{}; a.M = Mv; a.N = m.dhv; a.nseg = 1;
         a.seg[0].kind = MK_GATHER; a.seg[0].a = feats; a.seg[0].lda = d.dv; a.seg[0].idx = img_idx; a.seg[0].klen = d.dv;
@@ -101,7 +140,7 @@ int ncx_vqa_forward(const ncx_dims* dp, const float* feats, const int32_t* img_i
         a.out[0] = xv; a.ldo[0] = m.dhv; a.n_cols[0] = m.dhv; a.epi.relu = m.act_v;
         rc = run_gemm_planned(a, FORM_NT, plans[2], slab, w.slab_bytes, m.bv, s); if (rc) return rc;
     }
-    if (mutan_fold_supported(d, m)) {
+    if (route.fold) {
         // z = sum_r (x_v . Whv_r^T + bhv_r) * hq_r[question] as ONE product per question against Weff_q = sum_r diag(hq_r[q]) Whv_r,
         // built on the vector ALU on the way into LDS (ncx_mutan.hip): 4.2 + 0.7 GF instead of 33.2 at configs[2]        fusion.py:96-115
         rc = mutan_fold(d, m, xv, hq, z_orig, z_knns, s); if (rc) return rc;
@@ -118,11 +157,11 @@ int ncx_vqa_forward(const ncx_dims* dp, const float* feats, const int32_t* img_i
         a.epi.rowsplit_g = d.K + 1; a.epi.out0 = z_orig; a.epi.ldo0 = d.dz;
         rc = run_gemm_nt_fold(a, s); if (rc) return rc;
     }
-    if (d.dz % 4 == 0 && d.dz >= 4 && d.A % 4 == 0 && !hook_env("NCX_VQA_NO_MAIN")) {      // (the kernel's epilogue wants whole 16-byte pieces per output row)
+    if (route.main_c) {      // (the kernel's epilogue wants whole 16-byte pieces per output row)
         // a_knns = z_knns . Wc^T + bc on the fused forward kernel (round 4): 11-12 k-steps per workgroup -> 64 x 64 tiles at three
         // workgroups per CU (the plan the answer-embedding gradient takes); generic engine: 241 us at configs[2]          noatt.py:24-29
         const float* wc = m.wc; long long ldw = d.dz;
-        if (d.dz % 32) {
+        if (route.pad_c) {
             float* wcp = (float*)(ws + w.wcp);
             const int ldd = pad_to(d.dz, 32);
             NCX_HIP_TRY(pad_rows(m.wc, (long long)d.dz, d.dz, wcp, ldd, d.A, s));

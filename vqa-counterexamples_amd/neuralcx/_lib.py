@@ -19,7 +19,8 @@ NCX_F_BF16 = 16       # BASELINE configs[4]: bf16 operands for the two dominant 
 
 EXPORTS = ("ncx_input_size", "ncx_workspace_bytes", "ncx_forward", "ncx_forward_phase", "ncx_loss_rank", "ncx_backward", "ncx_backward_phase",
            "ncx_adam_step", "ncx_backward_adam", "ncx_version", "ncx_profile_begin", "ncx_profile_end", "ncx_plan_query",
-           "ncx_vqa_workspace_bytes", "ncx_vqa_forward", "ncx_mlb_workspace_bytes", "ncx_mlb_forward", "ncx_mlb_att_workspace_bytes", "ncx_mlb_att_forward", "ncx_mlb_att_forward_flags", "ncx_mlb_att_logits_form", "ncx_knn_workspace_bytes", "ncx_knn_status_offset", "ncx_knn", "ncx_cosine_gram_workspace_bytes", "ncx_cosine_gram", "ncx_semantic_scores",
+           "ncx_vqa_workspace_bytes", "ncx_vqa_forward", "ncx_mlb_workspace_bytes", "ncx_mlb_forward",
+           "ncx_vqa_route", "ncx_vqa_ws_region", "ncx_mlb_route", "ncx_mlb_ws_region", "ncx_mlb_att_workspace_bytes", "ncx_mlb_att_forward", "ncx_mlb_att_forward_flags", "ncx_mlb_att_logits_form", "ncx_knn_workspace_bytes", "ncx_knn_status_offset", "ncx_knn", "ncx_cosine_gram_workspace_bytes", "ncx_cosine_gram", "ncx_semantic_scores",
            "ncx_similarity_scores",
            "ncx_gru_packed_bytes", "ncx_gru_pack", "ncx_gru_workspace_bytes", "ncx_gru_encode", "ncx_gru_encode_flags", "ncx_gru_step_form",
            "ncx_gru_train_workspace_bytes", "ncx_gru_packed_t_bytes", "ncx_gru_pack_t", "ncx_gru_train_forward", "ncx_gru_train_forward_flags", "ncx_gru_train_backward",
@@ -189,6 +190,11 @@ def lib():
     L.ncx_mlb_forward.restype = C.c_int
     L.ncx_mlb_forward.argtypes = [C.POINTER(NcxDims), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NcxMlbParams), C.c_void_p,
                                   C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    for name, P_M in (("vqa", C.POINTER(NcxMutanParams)), ("mlb", C.POINTER(NcxMlbParams))):
+        route, region = getattr(L, "ncx_%s_route" % name), getattr(L, "ncx_%s_ws_region" % name)
+        route.restype = region.restype = C.c_int
+        route.argtypes = [C.POINTER(NcxDims), P_M, C.POINTER(C.c_int32)]
+        region.argtypes = [C.POINTER(NcxDims), P_M, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.ncx_mlb_att_workspace_bytes.restype = C.c_size_t
     L.ncx_mlb_att_workspace_bytes.argtypes = [C.POINTER(NcxMlbAttDims), C.POINTER(NcxMlbAttParams)]
     L.ncx_mlb_att_forward.restype = C.c_int
@@ -463,6 +469,26 @@ def plan_query(d, name):
                 tile=("64x64", "128x128", "96x128", "96x64", "128x64", "48x128", "48x64 (per-triplet fold of the two v segments)",
                       "96x64 (per-triplet fold of the two v segments, four triplets per workgroup)",
                       "192x64 (per-triplet fold of the two v segments, eight triplets per 8-wave workgroup, one workgroup per CU)")[out[4]], ksplit=out[5])
+
+
+NCX_VQA_WS = dict(xq=1, hq=2, xv=3)                          # include/neuralcx.h: NCX_VQA_WS_*
+NCX_MLB_WS = dict(xq=1, t_knns=2, t_orig=3, xv=4)            # NCX_MLB_WS_*
+
+
+def vqa_route(d, m):
+    """ncx_vqa_route: what ncx_vqa_forward launches for the dims and ncx_mutan_params (host only)."""
+    out = (C.c_int32 * 4)()
+    check(lib().ncx_vqa_route(C.byref(d), C.byref(m), out), "ncx_vqa_route")
+    return dict(main_v=bool(out[0]), fold_kernel=bool(out[1]), classifier=("generic", "main", "main_padded")[out[2]],
+                v_tile=FWD_CHAIN_FORMS[out[3]] if out[3] >= 0 else None)
+
+
+def mlb_route(d, m):
+    """ncx_mlb_route: what ncx_mlb_forward launches for the dims and ncx_mlb_params (host only)."""
+    out = (C.c_int32 * 4)()
+    check(lib().ncx_mlb_route(C.byref(d), C.byref(m), out), "ncx_mlb_route")
+    return dict(main_v=bool(out[0]), v_tile=FWD_CHAIN_FORMS[out[1]] if out[1] >= 0 else None,
+                classifier=("generic", "main", "main_padded")[out[2]], t_stored=bool(out[3]))
 
 
 # ---- the C ABI's RCCL handle (include/neuralcx.h: ncx_comm_*, ncx_allreduce) ---------------------------------------------

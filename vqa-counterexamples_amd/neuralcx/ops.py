@@ -409,14 +409,50 @@ def vqa_weights(vqa_model):
     return MlbWeights(vqa_model) if isinstance(vqa_model.fusion, MLBFusion) else MutanWeights(vqa_model)
 
 
-def vqa_forward(feats: torch.Tensor, img_idx: torch.Tensor, q_emb: torch.Tensor, mw, want_a_orig=False, ws=None):
+def vqa_dims(B: int, K1: int, dv: int, dq: int, n_img: int, mw) -> NcxDims:
+    """The dims the frozen producers read (B, K, dv, dq, dz, A, n_img) for B questions of K1 = K + 1 images each."""
+    d = NcxDims()
+    d.B, d.K, d.dv, d.dq, d.dz, d.da, d.A, d.H, d.L = B, K1 - 1, dv, dq, mw.dz, 4, mw.A, 4, 1
+    d.n_img = n_img
+    return d
+
+
+def vqa_workspace(d: NcxDims, mw, device) -> torch.Tensor:
+    """A workspace of the size the producer `mw` belongs to asks for (+ the alignment slack of _ws_ptr)."""
+    ws_name = getattr(mw, "WS_BYTES", "ncx_vqa_workspace_bytes")
+    m = mw.c_struct()
+    need = getattr(_lib.lib(), ws_name)(C.byref(d), C.byref(m))
+    if need == 0:
+        raise _lib.NcxError("%s: invalid dims" % ws_name)
+    return torch.empty(need + 256, dtype=torch.uint8, device=device)
+
+
+def vqa_route(d: NcxDims, mw) -> dict:
+    """What vqa_forward launches for the dims (ncx_vqa_route / ncx_mlb_route; tests, diagnostics)."""
+    return (_lib.mlb_route if isinstance(mw, MlbWeights) else _lib.vqa_route)(d, mw.c_struct())
+
+
+def vqa_ws_view(d: NcxDims, mw, ws: torch.Tensor, name: str) -> torch.Tensor:
+    """An intermediate tensor of the last vqa_forward on `ws` as a 2-d view of the workspace: MutanWeights "xq" [B, dhq], "hq" [B, R dz],
+    "xv" [B (K + 1), dhv]; MlbWeights "xq" [B, dh], "t_knns" [B K, dh], "t_orig" [B, dh] (with classif.activation), "xv" [B (K + 1), dh]
+    (generic route only).  NcxError for a tensor the route does not store."""
+    mlb = isinstance(mw, MlbWeights)
+    sym, ids = ("ncx_mlb_ws_region", _lib.NCX_MLB_WS) if mlb else ("ncx_vqa_ws_region", _lib.NCX_VQA_WS)
+    rows = dict(xq=d.B, hq=d.B, t_orig=d.B, t_knns=d.B * d.K, xv=d.B * (d.K + 1))[name]
+    m = mw.c_struct()
+    off, nb = C.c_size_t(), C.c_size_t()
+    _lib.check(getattr(_lib.lib(), sym)(C.byref(d), C.byref(m), ids[name], C.byref(off), C.byref(nb)), sym)
+    pad = (-ws.data_ptr()) % 256
+    return ws[pad + off.value: pad + off.value + nb.value].view(torch.float32).view(rows, -1)
+
+
+def vqa_forward(feats: torch.Tensor, img_idx: torch.Tensor, q_emb: torch.Tensor, mw, want_a_orig=False, ws=None, out=None):
     """HIP replacement of CXModelBase.vqa_forward below the question encoder (cx.py:64-104), for the producer `mw`
-    belongs to (MutanWeights: ncx_vqa_forward; MlbWeights: ncx_mlb_forward).
+    belongs to (MutanWeights: ncx_vqa_forward; MlbWeights: ncx_mlb_forward).  out: caller-owned contiguous
+    (a_orig or None, z_orig, a_knns, z_knns) to write into instead of fresh tensors.
     -> (a_orig or None, z_orig [B,dz], a_knns [B,K,A], z_knns [B,K,dz])."""
     B, K1 = img_idx.shape
-    d = NcxDims()
-    d.B, d.K, d.dv, d.dq, d.dz, d.da, d.A, d.H, d.L = B, K1 - 1, feats.shape[1], q_emb.shape[1], mw.dz, 4, mw.A, 4, 1
-    d.n_img = feats.shape[0]
+    d = vqa_dims(B, K1, feats.shape[1], q_emb.shape[1], feats.shape[0], mw)
     m = mw.c_struct()
     ws_name, fwd_name = getattr(mw, "WS_BYTES", "ncx_vqa_workspace_bytes"), getattr(mw, "FORWARD", "ncx_vqa_forward")
     need = getattr(_lib.lib(), ws_name)(C.byref(d), C.byref(m))
@@ -425,9 +461,17 @@ def vqa_forward(feats: torch.Tensor, img_idx: torch.Tensor, q_emb: torch.Tensor,
     if ws is None or ws.numel() < need + 256:
         ws = torch.empty(need + 256, dtype=torch.uint8, device=feats.device)
     dev = feats.device
-    z_o = torch.empty(B, mw.dz, device=dev); z_k = torch.empty(B, K1 - 1, mw.dz, device=dev)
-    a_k = torch.empty(B, K1 - 1, mw.A, device=dev)
-    a_o = torch.empty(B, mw.A, device=dev) if want_a_orig else None
+    if out is not None:
+        a_o, z_o, a_k, z_k = out
+        for t, shape in ((z_o, (B, mw.dz)), (z_k, (B, K1 - 1, mw.dz)), (a_k, (B, K1 - 1, mw.A))) + (((a_o, (B, mw.A)),) if want_a_orig else ()):
+            if tuple(t.shape) != shape:
+                raise _lib.NcxError("vqa_forward: an output of shape %r where %r is written" % (tuple(t.shape), shape))
+            _ptr(t, torch.float32, "out")
+        a_o = a_o if want_a_orig else None
+    else:
+        z_o = torch.empty(B, mw.dz, device=dev); z_k = torch.empty(B, K1 - 1, mw.dz, device=dev)
+        a_k = torch.empty(B, K1 - 1, mw.A, device=dev)
+        a_o = torch.empty(B, mw.A, device=dev) if want_a_orig else None
     p, n = _ws_ptr(ws)
     _lib.check(getattr(_lib.lib(), fwd_name)(C.byref(d), _ptr(feats, torch.float32, "feats"), _ptr(img_idx, torch.int32, "img_idx"),
                                              _ptr(q_emb, torch.float32, "q_emb"), C.byref(m), p, n, C.c_void_p(z_o.data_ptr()),
