@@ -957,6 +957,55 @@ int ncx_bf16_layout(const ncx_dims* d, int32_t* out10);
  * layout with its padding ids): 0 when decode/encode are mutually inverse and cover every (tile, chunk) exactly once. */
 int ncx_wgmap_check(int32_t tiles_m, int32_t tiles_n, int32_t S);
 
+/* The generic segmented GEMM engine (csrc/ncx_gemm.h) called directly, for tests: one launch through the driver every caller in the
+ * library uses, with the tile config, the mode and the k-split given instead of planned.  Forms: 0 NT  C = sum_p A_p[M, k] . B_p[N, k]^T,
+ * 1 TN  C = A[k, M]^T . B[k, N], 2 NN  C = A[M, k] . B[k, N].  Operand kinds: 0 plain x(r, c) = base[r ld + c]; 1 gather
+ * base[idx[r idx_stride] ld + c]; 2 gather-mul base[idx[..] ld + c] * base[idx2[..] ld + c]; 3 softmax exp2(base[r ld + c] log2(e) - lse2[r]).
+ * mode 0: a CHAIN of nseg (a, b, klen) pairs summed into out[0] ([M, n_cols[0]], split[0] k-chunks); mode 1: a GROUP of nseg problems
+ * that share M, each with its own operands, n_cols, split, out and ldo.  fold != 0: the FOLD kernel (NT chain on 64 x 64 tiles): after
+ * pair s, z += (acc + fold_bias[s N + n]) * fold_mul[(r / fold_div) ld_fold + s N + n]; the output is z.
+ * Epilogue, in this order: + rowadd[(r / rowdiv) ld_rowadd + n]; + bias[n]; act (0 none, 1 relu, 2 tanh); dropout (0 none, 1 the
+ * counter-based generator on index r n_cols + n, 2 keep_mask[r ld_mask + n] != 0) times drop_scale; gate[r ld_gate + n] > 0 ? times
+ * gate_scale : 0.  rowsplit_g = g > 0: row r = g b + j goes to out0[b ldo0 + n] when j == 0, else to out[((g - 1) b + j - 1) ldo + n].
+ * split > 1 puts partial tiles in `slab` (ncx_diag_gemm_slab_bytes; NCX_E_WORKSPACE when slab_bytes is short) and a fix-up kernel sums
+ * them and applies bias and act.  no_fast != 0: the generic k-loop only (what the hook NCX_NO_FAST selects).  The entry writes a->grid.
+ * NCX_E_DIMS, before any launch, for what the engine does not implement: a cfg the form has no instantiation for (NT 0 1 2 3, TN 0 1 4,
+ * NN 0 1); an operand with cols < 4; klen or M or n_cols disagreeing with the operands' extents; ld < cols; nseg outside
+ * 1 .. NCX_DIAG_MAX_SEG; a kind, form, mode, act or dropout code out of range; split > 1 together with rowadd, dropout, gate, rowsplit_g
+ * or fold; fold outside an NT chain on cfg 0; rowdiv / fold_div < 1 where used.  NCX_E_NULL: a pointer the description needs is NULL.
+ * Indices are not clamped: every idx entry must name a row of its table. */
+#define NCX_DIAG_MAX_SEG 10
+typedef struct ncx_diag_operand {
+    const float* base; const int32_t* idx; const int32_t* idx2; const float* lse2;
+    int64_t ld;
+    int32_t kind, rows, cols, idx_stride;
+} ncx_diag_operand;
+typedef struct ncx_diag_gemm_args {
+    int32_t form, cfg, mode, nseg, M, fold, no_fast;
+    int32_t grid;                /* out: workgroups the GEMM launch was given (fewer than its work items under the persistent loop) */
+    ncx_diag_operand a[NCX_DIAG_MAX_SEG], b[NCX_DIAG_MAX_SEG];
+    int32_t klen[NCX_DIAG_MAX_SEG], n_cols[NCX_DIAG_MAX_SEG], split[NCX_DIAG_MAX_SEG];
+    float* out[NCX_DIAG_MAX_SEG];
+    int64_t ldo[NCX_DIAG_MAX_SEG];
+    const float* rowadd; int64_t ld_rowadd; int32_t rowdiv; int32_t act;
+    const float* bias;
+    int32_t dropout; float drop_p, drop_scale; uint32_t seed_lo, seed_hi, layer;
+    const float* keep_mask; int64_t ld_mask;
+    const float* gate; int64_t ld_gate; float gate_scale; int32_t fold_div;
+    const float* fold_mul; const float* fold_bias; int64_t ld_fold;
+    int32_t rowsplit_g; int32_t pad2_; float* out0; int64_t ldo0;
+    float* slab; size_t slab_bytes;
+} ncx_diag_gemm_args;
+int ncx_diag_gemm(ncx_diag_gemm_args* a, void* stream);
+/* Bytes of the split-K slab that launch needs (0: unsplit, or the arguments are ones ncx_diag_gemm rejects). */
+size_t ncx_diag_gemm_slab_bytes(const ncx_diag_gemm_args* a);
+/* 1 when the form instantiates the tile config, else 0 (the predicate ncx_diag_gemm and the NCX_CFG_<id> hook ask). */
+int ncx_diag_cfg_supported(int32_t form, int32_t cfg);
+/* plan_gemm, the planner behind every launch on the generic engine that is not placed by hand: out2 = {tile cfg, k-chunks per tile} for
+ * an M x N product of `ksteps` 32-deep steps; allow_96: the caller takes the big NT tiles (the forward layers).  Depends on the device's
+ * CU count (256 without a device). */
+int ncx_diag_plan_gemm(int32_t form, int64_t M, int64_t N, int64_t ksteps, int32_t allow_96, int32_t* out2);
+
 /* Library build id ("neuralcx-hip gfx950 <date>"). */
 const char* ncx_version(void);
 

@@ -39,6 +39,10 @@ def test_host_only_entry_points():
     assert _lib.lib().ncx_adam_step(None, None, None, None, 4, 1e-4, 0.9, 0.999, 1e-8, 1, 1.0, None) == -1
     # the RCCL handle validates its arguments before it loads RCCL
     assert _lib.lib().ncx_allreduce(None, None, 4, None) == -1 and _lib.lib().ncx_comm_unique_id(None) == -1
+    # the GEMM engine's diagnostic entry checks its description before it launches
+    assert _lib.lib().ncx_diag_gemm(None, None) == -1 and _lib.lib().ncx_diag_gemm_slab_bytes(None) == 0
+    assert _lib.lib().ncx_diag_gemm(ctypes.byref(_lib.NcxDiagGemmArgs()), None) == -2                       # nseg = 0
+    assert _lib.lib().ncx_diag_plan_gemm(0, 64, 64, 1, 0, None) == -1 and _lib.lib().ncx_diag_cfg_supported(0, 4) == 0
     comm = ctypes.c_void_p()
     assert _lib.lib().ncx_comm_create(ctypes.create_string_buffer(128), 2, 2, ctypes.byref(comm)) == -2     # rank >= nranks
 
@@ -47,6 +51,9 @@ def test_struct_layout_matches_header():
     from neuralcx._lib import NcxDims, NcxInputs, NcxParams, NcxGrads
     assert ctypes.sizeof(NcxDims) == 64
     assert ctypes.sizeof(NcxInputs) == 80 and ctypes.sizeof(NcxParams) == 72 == ctypes.sizeof(NcxGrads)
+    from neuralcx._lib import NcxDiagGemmArgs, NcxDiagOperand, NCX_DIAG_MAX_SEG
+    assert NCX_DIAG_MAX_SEG == 10 and ctypes.sizeof(NcxDiagOperand) == 56          # 4 pointers, ld, 4 ints
+    assert ctypes.sizeof(NcxDiagGemmArgs) == 32 + 20 * 56 + 3 * 40 + 2 * 80 + 160 == 1592
 
 
 def test_missing_library_fails_loudly(monkeypatch):

@@ -4,7 +4,100 @@
 #include <stdlib.h>
 
 using namespace ncx;
+
+// ncx_diag_gemm: the description checked against what the engine implements, then turned into the GemmArgs every caller builds.
+namespace {
+int diag_operand(const ncx_diag_operand& o, XDesc& x) {
+    if (o.kind < X_PLAIN || o.kind > X_SOFTMAX || o.rows < 1 || o.cols < 4 || o.ld < o.cols || o.idx_stride < 1) return NCX_E_DIMS;
+    if (!o.base || ((o.kind == X_GATHER || o.kind == X_GATHER_MUL) && !o.idx) || (o.kind == X_GATHER_MUL && !o.idx2) ||
+        (o.kind == X_SOFTMAX && !o.lse2)) return NCX_E_NULL;
+    x = XDesc{};
+    x.base = o.base; x.idx = o.idx; x.idx2 = o.idx2; x.mx = o.lse2; x.ld = o.ld; x.kind = o.kind; x.rows = o.rows; x.cols = o.cols;
+    x.idx_stride = o.idx_stride;
+    return NCX_OK;
+}
+int diag_gemm_args(const ncx_diag_gemm_args* d, GemmArgs& g, GemmPlan& pl) {
+    if (!d) return NCX_E_NULL;
+    if (d->form < FORM_NT || d->form > FORM_NN || !cfg_supported(d->form, d->cfg)) return NCX_E_DIMS;
+    if ((d->mode != MODE_CHAIN && d->mode != MODE_GROUP) || d->nseg < 1 || d->nseg > NCX_MAX_SEG || d->nseg > NCX_DIAG_MAX_SEG || d->M < 1) return NCX_E_DIMS;
+    if (d->act < 0 || d->act > 2 || d->dropout < 0 || d->dropout > 2 || d->rowsplit_g < 0) return NCX_E_DIMS;
+    if (d->fold && (d->form != FORM_NT || d->mode != MODE_CHAIN || d->cfg != CFG_64x64)) return NCX_E_DIMS;
+    g = GemmArgs{};
+    g.mode = d->mode; g.nseg = d->nseg; g.M = d->M;
+    const bool a_colk = d->form != FORM_TN, b_colk = d->form == FORM_NT;
+    const int np = d->mode == MODE_GROUP ? d->nseg : 1;
+    bool any_split = false;
+    for (int i = 0; i < d->nseg; ++i) {
+        int rc = diag_operand(d->a[i], g.a[i]); if (rc) return rc;
+        rc = diag_operand(d->b[i], g.b[i]); if (rc) return rc;
+        const int p = d->mode == MODE_GROUP ? i : 0, N = d->n_cols[p], k = d->klen[i];
+        if (N < 1 || k < 1) return NCX_E_DIMS;
+        // the reduction runs along the columns of a col-is-k operand and along the rows of a row-is-k one; the other extent is M / N
+        if ((a_colk ? d->a[i].cols : d->a[i].rows) != k || (a_colk ? d->a[i].rows : d->a[i].cols) != d->M) return NCX_E_DIMS;
+        if ((b_colk ? d->b[i].cols : d->b[i].rows) != k || (b_colk ? d->b[i].rows : d->b[i].cols) != N) return NCX_E_DIMS;
+        g.klen[i] = k;
+    }
+    for (int p = 0; p < np; ++p) {
+        if (!d->out[p]) return NCX_E_NULL;
+        if (d->ldo[p] < d->n_cols[p]) return NCX_E_DIMS;
+        g.out[p] = d->out[p]; g.ldo[p] = d->ldo[p]; g.n_cols[p] = d->n_cols[p];
+        g.split[p] = d->split[p] > 1 ? d->split[p] : 1;
+        any_split |= g.split[p] > 1;
+    }
+    EpiArgs& e = g.epi;
+    e.rowadd = d->rowadd; e.ld_rowadd = d->ld_rowadd; e.rowdiv = d->rowdiv; e.bias = d->bias; e.relu = d->act;
+    e.dropout = d->dropout; e.drop_p = d->drop_p; e.drop_scale = d->drop_scale; e.seed_lo = d->seed_lo; e.seed_hi = d->seed_hi; e.layer = d->layer;
+    e.keep_mask = d->keep_mask; e.ld_mask = d->ld_mask; e.gate = d->gate; e.ld_gate = d->ld_gate; e.gate_scale = d->gate_scale;
+    e.rowsplit_g = d->rowsplit_g; e.out0 = d->out0; e.ldo0 = d->ldo0;
+    int n_max = 0;
+    for (int p = 0; p < np; ++p) n_max = d->n_cols[p] > n_max ? d->n_cols[p] : n_max;
+    if (d->rowadd && (d->rowdiv < 1 || d->ld_rowadd < n_max)) return NCX_E_DIMS;
+    if ((d->dropout == 2 && d->ld_mask < n_max) || (d->gate && d->ld_gate < n_max) || (d->rowsplit_g > 0 && d->ldo0 < n_max)) return NCX_E_DIMS;
+    if (d->fold && d->ld_fold < (int64_t)d->nseg * n_max) return NCX_E_DIMS;
+    if (d->dropout == 2 && !d->keep_mask) return NCX_E_NULL;
+    if (d->rowsplit_g > 0 && !d->out0) return NCX_E_NULL;
+    if (d->fold) {
+        if (!d->fold_mul || !d->fold_bias) return NCX_E_NULL;
+        if (d->fold_div < 1) return NCX_E_DIMS;
+        e.fold_mul = d->fold_mul; e.fold_bias = d->fold_bias; e.ld_fold = d->ld_fold; e.fold_div = d->fold_div;
+    }
+    // a split launch's fix-up applies bias and activation only
+    if (any_split && (d->rowadd || d->dropout || d->gate || d->rowsplit_g > 0 || d->fold)) return NCX_E_DIMS;
+    pl.cfg = d->cfg; pl.split = 1;
+    return NCX_OK;
+}
+}  // namespace
+
 extern "C" {
+int ncx_diag_cfg_supported(int32_t form, int32_t cfg) { return cfg_supported(form, cfg) ? 1 : 0; }
+
+size_t ncx_diag_gemm_slab_bytes(const ncx_diag_gemm_args* d) {
+    GemmArgs g; GemmPlan pl;
+    if (diag_gemm_args(d, g, pl) != NCX_OK) return 0;
+    return gemm_slab_bytes(g, pl);
+}
+
+int ncx_diag_gemm(ncx_diag_gemm_args* d, void* stream) {
+    GemmArgs g; GemmPlan pl;
+    int rc = diag_gemm_args(d, g, pl);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (!d->fold && gemm_slab_bytes(g, pl) > 0 && !d->slab) return NCX_E_NULL;
+    // the FOLD launch does not pass the driver: its no_fast bit is set here
+    if (d->fold) { g.pad_ = d->no_fast ? 1 : 0; rc = run_gemm_nt_fold(g, s); }
+    else rc = run_gemm_planned(g, d->form, pl, d->slab, d->slab_bytes, nullptr, s, d->no_fast != 0);
+    d->grid = g.grid_;
+    return rc;
+}
+
+int ncx_diag_plan_gemm(int32_t form, int64_t M, int64_t N, int64_t ksteps, int32_t allow_96, int32_t* out2) {
+    if (!out2) return NCX_E_NULL;
+    if (form < FORM_NT || form > FORM_NN || M < 1 || N < 1 || ksteps < 1) return NCX_E_DIMS;
+    const GemmPlan p = plan_gemm(form, M, N, ksteps, allow_96 != 0);
+    out2[0] = p.cfg; out2[1] = p.split;
+    return NCX_OK;
+}
+
 int ncx_profile_begin(uint32_t gemm_mask, int32_t max_launches) {
     if (g_prof.on || gemm_mask == 0 || (gemm_mask >> U_COUNT) != 0 || max_launches < 1 || max_launches > 65536) return NCX_E_DIMS;
     g_prof.ev = (hipEvent_t*)malloc(sizeof(hipEvent_t) * 2 * (size_t)max_launches);

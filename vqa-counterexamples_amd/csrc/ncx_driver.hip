@@ -88,8 +88,8 @@ static size_t default_splits(GemmArgs& a, const GemmPlan& pl) {
     return (size_t)gemm_layout(a, bm, bn, nullptr) * bm * bn * 4;
 }
 size_t gemm_slab_bytes(GemmArgs a, const GemmPlan& pl) { return default_splits(a, pl); }
-int run_gemm_planned(GemmArgs& a, int form, const GemmPlan& pl, float* slab, size_t slab_bytes, const float* reduce_bias, hipStream_t s) {
-    { const char* nf = hook_env("NCX_NO_FAST"); a.pad_ = nf && atoi(nf) ? 1 : 0; }
+int run_gemm_planned(GemmArgs& a, int form, const GemmPlan& pl, float* slab, size_t slab_bytes, const float* reduce_bias, hipStream_t s, bool no_fast) {
+    { const char* nf = hook_env("NCX_NO_FAST"); a.pad_ = (no_fast || (nf && atoi(nf))) ? 1 : 0; }
     const size_t need = default_splits(a, pl);
     if (need > slab_bytes) return NCX_E_WORKSPACE;
     if (need) a.slab = slab;

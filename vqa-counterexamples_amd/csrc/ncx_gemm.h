@@ -105,7 +105,7 @@ struct GemmArgs {
     int   mode, nseg, M, pad_;
     int   total_wgs;             // work items (filled by the launcher); the grid may be smaller: persistent loop
     struct FixupArgs* defer_fix; // host only: when set, a split launch hands its fix-up back instead of launching it (merged fix-ups)
-    int   pad2_;
+    int   grid_;                 // host only: workgroups of the last launch (filled by the launcher; < total_wgs under the persistent loop)
     float* slab;                 // [workgroups][BM*BN] partial tiles of the split problems
     EpiArgs epi;
 };
@@ -1040,6 +1040,7 @@ static inline hipError_t launch_seg_gemm(GemmArgs& args, hipStream_t stream) {
         const char* pe = hook_env("NCX_PERSISTENT");
         if (pe && atoi(pe) && wgs > 2 * slots) grid = slots;
     }
+    args.grid_ = (int)grid;
     hipLaunchKernelGGL((seg_gemm_kernel<BM, BN, A_COLK, B_COLK, FOLD>), dim3((unsigned)grid), dim3(256), Cfg::LDS_BYTES, stream, args);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !any_split) return e;

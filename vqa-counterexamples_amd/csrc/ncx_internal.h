@@ -8,6 +8,16 @@ namespace ncx {
 
 enum TileCfg : int { CFG_64x64 = 0, CFG_128x128 = 1, CFG_96x128 = 2, CFG_96x64 = 3, CFG_128x64 = 4 };
 enum GemmForm : int { FORM_NT = 0, FORM_TN = 1, FORM_NN = 2 };
+// The tile configs run_gemm_nt / _tn / _nn (ncx_gemm_inst.hip) instantiate for a form.  Any other value falls through their `default:` to
+// 64x64 while default_splits and run_fixup2 size by cfg_tile(cfg): whoever takes a cfg from outside the planner asks here first.
+static inline bool cfg_supported(int form, int cfg) {
+    switch (form) {
+    case FORM_NT: return cfg == CFG_64x64 || cfg == CFG_128x128 || cfg == CFG_96x128 || cfg == CFG_96x64;
+    case FORM_TN: return cfg == CFG_64x64 || cfg == CFG_128x128 || cfg == CFG_128x64;
+    case FORM_NN: return cfg == CFG_64x64 || cfg == CFG_128x128;
+    default:      return false;
+    }
+}
 
 int run_gemm_nt(GemmArgs& a, int cfg, hipStream_t s);
 int run_fixup2(const FixupArgs& a, const FixupArgs& b, int cfg, hipStream_t s);
@@ -46,10 +56,13 @@ static inline long long cdiv(long long a, long long b) { return (a + b - 1) / b;
 static inline long long ksteps(long long k) { return cdiv(k, GEMM_BK); }      // 32-deep reduction steps of a k extent
 // The GEMM driver (ncx_driver.hip) of every launch on the generic engine.  Problems whose a.split[i] is 0 take pl.split (callers
 // may preset per-problem splits); a split launch puts its partial tiles in `slab` (NCX_E_WORKSPACE when slab_bytes is short).
-// reduce_bias (nullable): applied by the epilogue or by the fix-up kernel.  Hook NCX_NO_FAST: the diagnostic tile path.
+// reduce_bias (nullable): applied by the epilogue or by the fix-up kernel.  Hook NCX_NO_FAST, or no_fast (ncx_diag_gemm only): the diagnostic tile path.
+// Preconditions (callers keep them; ncx_diag_gemm, ncx_diag.hip, checks them): cfg_supported(form, pl.cfg); every operand has cols >= 4
+// (16-byte windows); klen[i] == the operands' reduction extents; a split problem applies bias and activation only (the fix-up drops
+// rowadd, dropout, gate and rowsplit_g).
 __attribute__((visibility("hidden"))) size_t gemm_slab_bytes(GemmArgs a, const GemmPlan& pl);      // 0 when unsplit
 __attribute__((visibility("hidden"))) int run_gemm_planned(GemmArgs& a, int form, const GemmPlan& pl, float* slab, size_t slab_bytes,
-                                                           const float* reduce_bias, hipStream_t s);
+                                                           const float* reduce_bias, hipStream_t s, bool no_fast = false);
 // ncx_scorers.hip: out[c] = sum over rows r < R of in[r * ld + c], c < cols, in a fixed order (k_colsum)
 __attribute__((visibility("hidden"))) hipError_t colsum_rows(const float* in, long long ld, int R, int cols, float* out, hipStream_t s);
 

@@ -244,7 +244,7 @@ void list_uses(const ncx_dims& d, const StepRoutes& r, GemmUse* u) {
             char name[32];
             snprintf(name, sizeof name, "NCX_CFG_%d", i);
             const char* c = getenv(name);
-            if (c) u[i].plan.cfg = atoi(c);
+            if (c && cfg_supported(u[i].form, atoi(c))) u[i].plan.cfg = atoi(c);      // a tile the form does not instantiate: ignored
             snprintf(name, sizeof name, "NCX_SPLIT_%d", i);
             const char* e = getenv(name);
             if (e && i != U_MAIN && i != U_FWD_L && i != U_DXL) u[i].plan.split = atoi(e) > 1 ? atoi(e) : 1;

@@ -50,7 +50,7 @@ static VqaLayout vqa_layout(const ncx_dims& d, const ncx_mutan_params& m, GemmPl
         {   // experiment hook
             char name[32]; snprintf(name, sizeof name, "NCX_VQA_CFG_%d", i);
             const char* c = hook_env(name);
-            if (c) { plans[i].cfg = atoi(c); plans[i].split = 1; }
+            if (c && cfg_supported(FORM_NT, atoi(c))) { plans[i].cfg = atoi(c); plans[i].split = 1; }
         }
         if (i == 3) { plans[i].cfg = CFG_64x64; plans[i].split = 1; }
         int bm, bn; cfg_tile(plans[i].cfg, bm, bn);

@@ -36,7 +36,8 @@ EXPORTS = ("ncx_input_size", "ncx_workspace_bytes", "ncx_forward", "ncx_forward_
            "ncx_vqa_train_workspace_bytes", "ncx_vqa_train_forward", "ncx_ce_loss", "ncx_vqa_train_backward", "ncx_vqa_train_ws_region",
            "ncx_mlb_train_workspace_bytes", "ncx_mlb_train_forward", "ncx_mlb_train_backward", "ncx_mlb_train_ws_region",
            "ncx_mlb_att_train_workspace_bytes", "ncx_mlb_att_train_forward", "ncx_mlb_att_train_forward_flags", "ncx_mlb_att_train_backward", "ncx_mlb_att_train_ws_region",
-           "ncx_mlb_att_train_backward_flags", "ncx_mlb_att_dwv_form")
+           "ncx_mlb_att_train_backward_flags", "ncx_mlb_att_dwv_form",
+           "ncx_diag_gemm", "ncx_diag_gemm_slab_bytes", "ncx_diag_cfg_supported", "ncx_diag_plan_gemm")
 
 
 class NcxDims(C.Structure):
@@ -116,6 +117,30 @@ class NcxScorerDims(C.Structure):
 
 class NcxContrastiveDims(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("B", "P", "dv", "dz", "n_img")]
+
+
+NCX_DIAG_MAX_SEG = 10
+
+
+class NcxDiagOperand(C.Structure):           # ncx_diag_operand (include/neuralcx.h)
+    _fields_ = [(n, C.c_void_p) for n in ("base", "idx", "idx2", "lse2")] + [("ld", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("kind", "rows", "cols", "idx_stride")]
+
+
+class NcxDiagGemmArgs(C.Structure):          # ncx_diag_gemm_args: one launch of the generic GEMM engine, described field by field
+    _fields_ = [(n, C.c_int32) for n in ("form", "cfg", "mode", "nseg", "M", "fold", "no_fast", "grid")] + \
+               [("a", NcxDiagOperand * NCX_DIAG_MAX_SEG), ("b", NcxDiagOperand * NCX_DIAG_MAX_SEG)] + \
+               [(n, C.c_int32 * NCX_DIAG_MAX_SEG) for n in ("klen", "n_cols", "split")] + \
+               [("out", C.c_void_p * NCX_DIAG_MAX_SEG), ("ldo", C.c_int64 * NCX_DIAG_MAX_SEG),
+                ("rowadd", C.c_void_p), ("ld_rowadd", C.c_int64), ("rowdiv", C.c_int32), ("act", C.c_int32),
+                ("bias", C.c_void_p),
+                ("dropout", C.c_int32), ("drop_p", C.c_float), ("drop_scale", C.c_float),
+                ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("layer", C.c_uint32),
+                ("keep_mask", C.c_void_p), ("ld_mask", C.c_int64),
+                ("gate", C.c_void_p), ("ld_gate", C.c_int64), ("gate_scale", C.c_float), ("fold_div", C.c_int32),
+                ("fold_mul", C.c_void_p), ("fold_bias", C.c_void_p), ("ld_fold", C.c_int64),
+                ("rowsplit_g", C.c_int32), ("pad2_", C.c_int32), ("out0", C.c_void_p), ("ldo0", C.c_int64),
+                ("slab", C.c_void_p), ("slab_bytes", C.c_size_t)]
 
 
 _PL_NAMES = ("answer_embedding", "w", "b", "w_out", "b_out")
@@ -366,6 +391,14 @@ def lib():
     L.ncx_mlb_att_dwv_form.argtypes = [P_AD, C.c_uint32]
     L.ncx_mlb_att_train_ws_region.restype = C.c_int
     L.ncx_mlb_att_train_ws_region.argtypes = [P_AD, P_AT, P_AP, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.ncx_diag_gemm.restype = C.c_int
+    L.ncx_diag_gemm.argtypes = [C.POINTER(NcxDiagGemmArgs), C.c_void_p]
+    L.ncx_diag_gemm_slab_bytes.restype = C.c_size_t
+    L.ncx_diag_gemm_slab_bytes.argtypes = [C.POINTER(NcxDiagGemmArgs)]
+    L.ncx_diag_cfg_supported.restype = C.c_int
+    L.ncx_diag_cfg_supported.argtypes = [C.c_int32, C.c_int32]
+    L.ncx_diag_plan_gemm.restype = C.c_int
+    L.ncx_diag_plan_gemm.argtypes = [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]
     _lib = L
     return L
 

@@ -1762,3 +1762,33 @@ class NeuralCXFunction(torch.autograd.Function):
         call["pool"].give(ctx.ws)
         ctx.ws = None
         return (None,) + tuple(gbuf[n] for n in names)
+
+
+# ---- diagnostics: the generic GEMM engine called directly (include/neuralcx.h: ncx_diag_gemm) ------------------------------------
+GEMM_FORMS = ("NT", "TN", "NN")
+GEMM_TILES = ("64x64", "128x128", "96x128", "96x64", "128x64")          # tile cfg codes
+
+
+def diag_cfg_supported(form: int, cfg: int) -> bool:
+    return bool(_lib.lib().ncx_diag_cfg_supported(form, cfg))
+
+
+def diag_plan_gemm(form: int, M: int, N: int, ksteps: int, allow_96: bool = False) -> dict:
+    """plan_gemm: the tile config and k-split the planner gives an M x N product of `ksteps` 32-deep steps (host only)."""
+    out = (C.c_int32 * 2)()
+    _lib.check(_lib.lib().ncx_diag_plan_gemm(form, M, N, ksteps, int(allow_96), out), "ncx_diag_plan_gemm")
+    return dict(cfg=int(out[0]), tile=GEMM_TILES[out[0]], split=int(out[1]))
+
+
+def diag_gemm_slab_bytes(a: _lib.NcxDiagGemmArgs) -> int:
+    return int(_lib.lib().ncx_diag_gemm_slab_bytes(C.byref(a)))
+
+
+def diag_gemm_rc(a: _lib.NcxDiagGemmArgs, stream=None) -> int:
+    """One launch of the engine as `a` describes it, on torch's current stream; -> the status code (a rejected description launches nothing,
+    so this needs no device for one)."""
+    return int(_lib.lib().ncx_diag_gemm(C.byref(a), _stream() if stream is None else stream))
+
+
+def diag_gemm(a: _lib.NcxDiagGemmArgs) -> None:
+    _lib.check(diag_gemm_rc(a), "ncx_diag_gemm")
